@@ -5,13 +5,16 @@
         N > 1 launches N ranks itself (torch.distributed.run, one rank per GPU over RCCL); the same
         file also runs under an external launcher (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the env).
     python bench.py --workload speech|fc4096        # one of the other BASELINE configs as the headline
+    python bench.py --full                          # everything below beside the headline (+ bench_details.json)
+    python bench.py --dump-outputs DIR              # the last timed step's outputs as DIR/<name>.npy (float32)
 
 Workload (BASELINE.json): person_detect.tflite, int8, 65536 independent inferences per GPU (configs[2];
 configs[3] = the same shard on each of 8 GPUs: weak scaling, no data-path collective).  One "step" = one
 pass of predict_inner (31 operators: 14 DepthwiseConv2D, 14 Conv2D, AveragePool2D, Reshape, Softmax) over
 the GPU's batch, int8 in -> int8 out, with the synthetic input batch resident in HBM when the timed region
 starts.  `value` follows the driver's contract: W untimed steps, then exactly K steps between two
-barrier + synchronize fences, wall clock, max over ranks.  Beside it the line carries
+barrier + synchronize fences, wall clock, max over ranks.  A plain run stops there: it prints the headline
+fields (metric, value, unit, ms_per_step, ...) and nothing else.  With --full the line also carries
   event_median : the same step timed per iteration with HIP events on the launch stream, median
   roofline     : the dominant kernel -- algorithmic bytes / its median HIP-event duration vs the 8 TB/s HBM peak
   kernels      : the same figure for every launch of the step; layerwise: with the fusions switched off
@@ -52,6 +55,20 @@ WORKLOADS = {
 }
 PARITY_NOTE = ("bit-exact vs the restated CPU oracle (oracle/mf_oracle.c, pinned to every reference KAT; "
                "softmax's expf is pinned at the reference's 9 points only)")
+DUMP_CAP_BYTES = 32 << 20  # --dump-outputs: an output larger than this is written as a fixed, seeded sample of its rows
+
+
+def dump_outputs(d, name, rows):
+    """--dump-outputs: one output tensor of the timed path's last step ([rows, row elements], int8 on the device) as float32
+    DIR/<name>.npy.  Above DUMP_CAP_BYTES a fixed, seeded sample of the rows (in order) is written instead."""
+    n, width = rows.shape
+    keep = max(1, DUMP_CAP_BYTES // (4 * width))
+    if n > keep:
+        import torch
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        rows = rows[torch.from_numpy(idx).to(rows.device)]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, name + ".npy"), rows.cpu().numpy().astype(np.float32))
 
 
 def free_port():
@@ -84,9 +101,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="person_detect", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the BASELINE size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-fed", action="store_true", help="skip the PCIe-inclusive and f32 legs")
-    ap.add_argument("--no-extra", action="store_true", help="skip the speech / fc4096 sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: event timing, per-kernel / layer-wise / roofline tables, parity with the CPU oracle, "
+                         "the CPU baseline, the host-fed and f32 legs, the other workloads; the full record goes to bench_details.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-host-fed", action="store_true", help="(--full) skip the PCIe-inclusive and f32 legs")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the speech / fc4096 sub-records")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of the N > 1 path (nccl = RCCL; gloo: tests on a 1-GPU box)")
@@ -96,6 +118,8 @@ def main():
     ap.add_argument("--share-device", action="store_true",
                     help="every rank uses GPU 0 (only with --backend gloo: exercises the real multi-rank launch path on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -149,8 +173,10 @@ def main():
                synth_i8=synth_i8, checksum_i8=checksum_i8, SEED=SEED, checker=O)
     fname, cfg, base_batch = WORKLOADS[args.workload]
     B = args.batch or base_batch
+    out_name = "output" if world == 1 else "output_rank%d" % rank
     if args.workload == "fc4096":
-        result = headline_from_sub(args, fc4096_record(ctx, args.steps, args.warmup, wzp=0), world)
+        dump = (lambda y: dump_outputs(args.dump_outputs, out_name, y)) if args.dump_outputs else None
+        result = headline_from_sub(args, fc4096_record(ctx, args.steps, args.warmup, wzp=0, full=args.full, dump=dump), world)
         finish(ctx, result)
         return
     m = mf.model(os.path.join(ROOT, "models", fname))
@@ -188,6 +214,22 @@ def main():
         elapsed = max_over_ranks(dist, elapsed, device=coll_dev)
     ms_per_step = elapsed / args.steps * 1e3
     value = B * world / (elapsed / args.steps)
+    if args.dump_outputs:  # y holds what the last timed step computed
+        dump_outputs(args.dump_outputs, out_name, y.reshape(count, -1))
+    head = {
+        "metric": "inferences/sec (int8) for %s" % fname, "value": round(value, 1),
+        "unit": "inferences/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
+        "prewarm_steps": prewarm_steps,  # untimed launches in front of the W warm-up steps (benchlib/roofline.py prewarm: 60 ms, clock ramp)
+        "vs_baseline": None, "dtype": "i8", "data": "synthetic",
+        "config": {"workload": "%s batch=%d per GPU, predict_inner int8->int8, inputs resident in HBM"
+                               % (fname, B), "per_gpu_batch": B, "global_batch": B * world,
+                   "parallelism": "batch shard x%d, no data-path collective" % world,
+                   "backend": (args.backend if (world > 1 or args.dist) else None),
+                   "shards": [list(shard_range(B * world, r, world)) for r in range(world)]}}
+    if not args.full:  # a plain run: the headline and nothing else
+        finish(ctx, head if rank == 0 else None)
+        return
 
     # the same step, one HIP event pair per iteration on the launch stream: median
     ev = event_times(torch, step, max(20, args.steps))
@@ -408,17 +450,7 @@ def main():
             rt_rec["general_conv"] = general_conv_record(ctx)
             rt_rec["general_depthwise"] = general_depthwise_record(ctx)
 
-        result = {
-            "metric": "inferences/sec (int8) for %s" % fname, "value": round(value, 1),
-            "unit": "inferences/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
-            "prewarm_steps": prewarm_steps,  # untimed launches in front of the W warm-up steps (benchlib/roofline.py prewarm: 60 ms, clock ramp)
-            "vs_baseline": None, "dtype": "i8", "data": "synthetic",
-            "config": {"workload": "%s batch=%d per GPU, predict_inner int8->int8, inputs resident in HBM"
-                                   % (fname, B), "per_gpu_batch": B, "global_batch": B * world,
-                       "parallelism": "batch shard x%d, no data-path collective" % world,
-                       "backend": (args.backend if (world > 1 or args.dist) else None),
-                       "shards": [list(shard_range(B * world, r, world)) for r in range(world)]},
+        result = dict(head, **{
             "roofline": roofline,
             "requant_ceiling": rl.REQUANT_CEILING,
             "event_median": {"ms_per_step": round(ev_med, 4), "value": round(B * world / (ev_med * 1e-3), 1),
@@ -442,7 +474,7 @@ def main():
                        "structured_images": n_struct, "structured_distinct_outputs": n_distinct,
                        "structured_bit_exact": structured_ok,
                        "output_checksums": ["%016x" % c for c in cks]},
-        }
+        })
         x = y = m = None
         torch.cuda.empty_cache()
         if args.workload == "person_detect" and not args.no_extra:
@@ -462,16 +494,17 @@ def finish(ctx, result):
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        full = ctx["args"].full
         # the full record goes to a file next to bench.py (and to gpurun_out/ when that exists); stdout carries ONE
-        # compact line, the last thing printed
+        # compact line, the last thing printed.  A plain run (no --full) writes no file and prints its headline record as it is.
         for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
-            if os.path.isdir(d):
+            if full and os.path.isdir(d):
                 try:
                     with open(os.path.join(d, DETAILS_FILE), "w") as f:
                         json.dump(result, f, indent=1)
                 except OSError as e:
                     print("bench.py: cannot write %s: %s" % (os.path.join(d, DETAILS_FILE), e), file=sys.stderr)
-        _, line = compact_record(result)
+        line = compact_record(result)[1] if full else json.dumps(result, separators=(",", ":"))
         sys.stderr.flush()
         try:  # whatever native libraries have buffered for stdout comes out BEFORE the line ...
             ctypes.CDLL(None).fflush(None)
@@ -479,6 +512,8 @@ def finish(ctx, result):
             pass
         print(line, flush=True)
         os.dup2(2, 1)  # ... and whatever they still print at exit (RCCL does) goes to stderr: the JSON line stays the last on stdout
+        if not full:  # (the parity legs are --full's)
+            return
         ok = result.get("parity", {}).get("bit_exact_vs_oracle", False)
         for sub in ("speech", "fc4096", "fc4096_wzp"):
             if sub in result and not result[sub]["parity"]["bit_exact_vs_oracle"]:

@@ -75,10 +75,11 @@ def speech_record(ctx):
     return rec
 
 
-def fc4096_record(ctx, steps, warmup, wzp=0):
+def fc4096_record(ctx, steps, warmup, wzp=0, full=True, dump=None):
     """BASELINE config 5: FullyConnected 4096x4096x4096 through the model API: one step = one predict_inner
     over a [4096, 4096] int8 input (one dense int8 GEMM + fused requantize epilogue; with a non-zero weight
-    zero point also the row-sum pre-pass of src/ops/fully_connected.rs:60-72)."""
+    zero point also the row-sum pre-pass of src/ops/fully_connected.rs:60-72).  dump(y [4096, 4096]) receives the last timed
+    step's output; full=False returns after the timed steps with the headline fields only."""
     mf, _lib, torch = ctx["mf"], ctx["_lib"], ctx["torch"]
     from tools.make_fc_model import synthetic_fc
     O = ctx["checker"]  # the CPU restatement, imported by bench.py
@@ -101,6 +102,16 @@ def fc4096_record(ctx, steps, warmup, wzp=0):
         step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    ops = 2.0 * M * K * N
+    if dump:
+        dump(y.reshape(M, N))
+    head = {"metric": "int8 GEMM TOP/s, FullyConnected 4096x4096x4096 via predict_inner",
+            "value": round(ops / (elapsed / steps) / 1e12, 1), "unit": "TOP/s",
+            "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 4),
+            "config": {"workload": "FullyConnected int8 M=K=N=4096 (generated single-op .tflite), weight zero point %d, "
+                                   "uniform random int8 operands" % wzp}}
+    if not full:
+        return head
     ev = event_times(torch, step, max(20, steps))
     ms = median(ev)
     # ... and the same launch inside ONE event pair per 20 back-to-back steps (a per-step event pair adds its own packet processing
@@ -115,7 +126,6 @@ def fc4096_record(ctx, steps, warmup, wzp=0):
         e1.record()
         torch.cuda.synchronize()
         regs.append(e0.elapsed_time(e1) / nreg)
-    ops = 2.0 * M * K * N
     tops = ops / (ms * 1e-3) / 1e12
     rows = sorted(set([0, 777, 4095] + list(range(5, M, 131))))[:40]
     om = O.Model(synthetic_fc(len(rows), K, N, wzp=wzp, seed=5))
@@ -128,11 +138,7 @@ def fc4096_record(ctx, steps, warmup, wzp=0):
         del w_nk
     return {
         "crosscheck": crosscheck,
-        "metric": "int8 GEMM TOP/s, FullyConnected 4096x4096x4096 via predict_inner",
-        "value": round(ops / (elapsed / steps) / 1e12, 1), "unit": "TOP/s",
-        "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 4),
-        "config": {"workload": "FullyConnected int8 M=K=N=4096 (generated single-op .tflite), weight zero point %d, "
-                               "uniform random int8 operands" % wzp},
+        **head,
         "roofline": {"bound": "mfma", "kernel": m.op(0)["kernel"], "achieved": round(tops, 1),
                      "peak": INT8_MFMA_PEAK_NOMINAL, "unit": "TOP/s", "frac": round(tops / INT8_MFMA_PEAK_NOMINAL, 4),
                      "peak_guide_floor": INT8_MFMA_PEAK_GUIDE_FLOOR,

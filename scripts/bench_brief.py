@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""stdin: bench.py's JSON line -> one short line (step time, parity, per-kernel ms)."""
+"""stdin: the JSON line of `bench.py --full` -> one short line (step time, parity, per-kernel ms)."""
 import json
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""stdin: bench.py's JSON line -> layer-wise step time and the pointwise kernels' times."""
+"""stdin: the JSON line of `bench.py --full` -> layer-wise step time and the pointwise kernels' times."""
 import json
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""stdin: bench.py's JSON line -> step time and the stage kernel's time."""
+"""stdin: the JSON line of `bench.py --full` -> step time and the stage kernel's time."""
 import json
 import sys
 

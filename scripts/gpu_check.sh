@@ -21,7 +21,7 @@ if [[ $STEPS == all || $STEPS == *smoke* ]]; then
   tail -3 $OUT/smoke.log
 fi
 if [[ $STEPS == all || $STEPS == *bench* ]]; then
-  timeout 600 python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
+  timeout 600 python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
   echo "bench exit $?"
   cp $OUT/bench_details.json $OUT/bench_details_default.json   # (the profiling passes below run bench.py again and overwrite it)
   tail -5 $OUT/bench.err
@@ -46,7 +46,7 @@ fi
 if [[ $STEPS == all || $STEPS == *prof* ]]; then
   rm -rf $OUT/prof
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -- \
-      python "$OLDPWD/bench.py" --steps 20 --warmup 3 --no-cpu-baseline --no-host-fed --no-extra > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err")
+      python "$OLDPWD/bench.py" --full --steps 20 --warmup 3 --no-cpu-baseline --no-host-fed --no-extra > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err")
   echo "rocprof exit $?"
   find $OUT/prof -name "*kernel_stats*" | head
   f=$(find $OUT/prof -name "*kernel_stats.csv" | head -1)
@@ -58,7 +58,7 @@ if [[ $STEPS == *pmc* && $STEPS != sqpmc ]]; then
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $OUT/pmc_$c
     (cd /tmp && timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$OLDPWD/$OUT/pmc_$c" -- \
-        python "$OLDPWD/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-host-fed > /dev/null 2> "$OLDPWD/$OUT/pmc_$c.err")
+        python "$OLDPWD/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline --no-host-fed > /dev/null 2> "$OLDPWD/$OUT/pmc_$c.err")
     echo "pmc $c exit $?"
     find $OUT/pmc_$c -name "*.csv" | head -5
   done
@@ -75,16 +75,16 @@ if [[ $STEPS == *sqpmc* ]]; then
   # SQ counters (8 slots per pass) for the issue/stall breakdown of every kernel
   rm -rf $OUT/pmc_sq
   (cd /tmp && timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d "$OLDPWD/$OUT/pmc_sq" -- \
-      python "$OLDPWD/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed > /dev/null 2> "$OLDPWD/$OUT/pmc_sq.err")
+      python "$OLDPWD/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed > /dev/null 2> "$OLDPWD/$OUT/pmc_sq.err")
   echo "sq pmc exit $?"
   rm -rf $OUT/pmc_sq2
   (cd /tmp && timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_CVT GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OLDPWD/$OUT/pmc_sq2" -- \
-      python "$OLDPWD/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed > /dev/null 2> "$OLDPWD/$OUT/pmc_sq2.err")
+      python "$OLDPWD/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed > /dev/null 2> "$OLDPWD/$OUT/pmc_sq2.err")
   echo "sq2 pmc exit $?"
   # third pass: how busy the matrix pipes are (what the launches whose matrix-pipe and VALU time add up are bounded by)
   rm -rf $OUT/pmc_sq3
   (cd /tmp && timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$OLDPWD/$OUT/pmc_sq3" -- \
-      python "$OLDPWD/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra > /dev/null 2> "$OLDPWD/$OUT/pmc_sq3.err")
+      python "$OLDPWD/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra > /dev/null 2> "$OLDPWD/$OUT/pmc_sq3.err")
   echo "sq3 pmc exit $?"
   python - <<'PY'
 import csv, glob, re
@@ -111,7 +111,7 @@ if [[ $STEPS == *fcprof* ]]; then
   # kernel stats of the 4096^3 FullyConnected workload alone (BASELINE config 5)
   rm -rf $OUT/prof_fc
   (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof_fc" -- \
-      python "$OLDPWD/bench.py" --workload fc4096 --steps 50 --warmup 5 > "$OLDPWD/$OUT/prof_fc_bench.json" 2> "$OLDPWD/$OUT/prof_fc.err")
+      python "$OLDPWD/bench.py" --full --workload fc4096 --steps 50 --warmup 5 > "$OLDPWD/$OUT/prof_fc_bench.json" 2> "$OLDPWD/$OUT/prof_fc.err")
   echo "fc rocprof exit $?"
   f=$(find $OUT/prof_fc -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && grep -i "fc_mfma\|fc_rowsum\|Name" "$f" | cut -c1-200

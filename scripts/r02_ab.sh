@@ -21,14 +21,14 @@ except Exception as e:
     print("bench parse failed", sys.argv[1], e)
 PY
 }
-timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-fed > $OUT/bench_mm.json 2> $OUT/bench_mm.err
+timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-fed > $OUT/bench_mm.json 2> $OUT/bench_mm.err
 echo "bench mm exit $?"; tail -3 $OUT/bench_mm.err; summ $OUT/bench_mm.json
-MF_DWPW_IMPL=valu timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-fed > $OUT/bench_valu.json 2> $OUT/bench_valu.err
+MF_DWPW_IMPL=valu timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-fed > $OUT/bench_valu.json 2> $OUT/bench_valu.err
 echo "bench valu exit $?"; tail -3 $OUT/bench_valu.err; summ $OUT/bench_valu.json
 if [[ "$1" == *prof* ]]; then
   rm -rf $OUT/prof
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -- \
-      python "$OLDPWD/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-host-fed > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err")
+      python "$OLDPWD/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-fed > "$OLDPWD/$OUT/prof_bench.json" 2> "$OLDPWD/$OUT/prof.err")
   echo "rocprof exit $?"
   f=$(find $OUT/prof -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && head -30 "$f"

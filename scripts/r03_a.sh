@@ -11,7 +11,7 @@ rocm-smi --showproductname 2>/dev/null | head -8 > $OUT/gpu.txt
 timeout 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1
 echo "pytest exit $?" >> $OUT/pytest_gpu.log
 tail -15 $OUT/pytest_gpu.log
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-fed --no-extra"
+B="python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-fed --no-extra"
 python scripts/variants.py run "$B 2>/dev/null | python scripts/bench_brief.py" > $OUT/ab.txt 2>&1
 cat $OUT/ab.txt
 MF_NO_SAT_PACK=1 $B 2>/dev/null | python scripts/bench_brief.py > $OUT/nosat.txt 2>&1

@@ -10,4 +10,4 @@ print([ (i, m.op_epilogue_mode(i)) for i in range(m.num_ops) if not m.op(i)['ker
 " 2>&1 | grep -v "^\[epi\] \(conv\|depthwise\)" | tail -32
 timeout 600 python scripts/time_kernels.py 30
 timeout 600 python scripts/time_kernels.py 30
-timeout 900 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-host-fed --no-extra > $OUT/bench.log 2> $OUT/bench.err; tail -c 1200 $OUT/bench.log
+timeout 900 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-host-fed --no-extra > $OUT/bench.log 2> $OUT/bench.err; tail -c 1200 $OUT/bench.log

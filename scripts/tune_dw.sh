@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 N=${1:-25}
 for i in -1 $(seq 0 $((N-1))); do
   if [ $i -ge 0 ]; then export MF_DW_ALT=$i; else unset MF_DW_ALT; fi
-  python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-host-fed 2>/dev/null | python -c "
+  python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-host-fed 2>/dev/null | python -c "
 import sys, json
 r = json.loads(sys.stdin.read().strip().splitlines()[-1])
 ks = {}

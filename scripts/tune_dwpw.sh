@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 N=${1:-15}
 for i in -1 $(seq 0 $((N-1))); do
   if [ $i -ge 0 ]; then export MF_DWPW_ALT=$i; else unset MF_DWPW_ALT; fi
-  python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-fed 2>/dev/null | python -c "
+  python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-host-fed 2>/dev/null | python -c "
 import sys, json
 r = json.loads(sys.stdin.read().strip().splitlines()[-1])
 ks = {k['kernel']: k['ms'] for k in r['kernels']}

@@ -7,7 +7,7 @@ VAR=$1; N=$2; shift 2
 for e in "$@"; do export "$e"; done
 for i in -1 $(seq 0 $((N-1))); do
   if [ $i -ge 0 ]; then export $VAR=$i; else unset $VAR; fi
-  timeout 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-fed 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-host-fed 2>/dev/null | python -c "
 import sys, json
 try:
     r = json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -49,3 +49,24 @@ def test_compact_line_survives_an_eight_gpu_record():
     rec, line = bench.compact_record(full)
     check_compact(rec, line)
     assert len(line) < 4096
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: int8 rows -> float32 .npy; above the size cap a seeded sample of the rows, in order, the same every run."""
+    import numpy as np
+    import torch
+    import bench
+    r = torch.arange(1000)
+    y = torch.zeros((1000, 8), dtype=torch.int8)
+    y[:, 0], y[:, 1] = (r % 256 - 128).to(torch.int8), (r // 256 - 128).to(torch.int8)  # row r is readable from its first two bytes
+    bench.dump_outputs(str(tmp_path / "all"), "output", y[:50])
+    a = np.load(tmp_path / "all" / "output.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, y[:50].numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 4 * 8 * 100)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), "output", y)
+    s1, s2 = np.load(tmp_path / "s1" / "output.npy"), np.load(tmp_path / "s2" / "output.npy")
+    assert s1.dtype == np.float32 and s1.shape == (100, 8) and np.array_equal(s1, s2)
+    rows = (s1[:, 0] + 128).astype(np.int64) + 256 * (s1[:, 1] + 128).astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and rows[-1] < 1000
+    assert np.array_equal(s1, y[torch.from_numpy(rows)].numpy().astype(np.float32))

@@ -22,7 +22,7 @@ def test_bench_ranks_share_one_device(O, per_gpu, world):
     """world = 8: what an 8-GPU run can fail at for host-side reasons -- eight concurrent model creations (each runs the
     device verifier of the single-fma epilogue), eight step queues on one device, rendezvous, gather, teardown, one line."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
-           "--batch", str(per_gpu), "--no-extra", "--no-cpu-baseline", "--no-host-fed", "--backend", "gloo", "--share-device"]
+           "--batch", str(per_gpu), "--full", "--no-extra", "--no-cpu-baseline", "--no-host-fed", "--backend", "gloo", "--share-device"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -106,7 +106,7 @@ def test_bench_single_rank_over_rccl(O):
     barrier-bracketed timed region, max over ranks, the checksum all_gather, teardown before the single-rank extras."""
     per_gpu = 64
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist", "--steps", "3", "--warmup", "1",
-           "--batch", str(per_gpu), "--no-extra", "--no-cpu-baseline", "--no-host-fed"]
+           "--batch", str(per_gpu), "--full", "--no-extra", "--no-cpu-baseline", "--no-host-fed"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -115,3 +115,25 @@ def test_bench_single_rank_over_rccl(O):
     om = O.Model(model_path("person_detect"))
     y = om.run_quantized_batch(synth_i8(3, 0, per_gpu, om.in_elems))
     assert rec["parity"]["output_checksums"] == ["%016x" % (int(layer_checksum(y)) & 0x7FFFFFFFFFFFFFFF)]
+
+
+def test_bench_plain_run_dumps_the_last_step(O, tmp_path):
+    """`bench.py` without --full: the headline fields alone (no roofline, parity or details file), and --dump-outputs writes
+    what the last timed step computed -- the oracle's outputs for the same slice of the synthetic stream, as float32."""
+    per_gpu = 64
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--batch", str(per_gpu), "--dump-outputs", str(tmp_path / "out")]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rec["metric"] == "inferences/sec (int8) for person_detect.tflite" and rec["unit"] == "inferences/s"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "i8" and rec["steps"] == 3 and rec["warmup"] == 1
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] - per_gpu / (rec["ms_per_step"] * 1e-3)) <= 1e-2 * rec["value"]
+    for k in ("roofline", "parity", "cpu_baseline", "kernels", "details"):
+        assert k not in rec, k
+    got = np.load(tmp_path / "out" / "output.npy")
+    om = O.Model(model_path("person_detect"))
+    want = om.run_quantized_batch(synth_i8(3, 0, per_gpu, om.in_elems)).reshape(per_gpu, -1)
+    assert got.dtype == np.float32 and got.shape == want.shape
+    assert np.array_equal(got, want.astype(np.float32))
