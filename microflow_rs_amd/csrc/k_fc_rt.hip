@@ -1,0 +1,441 @@
+// k_fc_rt.hip -- FullyConnected of ANY K and N on the int8 matrix pipe (microflow::ops::fully_connected,
+// src/ops/fully_connected.rs:24-82: const generics INPUT_ROWS x INPUT_COLS x WEIGHTS_COLS, any of them).
+//
+// The shape-specialised kernels take two corners of that space (fc_rowwave: N in {1, 2, 4, 8}, K % 16 == 0, K >= 256;
+// fc_mfma: N % 128 == 0, K % 128 == 0); every other shape with finite constants runs here instead of on the byte-wise
+// fc_generic.  The product is pw_rt_lds's (k_rt.hip): v_mfma_i32_16x16x64_i8 with the weights as operand A (16 output
+// columns x 64 k per tile and k step) and 16 rows of the batch as operand B.  What differs:
+//
+//   rows    : a step is R consecutive rows (a multiple of 16).  Their input is ONE contiguous byte range
+//             [r0 K, (r0 + R) K) of the batch, staged by LDS-DMA (dma16) from the 16-byte-aligned address below it; a lane
+//             builds its operand bytes from LDS at the row's byte offset (dword reads; + v_alignbyte when K % 4 != 0).
+//             Only the staged range is read from HBM: an odd K costs no extra bytes.  The last DMA piece of the batch
+//             reads at most 15 bytes past its end, inside the same 16-byte block (so inside the same page).
+//   k tail  : the k positions past K are zeroed in the OPERAND (per-lane byte masks on the last k step), never in
+//             memory, so neither the dot product nor the row sum sees them.
+//   N       : the host image pads N to 16-column tiles with zero weights; padded columns are computed and never stored.
+//   weights : a slice of NTS tiles (all of them when the padded image fits the LDS budget) stays resident for the
+//             whole launch; the grid is NSL slices x row-tile walkers, and each slice re-reads the rows (L2 / MALL).
+//   wzp     : the per-tensor weight zero point needs sum_k x[row][k]: one more MFMA per k step against a constant tile
+//             of ones (registers), formed inside the launch from the staged tile: no scratch, no pre-pass, no counters.
+//   output  : results go to an LDS patch; a single-slice step's R x N output bytes are one contiguous range and leave
+//             in 16-byte stores, with bytes at the two unaligned edges; nothing past row `rows` is ever written.
+//   work    : the 4 waves of a workgroup share the step's (16-row chunk, group of TB tiles) units.
+//   buffers : NBUF = 2 row buffers where they fit (the next step's DMA flies during this step's products), else 1.
+//
+// Epilogue: requant_pack4<MG, XR4> (k_common.hpp), modes 0 .. 2 as the host proved them for the operator's constants;
+// mode 0 converts the accumulator with v_cvt (round to nearest), which is fc_generic's (float)acc for every |acc|.
+#include "k_common.hpp"
+
+#include <algorithm>
+
+namespace mf {
+namespace k {
+
+template <int AL, int MG, uint32_t XR4>
+__global__ __launch_bounds__(256) void fc_rt(const int8_t *__restrict__ in, int8_t *__restrict__ out, FcRtArgs p, long long rows) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int K = p.K, N = p.N, KS = p.KS, R = p.R, TB = p.TB;
+    const int slice = blockIdx.x % p.NSL, walker = blockIdx.x / p.NSL, nwalk = gridDim.x / p.NSL;
+    const int nt0 = slice * p.NTS, nts = min(p.NTS, p.NT - nt0);
+    const int n0 = nt0 * 16, ns = min(nts * 16, N - n0); // this slice's output columns
+    uint8_t *W = lds, *PT = lds + p.poff;
+    const int col = lane & 15, g = lane >> 4;
+
+    // resident weights: the slice's tiles are one contiguous run of the image (whole 1 KiB pieces)
+    const int8_t *wsrc = (const int8_t *)p.wimg + (size_t)nt0 * KS * 1024;
+    for (int b = wave * 64; b < nts * KS * 64; b += 256) dma16(wsrc + (size_t)(b + lane) * 16, W + b * 16);
+
+    // the row tile t: bytes [a0, r1 K) of the batch, a0 = r0 K rounded down to 16
+    auto stage = [&](long long t, uint8_t *buf) {
+        const long long r0 = t * R, r1 = min(r0 + R, rows);
+        const long long a0 = (r0 * K) & ~15ll;
+        const int P = (int)((r1 * K - a0 + 15) >> 4);
+        for (int b = wave * 64; b < P; b += 256)
+            if (b + lane < P) dma16(in + a0 + (long long)(b + lane) * 16, buf + b * 16);
+    };
+    // operand bytes past K: masks of the last k step (lane group g holds k = 64 ks + 16 g .. + 15)
+    uint32_t km[4];
+    {
+        const int rem = K - (KS - 1) * 64 - g * 16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int nb = min(max(rem - 4 * i, 0), 4);
+            km[i] = nb >= 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u;
+        }
+    }
+    const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+    const long long ntiles = (rows + R - 1) / R;
+    const int CH = R / 16, ngr = (nts + TB - 1) / TB, units = CH * ngr;
+    int cur = 0;
+    if (walker < ntiles) stage(walker, lds + p.xoff);
+    for (long long t = walker; t < ntiles; t += nwalk) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's DMAs of the tile (and of the weights) have landed ...
+        wg_sync();                                       // ... and every other wave's
+        const uint8_t *xb = lds + p.xoff + cur * p.xbytes;
+        if (p.NBUF == 2 && t + nwalk < ntiles) stage(t + nwalk, lds + p.xoff + (cur ^ 1) * p.xbytes);
+        const long long r0 = t * R, r1 = min(r0 + R, rows);
+        const int tsh = (int)((r0 * K) & 15);            // row r0's offset in the buffer
+        const int osh = (int)(((uintptr_t)out + r0 * N) & 15); // the patch sits at the output's alignment (single slice)
+        for (int u = wave; u < units; u += 4) {
+            const int c = u % CH, grp = u / CH;
+            const int lt0 = grp * TB, tb = min(TB, nts - lt0);
+            const int rr = c * 16 + col;                 // this lane's row in the tile (operand B column)
+            const int base = tsh + rr * K + g * 16;
+            v4i acc[4], rsa = {0, 0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (i < tb) {
+                    const int4 kc = magic4<MG>(*(const int4 *)(p.Kc + n0 + (lt0 + i) * 16 + g * 4));
+                    acc[i] = v4i{kc.x, kc.y, kc.z, kc.w};
+                }
+            }
+            for (int ks = 0; ks < KS; ++ks) {
+                const int off = base + ks * 64;
+                v4i b;
+                if constexpr (AL == 4) {
+                    const uint32_t *q = (const uint32_t *)(xb + off);
+                    b = v4i{(int)q[0], (int)q[1], (int)q[2], (int)q[3]};
+                } else {
+                    const uint32_t *q = (const uint32_t *)(xb + (off & ~3));
+                    const uint32_t sh = off & 3, d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
+                    b = v4i{(int)__builtin_amdgcn_alignbyte(d1, d0, sh), (int)__builtin_amdgcn_alignbyte(d2, d1, sh),
+                            (int)__builtin_amdgcn_alignbyte(d3, d2, sh), (int)__builtin_amdgcn_alignbyte(d4, d3, sh)};
+                }
+                if (ks == KS - 1) b &= v4i{(int)km[0], (int)km[1], (int)km[2], (int)km[3]};
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (i < tb) acc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(*(const v4i *)(W + (((lt0 + i) * KS + ks) * 64 + lane) * 16), b, acc[i], 0, 0, 0);
+                if (p.wzp) rsa = __builtin_amdgcn_mfma_i32_16x16x64_i8(ones, b, rsa, 0, 0, 0); // every row: sum_k x[row][k]
+            }
+            const int wr = p.wzp * rsa[0];
+            const float4 S4 = {p.S, p.S, p.S, p.S};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (i < tb) {
+                    const int lc = (lt0 + i) * 16 + g * 4, ch = n0 + lc; // slice-local / global column of the lane's 4 results
+                    v4i a = acc[i];
+                    a[0] -= wr, a[1] -= wr, a[2] -= wr, a[3] -= wr;
+                    const float4 A4 = *(const float4 *)(p.A + ch);
+                    const uint32_t d = requant_pack4<MG, XR4>(a[0], a[1], a[2], a[3], A4, S4, p.lo_f, p.hi_f);
+                    if (p.NSL == 1) {
+                        uint8_t *dst = PT + osh + rr * N + ch;
+                        if ((N & 3) == 0) {
+                            if (ch < N) *(uint32_t *)dst = d;
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j)
+                                if (ch + j < N) dst[j] = (uint8_t)(d >> (8 * j));
+                        }
+                    } else {
+                        *(uint32_t *)(PT + rr * (p.NTS * 16) + lc) = d;
+                    }
+                }
+            }
+        }
+        wg_sync();                                       // the patch is complete; the row buffer is free
+        if (p.NBUF == 1 && t + nwalk < ntiles) stage(t + nwalk, lds + p.xoff);
+        const int nr = (int)(r1 - r0);
+        if (p.NSL == 1) {
+            // R x N contiguous output bytes [gs, ge): bytes up to the first 16-byte boundary, 16-byte stores, bytes after the last
+            int8_t *gs = out + r0 * N, *ge = gs + (long long)nr * N;
+            const uintptr_t ugs = (uintptr_t)gs, uge = (uintptr_t)ge;
+            const uintptr_t up = (ugs + 15) & ~(uintptr_t)15, dn = uge & ~(uintptr_t)15;
+            const uintptr_t hb = up < uge ? up : uge, te = dn > hb ? dn : hb;
+            const int nhead = (int)(hb - ugs), nbody = (int)((te - hb) >> 4), ntail = (int)(uge - te);
+            const uint8_t *src = PT + osh;               // src[i] is output byte gs + i
+            for (int i = tid; i < nbody; i += 256)
+                *(v4i *)(gs + nhead + i * 16) = *(const v4i *)(src + nhead + i * 16);
+            if (tid < nhead) gs[tid] = (int8_t)src[tid];
+            else if (tid >= 64 && tid < 64 + ntail) gs[nhead + nbody * 16 + (tid - 64)] = (int8_t)src[nhead + nbody * 16 + (tid - 64)];
+        } else {
+            // one slice: ns bytes of each row at column n0
+            const int pitch = p.NTS * 16;
+            if ((N & 3) == 0) {
+                const int n4 = ns >> 2;
+                for (int e = tid; e < nr * n4; e += 256) {
+                    const int r = e / n4, q = e - r * n4;
+                    *(uint32_t *)(out + (r0 + r) * N + n0 + q * 4) = *(const uint32_t *)(PT + r * pitch + q * 4);
+                }
+            } else {
+                for (int e = tid; e < nr * ns; e += 256) {
+                    const int r = e / ns, q = e - r * ns;
+                    out[(r0 + r) * N + n0 + q] = (int8_t)PT[r * pitch + q];
+                }
+            }
+        }
+        cur ^= p.NBUF - 1;
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+std::vector<int8_t> fc_rt_weight_image(const int8_t *w /*[N][K]*/, int K, int N) {
+    const int KS = (K + 63) / 64, NT = (N + 15) / 16;
+    std::vector<int8_t> img((size_t)NT * KS * 1024, 0);
+    for (int nt = 0; nt < NT; ++nt)
+        for (int ks = 0; ks < KS; ++ks)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int n = nt * 16 + (lane & 15), k0 = ks * 64 + (lane >> 4) * 16;
+                if (n >= N) continue;
+                int8_t *dst = &img[(((size_t)nt * KS + ks) * 64 + lane) * 16];
+                for (int i = 0; i < 16 && k0 + i < K; ++i) dst[i] = w[(size_t)n * K + k0 + i];
+            }
+    return img;
+}
+
+// Geometry: the widest N slice (most tiles resident) first; for it two row buffers if they fit, else one; rows per step
+// aimed at ~32 KiB of input per buffer, at least enough 16-row chunks to give each of the 4 waves a unit, at most 1024 rows
+// and 32 KiB of output patch; then as few rows as it takes to fit the LDS budget.
+bool fc_rt_plan(FcRtArgs &a, int K, int N) {
+    if (K < 1 || N < 1) return false;
+    const int KS = (K + 63) / 64, NT = (N + 15) / 16;
+    a.K = K, a.N = N, a.KS = KS, a.NT = NT;
+    auto xbytes = [&](int R) { return (int)(((long long)R * K + 112 + 15) & ~15ll); };
+    for (int NTS = NT; NTS >= 1; --NTS) {
+        const int NSL = (NT + NTS - 1) / NTS;
+        if (NSL > 1 && (NT + NSL - 1) / NSL != NTS) continue; // (the same slicing as a wider NTS: balanced slices only)
+        const long long W = (long long)NTS * KS * 1024;
+        const int pw = NSL == 1 ? N : NTS * 16;              // patch bytes per row
+        for (int NBUF = 2; NBUF >= 1; --NBUF) {
+            int R = std::max(32768 / K / 16 * 16, 16 * ((4 + NTS - 1) / NTS));
+            R = std::min(R, 1024);
+            while (R > 16 && (long long)R * pw > 32768) R -= 16;
+            for (; R >= 16; R -= 16) {
+                const long long patch = NSL == 1 ? (((long long)R * N + 32 + 15) & ~15ll) : (long long)R * pw;
+                const long long total = W + (long long)NBUF * xbytes(R) + patch;
+                if (total > FC_RT_LDS_MAX) continue;
+                int TB = std::min(4, NTS);
+                while (TB > 1 && (R / 16) * ((NTS + TB - 1) / TB) < 4) TB /= 2;
+                a.R = R, a.NTS = NTS, a.NSL = NSL, a.TB = TB, a.NBUF = NBUF;
+                a.xoff = (int)W, a.xbytes = xbytes(R), a.poff = (int)(W + (long long)NBUF * xbytes(R)), a.lds = (int)total;
+                return true;
+            }
+        }
+    }
+    return false;
+}
+
+template <int AL, int MG, uint32_t XR4>
+static void launch_fc_rt_t(const int8_t *in, int8_t *out, const FcRtArgs &a, long long rows, hipStream_t s) {
+    static LaunchState st[FC_RT_LDS_MAX / 1024 + 2]; // occupancy per (device, LDS KiB): asked once, never during a capture
+    const int per_cu = prepared(st[(a.lds + 1023) / 1024], fc_rt<AL, MG, XR4>, 256, a.lds);
+    // fewer rows per step than planned when the batch would otherwise give fewer than ~1024 steps (a small K plans up to 1024
+    // rows: 64 steps for 65 536 rows would leave most CUs idle); the planned LDS layout holds any smaller step
+    FcRtArgs b = a;
+    b.R = (int)std::min<long long>(a.R, std::max<long long>(16, rows / 1024 / 16 * 16));
+    const long long ntiles = (rows + b.R - 1) / b.R;
+    long long walkers = std::max(1LL, 256LL * per_cu / a.NSL); // persistent: the resident slice is staged once per workgroup
+    walkers = std::min(walkers, ntiles);
+    hipLaunchKernelGGL((fc_rt<AL, MG, XR4>), dim3((unsigned)(walkers * a.NSL)), dim3(256), a.lds, s, in, out, b, rows);
+}
+void launch_fc_rt(const int8_t *in, int8_t *out, const FcRtArgs &a, long long rows, hipStream_t s) {
+    if (rows <= 0) return;
+    if (a.K % 4 == 0) MF_DISPATCH4(a.magic, a.xr, launch_fc_rt_t, (in, out, a, rows, s), 4)
+    else MF_DISPATCH4(a.magic, a.xr, launch_fc_rt_t, (in, out, a, rows, s), 1)
+}
+
+// ------------------------------------------------------------------------
+// fc_chain -- L consecutive FullyConnected layers (+ a Softmax over one row) in one launch.  The structure is fc_rt's with one
+// N slice: every layer's whole image resident in LDS, the step's R input rows staged by LDS-DMA (from the 16-byte-aligned
+// ABSOLUTE address below them, so that no pointer needs any alignment), and then per layer: products over the source rows in LDS
+// -> the layer's own epilogue (requant_pack4, same bytes as its layer-wise launch) -> its int8 [R][N_l] tile in an LDS activation
+// buffer, which is the next layer's operand.  Only the first input and the last output touch HBM.
+// ------------------------------------------------------------------------
+template <int MG, uint32_t XR4>
+__device__ __forceinline__ void fc_chain_layer(const FcChainLayer &L, const uint8_t *src, uint8_t *dst, const uint8_t *W, int R, int wave,
+                                               int lane) {
+    const int K = L.K, N = L.N, KS = L.KS, TB = L.TB, nts = L.NT;
+    const int col = lane & 15, g = lane >> 4;
+    uint32_t km[4];
+    {
+        const int rem = K - (KS - 1) * 64 - g * 16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int nb = min(max(rem - 4 * i, 0), 4);
+            km[i] = nb >= 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u;
+        }
+    }
+    const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+    const int CH = R / 16, ngr = (nts + TB - 1) / TB, units = CH * ngr;
+    for (int u = wave; u < units; u += 4) {
+        const int c = u % CH, grp = u / CH;
+        const int lt0 = grp * TB, tb = min(TB, nts - lt0);
+        const int rr = c * 16 + col;
+        const int base = rr * K + g * 16;
+        v4i acc[4], rsa = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i < tb) {
+                const int4 kc = magic4<MG>(*(const int4 *)(L.Kc + (lt0 + i) * 16 + g * 4));
+                acc[i] = v4i{kc.x, kc.y, kc.z, kc.w};
+            }
+        }
+        for (int ks = 0; ks < KS; ++ks) {
+            const int off = base + ks * 64;
+            const uint32_t *q = (const uint32_t *)(src + (off & ~3));
+            const uint32_t sh = off & 3, d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
+            v4i b = v4i{(int)__builtin_amdgcn_alignbyte(d1, d0, sh), (int)__builtin_amdgcn_alignbyte(d2, d1, sh),
+                        (int)__builtin_amdgcn_alignbyte(d3, d2, sh), (int)__builtin_amdgcn_alignbyte(d4, d3, sh)};
+            if (ks == KS - 1) b &= v4i{(int)km[0], (int)km[1], (int)km[2], (int)km[3]};
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (i < tb) acc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(*(const v4i *)(W + (((lt0 + i) * KS + ks) * 64 + lane) * 16), b, acc[i], 0, 0, 0);
+            if (L.wzp) rsa = __builtin_amdgcn_mfma_i32_16x16x64_i8(ones, b, rsa, 0, 0, 0);
+        }
+        const int wr = L.wzp * rsa[0];
+        const float4 S4 = {L.S, L.S, L.S, L.S};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i < tb) {
+                const int ch = (lt0 + i) * 16 + g * 4;
+                v4i a = acc[i];
+                a[0] -= wr, a[1] -= wr, a[2] -= wr, a[3] -= wr;
+                const float4 A4 = *(const float4 *)(L.A + ch);
+                const uint32_t d = requant_pack4<MG, XR4>(a[0], a[1], a[2], a[3], A4, S4, L.lo_f, L.hi_f);
+                uint8_t *dp = dst + rr * N + ch;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (ch + j < N) dp[j] = (uint8_t)(d >> (8 * j));
+            }
+        }
+    }
+}
+
+template <int MG, uint32_t XR4>
+__global__ __launch_bounds__(256) void fc_chain(const int8_t *__restrict__ in, int8_t *__restrict__ out, FcChainArgs p, long long rows) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int R = p.R, L = p.L, K0 = p.l[0].K, NL = p.l[L - 1].N;
+    uint8_t *PT = lds + p.poff;
+    for (int l = 0; l < L; ++l) {
+        const int8_t *wsrc = (const int8_t *)p.l[l].wimg;
+        for (int b = wave * 64; b < p.l[l].NT * p.l[l].KS * 64; b += 256) dma16(wsrc + (size_t)(b + lane) * 16, lds + p.l[l].woff + b * 16);
+    }
+    const uintptr_t uin = (uintptr_t)in;
+    auto stage = [&](long long t, uint8_t *buf) {
+        const long long r0 = t * R, r1 = min(r0 + R, rows);
+        const uintptr_t a0 = (uin + r0 * K0) & ~(uintptr_t)15, e = uin + r1 * K0;
+        const int P = (int)((e - a0 + 15) >> 4);
+        for (int b = wave * 64; b < P; b += 256)
+            if (b + lane < P) dma16((const int8_t *)(a0 + (uintptr_t)(b + lane) * 16), buf + b * 16);
+    };
+    const long long ntiles = (rows + R - 1) / R;
+    int cur = 0;
+    if ((long long)blockIdx.x < ntiles) stage(blockIdx.x, lds + p.xoff);
+    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wg_sync();
+        const uint8_t *xb = lds + p.xoff + cur * p.xbytes;
+        if (p.NBUF == 2 && t + gridDim.x < ntiles) stage(t + gridDim.x, lds + p.xoff + (cur ^ 1) * p.xbytes);
+        const long long r0 = t * R, r1 = min(r0 + R, rows);
+        const int nr = (int)(r1 - r0);
+        const int tsh = (int)((uin + r0 * K0) & 15);
+        const int osh = (int)(((uintptr_t)out + r0 * NL) & 15);
+        const uint8_t *src = xb + tsh;
+        for (int l = 0; l < L; ++l) {
+            const bool last = l == L - 1;
+            uint8_t *dst = (last && !p.softmax) ? PT + osh : lds + p.aoff + (l & 1) * p.abytes;
+            fc_chain_layer<MG, XR4>(p.l[l], src, dst, lds + p.l[l].woff, R, wave, lane);
+            wg_sync();                                   // the layer's tile is complete: the next layer's operand
+            src = dst;
+        }
+        if (p.softmax) {
+            // microflow::ops::softmax over the N outputs of each row (softmax_table's arithmetic, k_generic.hip)
+            for (int r = tid; r < nr; r += 256) {
+                const int8_t *x = (const int8_t *)src + r * NL;
+                uint8_t *y = PT + osh + r * NL;
+                float sum = 0.0f;
+                for (int j = 0; j < NL; ++j) sum = __fadd_rn(sum, p.sm.exp_table[(int)x[j] + 128]);
+                for (int j = 0; j < NL; ++j) {
+                    const float ev = p.sm.exp_table[(int)x[j] + 128];
+                    const float prob = __fdiv_rn(ev, sum);
+                    const float q = __fadd_rn(__fdiv_rn(prob, p.sm.oscale), p.sm.ozp_f);
+                    const float rq = __fadd_rn(q, __builtin_copysignf(0x1.fffffep-2f, q));
+                    const int qi = (rq != rq) ? 0 : (int)__builtin_amdgcn_fmed3f(rq, p.sm.sat_lo, p.sm.sat_hi);
+                    y[j] = (uint8_t)(qi ^ p.sm.xr);
+                }
+            }
+            wg_sync();
+        }
+        if (p.NBUF == 1 && t + gridDim.x < ntiles) stage(t + gridDim.x, lds + p.xoff);
+        int8_t *gs = out + r0 * NL, *ge = gs + (long long)nr * NL;
+        const uintptr_t ugs = (uintptr_t)gs, uge = (uintptr_t)ge;
+        const uintptr_t up = (ugs + 15) & ~(uintptr_t)15, dn = uge & ~(uintptr_t)15;
+        const uintptr_t hb = up < uge ? up : uge, te = dn > hb ? dn : hb;
+        const int nhead = (int)(hb - ugs), nbody = (int)((te - hb) >> 4), ntail = (int)(uge - te);
+        const uint8_t *po = PT + osh;
+        for (int i = tid; i < nbody; i += 256)
+            *(v4i *)(gs + nhead + i * 16) = *(const v4i *)(po + nhead + i * 16);
+        if (tid < nhead) gs[tid] = (int8_t)po[tid];
+        else if (tid >= 64 && tid < 64 + ntail) gs[nhead + nbody * 16 + (tid - 64)] = (int8_t)po[nhead + nbody * 16 + (tid - 64)];
+        cur ^= p.NBUF - 1;
+    }
+}
+
+bool fc_chain_plan(FcChainArgs &a) {
+    if (a.L < 2 || a.L > FC_CHAIN_MAX) return false;
+    long long W = 0;
+    int nmax = 0;                                    // widest tensor kept in an activation buffer
+    for (int l = 0; l < a.L; ++l) {
+        FcChainLayer &y = a.l[l];
+        y.KS = (y.K + 63) / 64, y.NT = (y.N + 15) / 16;
+        if (l > 0 && y.K != a.l[l - 1].N) return false;
+        y.woff = (int)W;
+        W += (long long)y.NT * y.KS * 1024;
+        if (l < a.L - 1 || a.softmax) nmax = std::max(nmax, y.N);
+    }
+    const int K0 = a.l[0].K, NL = a.l[a.L - 1].N;
+    auto rb = [](long long bytes) { return (int)((bytes + 112 + 15) & ~15ll); }; // (+ the over-read of a 16-byte operand piece)
+    // rows per step as fc_rt aims them (~32 KiB of input, >= 64 rows, <= 32 KiB per activation tile).  A chain whose weights leave
+    // room for fewer rows than that is not formed: with fewer bytes in flight it was slower than its layers' own launches (784 ->
+    // 128 -> 10 at 16 rows per step: 0.140 against 0.066 ms at 65 536 rows), so those layers keep their launches.
+    int R0 = std::min(std::max(32768 / K0 / 16 * 16, 64), 1024);
+    while (R0 > 16 && ((long long)R0 * std::max(nmax, NL) > 32768)) R0 -= 16;
+    for (int NBUF = 2; NBUF >= 1; --NBUF) {
+        {
+            const int R = R0;
+            const long long total = W + (long long)NBUF * rb((long long)R * K0) + 2LL * rb((long long)R * nmax) + (((long long)R * NL + 32 + 15) & ~15ll);
+            if (total > FC_RT_LDS_MAX) continue;
+            a.R = R, a.NBUF = NBUF;
+            a.xoff = (int)W, a.xbytes = rb((long long)R * K0);
+            a.aoff = a.xoff + NBUF * a.xbytes, a.abytes = rb((long long)R * nmax);
+            a.poff = a.aoff + 2 * a.abytes, a.lds = (int)total;
+            for (int l = 0; l < a.L; ++l) {
+                FcChainLayer &y = a.l[l];
+                y.TB = std::min(4, y.NT);
+                while (y.TB > 1 && (R / 16) * ((y.NT + y.TB - 1) / y.TB) < 4) y.TB /= 2;
+            }
+            return true;
+        }
+    }
+    return false;
+}
+
+template <int MG, uint32_t XR4>
+static void launch_fc_chain_t(const int8_t *in, int8_t *out, const FcChainArgs &a, long long rows, hipStream_t s) {
+    static LaunchState st[FC_RT_LDS_MAX / 1024 + 2];
+    const int per_cu = prepared(st[(a.lds + 1023) / 1024], fc_chain<MG, XR4>, 256, a.lds);
+    FcChainArgs b = a;
+    b.R = (int)std::min<long long>(a.R, std::max<long long>(16, rows / 1024 / 16 * 16)); // (as launch_fc_rt_t)
+    const long long ntiles = (rows + b.R - 1) / b.R;
+    const long long grid = std::min(ntiles, 256LL * per_cu);
+    hipLaunchKernelGGL((fc_chain<MG, XR4>), dim3((unsigned)grid), dim3(256), a.lds, s, in, out, b, rows);
+}
+void launch_fc_chain(const int8_t *in, int8_t *out, const FcChainArgs &a, long long rows, hipStream_t s) {
+    if (rows <= 0) return;
+    if (a.xr) {
+        if (a.magic == 2) launch_fc_chain_t<2, 0x80808080u>(in, out, a, rows, s);
+        else if (a.magic) launch_fc_chain_t<1, 0x80808080u>(in, out, a, rows, s);
+        else launch_fc_chain_t<0, 0x80808080u>(in, out, a, rows, s);
+    } else {
+        if (a.magic == 2) launch_fc_chain_t<2, 0u>(in, out, a, rows, s);
+        else if (a.magic) launch_fc_chain_t<1, 0u>(in, out, a, rows, s);
+        else launch_fc_chain_t<0, 0u>(in, out, a, rows, s);
+    }
+}
+
+} // namespace k
+} // namespace mf

@@ -581,6 +581,53 @@ void launch_fc_mfma(const int8_t *in, int8_t *out, const FcGemmArgs &a, hipStrea
 bool fc_mfma_rowsum_prepass();
 bool fc_mfma_rowsum_prologue(size_t rows, int N); // the in-launch row sums (fc_mfma<..., RSP>) take this shape
 bool fc_mfma_rowsum_prologue(size_t rows, int N); // the RSP instance takes this shape (256 x 256 tiles, tile columns dividing 256) // true (default): fc_rowsum runs in front of the GEMM; MF_FC_ROWSUM_FOLD=1: the GEMM forms the sums itself
+// FullyConnected of any K and N on the int8 matrix pipe (k_fc_rt.hip).  The weight image ([tile][k step][lane] x 16 bytes,
+// zero beyond K and N) and the launch geometry come from the host (fc_rt_plan); the kernel keeps a slice of NTS 16-column
+// tiles resident in LDS and streams the rows through LDS by LDS-DMA.
+struct FcRtArgs {
+    const void *wimg;   // [NT][KS][64 lanes][16 bytes]: operand A of v_mfma_i32_16x16x64_i8, zero beyond K and N
+    const float *A;     // [NT * 16], zero beyond N
+    const int *Kc;      // [NT * 16], zero beyond N
+    float S, lo_f, hi_f;
+    int K, N, KS, NT;   // KS = ceil(K / 64), NT = ceil(N / 16)
+    int wzp;            // weight zero point (i8 domain); 0: no row-sum term
+    int R;              // rows per step (a multiple of 16)
+    int NTS, NSL, TB;   // tiles per N slice, slices, tiles per wave work unit (1, 2, 4)
+    int NBUF;           // row-tile buffers (2: the next tile's DMA flies during this tile's products)
+    int xoff, xbytes, poff, lds; // LDS plan: row buffers at xoff (xbytes each), output patch at poff, total bytes
+    int magic, xr;
+};
+// the LDS budget of fc_rt; a shape whose single 16-column slice does not fit with one 16-row buffer is not supported
+constexpr int FC_RT_LDS_MAX = 160 * 1024 - 1024;
+bool fc_rt_plan(FcRtArgs &a, int K, int N); // fills the geometry fields; false: the shape is beyond the budget
+std::vector<int8_t> fc_rt_weight_image(const int8_t *w /*[N][K]*/, int K, int N);
+void launch_fc_rt(const int8_t *in, int8_t *out, const FcRtArgs &a, long long rows, hipStream_t s);
+// Consecutive FullyConnected layers (+ a Softmax over one row) in one launch (k_fc_rt.hip: fc_chain).  Every layer's weight image
+// (its fc_rt image, all tiles) stays resident in LDS; the int8 tensors between the layers never leave LDS.
+constexpr int FC_CHAIN_MAX = 8;
+struct FcChainLayer {
+    const void *wimg;   // the layer's fc_rt image [NT][KS][64][16]
+    const float *A;     // [NT * 16]
+    const int *Kc;      // [NT * 16]
+    float S, lo_f, hi_f;
+    int K, N, KS, NT, wzp, TB;
+    int woff;           // LDS offset of the image
+};
+struct FcChainArgs {
+    FcChainLayer l[FC_CHAIN_MAX];
+    int L;              // layers (2 .. FC_CHAIN_MAX)
+    int R, NBUF;        // rows per step, input row buffers
+    int xoff, xbytes;   // input row buffers
+    int aoff, abytes;   // two activation buffers [R][N_l] (pitch N_l) at aoff, aoff + abytes
+    int poff, lds;      // output patch, total LDS bytes
+    int softmax;        // 1: a Softmax over the last layer's N outputs follows (one row per inference)
+    SoftmaxArgs sm;
+    int magic, xr;      // epilogue mode of the launch (the layers' minimum), element type
+};
+// fills the geometry of a chain whose layers' K, N, S, ... are set in a.l[0 .. L-1]; false: it does not fit the LDS budget
+bool fc_chain_plan(FcChainArgs &a);
+void launch_fc_chain(const int8_t *in, int8_t *out, const FcChainArgs &a, long long rows, hipStream_t s);
+
 void launch_softmax(const int8_t *in, int8_t *out, const SoftmaxArgs &a, size_t batch, hipStream_t s);
 // number of float bit patterns (of all 2^32) whose quantised byte differs between quant_div's fast form and the true
 // division, for these parameters; synchronises the stream

@@ -148,6 +148,9 @@ FusedImpl *fused_create(OpImpl *dw, OpImpl *pw);
 FusedImpl *fused_tail_create(OpImpl *pool, OpImpl *conv, OpImpl *softmax);
 // fused FullyConnected (row-wave kernel, one row per inference) -> Softmax over its outputs
 FusedImpl *fused_fc_softmax_create(OpImpl *fc, OpImpl *softmax);
+// consecutive FullyConnected operators (+ a Softmax over one row: sm, or nullptr) as one fc_chain launch (k_fc_rt.hip)
+bool fused_fc_chain_fits(OpImpl *const *fcs, int n, OpImpl *sm);
+FusedImpl *fused_fc_chain_create(OpImpl *const *fcs, int n, OpImpl *sm);
 // a run of identical depthwise + pointwise pair groups as one persistent kernel (borrows their device buffers:
 // destroy it before them); nullptr when no stage kernel exists for the shape / count
 FusedImpl *fused_stage_create(FusedImpl *const *pairs, int npairs);

@@ -345,6 +345,54 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             if (j < n && fused[j] && !covered(j))
                 if (FusedImpl *f = fused_dwfc_create(ops[i], fused[j])) sg.v.push_back({f, (int)i, fused_last[j]});
         }
+        // (6) runs of consecutive FullyConnected operators (Reshapes between them keeping the [M][N] rows; + a Softmax over one row at
+        // the end) that no group above took -> fc_chain launches (k_fc_rt.hip), cut greedily into the longest chains whose weights fit
+        // the LDS budget; a layer that fits no chain keeps its own launch
+        auto owned = [&](size_t i) {
+            for (size_t j = 0; j < i; ++j)
+                if (fused[j] && fused_last[j] >= (int)i) return true;
+            return false;
+        };
+        auto free_fc = [&](size_t i) {
+            return i < n && ops[i] && m->pm.ops[i].kind == MF_OP_FULLY_CONNECTED && !fused[i] && !covered(i) && !owned(i);
+        };
+        for (size_t i = 0; i < n; ++i) {
+            if (!free_fc(i)) continue;
+            std::vector<size_t> idx{i};
+            for (;;) {
+                size_t j = idx.back() + 1;
+                while (j < n && m->pm.ops[j].kind == MF_OP_RESHAPE) ++j;
+                if (!free_fc(j) || m->pm.ops[j].M != m->pm.ops[idx.back()].M || m->pm.ops[j].K != m->pm.ops[idx.back()].N) break;
+                idx.push_back(j);
+            }
+            size_t smi = idx.back() + 1;
+            while (smi < n && m->pm.ops[smi].kind == MF_OP_RESHAPE) ++smi;
+            OpImpl *sm = (smi < n && ops[smi] && m->pm.ops[smi].kind == MF_OP_SOFTMAX && !fused[smi] && !covered(smi) && !owned(smi)) ? ops[smi] : nullptr;
+            std::vector<OpImpl *> run;
+            for (size_t j : idx) run.push_back(ops[j]);
+            size_t pos = 0;
+            while (pos < run.size()) {
+                int best = 0;
+                bool best_sm = false;
+                for (size_t len = 2; pos + len <= run.size(); ++len) {
+                    const bool end = pos + len == run.size();
+                    if (fused_fc_chain_fits(run.data() + pos, (int)len, end ? sm : nullptr)) {
+                        best = (int)len, best_sm = end && sm;
+                    } else {
+                        if (end && sm && fused_fc_chain_fits(run.data() + pos, (int)len, nullptr)) best = (int)len, best_sm = false;
+                        break;
+                    }
+                }
+                if (best >= 2) {
+                    if (FusedImpl *f = fused_fc_chain_create(run.data() + pos, best, best_sm ? sm : nullptr))
+                        sg.v.push_back({f, (int)idx[pos], (int)(best_sm ? smi : idx[pos + (size_t)best - 1])});
+                    pos += (size_t)best;
+                } else {
+                    ++pos;
+                }
+            }
+            i = idx.back();
+        }
         // commit (nothing below throws)
         m->stages.swap(sg.v);
         m->device = device;

@@ -89,7 +89,7 @@ struct OpImpl {
     bool accepts_f32 = false;  // op_set_input_quant succeeded: op_run_f32 may replace quantize + op_run
     bool finite_consts = true; // A / S all finite (the shape-specialised and fused epilogues assume it)
     std::string generic_name, fast_name;
-    enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM } fast = NONE;
+    enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM, FC_RT } fast = NONE;
     int *d_rowsum = nullptr; // FC_MFMA with wzp != 0: per-row input sums
     size_t rowsum_cap = 0, rowsum_rows = 0; // (ints allocated; the row count the counter pairs currently sit behind)
     int8_t *d_ext = nullptr; // op_run_external on a u8 operator: input moved to the i8 domain
@@ -141,6 +141,9 @@ struct OpImpl {
     // run-time-geometry kernels (k_rt.hip): shapes outside the tables of kernels.hpp
     k::DwRtArgs dwrt{};
     k::PwRtArgs pwrt{};
+    k::FcRtArgs fcrt{};    // FullyConnected on the matrix pipe, any K and N (k_fc_rt.hip)
+    bool fcrt_ok = false;  // ... its image and constants exist (also where the operator alone stays on fc_generic)
+    DevBuf d_fcw, d_fcA, d_fcKc; // ... its weight image and constants padded to 16-column tiles
     k::ConvRowsArgs crows{};
     k::ConvMmArgs cmm{};
     DevBuf d_tap;          // conv_mm_rt: tap offset table
@@ -899,6 +902,41 @@ OpImpl *op_create(int device, const OpSpec &spec) {
             op->fast = OpImpl::FC_MFMA;
             op->fast_name = "fc_mfma";
         }
+        if (finite && op->fast == OpImpl::NONE && k::fc_rt_plan(op->fcrt, s.K, s.N)) {
+            // every other shape: the int8 matrix pipe with the (sliced) weight image resident in LDS.  The image and constants are
+            // built for every such operator: a fused FullyConnected chain (fc_chain) takes them from its members.
+            k::FcRtArgs &f = op->fcrt;
+            const std::vector<int8_t> img = k::fc_rt_weight_image(s.weights, s.K, s.N);
+            std::vector<float> pA((size_t)f.NT * 16, 0.0f);
+            std::vector<int32_t> pK((size_t)f.NT * 16, 0);
+            // epilogue mode (k_common.hpp): |acc| <= 128 sum_k |w - wzp| + |Kc| in the i8 domain, exactly, over every input
+            int64_t bound = 0;
+            double xmax = 0.0;
+            for (int j = 0; j < s.N; ++j) {
+                int64_t b = std::abs((int64_t)Kc[(size_t)j]);
+                for (int k = 0; k < s.K; ++k) b += 128 * std::abs((int64_t)s.weights[(size_t)j * s.K + k] - a.wzp);
+                bound = std::max(bound, b);
+                xmax = std::max(xmax, std::fabs((double)A[(size_t)j]) + std::fabs((double)a.S) * (double)b);
+                pA[(size_t)j] = A[(size_t)j], pK[(size_t)j] = Kc[(size_t)j];
+            }
+            int magic = !switches().no_magic && bound < (1 << 22) ? 1 : 0;
+            if (magic && !switches().no_sat_pack && lo == (s.u8 ? 0 : -128) && hi == (s.u8 ? 255 : 127) && xmax < 30000.0) magic = 2;
+            if (switches().debug_epi)
+                fprintf(stderr, "[epi] fully_connected %dx%d -> %d: |acc| <= %lld -> mode %d\n", s.M, s.K, s.N, (long long)bound, magic);
+            op->d_fcw.upload(img.data(), img.size());
+            op->d_fcA.upload(pA.data(), pA.size() * 4);
+            op->d_fcKc.upload(pK.data(), pK.size() * 4);
+            f.wimg = op->d_fcw.p, f.A = op->d_fcA.as<float>(), f.Kc = op->d_fcKc.as<int>();
+            f.S = a.S, f.lo_f = a.lo_f, f.hi_f = a.hi_f, f.wzp = a.wzp, f.magic = magic, f.xr = xr;
+            op->fcrt_ok = true;
+            // (At most one 16 x 16 weight tile of work per row -- sine.tflite's 1 -> 16 -> 16 -> 1 -- stays on fc_generic when it
+            // runs alone, which moves the same bytes without the staging latency: fc_rt was 11 % slower on sine at 65 536 rows,
+            // scripts/time_fc_rt.py.  In a chain those layers run inside fc_chain.)
+            if ((long long)s.K * s.N > 256 && !switches().no_fc_rt) {
+                op->fast = OpImpl::FC_RT;
+                op->fast_name = a.wzp ? "fc_rt<wzp>" : "fc_rt";
+            }
+        }
         break;
     }
     case MF_OP_SOFTMAX: {
@@ -1037,6 +1075,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
         case OpImpl::FC_ROWWAVE:
             done = k::launch_fc_rowwave(d_in, d_out, op->fc, batch * sp.M, s);
             break;
+        case OpImpl::FC_RT:
+            k::launch_fc_rt(d_in, d_out, op->fcrt, (long long)(batch * sp.M), s);
+            done = true;
+            break;
         case OpImpl::FC_MFMA: {
             const size_t rows = batch * sp.M;
             if (!k::fc_mfma_supported(rows, sp.N, sp.K)) break; // fewer than 64 rows: generic kernel
@@ -1164,7 +1206,7 @@ void op_run_f32(OpImpl *op, const float *d_in, size_t batch, int8_t *d_out, void
 }
 
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN } kind;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN } kind;
     OpImpl *a, *b, *c;
     k::DwPwArgs dwpw;
     k::TailArgs tail;
@@ -1187,6 +1229,9 @@ struct FusedImpl {
     // CHAIN: 1 .. CHAIN_MAX consecutive pairs of any geometry in one launch (k_chain.hip); table and weights in stage_w
     k::ChainArgs chain{};
     std::vector<std::pair<OpImpl *, OpImpl *>> chain_members;
+    // FCCHAIN: consecutive FullyConnected layers (+ Softmax) in one launch (k_fc_rt.hip fc_chain); the layers' fc_rt images
+    k::FcChainArgs fcchain{};
+    long long fcchain_M = 1; // rows per inference
     int epi_mode = -1; // epilogue mode (k_common.hpp) of the launch's requantising operators; -1: not recorded (the operators' minimum)
 };
 // the pair's argument blocks as the operators hold them (two-rounding constants), and switched to the single-fma form when
@@ -1675,6 +1720,44 @@ FusedImpl *fused_fc_softmax_create(OpImpl *fc, OpImpl *sm) {
     return new FusedImpl{FusedImpl::FCSM, fc, sm, nullptr, {}, {}, "fc_rowwave_softmax<" + std::to_string(fc->s.N) + ">"};
 }
 
+// Consecutive FullyConnected operators (each reading the previous one's [M][N] output) + optionally a Softmax over one row, as
+// one fc_chain launch; nullptr when a member has no fc_rt image or the layers' images and tiles do not fit the LDS budget
+static bool fc_chain_args(OpImpl *const *fcs, int n, OpImpl *sm, k::FcChainArgs &a) {
+    if (switches().no_fc_chain || n < 2 || n > k::FC_CHAIN_MAX) return false;
+    a = k::FcChainArgs{};
+    a.L = n;
+    int mode = 3;
+    for (int l = 0; l < n; ++l) {
+        const OpImpl *o = fcs[l];
+        if (!o || o->s.kind != MF_OP_FULLY_CONNECTED || !o->fcrt_ok || o->s.M != fcs[0]->s.M || o->s.u8 != fcs[0]->s.u8 ||
+            o->device != fcs[0]->device)
+            return false;
+        const k::FcRtArgs &f = o->fcrt;
+        k::FcChainLayer &y = a.l[l];
+        y.wimg = f.wimg, y.A = f.A, y.Kc = f.Kc, y.S = f.S, y.lo_f = f.lo_f, y.hi_f = f.hi_f, y.K = f.K, y.N = f.N, y.wzp = f.wzp;
+        mode = std::min(mode, f.magic);
+    }
+    if (sm) {
+        if (sm->s.kind != MF_OP_SOFTMAX || fcs[0]->s.M != 1 || sm->s.M != 1 || sm->s.N != fcs[n - 1]->s.N || sm->s.u8 != fcs[0]->s.u8 ||
+            sm->device != fcs[0]->device)
+            return false;
+        a.softmax = 1, a.sm = sm->sm;
+    }
+    a.magic = mode, a.xr = fcs[0]->fcrt.xr;
+    return k::fc_chain_plan(a);
+}
+bool fused_fc_chain_fits(OpImpl *const *fcs, int n, OpImpl *sm) {
+    k::FcChainArgs a;
+    return fc_chain_args(fcs, n, sm, a);
+}
+FusedImpl *fused_fc_chain_create(OpImpl *const *fcs, int n, OpImpl *sm) {
+    k::FcChainArgs a;
+    if (!fc_chain_args(fcs, n, sm, a)) return nullptr;
+    FusedImpl *f = new FusedImpl{FusedImpl::FCCHAIN, fcs[0], fcs[n - 1], sm, {}, {}, "fc_chain<" + std::to_string(n) + (sm ? ">+sm" : ">")};
+    f->fcchain = a, f->fcchain_M = fcs[0]->s.M, f->epi_mode = a.magic;
+    return f;
+}
+
 // Pointwise weights [N][K] as operands A of v_mfma_i32_16x16x64_i8 for the stage kernel: [tile][k-step][lane][16 B],
 // row r = lane & 15 of tile tt is output channel 16 tt + r, K-bytes 64 ks + 16 (lane >> 4) .. + 15
 static std::vector<int8_t> build_pw_plain_weights(const int8_t *w, int K, int N) {
@@ -2073,6 +2156,11 @@ void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, vo
     }
     if (f->kind == FusedImpl::DWFC) {
         if (batch) k::launch_dwfc(d_in, d_out, f->dwfc, batch, (hipStream_t)stream);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (f->kind == FusedImpl::FCCHAIN) { // (no pointer alignment needed: fc_chain aligns its DMA and stores itself)
+        k::launch_fc_chain(d_in, d_out, f->fcchain, (long long)(batch * f->fcchain_M), (hipStream_t)stream);
         MF_HIP(hipGetLastError());
         return;
     }

@@ -24,6 +24,8 @@ Switches switches_parse() {
     s.chain_no_sp = env_set("MF_CHAIN_NO_SP");
     s.no_stage = env_set("MF_NO_STAGE");
     s.no_dwfc = env_set("MF_NO_DWFC");
+    s.no_fc_rt = env_set("MF_NO_FC_RT");
+    s.no_fc_chain = env_set("MF_NO_FC_CHAIN");
     s.no_pairtail = env_set("MF_NO_PAIRTAIL");
     s.no_quad = env_set("MF_NO_QUAD");
     s.no_pair_front = env_set("MF_NO_PAIR_FRONT");

@@ -210,6 +210,32 @@ def speech_like(rng, elem=INT8, fc_wzp=0, per_channel=True, act="relu"):
     return build_model((1, 1960), in_q, layers, elem)
 
 
+def mlp(rng, sizes, elem=INT8, wzp_nonzero=False, softmax=False, act="relu"):
+    """A FullyConnected-only network: sizes = (K, N1, N2, ...) gives the layers K -> N1 -> N2 ...; every hidden layer has
+    the activation `act`, the last one none, optionally followed by a Softmax.  Per-tensor weight quantization (what
+    FullyConnected has), random scales and zero points; wzp_nonzero gives every layer a weight zero point off the middle."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    in_q, layers = q, []
+    for i in range(len(sizes) - 1):
+        K, N = int(sizes[i]), int(sizes[i + 1])
+        last = i == len(sizes) - 2
+        a = "none" if last else act
+        wsc = np.float32(rng.uniform(0.002, 0.02))
+        wzp = mid + (int(rng.integers(-20, 21)) or 7 if wzp_nonzero else 0)
+        # output scale chosen so that the layer's outputs spread over the int8 range instead of saturating
+        osc = float(np.float32(q[0] * wsc * 120.0 * np.sqrt(K)))
+        ozp = lo if a in ("relu", "relu6") else int(rng.integers(lo + 20, hi - 20))
+        layers.append(dict(op="fully_connected", weights=rng.integers(lo, hi, (N, K)), wscale=[wsc], wzp=[wzp],
+                           bias=rng.integers(-2000, 2000, N), bscale=[np.float32(q[0]) * wsc], bzp=[0], act=a,
+                           out_shape=(1, N), out_q=(osc, ozp)))
+        q = (osc, ozp)
+    if softmax:
+        layers.append(dict(op="softmax", out_shape=(1, int(sizes[-1])), out_q=(1.0 / 256.0, lo)))
+    return build_model((1, int(sizes[0])), in_q, layers, elem)
+
+
 def person_detect_like(rng, side=96, width=1.0, elem=INT8, wzp_nonzero=False, n_stage=5, classes=2, wmax=None):
     """The layer structure of person_detect.tflite (MobileNet-v1 0.25, grey input: a one-channel 3x3 stride-2 stem, then
     depthwise 3x3 + 1x1 pairs with strides 1 2 1 2 1 2 [1 x n_stage] 2 1, AveragePool2D over what is left, a 1x1 head,
