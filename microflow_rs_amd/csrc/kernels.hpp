@@ -602,6 +602,32 @@ constexpr int FC_RT_LDS_MAX = 160 * 1024 - 1024;
 bool fc_rt_plan(FcRtArgs &a, int K, int N); // fills the geometry fields; false: the shape is beyond the budget
 std::vector<int8_t> fc_rt_weight_image(const int8_t *w /*[N][K]*/, int K, int N);
 void launch_fc_rt(const int8_t *in, int8_t *out, const FcRtArgs &a, long long rows, hipStream_t s);
+// Conv2D of any C and N outside the other Conv2D kernels, (W C) % 4 == 0, as an MFMA product over K' = KH * KWCP with KWCP = KW C
+// rounded up to 16 (k_conv_gemm.hip: conv_gemm_rt); the weights in fc_rt's image, sliced by N across workgroups when they are large
+struct ConvGemmArgs {
+    int H, W, C, N, KH, KW, sh, sw, OH, OW;
+    int padl, padt;      // SAME: (KW - 1) / 2, (KH - 1) / 2 (src/tensor.rs:193); VALID: 0
+    int KWCP, KS, NT;    // padded filter row, 64-deep k steps over K', 16-column tiles over N
+    int NTS, NSL, TB;    // tiles per N slice (resident in LDS), slices, tiles per block (<= 4)
+    int LP, ROW, RB, TILE, G, BH, NBANDS; // image tile geometry as ConvMmArgs
+    int xoff, toff, moff, lds; // LDS plan: image tiles, tap table [KS][4], masks [KS][4][16 bytes] (filter zero points), total
+    uint32_t izp4;
+    float lo_f, hi_f;
+    const void *wimg;    // fc_rt_weight_image of the padded [N][K'] matrix: [NT][KS][64 lanes][16 bytes]
+    const int *tap;      // [KS][4]: byte offset, from a pixel's window start, of the 16 bytes lane group g supplies in k step ks
+    const uint32_t *kmask; // [KS][4][4]: bytes of those 16 that are real taps (the window sum for filter zero points)
+    const float *A;      // [NT * 16], zero beyond N
+    const float *S;      // [NT * 16]
+    const int *Kc;       // [NT * 16]
+    const int *wzp;      // [NT * 16]
+    int magic, xr;
+};
+constexpr int CONV_GEMM_LDS_MAX = 160 * 1024 - 1024;
+constexpr int CONV_GEMM_KS_MAX = 128; // K' <= 8192: one resident 16-column tile is at most 128 KiB
+bool conv_gemm_plan(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uint32_t> &mask, int H, int W, int C, int N, int KH, int KW, int sh,
+                    int sw, int OH, int OW, bool pad_same, bool wz); // false: beyond the limits
+std::vector<int8_t> conv_gemm_weight_image(const int8_t *w /*[N][KH][KW][C]*/, const ConvGemmArgs &a);
+void launch_conv_gemm(const int8_t *in, int8_t *out, const ConvGemmArgs &a, bool wz, int batch, hipStream_t s);
 // Consecutive FullyConnected layers (+ a Softmax over one row) in one launch (k_fc_rt.hip: fc_chain).  Every layer's weight image
 // (its fc_rt image, all tiles) stays resident in LDS; the int8 tensors between the layers never leave LDS.
 constexpr int FC_CHAIN_MAX = 8;

@@ -89,7 +89,8 @@ struct OpImpl {
     bool accepts_f32 = false;  // op_set_input_quant succeeded: op_run_f32 may replace quantize + op_run
     bool finite_consts = true; // A / S all finite (the shape-specialised and fused epilogues assume it)
     std::string generic_name, fast_name;
-    enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM, FC_RT } fast = NONE;
+    enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM, FC_RT,
+                CONV_GEMM } fast = NONE;
     int *d_rowsum = nullptr; // FC_MFMA with wzp != 0: per-row input sums
     size_t rowsum_cap = 0, rowsum_rows = 0; // (ints allocated; the row count the counter pairs currently sit behind)
     int8_t *d_ext = nullptr; // op_run_external on a u8 operator: input moved to the i8 domain
@@ -147,6 +148,8 @@ struct OpImpl {
     k::ConvRowsArgs crows{};
     k::ConvMmArgs cmm{};
     DevBuf d_tap;          // conv_mm_rt: tap offset table
+    k::ConvGemmArgs cgm{}; // Conv2D of any C and N on the matrix pipe (k_conv_gemm.hip); tap table in d_tap, image in d_fcw,
+    DevBuf d_cgm_mask;     // ... constants padded to 16-column tiles in d_rtA, d_rtS, d_rtKc, d_rtwzp; window-sum byte masks
     DevBuf d_crw, d_crm;   // conv_rows_lds: packed weights, tap masks
     bool rt_wz = false;    // non-zero weight zero points
     int magic_mode = 0;    // conv-like operators: epilogue mode the host proved usable (k_common.hpp: 0, 1 or 2)
@@ -825,6 +828,38 @@ OpImpl *op_create(int device, const OpSpec &spec) {
         }
         if (op->fast == OpImpl::NONE && !dw && k::conv1x1_rowwave_supported(a)) // few outputs: one wavefront per pixel
             op->fast = OpImpl::CONV1X1_ROW, op->fast_name = "conv1x1_rowwave";
+        // every other Conv2D with whole-dword image rows: the MFMA product over K' = KH x (KW C rounded up to 16), the weights
+        // resident in LDS in N slices (k_conv_gemm.hip)
+        if (op->fast == OpImpl::NONE && !no_rt && !switches().no_conv_gemm && op->finite_consts && !dw) {
+            const bool wz = !all_zero(wzp);
+            std::vector<int> tap;
+            std::vector<uint32_t> mask;
+            k::ConvGemmArgs &f = op->cgm;
+            if (k::conv_gemm_plan(f, tap, mask, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.pad == MF_PAD_SAME, wz)) {
+                const std::vector<int8_t> img = k::conv_gemm_weight_image(s.weights, f);
+                const size_t np = (size_t)f.NT * 16;
+                std::vector<float> pA(np, 0.0f), pS(np, 0.0f);
+                std::vector<int32_t> pK(np, 0), pZ(np, 0);
+                for (int n = 0; n < s.N; ++n)
+                    pA[(size_t)n] = A[(size_t)n], pS[(size_t)n] = S[(size_t)n], pK[(size_t)n] = Kc[(size_t)n], pZ[(size_t)n] = wzp[(size_t)n];
+                op->d_fcw.upload(img.data(), img.size());
+                op->d_tap.upload(tap.data(), tap.size() * sizeof(int));
+                op->d_cgm_mask.upload(mask.data(), mask.size() * 4);
+                op->d_rtA.upload(pA.data(), np * 4), op->d_rtS.upload(pS.data(), np * 4);
+                op->d_rtKc.upload(pK.data(), np * 4), op->d_rtwzp.upload(pZ.data(), np * 4);
+                f.wimg = op->d_fcw.p, f.tap = op->d_tap.as<int>(), f.kmask = op->d_cgm_mask.as<uint32_t>();
+                f.A = op->d_rtA.as<float>(), f.S = op->d_rtS.as<float>(), f.Kc = op->d_rtKc.as<int>(), f.wzp = op->d_rtwzp.as<int>();
+                f.izp4 = 0x01010101u * (uint32_t)(uint8_t)(int8_t)s.izp;
+                f.lo_f = a.lo_f, f.hi_f = a.hi_f, f.magic = magic, f.xr = xr;
+                op->fast = OpImpl::CONV_GEMM;
+                op->rt_wz = wz;
+                op->fast_name = std::string("conv_gemm_rt") + (wz ? "<wzp>" : "");
+                if (switches().verbose)
+                    fprintf(stderr, "[microflow_amd] conv_gemm_rt %dx%dx%d -> %d %dx%d: K' %d (%d k steps), %d tiles in %d slice(s) of %d, %s %d x %d rows, %d B LDS\n",
+                            s.H, s.W, s.C, s.N, s.KH, s.KW, s.KH * f.KWCP, f.KS, f.NT, f.NSL, f.NTS, f.NBANDS > 1 ? "bands of" : "images per step:",
+                            f.NBANDS > 1 ? f.BH : f.G, f.RB, f.lds);
+            }
+        }
         if (op->fma_ok) { // the single-fma constants beside the two-rounding ones, in the blocks of the kernels that have the form
             op->dwf.A3 = op->pw.A3 = op->d_A3.as<float>(), op->dwf.S3 = op->pw.S3 = op->d_S3.as<float>();
             op->dwf.Kc3 = op->pw.Kc3 = op->d_Kc3.as<int>();
@@ -1053,6 +1088,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             break;
         case OpImpl::CONV_ROWS:
             k::launch_conv_rows(d_in, d_out, op->crows, op->rt_wz, (int)batch, s);
+            done = true;
+            break;
+        case OpImpl::CONV_GEMM:
+            k::launch_conv_gemm(d_in, d_out, op->cgm, op->rt_wz, (int)batch, s);
             done = true;
             break;
         case OpImpl::DW_RT:

@@ -236,6 +236,43 @@ def mlp(rng, sizes, elem=INT8, wzp_nonzero=False, softmax=False, act="relu"):
     return build_model((1, int(sizes[0])), in_q, layers, elem)
 
 
+def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None):
+    """A convolution stack: input_shape = (H, W, C); convs = [(op, N, K, stride), ...] with op "conv" (KxK Conv2D to N channels)
+    or "dw" (KxK depthwise, N ignored), all SAME, relu6; per-channel filter quantization, filter zero points off the middle when
+    wzp_nonzero (Conv2D only: the depthwise kernels keep theirs at the middle).  head = classes: AveragePool over the whole
+    image, FullyConnected(classes) and Softmax after the stack.  Output scales keep every layer's outputs spread over the range."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    H, W, C = input_shape
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers = in_q, []
+    for op, n, k, s in convs:
+        oh, ow = -(-H // s), -(-W // s)
+        dw = op == "dw"
+        n = C if dw else n
+        sc = rng.uniform(0.002, 0.01, n).astype(np.float32)
+        zp = rng.integers(mid - 10, mid + 11, n) if wzp_nonzero and not dw else np.full(n, mid)
+        taps = k * k * (1 if dw else C)
+        osc = float(np.float32(q[0] * float(sc.mean()) * 60.0 * np.sqrt(taps)))
+        d = dict(op="depthwise_conv_2d" if dw else "conv_2d", fscale=sc, fzp=zp, bias=rng.integers(-500, 500, n),
+                 bscale=(sc * np.float32(q[0])).astype(np.float32), bzp=np.zeros(n, np.int64), padding="same", strides=(s, s),
+                 act="relu6", out_shape=(1, oh, ow, n), out_q=(osc, lo))
+        d["weights" if dw else "filters"] = rng.integers(lo, hi, (1, k, k, n) if dw else (n, k, k, C))
+        layers.append(d)
+        q, H, W, C = d["out_q"], oh, ow, n
+    if head:
+        layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none",
+                           out_shape=(1, 1, 1, C), out_q=q))
+        layers.append(dict(op="reshape", out_shape=(1, C), out_q=q))
+        wsc = np.float32(rng.uniform(0.002, 0.02))
+        osc = float(np.float32(q[0] * wsc * 60.0 * np.sqrt(C)))
+        layers.append(dict(op="fully_connected", weights=rng.integers(lo, hi, (head, C)), wscale=[wsc], wzp=[mid],
+                           bias=rng.integers(-2000, 2000, head), bscale=[np.float32(q[0]) * wsc], bzp=[0], act="none",
+                           out_shape=(1, head), out_q=(osc, int(rng.integers(lo + 20, hi - 20)))))
+        layers.append(dict(op="softmax", out_shape=(1, head), out_q=(1.0 / 256.0, lo)))
+    return build_model((1,) + tuple(input_shape), in_q, layers, elem)
+
+
 def person_detect_like(rng, side=96, width=1.0, elem=INT8, wzp_nonzero=False, n_stage=5, classes=2, wmax=None):
     """The layer structure of person_detect.tflite (MobileNet-v1 0.25, grey input: a one-channel 3x3 stride-2 stem, then
     depthwise 3x3 + 1x1 pairs with strides 1 2 1 2 1 2 [1 x n_stage] 2 1, AveragePool2D over what is left, a 1x1 head,
