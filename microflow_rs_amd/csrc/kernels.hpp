@@ -628,6 +628,28 @@ bool conv_gemm_plan(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uint32_t
                     int sw, int OH, int OW, bool pad_same, bool wz); // false: beyond the limits
 std::vector<int8_t> conv_gemm_weight_image(const int8_t *w /*[N][KH][KW][C]*/, const ConvGemmArgs &a);
 void launch_conv_gemm(const int8_t *in, int8_t *out, const ConvGemmArgs &a, bool wz, int batch, hipStream_t s);
+// DepthwiseConv2D of any C >= 2 with one output per channel, filters up to 7 x 7, (W C) % 4 == 0, with or without filter zero points
+// (k_dw_gemm.hip: dw_gemm_rt): dw_mm_rt's block-diagonal product with operand B read at its natural alignment
+struct DwGemmArgs {
+    int H, W, C, KH, KW, sh, sw, OH, OW;
+    int padl, padt;      // SAME: (KW - 1) / 2, (KH - 1) / 2 (src/tensor.rs:193); VALID: 0
+    int KS, NBLK;        // k steps of four taps; 16-channel groups (the last one partial when C % 16 != 0)
+    int P;               // output pixels per 16-row group: 1, or 16 / C for C <= 8 at stride 1 along the row (NBLK == 1; row r = pixel
+                         // r / C, channel r % C of P adjacent pixels of one output row)
+    int LP, ROW, RB, TILE, G, BH, NBANDS; // image tile geometry as ConvMmArgs
+    int lds;             // dynamic LDS bytes: G tiles + 256
+    uint32_t izp4;
+    float lo_f, hi_f;
+    const void *wprep;   // build_dw_mm_rt_weights: [NBLK][KS][64 lanes][16 bytes]
+    const float *A;      // [NBLK * 16] per row: channel 16 q + r (P > 1: channel r % C), zero beyond the real rows
+    const float *S;      // [NBLK * 16]
+    const int *Kc;       // [NBLK * 16]
+    const int *wzp;      // [NBLK * 16]
+    int magic, xr;
+};
+constexpr int DW_GEMM_LDS_MAX = 160 * 1024 - 1024;
+bool dw_gemm_plan(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same); // false: beyond the limits
+void launch_dw_gemm(const int8_t *in, int8_t *out, const DwGemmArgs &a, bool wz, int batch, hipStream_t s);
 // Consecutive FullyConnected layers (+ a Softmax over one row) in one launch (k_fc_rt.hip: fc_chain).  Every layer's weight image
 // (its fc_rt image, all tiles) stays resident in LDS; the int8 tensors between the layers never leave LDS.
 constexpr int FC_CHAIN_MAX = 8;

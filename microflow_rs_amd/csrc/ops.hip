@@ -90,7 +90,7 @@ struct OpImpl {
     bool finite_consts = true; // A / S all finite (the shape-specialised and fused epilogues assume it)
     std::string generic_name, fast_name;
     enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM, FC_RT,
-                CONV_GEMM } fast = NONE;
+                CONV_GEMM, DW_GEMM } fast = NONE;
     int *d_rowsum = nullptr; // FC_MFMA with wzp != 0: per-row input sums
     size_t rowsum_cap = 0, rowsum_rows = 0; // (ints allocated; the row count the counter pairs currently sit behind)
     int8_t *d_ext = nullptr; // op_run_external on a u8 operator: input moved to the i8 domain
@@ -150,6 +150,7 @@ struct OpImpl {
     DevBuf d_tap;          // conv_mm_rt: tap offset table
     k::ConvGemmArgs cgm{}; // Conv2D of any C and N on the matrix pipe (k_conv_gemm.hip); tap table in d_tap, image in d_fcw,
     DevBuf d_cgm_mask;     // ... constants padded to 16-column tiles in d_rtA, d_rtS, d_rtKc, d_rtwzp; window-sum byte masks
+    k::DwGemmArgs dwg{};   // DepthwiseConv2D of any C on the matrix pipe (k_dw_gemm.hip); operand A in d_wprep, constants as cgm's
     DevBuf d_crw, d_crm;   // conv_rows_lds: packed weights, tap masks
     bool rt_wz = false;    // non-zero weight zero points
     int magic_mode = 0;    // conv-like operators: epilogue mode the host proved usable (k_common.hpp: 0, 1 or 2)
@@ -324,16 +325,20 @@ std::vector<int8_t> build_dw_sp_weights(const std::vector<int8_t> &dense /* buil
     return out;
 }
 
-// Depthwise weights [KH][KW][C] (C % 16 == 0) as operand A of conv_mm_rt's depthwise mode (k_rt.hip): [16-channel group][k step][lane]
-// x 16 bytes; lane (row r, group g) of step ks holds tap t = 4 ks + g: its only non-zero byte is byte r = w[t][16 q + r].
-std::vector<int8_t> build_dw_mm_rt_weights(const int8_t *w, int KH, int KW, int C, int KS /* >= (KH KW + 3) / 4: padded with zero steps */) {
-    const int NQ = C / 16, T = KH * KW;
+// Depthwise weights [KH][KW][C] as operand A of conv_mm_rt's depthwise mode (k_rt.hip) and of dw_gemm_rt (k_dw_gemm.hip): [16-channel
+// group][k step][lane] x 16 bytes; lane (row r, group g) of step ks holds tap t = 4 ks + g: its only non-zero byte is byte r = w[t][16 q
+// + r] (zero for the channels 16 q + r >= C of a last, partial group).  P > 1 (dw_gemm_rt, C <= 8): one group, row r is channel r % C
+// of the P adjacent pixels, byte r = w[t][r % C] for r < P C.
+std::vector<int8_t> build_dw_mm_rt_weights(const int8_t *w, int KH, int KW, int C, int KS /* >= (KH KW + 3) / 4: padded with zero steps */,
+                                           int P = 1) {
+    const int NQ = (C + 15) / 16, T = KH * KW;
     std::vector<int8_t> out((size_t)NQ * KS * 1024, 0);
     for (int q = 0; q < NQ; ++q)
         for (int ks = 0; ks < KS; ++ks)
             for (int lane = 0; lane < 64; ++lane) {
                 const int r = lane & 15, t = 4 * ks + (lane >> 4);
-                if (t < T) out[(((size_t)q * KS + ks) * 64 + lane) * 16 + r] = w[(size_t)t * C + 16 * q + r];
+                const int c = P > 1 ? (r < P * C ? r % C : -1) : (16 * q + r < C ? 16 * q + r : -1);
+                if (t < T && c >= 0) out[(((size_t)q * KS + ks) * 64 + lane) * 16 + r] = w[(size_t)t * C + c];
             }
     return out;
 }
@@ -799,6 +804,36 @@ OpImpl *op_create(int device, const OpSpec &spec) {
                 op->fast_name = "dw_mm_rt<" + std::to_string(s.KH) + "x" + std::to_string(s.KW) + ">";
             }
         }
+        // every other DepthwiseConv2D with one output per channel and whole-dword image rows -- C % 16 != 0, filter zero points, 3x3
+        // SAME shapes dw3x3_rt rejects -- : the same block-diagonal product, operand B read at its natural alignment (k_dw_gemm.hip)
+        const bool dw_gemm = dw && !no_rt && !switches().no_dw_gemm && op->finite_consts;
+        if (op->fast == OpImpl::NONE && dw_gemm && s.C == s.N && s.C >= 2) {
+            k::DwGemmArgs &f = op->dwg;
+            if (k::dw_gemm_plan(f, s.H, s.W, s.C, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.pad == MF_PAD_SAME)) {
+                const bool wz = !all_zero(wzp);
+                const std::vector<int8_t> prep = build_dw_mm_rt_weights(s.weights, s.KH, s.KW, s.C, f.KS, f.P);
+                const size_t np = (size_t)f.NBLK * 16;
+                std::vector<float> pA(np, 0.0f), pS(np, 0.0f);
+                std::vector<int32_t> pK(np, 0), pZ(np, 0);
+                for (int r = 0; r < (f.P > 1 ? f.P * s.C : s.C); ++r) { // the constants of each row's channel
+                    const size_t c = (size_t)(r % s.C);
+                    pA[(size_t)r] = A[c], pS[(size_t)r] = S[c], pK[(size_t)r] = Kc[c], pZ[(size_t)r] = wzp[c];
+                }
+                op->d_wprep.upload(prep.data(), prep.size());
+                op->d_rtA.upload(pA.data(), np * 4), op->d_rtS.upload(pS.data(), np * 4);
+                op->d_rtKc.upload(pK.data(), np * 4), op->d_rtwzp.upload(pZ.data(), np * 4);
+                f.wprep = op->d_wprep.p;
+                f.A = op->d_rtA.as<float>(), f.S = op->d_rtS.as<float>(), f.Kc = op->d_rtKc.as<int>(), f.wzp = op->d_rtwzp.as<int>();
+                f.izp4 = 0x01010101u * (uint32_t)(uint8_t)(int8_t)s.izp;
+                f.lo_f = a.lo_f, f.hi_f = a.hi_f, f.magic = magic, f.xr = xr;
+                op->fast = OpImpl::DW_GEMM;
+                op->rt_wz = wz;
+                op->fast_name = "dw_gemm_rt<" + std::to_string(s.KH) + "x" + std::to_string(s.KW) + (wz ? ",wzp>" : ">");
+                if (switches().verbose)
+                    fprintf(stderr, "[microflow_amd] dw_gemm_rt %dx%dx%d %dx%d: %d k steps, %d channel groups of %d pixels, %s %d x %d rows, %d B LDS\n", s.H,
+                            s.W, s.C, s.KH, s.KW, f.KS, f.NBLK, f.P, f.NBANDS > 1 ? "bands of" : "images per step:", f.NBANDS > 1 ? f.BH : f.G, f.RB, f.lds);
+            }
+        }
         // any other Conv2D with C % 16 == 0: MFMA product over K = KH KW C with the image staged in LDS
         if (op->fast == OpImpl::NONE && !no_rt && op->finite_consts && !dw && !(s.KH == 1 && s.KW == 1 && k::conv1x1_rowwave_supported(a))) {
             const bool wz = !all_zero(wzp);
@@ -829,14 +864,24 @@ OpImpl *op_create(int device, const OpSpec &spec) {
         if (op->fast == OpImpl::NONE && !dw && k::conv1x1_rowwave_supported(a)) // few outputs: one wavefront per pixel
             op->fast = OpImpl::CONV1X1_ROW, op->fast_name = "conv1x1_rowwave";
         // every other Conv2D with whole-dword image rows: the MFMA product over K' = KH x (KW C rounded up to 16), the weights
-        // resident in LDS in N slices (k_conv_gemm.hip)
-        if (op->fast == OpImpl::NONE && !no_rt && !switches().no_conv_gemm && op->finite_consts && !dw) {
+        // resident in LDS in N slices (k_conv_gemm.hip).  Also a one-channel DepthwiseConv2D with more outputs than the C = 1 kernels
+        // above take: the reference reads channel 0 for every output (depthwise_conv_2d.rs:67), so it IS this Conv2D with C = 1 and the
+        // filters [N][KH][KW][1] (the filter zero points and Kc are per output channel in both)
+        const bool dw_c1 = op->fast == OpImpl::NONE && dw_gemm && s.C == 1 && s.N > 1;
+        if ((op->fast == OpImpl::NONE && !no_rt && !switches().no_conv_gemm && op->finite_consts && !dw) || dw_c1) {
             const bool wz = !all_zero(wzp);
             std::vector<int> tap;
             std::vector<uint32_t> mask;
+            std::vector<int8_t> wt;
+            if (dw_c1) {
+                const int T = s.KH * s.KW;
+                wt.resize((size_t)s.N * T);
+                for (int n = 0; n < s.N; ++n)
+                    for (int t = 0; t < T; ++t) wt[(size_t)n * T + t] = s.weights[(size_t)t * s.N + n];
+            }
             k::ConvGemmArgs &f = op->cgm;
             if (k::conv_gemm_plan(f, tap, mask, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.pad == MF_PAD_SAME, wz)) {
-                const std::vector<int8_t> img = k::conv_gemm_weight_image(s.weights, f);
+                const std::vector<int8_t> img = k::conv_gemm_weight_image(dw_c1 ? wt.data() : s.weights, f);
                 const size_t np = (size_t)f.NT * 16;
                 std::vector<float> pA(np, 0.0f), pS(np, 0.0f);
                 std::vector<int32_t> pK(np, 0), pZ(np, 0);
@@ -853,7 +898,7 @@ OpImpl *op_create(int device, const OpSpec &spec) {
                 f.lo_f = a.lo_f, f.hi_f = a.hi_f, f.magic = magic, f.xr = xr;
                 op->fast = OpImpl::CONV_GEMM;
                 op->rt_wz = wz;
-                op->fast_name = std::string("conv_gemm_rt") + (wz ? "<wzp>" : "");
+                op->fast_name = std::string("conv_gemm_rt") + (dw ? (wz ? "<dw,wzp>" : "<dw>") : (wz ? "<wzp>" : ""));
                 if (switches().verbose)
                     fprintf(stderr, "[microflow_amd] conv_gemm_rt %dx%dx%d -> %d %dx%d: K' %d (%d k steps), %d tiles in %d slice(s) of %d, %s %d x %d rows, %d B LDS\n",
                             s.H, s.W, s.C, s.N, s.KH, s.KW, s.KH * f.KWCP, f.KS, f.NT, f.NSL, f.NTS, f.NBANDS > 1 ? "bands of" : "images per step:",
@@ -1092,6 +1137,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             break;
         case OpImpl::CONV_GEMM:
             k::launch_conv_gemm(d_in, d_out, op->cgm, op->rt_wz, (int)batch, s);
+            done = true;
+            break;
+        case OpImpl::DW_GEMM:
+            k::launch_dw_gemm(d_in, d_out, op->dwg, op->rt_wz, (int)batch, s);
             done = true;
             break;
         case OpImpl::DW_RT:

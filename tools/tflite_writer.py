@@ -273,6 +273,48 @@ def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None):
     return build_model((1,) + tuple(input_shape), in_q, layers, elem)
 
 
+def inverted_residual_net(rng, input_shape, blocks, elem=INT8, wzp_nonzero=False, head=10):
+    """MobileNetV2/V3-style inverted-residual blocks: input_shape = (H, W, C); blocks = [(expand, K, stride, out), ...], each a
+    1x1 Conv2D to `expand` channels (relu6) -> KxK depthwise SAME at `stride` (relu6) -> 1x1 Conv2D to `out` channels (no
+    activation); then AveragePool over the whole image, FullyConnected(head) and Softmax.  Per-channel filter quantization; with
+    wzp_nonzero every filter zero point (the depthwise ones included) sits off the middle, as in classic asymmetric-u8 models."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    H, W, C = input_shape
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers = in_q, []
+
+    def conv(dw, n, k, s, act):
+        nonlocal q, H, W, C
+        oh, ow = -(-H // s), -(-W // s)
+        sc = rng.uniform(0.002, 0.01, n).astype(np.float32)
+        zp = rng.integers(mid - 12, mid + 13, n) if wzp_nonzero else np.full(n, mid)
+        if wzp_nonzero:
+            zp[zp == mid] = mid + 5
+        taps = k * k * (1 if dw else C)
+        osc = float(np.float32(q[0] * float(sc.mean()) * 60.0 * np.sqrt(taps)))
+        d = dict(op="depthwise_conv_2d" if dw else "conv_2d", fscale=sc, fzp=zp, bias=rng.integers(-500, 500, n),
+                 bscale=(sc * np.float32(q[0])).astype(np.float32), bzp=np.zeros(n, np.int64), padding="same", strides=(s, s), act=act,
+                 out_shape=(1, oh, ow, n), out_q=(osc, lo if act == "relu6" else int(rng.integers(lo + 20, hi - 20))))
+        d["weights" if dw else "filters"] = rng.integers(lo, hi, (1, k, k, n) if dw else (n, k, k, C))
+        layers.append(d)
+        q, H, W, C = d["out_q"], oh, ow, n
+
+    for expand, k, s, out in blocks:
+        conv(False, expand, 1, 1, "relu6")
+        conv(True, expand, k, s, "relu6")
+        conv(False, out, 1, 1, "none")
+    layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none", out_shape=(1, 1, 1, C), out_q=q))
+    layers.append(dict(op="reshape", out_shape=(1, C), out_q=q))
+    wsc = np.float32(rng.uniform(0.002, 0.02))
+    osc = float(np.float32(q[0] * wsc * 60.0 * np.sqrt(C)))
+    layers.append(dict(op="fully_connected", weights=rng.integers(lo, hi, (head, C)), wscale=[wsc], wzp=[mid],
+                       bias=rng.integers(-2000, 2000, head), bscale=[np.float32(q[0]) * wsc], bzp=[0], act="none",
+                       out_shape=(1, head), out_q=(osc, int(rng.integers(lo + 20, hi - 20)))))
+    layers.append(dict(op="softmax", out_shape=(1, head), out_q=(1.0 / 256.0, lo)))
+    return build_model((1,) + tuple(input_shape), in_q, layers, elem)
+
+
 def person_detect_like(rng, side=96, width=1.0, elem=INT8, wzp_nonzero=False, n_stage=5, classes=2, wmax=None):
     """The layer structure of person_detect.tflite (MobileNet-v1 0.25, grey input: a one-channel 3x3 stride-2 stem, then
     depthwise 3x3 + 1x1 pairs with strides 1 2 1 2 1 2 [1 x n_stage] 2 1, AveragePool2D over what is left, a 1x1 head,
