@@ -580,6 +580,12 @@ void launch_fc_rowsum(const int8_t *in, int *rowsum, size_t rows, int K, hipStre
 void launch_fc_mfma(const int8_t *in, int8_t *out, const FcGemmArgs &a, hipStream_t s);
 bool fc_mfma_rowsum_prepass();
 bool fc_mfma_rowsum_prologue(size_t rows, int N); // the in-launch row sums (fc_mfma<..., RSP>) take this shape
+// FullyConnected with 2:4-sparse weights on v_smfmac_i32_16x16x128_i8 (k_fc_sparse.hip): fc_mfma's shapes (fc_mfma_supported), weights
+// with at most two non-zero bytes in every aligned group of four along K; the weight zero point term from the fc_rowsum pre-pass
+// (FcGemmArgs::rowsum), FcGemmArgs::w = the image below
+bool fc_sparse24_eligible(const int8_t *w /*[N][K], i8 domain*/, int N, int K);
+std::vector<int8_t> fc_sparse24_image(const int8_t *w /*[N][K], i8 domain*/, int N, int K); // K/128 x N/16 x (1 KiB values), then x 256 B index words
+void launch_fc_sparse24(const int8_t *in, int8_t *out, const FcGemmArgs &a, hipStream_t s);
 bool fc_mfma_rowsum_prologue(size_t rows, int N); // the RSP instance takes this shape (256 x 256 tiles, tile columns dividing 256) // true (default): fc_rowsum runs in front of the GEMM; MF_FC_ROWSUM_FOLD=1: the GEMM forms the sums itself
 // FullyConnected of any K and N on the int8 matrix pipe (k_fc_rt.hip).  The weight image ([tile][k step][lane] x 16 bytes,
 // zero beyond K and N) and the launch geometry come from the host (fc_rt_plan); the kernel keeps a slice of NTS 16-column

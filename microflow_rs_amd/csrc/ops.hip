@@ -90,8 +90,8 @@ struct OpImpl {
     bool finite_consts = true; // A / S all finite (the shape-specialised and fused epilogues assume it)
     std::string generic_name, fast_name;
     enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM, FC_RT,
-                CONV_GEMM, DW_GEMM } fast = NONE;
-    int *d_rowsum = nullptr; // FC_MFMA with wzp != 0: per-row input sums
+                CONV_GEMM, DW_GEMM, FC_SPARSE24 } fast = NONE;
+    int *d_rowsum = nullptr; // FC_MFMA / FC_SPARSE24 with wzp != 0: per-row input sums
     size_t rowsum_cap = 0, rowsum_rows = 0; // (ints allocated; the row count the counter pairs currently sit behind)
     int8_t *d_ext = nullptr; // op_run_external on a u8 operator: input moved to the i8 domain
     size_t ext_cap = 0;
@@ -145,6 +145,7 @@ struct OpImpl {
     k::FcRtArgs fcrt{};    // FullyConnected on the matrix pipe, any K and N (k_fc_rt.hip)
     bool fcrt_ok = false;  // ... its image and constants exist (also where the operator alone stays on fc_generic)
     DevBuf d_fcw, d_fcA, d_fcKc; // ... its weight image and constants padded to 16-column tiles
+    DevBuf d_sp24;         // FC_SPARSE24: the compressed 2:4 weight image (k_fc_sparse.hip fc_sparse24_image)
     k::ConvRowsArgs crows{};
     k::ConvMmArgs cmm{};
     DevBuf d_tap;          // conv_mm_rt: tap offset table
@@ -978,9 +979,16 @@ OpImpl *op_create(int device, const OpSpec &spec) {
             op->fast = OpImpl::FC_ROWWAVE;
             op->fast_name = "fc_rowwave<" + std::to_string(s.N) + ">";
         } else if (s.N % 128 == 0 && s.K % 128 == 0) {
-            // dense contraction: int8 MFMA GEMM whenever the batch supplies whole 128-row tiles
+            // dense contraction: int8 MFMA GEMM whenever the batch supplies whole 128-row tiles; weights with at most two non-zero
+            // bytes in every aligned group of four along K (judged on the stored i8 bytes) on the sparse matrix instruction
             op->fast = OpImpl::FC_MFMA;
             op->fast_name = "fc_mfma";
+            if (!switches().no_fc_sparse && k::fc_sparse24_eligible(s.weights, s.N, s.K)) {
+                const std::vector<int8_t> img = k::fc_sparse24_image(s.weights, s.N, s.K);
+                op->d_sp24.upload(img.data(), img.size());
+                op->fast = OpImpl::FC_SPARSE24;
+                op->fast_name = a.wzp ? "fc_sparse24<wzp>" : "fc_sparse24";
+            }
         }
         if (finite && op->fast == OpImpl::NONE && k::fc_rt_plan(op->fcrt, s.K, s.N)) {
             // every other shape: the int8 matrix pipe with the (sliced) weight image resident in LDS.  The image and constants are
@@ -1167,19 +1175,22 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             k::launch_fc_rt(d_in, d_out, op->fcrt, (long long)(batch * sp.M), s);
             done = true;
             break;
-        case OpImpl::FC_MFMA: {
+        case OpImpl::FC_MFMA:
+        case OpImpl::FC_SPARSE24: {
             const size_t rows = batch * sp.M;
             if (!k::fc_mfma_supported(rows, sp.N, sp.K)) break; // fewer than 64 rows: generic kernel
+            const bool sparse = op->fast == OpImpl::FC_SPARSE24;
             k::FcGemmArgs g{};
-            g.w = op->fc.w, g.A = op->fc.A, g.Kc = op->fc.Kc, g.wzp = op->fc.wzp, g.S = op->fc.S;
+            g.w = sparse ? op->d_sp24.as<int8_t>() : op->fc.w, g.A = op->fc.A, g.Kc = op->fc.Kc, g.wzp = op->fc.wzp, g.S = op->fc.S;
             g.lo_f = op->fc.lo_f, g.hi_f = op->fc.hi_f, g.M = (int)rows, g.N = sp.N, g.K = sp.K;
             g.xr4 = 0x01010101u * (uint32_t)op->fc.xr;
             g.rowsum = nullptr, g.rs_sums = nullptr, g.rs_sync = nullptr;
             // the weight-zero-point term needs sum_k x[m][k]: formed by the GEMM launch itself (its prologue) where the shape
             // allows, else by a pre-pass launch; either way in the operator's one row-sum scratch (+ the row tiles' counter pairs
             // behind it), whose uses the event handshake serialises across streams
-            const bool inlaunch = op->fc.wzp != 0 && k::fc_mfma_rowsum_prologue(rows, sp.N);
-            const bool prepass = op->fc.wzp != 0 && (inlaunch || k::fc_mfma_rowsum_prepass());
+            // (fc_sparse24 always takes the pre-pass)
+            const bool inlaunch = op->fc.wzp != 0 && !sparse && k::fc_mfma_rowsum_prologue(rows, sp.N);
+            const bool prepass = op->fc.wzp != 0 && (inlaunch || sparse || k::fc_mfma_rowsum_prepass());
             if (prepass) {
                 const size_t ntm = (rows + 255) / 256, need = rows + 2 * ntm;
                 op->scratch_acquire(s, op->rowsum_cap < need);
@@ -1198,7 +1209,8 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
                 if (inlaunch) g.rs_sums = op->d_rowsum, g.rs_sync = op->d_rowsum + rows;
                 else k::launch_fc_rowsum(d_in, op->d_rowsum, rows, sp.K, s), g.rowsum = op->d_rowsum;
             }
-            k::launch_fc_mfma(d_in, d_out, g, s);
+            if (sparse) k::launch_fc_sparse24(d_in, d_out, g, s);
+            else k::launch_fc_mfma(d_in, d_out, g, s);
             if (prepass) op->scratch_release(s);
             done = true;
             break;

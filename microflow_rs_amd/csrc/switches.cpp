@@ -28,6 +28,7 @@ Switches switches_parse() {
     s.no_fc_chain = env_set("MF_NO_FC_CHAIN");
     s.no_conv_gemm = env_set("MF_NO_CONV_GEMM");
     s.no_dw_gemm = env_set("MF_NO_DW_GEMM");
+    s.no_fc_sparse = env_set("MF_NO_FC_SPARSE");
     s.no_pairtail = env_set("MF_NO_PAIRTAIL");
     s.no_quad = env_set("MF_NO_QUAD");
     s.no_pair_front = env_set("MF_NO_PAIR_FRONT");

@@ -5,7 +5,7 @@ emitted before the objects it references, so all uoffsets point forward as the f
 requires.  Only the fields the MicroFlow front end reads are written
 (microflow-macros/src/lib.rs:46-151, microflow-macros/src/ops/fully_connected.rs:66-98).
 
-    python tools/make_fc_model.py out.tflite --m 4096 --k 4096 --n 4096 [--wzp 0] [--seed 5]
+    python tools/make_fc_model.py out.tflite --m 4096 --k 4096 --n 4096 [--wzp 0] [--seed 5] [--u8] [--sparse24]
 """
 import argparse
 import struct
@@ -155,22 +155,39 @@ def fc_model(M, K, N, weights, bias, in_q, w_q, b_q, out_q, activation=0):
     return bytes(fb.buf)
 
 
-def synthetic_fc(M, K, N, wzp=0, seed=5, activation=0, u8=False):
+def prune_2_4(w):
+    """2:4 structured sparsity along K: of every aligned group of four weights keep the two with the largest |w| (the
+    earlier position on a tie) and zero the others.  K % 4 == 0."""
+    g = np.asarray(w, np.int8).reshape(-1, 4)
+    order = np.argsort(-np.abs(g.astype(np.int16)), axis=1, kind="stable")
+    out = np.zeros_like(g)
+    rows = np.arange(g.shape[0])[:, None]
+    out[rows, order[:, :2]] = g[rows, order[:, :2]]
+    return out.reshape(np.shape(w))
+
+
+def synthetic_fc(M, K, N, wzp=0, seed=5, activation=0, u8=False, sparse24=False):
     """BASELINE config 5: uniform int8 weights, input zp -128, scales chosen so that the
     outputs spread over the int8 range instead of saturating.
-    u8=True: the same model with UINT8 tensors (`wzp` then is a u8 value)."""
+    u8=True: the same model with UINT8 tensors (`wzp` then is a u8 value).
+    sparse24=True: the weights pruned to 2:4 sparsity along K (prune_2_4), as a 2:4 pruning pass followed by int8
+    conversion leaves them."""
     if u8:
         from make_u8_model import to_u8
-        return to_u8(synthetic_fc(M, K, N, wzp - 128, seed, activation))
+        return to_u8(synthetic_fc(M, K, N, wzp - 128, seed, activation, sparse24=sparse24))
     rng = np.random.default_rng(seed)
     w = rng.integers(-128, 128, (N, K), dtype=np.int8)
+    if sparse24:
+        w = prune_2_4(w)
     bias = rng.integers(-4096, 4096, N).astype(np.int64)
     # a non-zero weight zero point shifts every accumulator by about -E[x - izp] * K * wzp:
     # compensate in the bias so that the outputs still spread instead of saturating
     bias = (bias + int(round(127.5 * K * wzp))).astype(np.int32)
     in_scale, w_scale = 1.0 / 128.0, 1.0 / 128.0
     # std of the accumulator ~ sqrt(K) * 74 * 74 ; map ~3 sigma onto the int8 range
-    out_scale = float(np.float32(in_scale * w_scale * np.sqrt(K) * 74.0 * 74.0 * 3.0 / 127.0))
+    # (2:4 weights: the two largest of four uniform bytes, std ~ 91; half the products)
+    out_scale = float(np.float32(in_scale * w_scale * np.sqrt(K) * 74.0 * 74.0 * 3.0 / 127.0)) if not sparse24 else \
+        float(np.float32(in_scale * w_scale * np.sqrt(K / 2) * 74.0 * 91.0 * 3.0 / 127.0))
     data = fc_model(M, K, N, w, bias, (in_scale, -128), (w_scale, wzp),
                     (in_scale * w_scale, 0), (out_scale, 3), activation)
     return data
@@ -185,7 +202,8 @@ if __name__ == "__main__":
     ap.add_argument("--wzp", type=int, default=0)
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--u8", action="store_true", help="UINT8 tensors (wzp is then a u8 value)")
+    ap.add_argument("--sparse24", action="store_true", help="weights pruned to 2:4 sparsity along K")
     a = ap.parse_args()
-    blob = synthetic_fc(a.m, a.k, a.n, a.wzp, a.seed, u8=a.u8)
+    blob = synthetic_fc(a.m, a.k, a.n, a.wzp, a.seed, u8=a.u8, sparse24=a.sparse24)
     open(a.out, "wb").write(blob)
     print(a.out, len(blob), "bytes")

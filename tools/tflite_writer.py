@@ -21,7 +21,7 @@ import struct
 
 import numpy as np
 
-from make_fc_model import FB, Table, TableVec, Vec, emit
+from make_fc_model import FB, Table, TableVec, Vec, emit, prune_2_4
 
 INT32, UINT8, INT8 = 2, 3, 9
 OPCODES = {"average_pool_2d": 1, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "reshape": 22,
@@ -210,10 +210,12 @@ def speech_like(rng, elem=INT8, fc_wzp=0, per_channel=True, act="relu"):
     return build_model((1, 1960), in_q, layers, elem)
 
 
-def mlp(rng, sizes, elem=INT8, wzp_nonzero=False, softmax=False, act="relu"):
+def mlp(rng, sizes, elem=INT8, wzp_nonzero=False, softmax=False, act="relu", sparse24=()):
     """A FullyConnected-only network: sizes = (K, N1, N2, ...) gives the layers K -> N1 -> N2 ...; every hidden layer has
     the activation `act`, the last one none, optionally followed by a Softmax.  Per-tensor weight quantization (what
-    FullyConnected has), random scales and zero points; wzp_nonzero gives every layer a weight zero point off the middle."""
+    FullyConnected has), random scales and zero points; wzp_nonzero gives every layer a weight zero point off the middle.
+    sparse24: indices of layers whose weights are pruned to 2:4 sparsity along K in the int8 domain (make_fc_model.prune_2_4;
+    the same random draws as without it)."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
@@ -227,7 +229,10 @@ def mlp(rng, sizes, elem=INT8, wzp_nonzero=False, softmax=False, act="relu"):
         # output scale chosen so that the layer's outputs spread over the int8 range instead of saturating
         osc = float(np.float32(q[0] * wsc * 120.0 * np.sqrt(K)))
         ozp = lo if a in ("relu", "relu6") else int(rng.integers(lo + 20, hi - 20))
-        layers.append(dict(op="fully_connected", weights=rng.integers(lo, hi, (N, K)), wscale=[wsc], wzp=[wzp],
+        w = rng.integers(lo, hi, (N, K))
+        if i in sparse24:
+            w = prune_2_4((w - (lo + 128)).astype(np.int8)).astype(np.int64) + (lo + 128)
+        layers.append(dict(op="fully_connected", weights=w, wscale=[wsc], wzp=[wzp],
                            bias=rng.integers(-2000, 2000, N), bscale=[np.float32(q[0]) * wsc], bzp=[0], act=a,
                            out_shape=(1, N), out_q=(osc, ozp)))
         q = (osc, ozp)
