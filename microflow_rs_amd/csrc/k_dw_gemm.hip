@@ -6,7 +6,7 @@
 // == 0 and zero filter zero points); every other such layer with finite constants and whole-dword image rows ((W C) % 4 == 0) runs
 // here instead of on the byte-wise dwconv_generic.  The contraction is dw_mm_rt's (k_rt.hip): for a 16-channel group the taps are a
 // block-diagonal K = 16 KH KW product -- lane group g of k step ks supplies the group's 16 bytes of tap 4 ks + g, operand A holds the
-// tap's weight of channel r in byte r of row r (ops.hip build_dw_mm_rt_weights) -- and a wave works through a contiguous range of
+// tap's weight of channel r in byte r of row r (wimage.cpp build_dw_mm_rt_weights) -- and a wave works through a contiguous range of
 // (group, 16-pixel chunk) items with the group's operand A and constants in registers.  What differs:
 //
 //   operand B : a group starts at (pixel) C + 16 (group), 16-byte aligned only when C % 16 == 0; it is read at its natural alignment:

@@ -216,7 +216,7 @@ struct RrPhase {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             tbase[q] = chunk_addr(q, 0, g);
-            // (ops.hip DW_SP_CHUNK: half 0 = chunks (0,0) (0,1) (0,2) (1,0) of lane groups 0..3, half 1 = (1,1) (1,2) (2,0) (2,1): neighbouring
+            // (wimage.cpp DW_SP_CHUNK: half 0 = chunks (0,0) (0,1) (0,2) (1,0) of lane groups 0..3, half 1 = (1,1) (1,2) (2,0) (2,1): neighbouring
             // lane groups read neighbouring chunk columns of one filter row wherever nine chunks allow it, like the dense form, whose
             // tile pitches were chosen for exactly that)
             tb0[q] = g < 3 ? chunk_addr(q, 0, g) : chunk_addr(q, 1, 0);

@@ -614,7 +614,7 @@ __global__ __launch_bounds__(NTHR) void conv_mm_rt(const int8_t *__restrict__ in
 // conv_mm_rt's staging and pixel walk with the depthwise contraction of k_fused_mm.hip: for a 16-channel group the taps are a
 // block-diagonal K = 16 KH KW product -- lane group g of k step ks supplies the group's 16 bytes of tap 4 ks + g (one ds_read_b128
 // at (window start) + (table offset of the tap) + 16 (group)), operand A holds the tap's weight of channel r in byte r of row r
-// (ops.hip build_dw_mm_rt_weights).  A wave works through a contiguous range of (group, 16-pixel chunk) items with the group's operand
+// (wimage.cpp build_dw_mm_rt_weights).  A wave works through a contiguous range of (group, 16-pixel chunk) items with the group's operand
 // A, tap offsets and epilogue constants in registers; a lane ends an item with 4 consecutive channels of its pixel = one packed dword,
 // which goes through a 256-byte per-wave LDS patch so that 16 lanes store a pixel's 16 bytes each.  (First versions, 24x24x32 5x5 at
 // batch 65 536: constants and stores per lane from / to device memory 1.08 TB/s; operand A per k step from LDS 1.58 TB/s.)

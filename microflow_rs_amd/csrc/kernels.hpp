@@ -106,7 +106,7 @@ constexpr int DYNQ_RING = 32;
 struct DwFastArgs {
     const int8_t *w;    // [3][3][C]
     const void *wmm;    // matrix-pipe form of w (k_fused_mm.hip): [C/16 or 1][3 filter rows][64 lanes] x 16 bytes
-    const void *wsp;    // the same taps for v_smfmac_i32_16x16x128_i8 + one v_mfma_i32_16x16x32_i8 (k_quad.hip; ops.hip build_dw_sp_weights):
+    const void *wsp;    // the same taps for v_smfmac_i32_16x16x128_i8 + one v_mfma_i32_16x16x32_i8 (k_quad.hip; wimage.cpp build_dw_sp_weights):
                         // [C/16 or 1][64 lanes] x 32 bytes = {sparse A (16 B), index dword, ninth tap's dense A (8 B), pad}
     const float *A;
     const float *S;
@@ -125,7 +125,7 @@ struct DwFastArgs {
     const int *Kc3;
     int npatch3;            // patched accumulators that come with A3 / S3 / Kc3 (0 for most operators)
     const EpiPatchRec *patch; // (device) this launch's patch table, indexed by the kernel's depthwise tiles (16-channel groups), or nullptr
-    // with_patches: the launch's kernel applies a patch table, which the launch builder provides (ops.hip); without, an operator
+    // with_patches: the launch's kernel applies a patch table, which the launch builder provides (fused.hip); without, an operator
     // that needs patches has no single-fma form
     bool use_fma(bool with_patches = false) {
         if (!A3 || (npatch3 != 0 && !with_patches)) return false;
@@ -258,7 +258,7 @@ struct ConvMmArgs {
     int KS, TB, NBLK;    // 64-deep k steps over K = KH KW C; tiles per block (<= 4); blocks
     int dwise;           // 1: DepthwiseConv2D with C % 16 == 0 (src/ops/depthwise_conv_2d.rs:28-105), kernel dw_mm_rt: block b is the 16-channel
                          // group b (TB = 1, NBLK = C / 16), its k steps run over the TAPS only -- lane group g of step ks supplies the
-                         // group's 16 bytes of tap 4 ks + g -- against block-diagonal weights (ops.hip build_dw_mm_rt_weights)
+                         // group's 16 bytes of tap 4 ks + g -- against block-diagonal weights (wimage.cpp build_dw_mm_rt_weights)
     int NTHR;            // threads per workgroup: 256, or 1024 when the weights leave room for one workgroup per CU only
     uint32_t izp4;
     float lo_f, hi_f;

@@ -260,7 +260,7 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             return false;
         };
         // (4) runs of consecutive pair groups on one tensor shape -> a persistent stage kernel, if one exists for that
-        // shape and count (ops.hip: fused_stage_create)
+        // shape and count (fused.hip: fused_stage_create)
         for (size_t i = 0; i + 1 < n; ++i) {
             if (!fused[i] || fused_last[i] != (int)i + 1) continue;
             std::vector<FusedImpl *> run;
@@ -296,7 +296,7 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
                 i += 3;
             }
         }
-        // (4b') the last pair group directly followed by the tail group -> one kernel (ops.hip: fused_pair_tail_create).  Before the
+        // (4b') the last pair group directly followed by the tail group -> one kernel (fused.hip: fused_pair_tail_create).  Before the
         // chain partition below, so that a run-time-geometry pair taken here is not also a candidate there
         for (size_t i = 0; i + 2 < n; ++i) {
             if (!fused[i] || fused_last[i] != (int)i + 1 || covered(i)) continue;
@@ -311,7 +311,7 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
                 }
         }
         // (4c) runs of consecutive run-time-geometry pairs (single-pair chain groups, k_chain.hip): the planner's cost model
-        // decides how the run is cut into chain launches (ops.hip: fused_chain_partition); a pair that is cheapest as two
+        // decides how the run is cut into chain launches (fused.hip: fused_chain_partition); a pair that is cheapest as two
         // separate launches loses its group
         for (size_t i = 0; i + 1 < n; ++i) {
             if (!fused_is_chain_single(fused[i]) || fused_last[i] != (int)i + 1 || covered(i)) continue;

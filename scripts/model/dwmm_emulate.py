@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Lane-level emulation of dwpw_mm's depthwise phase (k_fused_mm.hip) in numpy: the staging swizzle, the
-unit / wave decomposition, the host-built block-diagonal A operands (ops.hip: build_dw_mm_weights), the
+unit / wave decomposition, the host-built block-diagonal A operands (wimage.cpp: build_dw_mm_weights), the
 v_mfma_i32_16x16x64_i8 operand layouts and the planar MID, checked against a direct depthwise convolution;
 then the pointwise phase's MID reads are checked to fetch (pixel, k) at the K position the MFMA expects.
 Index arithmetic is transcribed from the kernel, formula by formula.  No GPU needed.
@@ -271,7 +271,7 @@ def rr_shapes_from_header():
 
 
 def build_pw_rr_weights(w, K, N):
-    """w [N][K] int8 -> [NT][64][8]   (ops.hip: build_pw_rr_weights)"""
+    """w [N][K] int8 -> [NT][64][8]   (wimage.cpp: build_pw_rr_weights)"""
     pair = K == 8
     NT = (2 * N if pair else N) // 16
     out = np.zeros((NT, 64, 8), np.int8)

@@ -1,6 +1,7 @@
 """k_dw_gemm.hip without a GPU: the generated code keeps the house rules (no barrier reached with LDS operations pending, M0
 written only inside the LDS-DMA helper's asm, the int8 matrix instruction, no scratch, no scalar stores or atomics).  The host-side
-plan and the routing are exercised through the library on the GPU (tests/test_gpu_dw_gemm.py)."""
+plan and the routing are exercised through the library on the GPU (tests/test_gpu_dw_gemm.py), its operand A layout in
+tests/test_wimage_host.py."""
 import importlib.util
 import os
 import re

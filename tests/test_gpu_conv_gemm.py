@@ -57,7 +57,7 @@ def _mm_ok(W, C, N, KH, KW, wz):
 
 
 def on_generic_today(H, W, C, N, KH, KW, sh, sw, same, wz):
-    """the Conv2D routing of the parent commit (ops.hip) for the shapes sampled here: no 1x1 stride-1 filters (pw_rt,
+    """the Conv2D routing of the parent commit (ops.hip route_*) for the shapes sampled here: no 1x1 stride-1 filters (pw_rt,
     conv1x1_rowwave, the tables), finite constants"""
     assert not (KH == 1 and KW == 1 and sh == 1 and sw == 1)
     OH, OW = _out_hw(H, W, KH, KW, sh, sw, same)

@@ -30,7 +30,7 @@ def _out_hw(H, W, KH, KW, sh, sw, same):
 
 
 def on_generic_today(H, W, C, KH, KW, sh, sw, same, wz):
-    """the DepthwiseConv2D routing of the parent commit (ops.hip) for the shapes sampled here: C == N >= 2, finite constants, images
+    """the DepthwiseConv2D routing of the parent commit (ops.hip route_*) for the shapes sampled here: C == N >= 2, finite constants, images
     small enough for every planner's budget.  The 3x3 SAME stride-1 / 2 family runs the tables or dw3x3_rt (dw_rt_plan: C % 4 == 0,
     W C % 16 == 0), with or without filter zero points; dw_mm_rt takes C % 16 == 0 without them; everything else ran dwconv_generic."""
     if KH == 3 and KW == 3 and same and sh == sw and sh in (1, 2) and C % 4 == 0 and (W * C) % 16 == 0:

@@ -400,7 +400,7 @@ def test_graph_replay_equals_eager(name, batch):
 @pytest.mark.gpu
 def test_graph_replay_of_a_fully_connected_with_a_weight_zero_point():
     """the row-sum pre-pass of a FullyConnected with wzp != 0 uses the operator's one scratch buffer, whose event
-    handshake (ops.hip scratch_acquire / _release) must stay out of a stream capture: a captured wait on an event recorded outside
+    handshake (ops_impl.hpp scratch_acquire / _release) must stay out of a stream capture: a captured wait on an event recorded outside
     the capture is not legal, and an event recorded into the graph would leave later eager waits looking at a stale record.
     Eager, captured + replayed, replayed again, then eager again on another stream -- all the same bytes."""
     import torch
