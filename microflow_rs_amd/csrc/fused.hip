@@ -734,6 +734,54 @@ void fused_chain_partition(FusedImpl *const *groups, int n, int *seg_len, bool *
         const std::pair<OpImpl *, OpImpl *> &m = groups[i]->chain_members[0];
         geo[(size_t)i] = chain_geom(m.first, m.second);
     }
+    // A forced plan (MF_CHAIN_PLAN, read NOW: one process prepares the same model under many plans) replaces both the dynamic
+    // programme and the timing.  Every segment is made by the functions autotune installs its winners with -- fused_chain_create,
+    // chain_create + swap -- behind the same chain_plan feasibility checks, so that the switch can install nothing autotune could
+    // not; a segment that cannot be made fails the preparation (a test must never pass on the planner's plan after all).
+    if (switches().dev) {
+        const Switches now = switches_parse();
+        if (now.chain_plan_set) {
+            if (!now.chain_plan_error.empty()) fail(MF_ERR_INVALID_ARG, "MF_CHAIN_PLAN: " + now.chain_plan_error);
+            const bool verbose = switches().chain_verbose;
+            for (int i = 0; i < n; ++i) seg_len[i] = 0, unfused[i] = false;
+            if (seg_G) for (int i = 0; i < n; ++i) seg_G[i] = 0;
+            int i = 0;
+            for (size_t e = 0; e < now.chain_plan.size(); ++e) {
+                const ChainPlanSeg &sp = now.chain_plan[e];
+                const int len = std::max(sp.len, 1);
+                const std::string what = "MF_CHAIN_PLAN segment " + std::to_string(e) + " (" + std::to_string(sp.len) + ":" + std::to_string(sp.G) + ":" +
+                                         std::to_string(sp.dbuf) + ", pairs " + std::to_string(i) + ".." + std::to_string(i + len - 1) + " of " + std::to_string(n) + ")";
+                if (i + len > n) fail(MF_ERR_UNSUPPORTED, what + ": past the end of the run");
+                seg_len[i] = len;
+                const k::ChainArgs *made = nullptr;
+                std::unique_ptr<FusedImpl> trial;
+                if (sp.len == 0) {
+                    unfused[i] = true;
+                } else if (sp.len == 1) {
+                    if (sp.G > 0 || sp.dbuf >= 0) {
+                        trial.reset(chain_create(&groups[i]->chain_members[0], 1, sp.G, sp.dbuf));
+                        if (!trial) fail(MF_ERR_UNSUPPORTED, what + ": no such plan");
+                        if (sp.dbuf >= 0 && trial->chain.dbuf != sp.dbuf) fail(MF_ERR_UNSUPPORTED, what + ": the input tile does not fit twice");
+                        std::swap(*groups[i], *trial);
+                    }
+                    made = &groups[i]->chain;
+                } else {
+                    if (!seg_G) fail(MF_ERR_UNSUPPORTED, what + ": the caller takes no images per step");
+                    trial.reset(fused_chain_create(groups + i, len, sp.G)); // (the caller makes the same one again from seg_G)
+                    if (!trial) fail(MF_ERR_UNSUPPORTED, what + ": no such plan");
+                    seg_G[i] = sp.G;
+                    made = &trial->chain;
+                }
+                if (verbose) {
+                    if (made) fprintf(stderr, "[microflow_amd] chain plan forced: pairs %d..%d G %d dbuf %d nwave %d lds %d\n", i, i + len - 1, made->G, made->dbuf, made->nwave, made->lds_bytes);
+                    else fprintf(stderr, "[microflow_amd] chain plan forced: pair %d unfused\n", i);
+                }
+                i += len;
+            }
+            if (i != n) fail(MF_ERR_UNSUPPORTED, "MF_CHAIN_PLAN covers " + std::to_string(i) + " pairs of a run of " + std::to_string(n));
+            return;
+        }
+    }
     const bool force_fuse = switches().chain_force; // tests: never prefer the unfused operators
     const double INF = 1e30;
     std::vector<double> best((size_t)n + 1, INF);

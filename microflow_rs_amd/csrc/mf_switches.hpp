@@ -6,11 +6,23 @@
 // (scripts/switch_matrix.sh: the parity suite must be green under every MF_NO_* switch, because each turns one fused kernel off
 // and sends its operators down the next more general path) and of the tuning scripts (scripts/tune_*.sh, scripts/dq_*.py).
 // The environment is read ONCE, at the first call of switches(); the only exception is the step-queue tuning set, re-read per
-// launch while MF_DQ_TUNE is set (scripts/dq_sweep.py changes it between launches of one process).
+// launch while MF_DQ_TUNE is set (scripts/dq_sweep.py changes it between launches of one process), and the forced chain plan,
+// re-read at every model preparation (tests/test_gpu_chain_plans.py prepares one model under many plans in one process).
 #pragma once
 #include <string>
+#include <vector>
 
 namespace mf {
+
+// One entry of a forced chain plan: `len` consecutive pairs of a run of run-time-geometry pairs as one chain_rt launch.
+struct ChainPlanSeg {
+    int len;   // 0: this ONE pair runs as its two separate operators; 1: alone in a launch; 2 .. 16: a chain of that many pairs
+    int G;     // images per step (0: the planner's choice)
+    int dbuf;  // double buffering of the input tile, a single pair's choice only (-1: the planner's rule, 0 off, 1 on)
+};
+// "len:G:dbuf,len:G:dbuf,..." -> segments; false (and why in `err`) for anything else.  Only the form is checked here: whether a
+// segment can be realised on a given run of pairs is decided where the plan is applied (fused.hip: fused_chain_partition).
+bool chain_plan_parse(const char *text, std::vector<ChainPlanSeg> &out, std::string &err);
 
 struct Switches {
     bool dev = false;              // MF_DEV=1            master switch: without it every field below the diagnostics keeps its default
@@ -60,6 +72,10 @@ struct Switches {
     bool chain_tune_g = true;      // MF_CHAIN_TUNE_G=0   autotune keeps the model's images-per-step
     double chain_opcost = 1.0;     // MF_CHAIN_OPCOST     weight of the operand-reload term of the chain cost model
     bool chain_dq_auto = false;    // MF_CHAIN_DQ_AUTO    chains take the automatic step-queue configuration even for short launches
+    bool chain_plan_set = false;   // MF_CHAIN_PLAN       "len:G:dbuf,..." one entry per segment of a run of pairs, in order: this plan instead of the
+                                   //                     cost model's or the measured one, or mf_model_prepare fails (no fallback); tests only
+    std::vector<ChainPlanSeg> chain_plan; // ... parsed
+    std::string chain_plan_error;  // ... why it did not parse (empty: it did)
     // ---- step queue (k_common.hpp dq_config) ----
     bool dq_tune = false;          // MF_DQ_TUNE          re-read MF_DQ_CFG / MF_DQ_CFGS at every launch
     bool dq_cfg_set = false;       // MF_DQ_CFG present

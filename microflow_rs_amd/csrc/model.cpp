@@ -313,8 +313,10 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
         // (4c) runs of consecutive run-time-geometry pairs (single-pair chain groups, k_chain.hip): the planner's cost model
         // decides how the run is cut into chain launches (fused.hip: fused_chain_partition); a pair that is cheapest as two
         // separate launches loses its group
+        bool chain_runs = false;
         for (size_t i = 0; i + 1 < n; ++i) {
             if (!fused_is_chain_single(fused[i]) || fused_last[i] != (int)i + 1 || covered(i)) continue;
+            chain_runs = true;
             std::vector<FusedImpl *> run;
             size_t a = i;
             while (a + 1 < n && fused_is_chain_single(fused[a]) && fused_last[a] == (int)a + 1 && !covered(a)) {
@@ -337,6 +339,9 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             }
             i = a - 1;
         }
+        // (a forced chain plan that met no run was applied to nothing: the caller must not take the result for that plan's)
+        if (!chain_runs && switches().dev && switches_parse().chain_plan_set)
+            fail(MF_ERR_UNSUPPORTED, "MF_CHAIN_PLAN segment 0: the model has no run of run-time-geometry pairs");
         // (5) DepthwiseConv2D with one input channel -> [Reshape] -> the FullyConnected + Softmax group -> one kernel
         for (size_t i = 0; i + 1 < n; ++i) {
             if (!ops[i] || fused[i] || covered(i) || m->pm.ops[i].kind != MF_OP_DEPTHWISE_CONV_2D) continue;

@@ -1,12 +1,53 @@
 // The library's environment switches, parsed once (mf_switches.hpp says what each one is for).
 #include "mf_switches.hpp"
 #include <cstdlib>
+#include <string>
 
 namespace mf {
 
 static bool env_set(const char *name) { return getenv(name) != nullptr; }
 static bool env_is(const char *name, char first) { const char *e = getenv(name); return e && e[0] == first; }
 static long long env_ll(const char *name, long long dflt) { const char *e = getenv(name); return e ? strtoll(e, nullptr, 0) : dflt; }
+
+bool chain_plan_parse(const char *text, std::vector<ChainPlanSeg> &out, std::string &err) {
+    out.clear(), err.clear();
+    auto bad = [&](const std::string &why) {
+        out.clear();
+        err = why;
+        return false;
+    };
+    if (!text || !*text) return bad("empty plan");
+    const char *p = text;
+    for (;;) {
+        int v[3];
+        for (int f = 0; f < 3; ++f) {
+            // a decimal integer, optionally negative, nothing else (no blanks, no '+', no hexadecimal)
+            const bool neg = *p == '-';
+            const char *d = p + (neg ? 1 : 0);
+            if (*d < '0' || *d > '9') return bad("entry " + std::to_string(out.size()) + ": expected len:G:dbuf");
+            long n = 0;
+            for (; *d >= '0' && *d <= '9'; ++d)
+                if ((n = n * 10 + (*d - '0')) > 100000) return bad("entry " + std::to_string(out.size()) + ": number too large");
+            v[f] = (int)(neg ? -n : n);
+            p = d;
+            if (f < 2) {
+                if (*p != ':') return bad("entry " + std::to_string(out.size()) + ": expected len:G:dbuf");
+                ++p;
+            }
+        }
+        const ChainPlanSeg s{v[0], v[1], v[2]};
+        const std::string at = "entry " + std::to_string(out.size()) + ": ";
+        if (s.len < 0 || s.len > 16) return bad(at + "len outside 0 .. 16");
+        if (s.G < 0 || s.G > 128) return bad(at + "G outside 0 .. 128");
+        if (s.dbuf < -1 || s.dbuf > 1) return bad(at + "dbuf outside -1 .. 1");
+        if (s.len == 0 && (s.G != 0 || s.dbuf != -1)) return bad(at + "an unfused pair (len 0) takes G 0 and dbuf -1");
+        if (s.len >= 2 && s.dbuf != -1) return bad(at + "double buffering is a single pair's choice (len 1): a chain takes dbuf -1");
+        out.push_back(s);
+        if (!*p) return true;
+        if (*p != ',') return bad(at + "expected ',' or the end");
+        ++p;
+    }
+}
 
 Switches switches_parse() {
     Switches s;
@@ -61,6 +102,7 @@ Switches switches_parse() {
     s.chain_tune_g = !env_is("MF_CHAIN_TUNE_G", '0');
     if (const char *e = getenv("MF_CHAIN_OPCOST")) s.chain_opcost = atof(e);
     s.chain_dq_auto = env_set("MF_CHAIN_DQ_AUTO");
+    if (const char *e = getenv("MF_CHAIN_PLAN")) s.chain_plan_set = true, chain_plan_parse(e, s.chain_plan, s.chain_plan_error);
     s.dq_tune = env_set("MF_DQ_TUNE");
     s.dq_cfg_set = env_set("MF_DQ_CFG");
     s.dq_cfg = (int)env_ll("MF_DQ_CFG", 0);

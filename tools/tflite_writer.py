@@ -241,15 +241,24 @@ def mlp(rng, sizes, elem=INT8, wzp_nonzero=False, softmax=False, act="relu", spa
     return build_model((1, int(sizes[0])), in_q, layers, elem)
 
 
-def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None):
+def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, wmax=None, in_zp=None, act_scale=None):
     """A convolution stack: input_shape = (H, W, C); convs = [(op, N, K, stride), ...] with op "conv" (KxK Conv2D to N channels)
     or "dw" (KxK depthwise, N ignored), all SAME, relu6; per-channel filter quantization, filter zero points off the middle when
     wzp_nonzero (Conv2D only: the depthwise kernels keep theirs at the middle).  head = classes: AveragePool over the whole
-    image, FullyConnected(classes) and Softmax after the stack.  Output scales keep every layer's outputs spread over the range."""
+    image, FullyConnected(classes) and Softmax after the stack.  Output scales keep every layer's outputs spread over the range.
+    `wmax`: weights within +-wmax of the type's middle (None: the full range, the worst case for the accumulator bounds that decide
+    the epilogue form); `in_zp`: the input's zero point (None: a random one; every later tensor's is the type's minimum);
+    `act_scale`: every tensor, the input included, has this scale (6 / 255: relu6 is then the type's whole range, as in
+    person_detect.tflite) and the filter scales are person_detect_like's, which keep the activations of a deep stack spread over it --
+    the default's growing output scales leave relu6 a few dozen levels after a few layers."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     H, W, C = input_shape
     in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    if in_zp is not None:
+        in_q = (in_q[0], int(in_zp))
+    if act_scale is not None:
+        in_q = (float(np.float32(act_scale)), in_q[1])
     q, layers = in_q, []
     for op, n, k, s in convs:
         oh, ow = -(-H // s), -(-W // s)
@@ -259,10 +268,14 @@ def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None):
         zp = rng.integers(mid - 10, mid + 11, n) if wzp_nonzero and not dw else np.full(n, mid)
         taps = k * k * (1 if dw else C)
         osc = float(np.float32(q[0] * float(sc.mean()) * 60.0 * np.sqrt(taps)))
+        if act_scale is not None:
+            sc = (rng.uniform(0.6, 1.4, n) * 2.2 / (74.0 * np.sqrt(taps)) * (128.0 / (wmax or 128))).astype(np.float32)
+            osc = float(np.float32(act_scale))
         d = dict(op="depthwise_conv_2d" if dw else "conv_2d", fscale=sc, fzp=zp, bias=rng.integers(-500, 500, n),
                  bscale=(sc * np.float32(q[0])).astype(np.float32), bzp=np.zeros(n, np.int64), padding="same", strides=(s, s),
                  act="relu6", out_shape=(1, oh, ow, n), out_q=(osc, lo))
-        d["weights" if dw else "filters"] = rng.integers(lo, hi, (1, k, k, n) if dw else (n, k, k, C))
+        wshape = (1, k, k, n) if dw else (n, k, k, C)
+        d["weights" if dw else "filters"] = rng.integers(lo, hi, wshape) if wmax is None else rng.integers(mid - wmax, mid + wmax + 1, wshape)
         layers.append(d)
         q, H, W, C = d["out_q"], oh, ow, n
     if head:
