@@ -14,7 +14,7 @@
 namespace mf {
 
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN } kind;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC } kind;
     OpImpl *a, *b, *c;
     k::DwPwArgs dwpw;
     k::TailArgs tail;
@@ -40,6 +40,8 @@ struct FusedImpl {
     // FCCHAIN: consecutive FullyConnected layers (+ Softmax) in one launch (k_fc_rt.hip fc_chain); the layers' fc_rt images
     k::FcChainArgs fcchain{};
     long long fcchain_M = 1; // rows per inference
+    // POOLFC: the global AveragePool2D + FullyConnected layers (+ Softmax) in one launch (k_pool_fc.hip pool_fc_chain); a = the pool
+    k::PoolFcArgs poolfc{};
     int epi_mode = -1; // epilogue mode (k_common.hpp) of the launch's requantising operators; -1: not recorded (the operators' minimum)
 };
 // the pair's argument blocks as the operators hold them (two-rounding constants), and switched to the single-fma form when
@@ -297,8 +299,8 @@ static bool fc_chain_args(OpImpl *const *fcs, int n, OpImpl *sm, k::FcChainArgs 
     int mode = 3;
     for (int l = 0; l < n; ++l) {
         const OpImpl *o = fcs[l];
-        if (!o || o->s.kind != MF_OP_FULLY_CONNECTED || !o->fcrt_ok || o->s.M != fcs[0]->s.M || o->s.u8 != fcs[0]->s.u8 ||
-            o->device != fcs[0]->device)
+        if (!o || o->s.kind != MF_OP_FULLY_CONNECTED || !o->fcrt_ok || o->fast == OpImpl::FC_ROWWAVE || o->s.M != fcs[0]->s.M ||
+            o->s.u8 != fcs[0]->s.u8 || o->device != fcs[0]->device)
             return false;
         const k::FcRtArgs &f = o->fcrt;
         k::FcChainLayer &y = a.l[l];
@@ -325,6 +327,55 @@ FusedImpl *fused_fc_chain_create(OpImpl *const *fcs, int n, OpImpl *sm) {
     f->fcchain = a, f->fcchain_M = fcs[0]->s.M, f->epi_mode = a.magic;
     return f;
 }
+
+// AveragePool2D over the whole image (one output pixel whose in-range taps are every pixel) -> [Reshape] -> FullyConnected layers
+// with one row per inference, the first reading the C pooled values -> [Softmax over the last layer's outputs], as one pool_fc_chain
+// launch; false when the pool is not the global one, C % 16 != 0, a constant is not finite, a layer has no fc_rt image, or the images
+// and tiles do not fit the LDS budget (k::pool_fc_plan)
+static bool pool_fc_args(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm, k::PoolFcArgs &a) {
+    if (switches().no_pool_fc || !pool || n < 1 || n > k::FC_CHAIN_MAX) return false;
+    const OpSpec &p = pool->s;
+    if (p.kind != MF_OP_AVERAGE_POOL_2D || p.OH != 1 || p.OW != 1 || p.C % 16 != 0) return false;
+    if (!std::isfinite(p.pool_c0) || !std::isfinite(p.pool_c1)) return false;
+    // the in-range taps of the single window (focus (0,0); src/tensor.rs:180-228) must be the whole image
+    const int shy = p.pad == MF_PAD_SAME ? (p.KH - 1) / 2 : 0, shx = p.pad == MF_PAD_SAME ? (p.KW - 1) / 2 : 0;
+    if (p.KH - 1 - shy < p.H - 1 || p.KW - 1 - shx < p.W - 1) return false;
+    a = k::PoolFcArgs{};
+    k::FcChainArgs &c = a.c;
+    c.L = n;
+    int mode = 3;
+    for (int l = 0; l < n; ++l) {
+        const OpImpl *o = fcs[l];
+        if (!o || o->s.kind != MF_OP_FULLY_CONNECTED || !o->fcrt_ok || o->s.M != 1 || o->s.u8 != p.u8 || o->device != pool->device) return false;
+        const k::FcRtArgs &f = o->fcrt;
+        k::FcChainLayer &y = c.l[l];
+        y.wimg = f.wimg, y.A = f.A, y.Kc = f.Kc, y.S = f.S, y.lo_f = f.lo_f, y.hi_f = f.hi_f, y.K = f.K, y.N = f.N, y.wzp = f.wzp;
+        mode = std::min(mode, f.magic);
+    }
+    if (fcs[0]->s.K != p.C) return false;
+    if (sm) {
+        if (sm->s.kind != MF_OP_SOFTMAX || sm->s.M != 1 || sm->s.N != fcs[n - 1]->s.N || sm->s.u8 != p.u8 || sm->device != pool->device) return false;
+        c.softmax = 1, c.sm = sm->sm;
+    }
+    c.magic = mode, c.xr = fcs[0]->fcrt.xr;
+    a.P = p.H * p.W, a.C = p.C;
+    a.c0 = pool->pool.c0, a.c1 = pool->pool.c1, a.lo = pool->pool.lo, a.hi = pool->pool.hi, a.bias = pool->pool.bias;
+    a.sat_lo = pool->pool.sat_lo, a.sat_hi = pool->pool.sat_hi;
+    if (pool->pool.xr != c.xr) return false;
+    return k::pool_fc_plan(a);
+}
+bool fused_pool_fc_fits(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm) {
+    k::PoolFcArgs a;
+    return pool_fc_args(pool, fcs, n, sm, a);
+}
+FusedImpl *fused_pool_fc_create(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm) {
+    k::PoolFcArgs a;
+    if (!pool_fc_args(pool, fcs, n, sm, a)) return nullptr;
+    FusedImpl *f = new FusedImpl{FusedImpl::POOLFC, pool, fcs[n - 1], sm, {}, {}, "pool_fc_chain<" + std::to_string(n) + (sm ? ">+sm" : ">")};
+    f->poolfc = a, f->epi_mode = a.c.magic;
+    return f;
+}
+bool fused_input_ok(const FusedImpl *f, const int8_t *d_in) { return f->kind != FusedImpl::POOLFC || ((uintptr_t)d_in & 15) == 0; }
 
 // A run of `npairs` identical DepthwiseConv2D 3x3 (stride 1) + Conv2D 1x1 pairs on one small tensor as one persistent
 // kernel (k_stage.hip: five pairs on 6x6x128 = person_detect ops 13..22).  `pairs` are the already created pair
@@ -659,6 +710,12 @@ void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, vo
     }
     if (f->kind == FusedImpl::FCCHAIN) { // (no pointer alignment needed: fc_chain aligns its DMA and stores itself)
         k::launch_fc_chain(d_in, d_out, f->fcchain, (long long)(batch * f->fcchain_M), (hipStream_t)stream);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (f->kind == FusedImpl::POOLFC) { // (any output pointer: the kernel aligns its stores itself)
+        if (!fused_input_ok(f, d_in)) fail(MF_ERR_INVALID_ARG, "pool_fc_chain: the input pointer is not 16-byte aligned");
+        k::launch_pool_fc(d_in, d_out, f->poolfc, (long long)batch, (hipStream_t)stream);
         MF_HIP(hipGetLastError());
         return;
     }

@@ -26,6 +26,7 @@
 // Epilogue: requant_pack4<MG, XR4> (k_common.hpp), modes 0 .. 2 as the host proved them for the operator's constants;
 // mode 0 converts the accumulator with v_cvt (round to nearest), which is fc_generic's (float)acc for every |acc|.
 #include "k_common.hpp"
+#include "k_fc_layer.hpp"
 
 #include <algorithm>
 
@@ -241,68 +242,9 @@ void launch_fc_rt(const int8_t *in, int8_t *out, const FcRtArgs &a, long long ro
 // N slice: every layer's whole image resident in LDS, the step's R input rows staged by LDS-DMA (from the 16-byte-aligned
 // ABSOLUTE address below them, so that no pointer needs any alignment), and then per layer: products over the source rows in LDS
 // -> the layer's own epilogue (requant_pack4, same bytes as its layer-wise launch) -> its int8 [R][N_l] tile in an LDS activation
-// buffer, which is the next layer's operand.  Only the first input and the last output touch HBM.
+// buffer, which is the next layer's operand.  Only the first input and the last output touch HBM.  (The layer step, the Softmax and
+// the patch store are k_fc_layer.hpp's: pool_fc_chain, k_pool_fc.hip, runs the same ones behind its pool phase.)
 // ------------------------------------------------------------------------
-template <int MG, uint32_t XR4>
-__device__ __forceinline__ void fc_chain_layer(const FcChainLayer &L, const uint8_t *src, uint8_t *dst, const uint8_t *W, int R, int wave,
-                                               int lane) {
-    const int K = L.K, N = L.N, KS = L.KS, TB = L.TB, nts = L.NT;
-    const int col = lane & 15, g = lane >> 4;
-    uint32_t km[4];
-    {
-        const int rem = K - (KS - 1) * 64 - g * 16;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int nb = min(max(rem - 4 * i, 0), 4);
-            km[i] = nb >= 4 ? 0xffffffffu : (1u << (8 * nb)) - 1u;
-        }
-    }
-    const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
-    const int CH = R / 16, ngr = (nts + TB - 1) / TB, units = CH * ngr;
-    for (int u = wave; u < units; u += 4) {
-        const int c = u % CH, grp = u / CH;
-        const int lt0 = grp * TB, tb = min(TB, nts - lt0);
-        const int rr = c * 16 + col;
-        const int base = rr * K + g * 16;
-        v4i acc[4], rsa = {0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (i < tb) {
-                const int4 kc = magic4<MG>(*(const int4 *)(L.Kc + (lt0 + i) * 16 + g * 4));
-                acc[i] = v4i{kc.x, kc.y, kc.z, kc.w};
-            }
-        }
-        for (int ks = 0; ks < KS; ++ks) {
-            const int off = base + ks * 64;
-            const uint32_t *q = (const uint32_t *)(src + (off & ~3));
-            const uint32_t sh = off & 3, d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = q[4];
-            v4i b = v4i{(int)__builtin_amdgcn_alignbyte(d1, d0, sh), (int)__builtin_amdgcn_alignbyte(d2, d1, sh),
-                        (int)__builtin_amdgcn_alignbyte(d3, d2, sh), (int)__builtin_amdgcn_alignbyte(d4, d3, sh)};
-            if (ks == KS - 1) b &= v4i{(int)km[0], (int)km[1], (int)km[2], (int)km[3]};
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < tb) acc[i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(*(const v4i *)(W + (((lt0 + i) * KS + ks) * 64 + lane) * 16), b, acc[i], 0, 0, 0);
-            if (L.wzp) rsa = __builtin_amdgcn_mfma_i32_16x16x64_i8(ones, b, rsa, 0, 0, 0);
-        }
-        const int wr = L.wzp * rsa[0];
-        const float4 S4 = {L.S, L.S, L.S, L.S};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (i < tb) {
-                const int ch = (lt0 + i) * 16 + g * 4;
-                v4i a = acc[i];
-                a[0] -= wr, a[1] -= wr, a[2] -= wr, a[3] -= wr;
-                const float4 A4 = *(const float4 *)(L.A + ch);
-                const uint32_t d = requant_pack4<MG, XR4>(a[0], a[1], a[2], a[3], A4, S4, L.lo_f, L.hi_f);
-                uint8_t *dp = dst + rr * N + ch;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (ch + j < N) dp[j] = (uint8_t)(d >> (8 * j));
-            }
-        }
-    }
-}
-
 template <int MG, uint32_t XR4>
 __global__ __launch_bounds__(256) void fc_chain(const int8_t *__restrict__ in, int8_t *__restrict__ out, FcChainArgs p, long long rows) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -343,34 +285,11 @@ __global__ __launch_bounds__(256) void fc_chain(const int8_t *__restrict__ in, i
             src = dst;
         }
         if (p.softmax) {
-            // microflow::ops::softmax over the N outputs of each row (softmax_table's arithmetic, k_generic.hip)
-            for (int r = tid; r < nr; r += 256) {
-                const int8_t *x = (const int8_t *)src + r * NL;
-                uint8_t *y = PT + osh + r * NL;
-                float sum = 0.0f;
-                for (int j = 0; j < NL; ++j) sum = __fadd_rn(sum, p.sm.exp_table[(int)x[j] + 128]);
-                for (int j = 0; j < NL; ++j) {
-                    const float ev = p.sm.exp_table[(int)x[j] + 128];
-                    const float prob = __fdiv_rn(ev, sum);
-                    const float q = __fadd_rn(__fdiv_rn(prob, p.sm.oscale), p.sm.ozp_f);
-                    const float rq = __fadd_rn(q, __builtin_copysignf(0x1.fffffep-2f, q));
-                    const int qi = (rq != rq) ? 0 : (int)__builtin_amdgcn_fmed3f(rq, p.sm.sat_lo, p.sm.sat_hi);
-                    y[j] = (uint8_t)(qi ^ p.sm.xr);
-                }
-            }
+            fc_chain_softmax(p.sm, src, PT + osh, nr, NL, tid);
             wg_sync();
         }
         if (p.NBUF == 1 && t + gridDim.x < ntiles) stage(t + gridDim.x, lds + p.xoff);
-        int8_t *gs = out + r0 * NL, *ge = gs + (long long)nr * NL;
-        const uintptr_t ugs = (uintptr_t)gs, uge = (uintptr_t)ge;
-        const uintptr_t up = (ugs + 15) & ~(uintptr_t)15, dn = uge & ~(uintptr_t)15;
-        const uintptr_t hb = up < uge ? up : uge, te = dn > hb ? dn : hb;
-        const int nhead = (int)(hb - ugs), nbody = (int)((te - hb) >> 4), ntail = (int)(uge - te);
-        const uint8_t *po = PT + osh;
-        for (int i = tid; i < nbody; i += 256)
-            *(v4i *)(gs + nhead + i * 16) = *(const v4i *)(po + nhead + i * 16);
-        if (tid < nhead) gs[tid] = (int8_t)po[tid];
-        else if (tid >= 64 && tid < 64 + ntail) gs[nhead + nbody * 16 + (tid - 64)] = (int8_t)po[nhead + nbody * 16 + (tid - 64)];
+        fc_chain_store_patch(out + r0 * NL, PT + osh, (long long)nr * NL, tid);
         cur ^= p.NBUF - 1;
     }
 }

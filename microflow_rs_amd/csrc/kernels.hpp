@@ -681,6 +681,21 @@ struct FcChainArgs {
 // fills the geometry of a chain whose layers' K, N, S, ... are set in a.l[0 .. L-1]; false: it does not fit the LDS budget
 bool fc_chain_plan(FcChainArgs &a);
 void launch_fc_chain(const int8_t *in, int8_t *out, const FcChainArgs &a, long long rows, hipStream_t s);
+// The global AveragePool2D of an [H][W][C] image (every pixel in the window, C % 16 == 0) + 1 .. FC_CHAIN_MAX FullyConnected layers
+// (+ a Softmax) in one launch (k_pool_fc.hip: pool_fc_chain).  The pool phase sums the pixels on the matrix pipe straight from HBM
+// and leaves the pooled int8 [R][C] tile in LDS; from there on the step is fc_chain's.
+struct PoolFcArgs {
+    FcChainArgs c;      // the layers (l[0].K == C), R images per step, softmax, magic, xr; xoff / xbytes: the pooled [R][C] tile; NBUF = 1
+    int P, C;           // pixels per image (H W), channels
+    int CGW, NS;        // a column of the product: channel group (pass 16 + j % CGW), pixel subset j / CGW (< NS); CGW = min(C / 16, 16)
+    int NPASS, NIT;     // passes of 16 channel groups over C; loads of 4 NS pixels per (image, pass)
+    float inv, c0, c1;  // 1 / f32(P); average_pool_2d's constants
+    int lo, hi, bias;   // as PoolArgs
+    float sat_lo, sat_hi;
+};
+// fills the geometry from c.L, c.l[].K / N, c.softmax, P and C; false: C % 16 != 0, or the images and tiles do not fit the LDS budget
+bool pool_fc_plan(PoolFcArgs &a);
+void launch_pool_fc(const int8_t *in, int8_t *out, const PoolFcArgs &a, long long batch, hipStream_t s); // `in` 16-byte aligned
 
 void launch_softmax(const int8_t *in, int8_t *out, const SoftmaxArgs &a, size_t batch, hipStream_t s);
 // number of float bit patterns (of all 2^32) whose quantised byte differs between quant_div's fast form and the true

@@ -154,6 +154,13 @@ FusedImpl *fused_fc_softmax_create(OpImpl *fc, OpImpl *softmax);
 // consecutive FullyConnected operators (+ a Softmax over one row: sm, or nullptr) as one fc_chain launch (k_fc_rt.hip)
 bool fused_fc_chain_fits(OpImpl *const *fcs, int n, OpImpl *sm);
 FusedImpl *fused_fc_chain_create(OpImpl *const *fcs, int n, OpImpl *sm);
+// the global AveragePool2D + the FullyConnected operators behind it (+ a Softmax over one row: sm, or nullptr) as one pool_fc_chain
+// launch (k_pool_fc.hip; second level: a fc_rowwave_softmax group inside it stays for run_until pieces)
+bool fused_pool_fc_fits(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm);
+FusedImpl *fused_pool_fc_create(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm);
+// false: this launch cannot take the group's kernel on this input pointer (pool_fc_chain loads 16-byte words) and the operators run
+// their own launches, as op_run decides for a single operator
+bool fused_input_ok(const FusedImpl *f, const int8_t *d_in);
 // a run of identical depthwise + pointwise pair groups as one persistent kernel (borrows their device buffers:
 // destroy it before them); nullptr when no stage kernel exists for the shape / count
 FusedImpl *fused_stage_create(FusedImpl *const *pairs, int npairs);

@@ -350,9 +350,6 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             if (j < n && fused[j] && !covered(j))
                 if (FusedImpl *f = fused_dwfc_create(ops[i], fused[j])) sg.v.push_back({f, (int)i, fused_last[j]});
         }
-        // (6) runs of consecutive FullyConnected operators (Reshapes between them keeping the [M][N] rows; + a Softmax over one row at
-        // the end) that no group above took -> fc_chain launches (k_fc_rt.hip), cut greedily into the longest chains whose weights fit
-        // the LDS budget; a layer that fits no chain keeps its own launch
         auto owned = [&](size_t i) {
             for (size_t j = 0; j < i; ++j)
                 if (fused[j] && fused_last[j] >= (int)i) return true;
@@ -361,6 +358,49 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
         auto free_fc = [&](size_t i) {
             return i < n && ops[i] && m->pm.ops[i].kind == MF_OP_FULLY_CONNECTED && !fused[i] && !covered(i) && !owned(i);
         };
+        auto free_sm = [&](size_t i) {
+            return i < n && ops[i] && m->pm.ops[i].kind == MF_OP_SOFTMAX && !fused[i] && !covered(i) && !owned(i);
+        };
+        auto skip_reshapes = [&](size_t j) {
+            while (j < n && m->pm.ops[j].kind == MF_OP_RESHAPE) ++j;
+            return j;
+        };
+        // (5b) AveragePool2D over the whole image -> [Reshape] -> FullyConnected layers (one row per inference) -> [Softmax] -> one
+        // pool_fc_chain launch (fused.hip: fused_pool_fc_create), the longest run of layers whose images fit.  Before (6), so that the
+        // FullyConnected run behind a pool is offered here first; what does not fit stays for (6) or keeps its own launches.  Where the
+        // head's FullyConnected + Softmax already are a group of (3), this stage sits over pool .. softmax and that group stays for
+        // mf_model_run_until pieces
+        for (size_t i = 0; i + 1 < n; ++i) {
+            if (!ops[i] || fused[i] || covered(i) || owned(i) || m->pm.ops[i].kind != MF_OP_AVERAGE_POOL_2D) continue;
+            const size_t j0 = skip_reshapes(i + 1);
+            if (j0 < n && fused[j0] && !covered(j0) && m->pm.ops[j0].kind == MF_OP_FULLY_CONNECTED && fused_last[j0] > (int)j0 &&
+                m->pm.ops[(size_t)fused_last[j0]].kind == MF_OP_SOFTMAX) {
+                OpImpl *fc = ops[j0];
+                if (FusedImpl *f = fused_pool_fc_create(ops[i], &fc, 1, ops[(size_t)fused_last[j0]])) sg.v.push_back({f, (int)i, fused_last[j0]});
+                continue;
+            }
+            if (!free_fc(j0) || m->pm.ops[j0].M != 1) continue;
+            std::vector<size_t> idx{j0};
+            for (;;) {
+                const size_t j = skip_reshapes(idx.back() + 1);
+                if (!free_fc(j) || m->pm.ops[j].M != 1 || m->pm.ops[j].K != m->pm.ops[idx.back()].N) break;
+                idx.push_back(j);
+            }
+            std::vector<OpImpl *> run;
+            for (size_t j : idx) run.push_back(ops[j]);
+            for (size_t len = run.size(); len >= 1; --len) {
+                const size_t smi = skip_reshapes(idx[len - 1] + 1);
+                OpImpl *sm = free_sm(smi) ? ops[smi] : nullptr;
+                if (sm && !fused_pool_fc_fits(ops[i], run.data(), (int)len, sm)) sm = nullptr; // (the layers without their Softmax)
+                if (FusedImpl *f = fused_pool_fc_create(ops[i], run.data(), (int)len, sm)) {
+                    sg.v.push_back({f, (int)i, (int)(sm ? smi : idx[len - 1])});
+                    break;
+                }
+            }
+        }
+        // (6) runs of consecutive FullyConnected operators (Reshapes between them keeping the [M][N] rows; + a Softmax over one row at
+        // the end) that no group above took -> fc_chain launches (k_fc_rt.hip), cut greedily into the longest chains whose weights fit
+        // the LDS budget; a layer that fits no chain keeps its own launch
         for (size_t i = 0; i < n; ++i) {
             if (!free_fc(i)) continue;
             std::vector<size_t> idx{i};
@@ -483,6 +523,7 @@ static const int8_t *run_ops(ModelImpl *m, const int8_t *src, size_t batch, int 
             dst = m->act[which];
         }
         const ModelImpl::Stage *staged = stage_at(m, i, last_op);
+        if (staged && !fused_input_ok(staged->f, cur)) staged = nullptr; // (the operators' own launches take any pointer)
         const bool grouped = !staged && fused_at(m, i) && m->fused_last[(size_t)i] <= last_op;
         const int end = staged ? staged->last : (grouped ? m->fused_last[(size_t)i] : i);
         if (final_dst && end >= last_real) dst = final_dst;
@@ -708,7 +749,9 @@ void model_time_device(ModelImpl *m, const int8_t *d_in, size_t batch, int8_t *d
                         which ^= 1;
                         dst = m->act[which];
                     }
-                    if (const ModelImpl::Stage *st = stage_at(m, i, nops - 1)) { // timed as one unit (index i), its other ops 0
+                    const ModelImpl::Stage *st = stage_at(m, i, nops - 1);
+                    if (st && !fused_input_ok(st->f, cur)) st = nullptr;
+                    if (st) { // timed as one unit (index i), its other ops 0
                         fused_run(st->f, cur, batch, dst, s);
                         for (int j = i; j < st->last; ++j) MF_HIP(hipEventRecord(ev[(size_t)j + 1], s));
                         i = st->last;

@@ -700,9 +700,10 @@ void create_fc(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
             op.fast_name = a.wzp ? "fc_sparse24<wzp>" : "fc_sparse24";
         }
     }
-    if (finite && op.fast == OpImpl::NONE && k::fc_rt_plan(op.fcrt, s.K, s.N)) {
+    if (finite && (op.fast == OpImpl::NONE || op.fast == OpImpl::FC_ROWWAVE) && k::fc_rt_plan(op.fcrt, s.K, s.N)) {
         // every other shape: the int8 matrix pipe with the (sliced) weight image resident in LDS.  The image and constants are
-        // built for every such operator: a fused FullyConnected chain (fc_chain) takes them from its members.
+        // built for every such operator: a fused FullyConnected chain (fc_chain) takes them from its members.  (A row-wave shape
+        // gets them too and keeps its kernel: behind a global pool it is a layer of pool_fc_chain, fused.hip.)
         k::FcRtArgs &f = op.fcrt;
         const std::vector<int8_t> img = k::fc_rt_weight_image(s.weights, s.K, s.N);
         std::vector<float> pA((size_t)f.NT * 16, 0.0f);
@@ -730,7 +731,7 @@ void create_fc(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
         // (At most one 16 x 16 weight tile of work per row -- sine.tflite's 1 -> 16 -> 16 -> 1 -- stays on fc_generic when it
         // runs alone, which moves the same bytes without the staging latency: fc_rt was 11 % slower on sine at 65 536 rows,
         // scripts/time_fc_rt.py.  In a chain those layers run inside fc_chain.)
-        if ((long long)s.K * s.N > 256 && !switches().no_fc_rt) {
+        if (op.fast == OpImpl::NONE && (long long)s.K * s.N > 256 && !switches().no_fc_rt) {
             op.fast = OpImpl::FC_RT;
             op.fast_name = a.wzp ? "fc_rt<wzp>" : "fc_rt";
         }

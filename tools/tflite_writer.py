@@ -241,6 +241,36 @@ def mlp(rng, sizes, elem=INT8, wzp_nonzero=False, softmax=False, act="relu", spa
     return build_model((1, int(sizes[0])), in_q, layers, elem)
 
 
+def pool_head(rng, shape, sizes, elem=INT8, wzp_nonzero=False, softmax=False, same_q=False):
+    """The usual classifier head alone: input [1, H, W, C] (shape = (H, W, C)) -> AveragePool2D over the whole image -> Reshape
+    -> FullyConnected layers C -> sizes[0] -> sizes[1] ... (relu between them, none after the last) -> optionally a Softmax.
+    Per-tensor weight quantization as in mlp; wzp_nonzero gives every layer a weight zero point off the middle.  same_q: the pool's
+    output has its input's scale and zero point, so that the pooled value is the plain mean and lands on .5 ties (H W even)."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    H, W, C = (int(v) for v in shape)
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    # (a mean of uniform bytes has 1 / sqrt(H W) of their spread: a finer output scale keeps the pooled values spread out)
+    q = in_q if same_q else (float(np.float32(in_q[0] * rng.uniform(0.8, 1.2) / np.sqrt(np.sqrt(H * W)))), int(rng.integers(lo + 20, hi - 20)))
+    layers = [dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none", out_shape=(1, 1, 1, C), out_q=q),
+              dict(op="reshape", out_shape=(1, C), out_q=q)]
+    K = C
+    for i, N in enumerate(int(v) for v in sizes):
+        last = i == len(sizes) - 1
+        a = "none" if last else "relu"
+        wsc = np.float32(rng.uniform(0.002, 0.02))
+        wzp = mid + (int(rng.integers(-20, 21)) or 7 if wzp_nonzero else 0)
+        osc = float(np.float32(q[0] * wsc * (60.0 if i == 0 else 120.0) * np.sqrt(K)))
+        ozp = lo if a == "relu" else int(rng.integers(lo + 20, hi - 20))
+        layers.append(dict(op="fully_connected", weights=rng.integers(lo, hi, (N, K)), wscale=[wsc], wzp=[wzp],
+                           bias=rng.integers(-2000, 2000, N), bscale=[np.float32(q[0]) * wsc], bzp=[0], act=a,
+                           out_shape=(1, N), out_q=(osc, ozp)))
+        q, K = (osc, ozp), N
+    if softmax:
+        layers.append(dict(op="softmax", out_shape=(1, K), out_q=(1.0 / 256.0, lo)))
+    return build_model((1, H, W, C), in_q, layers, elem)
+
+
 def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, wmax=None, in_zp=None, act_scale=None):
     """A convolution stack: input_shape = (H, W, C); convs = [(op, N, K, stride), ...] with op "conv" (KxK Conv2D to N channels)
     or "dw" (KxK depthwise, N ignored), all SAME, relu6; per-channel filter quantization, filter zero points off the middle when
