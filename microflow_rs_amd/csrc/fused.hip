@@ -14,7 +14,7 @@
 namespace mf {
 
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC } kind;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND } kind;
     OpImpl *a, *b, *c;
     k::DwPwArgs dwpw;
     k::TailArgs tail;
@@ -42,6 +42,8 @@ struct FusedImpl {
     long long fcchain_M = 1; // rows per inference
     // POOLFC: the global AveragePool2D + FullyConnected layers (+ Softmax) in one launch (k_pool_fc.hip pool_fc_chain); a = the pool
     k::PoolFcArgs poolfc{};
+    // PAIRBAND: one pair too large for chain_rt's LDS plan, walked in row bands (k_pair_band.hip); a = the depthwise, b = the conv
+    k::PairBandArgs pairband{};
     int epi_mode = -1; // epilogue mode (k_common.hpp) of the launch's requantising operators; -1: not recorded (the operators' minimum)
 };
 // the pair's argument blocks as the operators hold them (two-rounding constants), and switched to the single-fma form when
@@ -209,7 +211,63 @@ FusedImpl *fused_chain_create(FusedImpl *const *groups, int n, int force_G) {
 }
 bool fused_is_chain_single(const FusedImpl *f) { return f && f->kind == FusedImpl::CHAIN && f->chain_members.size() == 1; }
 
+// ---- one pair of any image size in row bands (k_pair_band.hip): fused_create's last resort ----
+// Takes a pair only when the table kernels and chain_create have both declined AND the pair is too large for chain_rt at one image
+// per step (pair_band_plan's size condition): chain_rt keeps every pair it takes, and a small pair chain_plan refuses for another
+// reason (12x12x48 -> 48: three output tiles) stays two operators.  Does not depend on which kernel the 1x1 runs on its own: the
+// operand image is built here from its host weights.
+static FusedImpl *pair_band_create(OpImpl *dw, OpImpl *pw) {
+    if (switches().no_pair_band || !dw || !pw || dw->device != pw->device || dw->force_generic || pw->force_generic) return nullptr;
+    const OpSpec &d = dw->s, &q = pw->s;
+    if (d.kind != MF_OP_DEPTHWISE_CONV_2D || q.kind != MF_OP_CONV_2D || d.u8 != q.u8) return nullptr;
+    // geometry as chain_pair_ok: 3x3 SAME, equal strides 1 or 2, one output per channel, the 1x1 at stride 1 on the depthwise output
+    if (d.KH != 3 || d.KW != 3 || d.pad != MF_PAD_SAME || d.sh != d.sw || (d.sh != 1 && d.sh != 2) || d.C != d.N) return nullptr;
+    if (d.sh == 2 && d.W % 2 != 0) return nullptr;
+    if (q.KH != 1 || q.KW != 1 || q.sh != 1 || q.sw != 1 || q.OH != q.H || q.OW != q.W) return nullptr;
+    if (q.H != d.OH || q.W != d.OW || q.C != d.N) return nullptr;
+    if (d.C % 16 != 0 || d.C < 16 || d.C > 256 || q.N % 16 != 0 || q.N < 16 || q.N > 1024) return nullptr;
+    // the depthwise member: dw3x3_rt or a table kernel with its taps in matrix-pipe form (none with filter zero points)
+    if (dw->fast != OpImpl::DW_RT && dw->fast != OpImpl::DW_NHWC) return nullptr;
+    const k::DwFastArgs &f = dw->fast == OpImpl::DW_NHWC ? dw->dwf : dw->dwrt.dw;
+    if (!f.wmm || (dw->fast == OpImpl::DW_RT && dw->rt_wz)) return nullptr;
+    // the 1x1: whatever it runs alone, its filter zero points must be zero in the i8 domain
+    if (pw->h_w.size() != (size_t)q.N * q.C || pw->h_A.size() != (size_t)q.N) return nullptr;
+    for (int32_t z : pw->h_wzp)
+        if (z != 0) return nullptr;
+    if (!dw->finite_consts || !pw->finite_consts) return nullptr;
+    std::unique_ptr<FusedImpl> c(new FusedImpl{FusedImpl::PAIRBAND, dw, pw, nullptr, {}, {}, ""});
+    k::PairBandArgs &a = c->pairband;
+    if (!k::pair_band_plan(k::ChainGeom{d.H, d.W, d.C, d.sh, d.OH, d.OW, q.N, f.izp4}, a)) return nullptr;
+    // Classes measured NOT faster than the operators' own launches (profiles/r07/time_pair_band.txt) stay layer-wise:
+    //   C < 64 -- 112x112x32 -> 64 ran x1.01, 96x96x32 -> 64 x1.13 inside a spread of 0.16 - 0.28;
+    //   a plan that needs more than half a CU's LDS with fewer than four k steps -- eight waves alone on a CU that the same kernel
+    //   fills with sixteen elsewhere: 56x56x128 s2 -> 256 ran x1.04 inside a spread of 0.09;
+    //   four k steps (one workgroup per CU: 180 registers) up to 256 outputs, where the 1x1 alone runs a weights-in-registers kernel --
+    //   28x28x256 -> 256 ran x1.00 with 4-row bands, x1.09 with 8-row bands inside a spread of 0.11 (-> 512 runs x1.88).
+    if (d.C < 64 || (a.wgs == 1 && a.KSC < 4) || (a.KSC == 4 && q.N <= 256)) return nullptr;
+    const int magic = std::min(dw->magic_mode, pw->magic_mode);
+    if (!k::pair_band_instance(a.KSC, magic)) return nullptr; // (no compiled instance: the pair stays layer-wise)
+    a.dw_wmm = f.wmm, a.dwA = f.A, a.dwS = f.S, a.dwK = f.Kc, a.dw_lo = f.lo_f, a.dw_hi = f.hi_f;
+    const std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(pw->h_w.data(), q.C, q.N, 1, a.TB, a.NBLK); // [N][1][1][C], i8 domain
+    a.pw_w = keep(*c, prep.data(), prep.size());
+    a.pwA = pw->conv.A, a.pwS = pw->conv.S, a.pwK = pw->conv.Kc, a.pw_lo = pw->conv.lo_f, a.pw_hi = pw->conv.hi_f;
+    a.magic = magic, a.xr = d.u8 ? 0x80 : 0;
+    a.queue = (int *)dw->d_queue.p, a.qlaunch = &dw->q_launches;
+    c->epi_mode = magic;
+    c->name = "pair_band_rt<" + std::to_string(d.H) + "x" + std::to_string(d.W) + "x" + std::to_string(d.C) + (d.sh == 2 ? "s2" : "") + "-" + std::to_string(q.N) +
+              ";RB" + std::to_string(a.RB) + ";NB" + std::to_string(a.NB) + ">";
+    if (switches().chain_verbose)
+        fprintf(stderr, "[microflow_amd] band group %s: tile %d rows x %d B%s, MID %d B, lds %d B, %d workgroup%s per CU, %d x %d output tiles, mode %d\n", c->name.c_str(), a.TR,
+                a.ROW, a.dbuf ? " (two)" : "", a.mid_bytes, a.lds_bytes, a.wgs, a.wgs == 1 ? "" : "s", a.NBLK, a.TB, magic);
+    return c.release();
+}
+
+static FusedImpl *pair_create(OpImpl *dw, OpImpl *pw);
 FusedImpl *fused_create(OpImpl *dw, OpImpl *pw) {
+    if (FusedImpl *f = pair_create(dw, pw)) return f; // the table pairs, then chain_rt
+    return pair_band_create(dw, pw);
+}
+static FusedImpl *pair_create(OpImpl *dw, OpImpl *pw) {
     const bool chain_all = switches().chain_all; // tests / A-B: the chain kernel on table shapes too
     if (dw && pw && (chain_all || dw->fast != OpImpl::DW_NHWC || pw->fast != OpImpl::PW_MFMA ||
                      !k::dwpw_name(dw->s.H, dw->s.W, dw->s.C, dw->s.sh, pw->s.N))) {
@@ -375,7 +433,9 @@ FusedImpl *fused_pool_fc_create(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl 
     f->poolfc = a, f->epi_mode = a.c.magic;
     return f;
 }
-bool fused_input_ok(const FusedImpl *f, const int8_t *d_in) { return f->kind != FusedImpl::POOLFC || ((uintptr_t)d_in & 15) == 0; }
+bool fused_input_ok(const FusedImpl *f, const int8_t *d_in) {
+    return (f->kind != FusedImpl::POOLFC && f->kind != FusedImpl::PAIRBAND) || ((uintptr_t)d_in & 15) == 0; // (these two read 16-byte words at the pointer)
+}
 
 // A run of `npairs` identical DepthwiseConv2D 3x3 (stride 1) + Conv2D 1x1 pairs on one small tensor as one persistent
 // kernel (k_stage.hip: five pairs on 6x6x128 = person_detect ops 13..22).  `pairs` are the already created pair
@@ -676,6 +736,13 @@ void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, vo
     if (f->kind == FusedImpl::CHAIN) {
         if (batch > 0x7fffffffull / 4) fail(MF_ERR_INVALID_ARG, "batch too large for one launch");
         k::launch_chain(d_in, d_out, f->chain, (int)batch, (hipStream_t)stream);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (f->kind == FusedImpl::PAIRBAND) {
+        if (batch > 0x7fffffffull / 4 / (size_t)f->pairband.NB) fail(MF_ERR_INVALID_ARG, "batch too large for one launch");
+        if (!fused_input_ok(f, d_in)) fail(MF_ERR_INVALID_ARG, "pair_band_rt: the input pointer is not 16-byte aligned");
+        k::launch_pair_band(d_in, d_out, f->pairband, (int)batch, (hipStream_t)stream);
         MF_HIP(hipGetLastError());
         return;
     }

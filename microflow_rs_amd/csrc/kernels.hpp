@@ -342,8 +342,49 @@ struct ChainArgs {
 bool chain_plan(const ChainGeom *g, int n, ChainPair *pairs, ChainArgs &a, int lds_budget, int force_G = 0, int force_dbuf = -1); // force_*: the caller's G / double buffering
 // estimated microseconds per image and CU of the same pairs run one operator at a time (the run-time-geometry kernels of k_rt.hip)
 double chain_unfused_us_per_image(const ChainGeom *g, int n);
+// the pads of a halo'd tile's row and image pitch that the bank model of the depthwise tap reads prefers (k_chain.hip; shared with pair_band_plan)
+void tile_bank_pads(int H, int W, int C, int S, int NQ, int lgCX, int lgCY, int CG, int swz_sh, int swz_mask, int &row_pad16, int &image_pad16);
 void chain_rtab(const ChainPair &c, std::vector<int> &out); // the unit offset table ChainPair::rtab points to
 void launch_chain(const int8_t *in, int8_t *out, const ChainArgs &a, int batch, hipStream_t s);
+
+// ---- one pair of any image size, band by band (k_pair_band.hip) ----
+// The pairs chain_rt cannot hold (a whole halo'd image + MID beyond its LDS budget): a step is ONE band of RB output rows of one
+// image; the band's (RB - 1) S + 3 input rows are staged into a halo'd tile, the depthwise result of the band sits in MID, the 1x1
+// convolution sweeps MID and stores the band's output rows.  Geometry and LDS plan by the host (pair_band_plan).
+struct PairBandArgs {
+    int H, W, C, S, OH, OW, N;
+    int NQ, lgNQ;                  // 16-channel groups (lg = -1: not a power of two)
+    int KS, KSC;                   // 64-deep k steps of the 1x1 product; the kernel instance's (1, 2 or 4)
+    int swz_sh, swz_mask;          // tile swizzle, as ChainPair's
+    int RB, NB, TR;                // output rows per band, bands per image, tile rows = (RB - 1) S + 3
+    int lgCX, lgCY, UX, UY;        // depthwise unit = CY band rows x CX columns (CY CX = 16); units per channel group along x / y
+    int ROW, TILE;                 // tile row pitch; bytes of one tile region
+    int dbuf;                      // two tile regions: the next step's tile is staged while this one computes
+    int tile_off, mid_off, q_off, lds_bytes; // regions, in this order: tile(s) at tile_off (+ TILE), MID, the step queue's slot
+    int NCH, PLANE, mid_bytes;     // 16-pixel chunks of a band; MID plane pitch = NCH * 256; NQ planes
+    int TB, NBLK;                  // output tiles per block (1 or 2) and blocks: TB NBLK = N / 16
+    int SLOTS, NWB;                // waves sweeping one block's chunks; blocks in flight: SLOTS NWB = 8 waves
+    int wgs;                       // workgroups per CU the plan leaves room for (2: lds_bytes <= 80 KiB - 512)
+    uint32_t izp4;                 // input zero point of the depthwise, in every byte
+    float dw_lo, dw_hi, pw_lo, pw_hi;
+    const void *dw_wmm;            // DwFastArgs::wmm
+    const float *dwA, *dwS;
+    const int *dwK;
+    const void *pw_w;              // build_pw_rt_reg_weights(C, N, group 1, TB, NBLK)
+    const float *pwA, *pwS;
+    const int *pwK;
+    int *queue;
+    unsigned long *qlaunch;        // HOST memory (k_common.hpp dq_slot)
+    int qcfg;
+    int magic, xr;                 // epilogue mode of the launch (min over the two operators), element type
+};
+constexpr int PAIR_BAND_LDS_MAX = 159 * 1024;     // fc_rt's budget
+constexpr int PAIR_BAND_LDS_HALF = 80 * 1024 - 512; // two workgroups per CU
+// fills the geometry and the LDS plan (everything but the operand pointers, clamps and modes); false: a channel count outside
+// 16 .. 256 / 16 .. 1024 in whole sixteens, an odd width at stride 2, or the smallest band does not fit PAIR_BAND_LDS_MAX
+bool pair_band_plan(const ChainGeom &g, PairBandArgs &a);
+bool pair_band_instance(int KSC, int magic); // a compiled kernel exists for this k-step count and epilogue mode
+void launch_pair_band(const int8_t *in, int8_t *out, const PairBandArgs &a, int batch, hipStream_t s);
 
 // two consecutive pairs in one launch (k_quad.hip)
 struct QuadArgs {

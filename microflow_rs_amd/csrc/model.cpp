@@ -524,7 +524,7 @@ static const int8_t *run_ops(ModelImpl *m, const int8_t *src, size_t batch, int 
         }
         const ModelImpl::Stage *staged = stage_at(m, i, last_op);
         if (staged && !fused_input_ok(staged->f, cur)) staged = nullptr; // (the operators' own launches take any pointer)
-        const bool grouped = !staged && fused_at(m, i) && m->fused_last[(size_t)i] <= last_op;
+        const bool grouped = !staged && fused_at(m, i) && m->fused_last[(size_t)i] <= last_op && fused_input_ok(m->fused[(size_t)i], cur);
         const int end = staged ? staged->last : (grouped ? m->fused_last[(size_t)i] : i);
         if (final_dst && end >= last_real) dst = final_dst;
         if (staged) { // several groups in one launch
@@ -755,7 +755,7 @@ void model_time_device(ModelImpl *m, const int8_t *d_in, size_t batch, int8_t *d
                         fused_run(st->f, cur, batch, dst, s);
                         for (int j = i; j < st->last; ++j) MF_HIP(hipEventRecord(ev[(size_t)j + 1], s));
                         i = st->last;
-                    } else if (fused_at(m, i)) { // the group is timed as one unit (index i), its other ops 0
+                    } else if (fused_at(m, i) && fused_input_ok(m->fused[(size_t)i], cur)) { // the group is timed as one unit (index i), its other ops 0
                         fused_run(m->fused[(size_t)i], cur, batch, dst, s);
                         for (int j = i; j < m->fused_last[(size_t)i]; ++j) MF_HIP(hipEventRecord(ev[(size_t)j + 1], s));
                         i = m->fused_last[(size_t)i];
