@@ -211,11 +211,12 @@ FusedImpl *fused_chain_create(FusedImpl *const *groups, int n, int force_G) {
 }
 bool fused_is_chain_single(const FusedImpl *f) { return f && f->kind == FusedImpl::CHAIN && f->chain_members.size() == 1; }
 
-// ---- one pair of any image size in row bands (k_pair_band.hip): fused_create's last resort ----
+// ---- one pair of any image size in row bands (k_pair_band.hip; 256 < C <= 512: k_pair_band_deep.hip): fused_create's last resort ----
 // Takes a pair only when the table kernels and chain_create have both declined AND the pair is too large for chain_rt at one image
 // per step (pair_band_plan's size condition): chain_rt keeps every pair it takes, and a small pair chain_plan refuses for another
 // reason (12x12x48 -> 48: three output tiles) stays two operators.  Does not depend on which kernel the 1x1 runs on its own: the
 // operand image is built here from its host weights.
+// Above 256 input channels there is no size condition (chain_rt never takes such a pair): pair_band_deep_plan takes whatever fits.
 static FusedImpl *pair_band_create(OpImpl *dw, OpImpl *pw) {
     if (switches().no_pair_band || !dw || !pw || dw->device != pw->device || dw->force_generic || pw->force_generic) return nullptr;
     const OpSpec &d = dw->s, &q = pw->s;
@@ -225,7 +226,7 @@ static FusedImpl *pair_band_create(OpImpl *dw, OpImpl *pw) {
     if (d.sh == 2 && d.W % 2 != 0) return nullptr;
     if (q.KH != 1 || q.KW != 1 || q.sh != 1 || q.sw != 1 || q.OH != q.H || q.OW != q.W) return nullptr;
     if (q.H != d.OH || q.W != d.OW || q.C != d.N) return nullptr;
-    if (d.C % 16 != 0 || d.C < 16 || d.C > 256 || q.N % 16 != 0 || q.N < 16 || q.N > 1024) return nullptr;
+    if (d.C % 16 != 0 || d.C < 16 || d.C > 512 || q.N % 16 != 0 || q.N < 16 || q.N > 1024) return nullptr;
     // the depthwise member: dw3x3_rt or a table kernel with its taps in matrix-pipe form (none with filter zero points)
     if (dw->fast != OpImpl::DW_RT && dw->fast != OpImpl::DW_NHWC) return nullptr;
     const k::DwFastArgs &f = dw->fast == OpImpl::DW_NHWC ? dw->dwf : dw->dwrt.dw;
@@ -237,16 +238,21 @@ static FusedImpl *pair_band_create(OpImpl *dw, OpImpl *pw) {
     if (!dw->finite_consts || !pw->finite_consts) return nullptr;
     std::unique_ptr<FusedImpl> c(new FusedImpl{FusedImpl::PAIRBAND, dw, pw, nullptr, {}, {}, ""});
     k::PairBandArgs &a = c->pairband;
-    if (!k::pair_band_plan(k::ChainGeom{d.H, d.W, d.C, d.sh, d.OH, d.OW, q.N, f.izp4}, a)) return nullptr;
+    const bool deep = d.C > 256; // 256 < C <= 512: pair_band_deep_rt's plan (k_pair_band_deep.hip: eight k steps, no lower size bound)
+    const k::ChainGeom geom{d.H, d.W, d.C, d.sh, d.OH, d.OW, q.N, f.izp4};
+    if (!(deep ? k::pair_band_deep_plan(geom, a) : k::pair_band_plan(geom, a))) return nullptr;
     // Classes measured NOT faster than the operators' own launches (profiles/r07/time_pair_band.txt) stay layer-wise:
     //   C < 64 -- 112x112x32 -> 64 ran x1.01, 96x96x32 -> 64 x1.13 inside a spread of 0.16 - 0.28;
     //   a plan that needs more than half a CU's LDS with fewer than four k steps -- eight waves alone on a CU that the same kernel
     //   fills with sixteen elsewhere: 56x56x128 s2 -> 256 ran x1.04 inside a spread of 0.09;
     //   four k steps (one workgroup per CU: 180 registers) up to 256 outputs, where the 1x1 alone runs a weights-in-registers kernel --
     //   28x28x256 -> 256 ran x1.00 with 4-row bands, x1.09 with 8-row bands inside a spread of 0.11 (-> 512 runs x1.88).
-    if (d.C < 64 || (a.wgs == 1 && a.KSC < 4) || (a.KSC == 4 && q.N <= 256)) return nullptr;
+    //   eight k steps (pair_band_deep_rt; profiles/r08/time_pair_band_deep.txt) up to 256 outputs, the same class: 14x14x512 -> 256
+    //   ran 0.496 ms against 0.555 (dw3x3_rt + pw_rt<512,256>), x1.12 with spreads of 0.104 and 0.106 -- a margin a rerun can eat.  Every
+    //   other class measured there (N >= 320, where the 1x1 alone runs conv_gemm_rt) ran x1.61 - x2.78 and stays.
+    if (d.C < 64 || (a.wgs == 1 && a.KSC < 4) || (a.KSC >= 4 && q.N <= 256)) return nullptr;
     const int magic = std::min(dw->magic_mode, pw->magic_mode);
-    if (!k::pair_band_instance(a.KSC, magic)) return nullptr; // (no compiled instance: the pair stays layer-wise)
+    if (!deep && !k::pair_band_instance(a.KSC, magic)) return nullptr; // (no compiled instance: the pair stays layer-wise)
     a.dw_wmm = f.wmm, a.dwA = f.A, a.dwS = f.S, a.dwK = f.Kc, a.dw_lo = f.lo_f, a.dw_hi = f.hi_f;
     const std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(pw->h_w.data(), q.C, q.N, 1, a.TB, a.NBLK); // [N][1][1][C], i8 domain
     a.pw_w = keep(*c, prep.data(), prep.size());
@@ -254,7 +260,7 @@ static FusedImpl *pair_band_create(OpImpl *dw, OpImpl *pw) {
     a.magic = magic, a.xr = d.u8 ? 0x80 : 0;
     a.queue = (int *)dw->d_queue.p, a.qlaunch = &dw->q_launches;
     c->epi_mode = magic;
-    c->name = "pair_band_rt<" + std::to_string(d.H) + "x" + std::to_string(d.W) + "x" + std::to_string(d.C) + (d.sh == 2 ? "s2" : "") + "-" + std::to_string(q.N) +
+    c->name = std::string(deep ? "pair_band_deep_rt<" : "pair_band_rt<") + std::to_string(d.H) + "x" + std::to_string(d.W) + "x" + std::to_string(d.C) + (d.sh == 2 ? "s2" : "") + "-" + std::to_string(q.N) +
               ";RB" + std::to_string(a.RB) + ";NB" + std::to_string(a.NB) + ">";
     if (switches().chain_verbose)
         fprintf(stderr, "[microflow_amd] band group %s: tile %d rows x %d B%s, MID %d B, lds %d B, %d workgroup%s per CU, %d x %d output tiles, mode %d\n", c->name.c_str(), a.TR,
@@ -742,7 +748,8 @@ void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, vo
     if (f->kind == FusedImpl::PAIRBAND) {
         if (batch > 0x7fffffffull / 4 / (size_t)f->pairband.NB) fail(MF_ERR_INVALID_ARG, "batch too large for one launch");
         if (!fused_input_ok(f, d_in)) fail(MF_ERR_INVALID_ARG, "pair_band_rt: the input pointer is not 16-byte aligned");
-        k::launch_pair_band(d_in, d_out, f->pairband, (int)batch, (hipStream_t)stream);
+        if (f->pairband.KSC == 8) k::launch_pair_band_deep(d_in, d_out, f->pairband, (int)batch, (hipStream_t)stream);
+        else k::launch_pair_band(d_in, d_out, f->pairband, (int)batch, (hipStream_t)stream);
         MF_HIP(hipGetLastError());
         return;
     }

@@ -354,7 +354,7 @@ void launch_chain(const int8_t *in, int8_t *out, const ChainArgs &a, int batch, 
 struct PairBandArgs {
     int H, W, C, S, OH, OW, N;
     int NQ, lgNQ;                  // 16-channel groups (lg = -1: not a power of two)
-    int KS, KSC;                   // 64-deep k steps of the 1x1 product; the kernel instance's (1, 2 or 4)
+    int KS, KSC;                   // 64-deep k steps of the 1x1 product; the kernel instance's (1, 2 or 4; 8: pair_band_deep_rt)
     int swz_sh, swz_mask;          // tile swizzle, as ChainPair's
     int RB, NB, TR;                // output rows per band, bands per image, tile rows = (RB - 1) S + 3
     int lgCX, lgCY, UX, UY;        // depthwise unit = CY band rows x CX columns (CY CX = 16); units per channel group along x / y
@@ -385,6 +385,11 @@ constexpr int PAIR_BAND_LDS_HALF = 80 * 1024 - 512; // two workgroups per CU
 bool pair_band_plan(const ChainGeom &g, PairBandArgs &a);
 bool pair_band_instance(int KSC, int magic); // a compiled kernel exists for this k-step count and epilogue mode
 void launch_pair_band(const int8_t *in, int8_t *out, const PairBandArgs &a, int batch, hipStream_t s);
+// the same launch for 256 < C <= 512 (k_pair_band_deep.hip: pair_band_deep_rt, eight k steps, KSC = 8): no lower size bound, always the
+// whole PAIR_BAND_LDS_MAX and wgs = 1; false: a channel count outside 272 .. 512 / 16 .. 1024 in whole sixteens, an odd width at
+// stride 2, or the smallest band does not fit.  Epilogue modes 0, 1 and 2 are all compiled.
+bool pair_band_deep_plan(const ChainGeom &g, PairBandArgs &a);
+void launch_pair_band_deep(const int8_t *in, int8_t *out, const PairBandArgs &a, int batch, hipStream_t s);
 
 // two consecutive pairs in one launch (k_quad.hip)
 struct QuadArgs {

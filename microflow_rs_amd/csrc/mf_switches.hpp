@@ -36,7 +36,7 @@ struct Switches {
     bool no_fc_sparse = false;     // MF_NO_FC_SPARSE     FullyConnected weights with 2:4 sparsity on fc_mfma, not fc_sparse24 (k_fc_sparse.hip)
     bool no_fc_chain = false;      // MF_NO_FC_CHAIN      consecutive FullyConnected layers one launch each, not one fc_chain launch
     bool no_pool_fc = false;       // MF_NO_POOL_FC       global AveragePool2D + FullyConnected (+ Softmax) heads one launch per operator, not one pool_fc_chain launch (k_pool_fc.hip)
-    bool no_pair_band = false;     // MF_NO_PAIR_BAND     pairs too large for chain_rt one launch per operator, not one pair_band_rt launch (k_pair_band.hip)
+    bool no_pair_band = false;     // MF_NO_PAIR_BAND     pairs too large for chain_rt one launch per operator, not one pair_band_rt / pair_band_deep_rt launch (k_pair_band.hip, k_pair_band_deep.hip)
     bool no_conv_gemm = false;     // MF_NO_CONV_GEMM     Conv2D shapes outside the other Conv2D kernels take conv2d_generic, not conv_gemm_rt (k_conv_gemm.hip)
     bool no_dw_gemm = false;       // MF_NO_DW_GEMM       DepthwiseConv2D shapes outside the other depthwise kernels take dwconv_generic, not dw_gemm_rt / conv_gemm_rt<dw> (k_dw_gemm.hip)
     bool no_dwfc = false;          // MF_NO_DWFC          no depthwise + FC + softmax kernel (k_dwfc.hip, speech)

@@ -3,7 +3,9 @@
 the same model with fusion off (dw3x3_rt + pw_rt / conv_gemm_rt: what ran before the group existed), in the same process, back
 to back.
 
-    python scripts/time_pair_band.py [--reps 20] [--only 3]
+    python scripts/time_pair_band.py [--reps 20] [--only 3] [--deep]
+
+--deep times the second shape set instead: pairs of 256 < C <= 512 input channels, pair_band_deep_rt (k_pair_band_deep.hip).
 
 One line per shape: the median of --reps runs of each path, each timed with HIP events after warm-up, the spread of the repeats
 ((max - min) / median of each path), their ratio, and hbm_frac = batch x (H W C + OH OW N) bytes (the least a launch must move) over
@@ -26,6 +28,11 @@ HBM = 8.0e12
 SHAPES = [(112, 112, 32, 1, 64, 1024), (112, 112, 64, 2, 128, 1024), (56, 56, 128, 1, 128, 1024), (56, 56, 128, 2, 256, 1024),
           (28, 28, 256, 1, 256, 1024), (28, 28, 256, 2, 512, 1024), (96, 96, 32, 1, 64, 4096), (64, 64, 64, 2, 128, 4096),
           (48, 48, 128, 1, 128, 4096)]
+# --deep: the 512-channel pairs of a MobileNet-v1 at 224 .. 96 input, the pair behind them at 256 input, widths 0.75 and 0.625, a
+# one-pass 1x1 and an odd image
+DEEP_SHAPES = [(14, 14, 512, 1, 512, 4096), (12, 12, 512, 1, 512, 4096), (10, 10, 512, 1, 512, 4096), (8, 8, 512, 1, 512, 4096),
+               (6, 6, 512, 1, 512, 4096), (16, 16, 512, 2, 1024, 4096), (14, 14, 384, 1, 384, 4096), (14, 14, 320, 1, 320, 4096),
+               (14, 14, 512, 1, 256, 4096), (7, 7, 512, 1, 512, 4096)]
 STEP_TIMEOUT = 240  # seconds per shape
 
 
@@ -45,12 +52,12 @@ def times_ms(fn, reps, warm=3):
     return float(np.median(ts)), float((max(ts) - min(ts)) / np.median(ts))
 
 
-def one(idx, reps):
+def one(idx, reps, shapes):
     import torch
     import microflow_rs_amd as mf
     import tflite_writer as tw
     assert torch.cuda.is_available(), "needs the GPU"
-    H, W, C, S, N, batch = SHAPES[idx]
+    H, W, C, S, N, batch = shapes[idx]
     m = mf.Model(tw.conv_net(np.random.default_rng(idx), (H, W, C), [("dw", 0, 3, S), ("conv", N, 1, 1)], act_scale=6.0 / 255.0))
     m.prepare(batch)
     x = torch.randint(-128, 128, (batch, m.input_elems), dtype=torch.int8, device="cuda")
@@ -75,12 +82,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--only", type=int, default=-1, help="run this shape in this process (what the parent starts per shape)")
+    ap.add_argument("--deep", action="store_true", help="the 256 < C <= 512 shape set (pair_band_deep_rt)")
     a = ap.parse_args()
+    shapes = DEEP_SHAPES if a.deep else SHAPES
     if a.only >= 0:
-        return one(a.only, a.reps)
-    for idx in range(len(SHAPES)):
+        return one(a.only, a.reps, shapes)
+    for idx in range(len(shapes)):
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--reps", str(a.reps), "--only", str(idx)], timeout=STEP_TIMEOUT)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--reps", str(a.reps), "--only", str(idx)] + (["--deep"] if a.deep else []),
+                               timeout=STEP_TIMEOUT)
         except subprocess.TimeoutExpired:
             sys.exit("shape %d ran into its %d s limit: nothing more is started" % (idx, STEP_TIMEOUT))
         if r.returncode != 0:
