@@ -465,6 +465,9 @@ int mf_model_set_graph(mf_model *model, int enabled) {
 unsigned long long mf_model_graph_launches(const mf_model *model) {
     return model && model->impl ? mf::model_graph_launches(model->impl) : 0;
 }
+unsigned long long mf_model_device_ops(const mf_model *model) {
+    return model && model->impl ? mf::model_device_ops(model->impl) : 0;
+}
 
 int mf_model_predict(mf_model *model, const float *input, size_t batch, float *output, int mem) {
     MF_TRY({

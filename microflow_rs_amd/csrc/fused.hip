@@ -44,6 +44,10 @@ struct FusedImpl {
     k::PoolFcArgs poolfc{};
     // PAIRBAND: one pair too large for chain_rt's LDS plan, walked in row bands (k_pair_band.hip); a = the depthwise, b = the conv
     k::PairBandArgs pairband{};
+    // the model's f32 boundary inside this group's launch (fused_set_input_quant / fused_set_output_dequant): FCCHAIN and DWFC both
+    // ends, POOLFC and PAIRTAIL the exit
+    k::F32Edge edge{};
+    bool edge_in = false, edge_out = false;
     int epi_mode = -1; // epilogue mode (k_common.hpp) of the launch's requantising operators; -1: not recorded (the operators' minimum)
 };
 // the pair's argument blocks as the operators hold them (two-rounding constants), and switched to the single-fma form when
@@ -716,16 +720,55 @@ int fused_epilogue_mode(const FusedImpl *f) {
     return mode;
 }
 // the f32 entry of a group that starts with the network's first operator (M::predict: the boundary quantisation inside the launch)
+bool fused_set_input_quant(FusedImpl *f, float scale, int zp, bool u8) {
+    if (!f || (f->kind != FusedImpl::FCCHAIN && f->kind != FusedImpl::DWFC) || !(scale == scale) || switches().no_f32_boundary) return false;
+    edge_set_in(f->edge, f->a->device, scale, zp, u8);
+    return f->edge_in = true;
+}
+bool fused_set_output_dequant(FusedImpl *f, float scale, int zp, bool u8) {
+    if (!f || switches().no_f32_boundary) return false;
+    if (f->kind != FusedImpl::FCCHAIN && f->kind != FusedImpl::POOLFC && f->kind != FusedImpl::DWFC && f->kind != FusedImpl::PAIRTAIL) return false;
+    edge_set_out(f->edge, scale, zp, u8);
+    return f->edge_out = true;
+}
 bool fused_accepts_f32(const FusedImpl *f) {
+    if (f && f->edge_in) return true;
     return f && f->kind == FusedImpl::QUAD && f->quad.stem && f->quad.f32_ok && !switches().no_f32_group;
 }
-void fused_run_f32(FusedImpl *f, const float *d_in, size_t batch, int8_t *d_out, void *stream) {
+bool fused_emits_f32(const FusedImpl *f) { return f && f->edge_out; }
+void fused_run_f32(FusedImpl *f, const void *d_in, bool in_f32, size_t batch, void *d_out, bool out_f32, void *stream) {
     if (!batch) return;
-    if (!fused_accepts_f32(f)) fail(MF_ERR_UNSUPPORTED, "group has no f32-input kernel");
-    if (!d_in || !d_out || ((uintptr_t)d_in & 15)) fail(MF_ERR_INVALID_ARG, "fused_run_f32: null or unaligned device pointer");
+    if (!in_f32 && !out_f32) return fused_run(f, (const int8_t *)d_in, batch, (int8_t *)d_out, stream);
+    if (in_f32 && !fused_accepts_f32(f)) fail(MF_ERR_UNSUPPORTED, "group has no f32-input kernel");
+    if (out_f32 && !fused_emits_f32(f)) fail(MF_ERR_UNSUPPORTED, "group has no f32-output kernel");
+    if (!d_in || !d_out || (in_f32 && ((uintptr_t)d_in & 15)) || (out_f32 && ((uintptr_t)d_out & 3)))
+        fail(MF_ERR_INVALID_ARG, "fused_run_f32: null or unaligned device pointer");
     if (batch > 0x7fffffffull / 4) fail(MF_ERR_INVALID_ARG, "batch too large for one launch");
+    const int edge = (in_f32 ? k::EDGE_IN : 0) | (out_f32 ? k::EDGE_OUT : 0);
+    if (f->kind == FusedImpl::FCCHAIN) {
+        k::launch_fc_chain_f32(d_in, d_out, f->fcchain, f->edge, edge, (long long)(batch * f->fcchain_M), (hipStream_t)stream);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (f->kind == FusedImpl::POOLFC) {
+        if (!fused_input_ok(f, (const int8_t *)d_in)) fail(MF_ERR_INVALID_ARG, "pool_fc_chain: the input pointer is not 16-byte aligned");
+        k::launch_pool_fc_f32((const int8_t *)d_in, (float *)d_out, f->poolfc, f->edge, (long long)batch, (hipStream_t)stream);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (f->kind == FusedImpl::DWFC) {
+        k::launch_dwfc_f32(d_in, d_out, f->dwfc, f->edge, edge, batch, (hipStream_t)stream);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (f->kind == FusedImpl::PAIRTAIL) { // (exit only: fused_set_input_quant refuses this kind)
+        if (f->has_front) k::launch_pair_front_tail((const int8_t *)d_in, (int8_t *)d_out, f->pairtail, f->pairfront, batch, (hipStream_t)stream, &f->edge);
+        else k::launch_pair_tail((const int8_t *)d_in, (int8_t *)d_out, f->pairtail, batch, (hipStream_t)stream, &f->edge);
+        MF_HIP(hipGetLastError());
+        return;
+    }
     const int *q = f->quad_shape;
-    if (!k::launch_quad_f32(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], d_in, d_out, f->quad, (int)batch, (hipStream_t)stream))
+    if (!k::launch_quad_f32(q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7], q[8], q[9], (const float *)d_in, (int8_t *)d_out, f->quad, (int)batch, (hipStream_t)stream))
         fail(MF_ERR_UNSUPPORTED, "f32 quad kernel missing");
     MF_HIP(hipGetLastError());
 }

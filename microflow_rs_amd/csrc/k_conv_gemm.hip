@@ -247,7 +247,7 @@ static void launch_conv_gemm_t(const int8_t *in, int8_t *out, const ConvGemmArgs
     const long long nsteps = (long long)((batch + a.G - 1) / a.G) * a.NBANDS;
     long long walkers = std::max(1LL, 256LL * per_cu / a.NSL); // persistent: the resident slice is staged once per workgroup
     walkers = std::min(walkers, nsteps);
-    hipLaunchKernelGGL((conv_gemm_rt<AL, WZ, MG, XR4>), dim3((unsigned)(walkers * a.NSL)), dim3(256), a.lds, s, in, out, a, batch);
+    MF_LAUNCH((conv_gemm_rt<AL, WZ, MG, XR4>), dim3((unsigned)(walkers * a.NSL)), dim3(256), a.lds, s, in, out, a, batch);
 }
 template <int AL, int MG, uint32_t XR4>
 static void launch_conv_gemm_w(const int8_t *in, int8_t *out, const ConvGemmArgs &a, bool wz, int batch, hipStream_t s) {

@@ -580,7 +580,7 @@ static void launch_dw(const int8_t *in, int8_t *out, const DwFastArgs &a, int ba
     DwFastArgs b = a;
     b.qcfg = dq_config(nsteps, grid, dq_est_us((double)batch * (H * W * C + OPIX * C), (double)batch * OPIX * C));
     b.queue = dq_slot(b.queue, b.qlaunch);
-    hipLaunchKernelGGL((dw3x3_nhwc<H, W, C, S, G, NTHR, MG, XR4>), dim3(grid), dim3(NTHR), lds, s, in, out, b, batch);
+    MF_LAUNCH((dw3x3_nhwc<H, W, C, S, G, NTHR, MG, XR4>), dim3(grid), dim3(NTHR), lds, s, in, out, b, batch);
 }
 
 const char *dw_fast_name(int H, int W, int C, int S) {
@@ -624,7 +624,7 @@ bool dw_c1_supported(const DwC1Args &a) {
 void launch_dw_c1(const int8_t *in, int8_t *out, const DwC1Args &a, size_t batch, hipStream_t s) {
     const int grid = (int)(batch < 256 * 8 ? batch : 256 * 8);
     const int lds = dw_c1_lds_bytes(a);
-#define MF_C1(MG, XR) hipLaunchKernelGGL((dw_c1_lds<MG, XR>), dim3(grid), dim3(512), lds, s, in, out, a, batch)
+#define MF_C1(MG, XR) MF_LAUNCH((dw_c1_lds<MG, XR>), dim3(grid), dim3(512), lds, s, in, out, a, batch)
     if (a.xr) { if (a.magic) MF_C1(true, 0x80808080u); else MF_C1(false, 0x80808080u); }
     else { if (a.magic) MF_C1(true, 0u); else MF_C1(false, 0u); }
 #undef MF_C1
@@ -646,7 +646,7 @@ bool launch_dw_stem(int H, int W, int DM, int S, const int8_t *in, int8_t *out, 
                                      : prepared(st, dw3x3_stem8<96, 96, G, false, 0u, false>, 256, lds);
         const int nsteps = (batch + G - 1) / G;
         const int grid = nsteps < 256 * per_cu ? nsteps : 256 * per_cu;
-#define MF_STEM(MG, XR, F) hipLaunchKernelGGL((dw3x3_stem8<96, 96, G, MG, XR, F>), dim3(grid), dim3(256), lds, s, in, out, a, batch)
+#define MF_STEM(MG, XR, F) MF_LAUNCH((dw3x3_stem8<96, 96, G, MG, XR, F>), dim3(grid), dim3(256), lds, s, in, out, a, batch)
 #define MF_STEM2(F)                                                                          \
     if (a.xr) { if (a.magic) MF_STEM(true, 0x80808080u, F); else MF_STEM(false, 0x80808080u, F); } \
     else { if (a.magic) MF_STEM(true, 0u, F); else MF_STEM(false, 0u, F); }
@@ -657,7 +657,7 @@ bool launch_dw_stem(int H, int W, int DM, int S, const int8_t *in, int8_t *out, 
             const int pcu = f32_input ? prepared(stmf, dw3x3_stem8_mm<96, 96, G, false, 0u, true>, 256, lds)
                                       : prepared(stm, dw3x3_stem8_mm<96, 96, G, false, 0u, false>, 256, lds);
             const int gridm = nsteps < 256 * pcu ? nsteps : 256 * pcu;
-#define MF_STEMM(MG, XR, F) hipLaunchKernelGGL((dw3x3_stem8_mm<96, 96, G, MG, XR, F>), dim3(gridm), dim3(256), lds, s, in, out, a, batch)
+#define MF_STEMM(MG, XR, F) MF_LAUNCH((dw3x3_stem8_mm<96, 96, G, MG, XR, F>), dim3(gridm), dim3(256), lds, s, in, out, a, batch)
 #define MF_STEMM2(F)                                                                               \
     if (a.xr) { if (a.magic == 2) MF_STEMM(2, 0x80808080u, F); else if (a.magic) MF_STEMM(1, 0x80808080u, F); else MF_STEMM(0, 0x80808080u, F); } \
     else { if (a.magic == 2) MF_STEMM(2, 0u, F); else if (a.magic) MF_STEMM(1, 0u, F); else MF_STEMM(0, 0u, F); }

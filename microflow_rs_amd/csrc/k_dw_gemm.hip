@@ -222,7 +222,7 @@ static void launch_dw_gemm_t(const int8_t *in, int8_t *out, const DwGemmArgs &a,
     }
     const long long nsteps = (long long)((batch + a.G - 1) / a.G) * a.NBANDS;
     const long long grid = std::min(nsteps, 256LL * per_cu); // persistent: a workgroup fills its halo once
-    hipLaunchKernelGGL((dw_gemm_rt<AL, WZ, KSMAX, MG, XR4>), dim3((unsigned)grid), dim3(256), a.lds, s, in, out, a, batch);
+    MF_LAUNCH((dw_gemm_rt<AL, WZ, KSMAX, MG, XR4>), dim3((unsigned)grid), dim3(256), a.lds, s, in, out, a, batch);
 }
 template <int AL, bool WZ, int MG, uint32_t XR4>
 static void launch_dw_gemm_k(const int8_t *in, int8_t *out, const DwGemmArgs &a, int batch, hipStream_t s) {

@@ -32,6 +32,7 @@
 //              requantise, softmax over the 4 outputs in the reference's order, store 64 bytes.
 // HBM traffic: input + 4 output bytes per inference; the kernel is bounded by the requantisation VALU work.
 #include "k_common.hpp"
+#include "k_fc_layer.hpp"
 
 namespace mf {
 namespace k {
@@ -51,9 +52,13 @@ __device__ long long g_dwfc_trace[32];
 #define MF_TR(k) do { } while (0)
 #endif
 
-template <int NTHR, int MG, uint32_t XR4, bool WZP>
-__global__ __launch_bounds__(NTHR, MF_DWFC_WPE) void dwc1_fc_softmax(const int8_t *__restrict__ in, int8_t *__restrict__ out, DwFcArgs p,
-                                                        size_t batch) {
+// EDGE (kernels.hpp: EDGE_IN | EDGE_OUT) != 0: the instances that hold a model's f32 boundary (dwc1_fc_softmax_f32 below).  Entry: `in`
+// points to floats; nothing is held in registers a step ahead (four times the bytes would not fit beside the operands) -- write_images
+// loads the chunk's four float4s itself, quantises them with quantize_f32's arithmetic (k_fc_layer.hpp edge_quant) and writes the same
+// tile dwords.  Exit: the finishing threads store the dequantised float instead of the byte.
+template <int NTHR, int MG, uint32_t XR4, bool WZP, int EDGE>
+__device__ __forceinline__ void dwc1_fc_softmax_body(const int8_t *__restrict__ in, int8_t *__restrict__ out, const DwFcArgs &p, size_t batch,
+                                                     const F32Edge &eg) {
     using Gm = DwFcGeom;
     constexpr int NW = NTHR / 64;
     constexpr int HW = Gm::H * Gm::W;
@@ -109,7 +114,12 @@ __global__ __launch_bounds__(NTHR, MF_DWFC_WPE) void dwc1_fc_softmax(const int8_
     const size_t nblk = (batch + Gm::IMGS - 1) / Gm::IMGS;
     // 16 images are contiguous in HBM: 16 B per lane, clamped at the end of the batch
     uint4 v[NE];
+    size_t fblk = 0;                                                      // (f32 entry: the block write_images stages)
     auto load_images = [&](size_t blk) {
+        if constexpr (EDGE & EDGE_IN) {
+            fblk = blk;
+            return;
+        }
         const int8_t *src = in + blk * (size_t)(Gm::IMGS * HW);
         const size_t left = (batch - blk * Gm::IMGS) * (size_t)HW;
         const int limit = left < (size_t)(Gm::IMGS * HW) ? (int)left : Gm::IMGS * HW; // valid bytes (multiple of 8)
@@ -125,11 +135,25 @@ __global__ __launch_bounds__(NTHR, MF_DWFC_WPE) void dwc1_fc_softmax(const int8_
         }
     };
     auto write_images = [&](uint8_t *set) {
+        const float *fsrc = (const float *)in + fblk * (size_t)(Gm::IMGS * HW);
+        const size_t fleft = (batch - fblk * Gm::IMGS) * (size_t)HW;
+        const int flimit = fleft < (size_t)(Gm::IMGS * HW) ? (int)fleft : Gm::IMGS * HW; // valid floats (a multiple of 8)
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             const int c = tid + NTHR * e;
             if (c < NCH) {
-                const uint32_t w4[4] = {v[e].x, v[e].y, v[e].z, v[e].w};
+                uint32_t w4[4] = {v[e].x, v[e].y, v[e].z, v[e].w};
+                if constexpr (EDGE & EDGE_IN) { // only whole quads of floats inside the batch are read
+                    float4 f[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        f[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        if (16 * c + 4 * q + 4 <= flimit) f[q] = *(const float4 *)(fsrc + 16 * c + 4 * q);
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        w4[q] = pack4(edge_quant(f[q].x, eg), edge_quant(f[q].y, eg), edge_quant(f[q].z, eg), edge_quant(f[q].w, eg)) ^ eg.in_xr4;
+                }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int d = 4 * c + q;                       // dword of the 16-image block
@@ -209,13 +233,28 @@ __global__ __launch_bounds__(NTHR, MF_DWFC_WPE) void dwc1_fc_softmax(const int8_
             const float rr = __fadd_rn(qf, __builtin_copysignf(0x1.fffffep-2f, qf));
             const int qi = (rr != rr) ? 0 : (int)__builtin_amdgcn_fmed3f(rr, p.sm.sat_lo, p.sm.sat_hi);
             const size_t image = blk * Gm::IMGS + img;
-            if (image < batch) out[image * 4 + n] = (int8_t)(qi ^ p.sm.xr);
+            if constexpr (EDGE & EDGE_OUT) {
+                if (image < batch) ((float *)out)[image * 4 + n] = __fmul_rn(eg.out_scale, __fsub_rn((float)(int)(int8_t)(qi ^ p.sm.xr), eg.out_zp_f));
+            } else {
+                if (image < batch) out[image * 4 + n] = (int8_t)(qi ^ p.sm.xr);
+            }
         }
         MF_TR(5);
 #if MF_DWFC_DIAG
         ++trace_step;
 #endif
     }
+}
+template <int NTHR, int MG, uint32_t XR4, bool WZP>
+__global__ __launch_bounds__(NTHR, MF_DWFC_WPE) void dwc1_fc_softmax(const int8_t *__restrict__ in, int8_t *__restrict__ out, DwFcArgs p,
+                                                        size_t batch) {
+    dwc1_fc_softmax_body<NTHR, MG, XR4, WZP, 0>(in, out, p, batch, F32Edge{});
+}
+template <int NTHR, int MG, uint32_t XR4, bool WZP, int EDGE>
+__global__ __launch_bounds__(NTHR, MF_DWFC_WPE) void dwc1_fc_softmax_f32(const int8_t *__restrict__ in, int8_t *__restrict__ out, DwFcArgs p,
+                                                            F32Edge eg, size_t batch) {
+    static_assert(MG <= 2 && EDGE >= 1 && EDGE <= 3, "both conversions need round-to-nearest: no single-fma epilogue here");
+    dwc1_fc_softmax_body<NTHR, MG, XR4, WZP, EDGE>(in, out, p, batch, eg);
 }
 
 bool dwfc_supported(int H, int W, int KH, int KW, int sh, int sw, int OH, int OW, int DM, int NFC) {
@@ -235,7 +274,7 @@ void launch_dwfc(const int8_t *in, int8_t *out, const DwFcArgs &a, size_t batch,
         static LaunchState st;                                                                        \
         const int per_cu = prepared(st, dwc1_fc_softmax<NTHR, MG, XR, WZ>, NTHR, lds);                \
         const size_t cap = (size_t)256 * per_cu;                                                      \
-        hipLaunchKernelGGL((dwc1_fc_softmax<NTHR, MG, XR, WZ>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(NTHR), lds, \
+        MF_LAUNCH((dwc1_fc_softmax<NTHR, MG, XR, WZ>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(NTHR), lds, \
                            s, in, out, a, batch);                                                     \
     } while (0)
 #define MF_DWFC2(MG, XR) \
@@ -257,6 +296,29 @@ void launch_dwfc(const int8_t *in, int8_t *out, const DwFcArgs &a, size_t batch,
         }
     }
 #endif
+}
+template <int EDGE, int MG, uint32_t XR4>
+static void launch_dwfc_f32_t(const void *in, void *out, const DwFcArgs &a, const F32Edge &e, size_t batch, hipStream_t s) {
+    using Gm = DwFcGeom;
+    constexpr int NTHR = MF_DWFC_THREADS;
+    constexpr int lds = 2 * Gm::IMGS * Gm::TILE + Gm::FCW_BYTES + 2 * (NTHR / 64) * 16 * 8 * 4 + 256 * 4;
+    const size_t nblk = (batch + Gm::IMGS - 1) / Gm::IMGS;
+    static LaunchState st[2];
+    if (a.fc.wzp != 0) {
+        const size_t cap = (size_t)256 * prepared(st[1], dwc1_fc_softmax_f32<NTHR, MG, XR4, true, EDGE>, NTHR, lds);
+        MF_LAUNCH((dwc1_fc_softmax_f32<NTHR, MG, XR4, true, EDGE>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(NTHR), lds, s, (const int8_t *)in,
+                  (int8_t *)out, a, e, batch);
+    } else {
+        const size_t cap = (size_t)256 * prepared(st[0], dwc1_fc_softmax_f32<NTHR, MG, XR4, false, EDGE>, NTHR, lds);
+        MF_LAUNCH((dwc1_fc_softmax_f32<NTHR, MG, XR4, false, EDGE>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(NTHR), lds, s, (const int8_t *)in,
+                  (int8_t *)out, a, e, batch);
+    }
+}
+void launch_dwfc_f32(const void *in, void *out, const DwFcArgs &a, const F32Edge &e, int edge, size_t batch, hipStream_t s) {
+    if (!batch) return;
+    if (edge == 3) MF_DISPATCH4(a.magic, a.xr, launch_dwfc_f32_t, (in, out, a, e, batch, s), 3)
+    else if (edge == EDGE_OUT) MF_DISPATCH4(a.magic, a.xr, launch_dwfc_f32_t, (in, out, a, e, batch, s), EDGE_OUT)
+    else MF_DISPATCH4(a.magic, a.xr, launch_dwfc_f32_t, (in, out, a, e, batch, s), EDGE_IN)
 }
 
 } // namespace k

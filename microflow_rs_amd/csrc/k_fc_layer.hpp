@@ -104,5 +104,28 @@ __device__ __forceinline__ void fc_chain_store_patch(int8_t *gs, const uint8_t *
     else if (tid >= 64 && tid < 64 + ntail) gs[nhead + nbody * 16 + (tid - 64)] = (int8_t)po[nhead + nbody * 16 + (tid - 64)];
 }
 
+// ---- the model boundary inside these launches (kernels.hpp: F32Edge) ----
+// quantize_f32's value-by-value arithmetic (k_generic.hip), the division in the form the host verified for the model's parameters
+__device__ __forceinline__ int edge_quant(float x, const F32Edge &e) {
+    const float t = __fadd_rn(quant_div(x, e.in_scale, e.in_rcp, e.in_fast != 0), e.in_zp_f);
+    const float r = __fadd_rn(t, __builtin_copysignf(0x1.fffffep-2f, t));
+    return (r != r) ? 0 : (int)__builtin_amdgcn_fmed3f(r, e.in_sat_lo, e.in_sat_hi);
+}
+// f32 entry: the step's `n` floats at `src` (16-byte aligned) become the int8 bytes buf[0 .. n) of the row buffer in LDS: 16-byte
+// loads of whole quads, the last n % 4 floats one by one.  Only those n floats are read.
+__device__ __forceinline__ void edge_stage_f32(const float *src, uint8_t *buf, int n, const F32Edge &e, int tid) {
+    const int n4 = n >> 2;
+    for (int i = tid; i < n4; i += 256) {
+        const float4 v = ((const float4 *)src)[i];
+        *(uint32_t *)(buf + 4 * i) = pack4(edge_quant(v.x, e), edge_quant(v.y, e), edge_quant(v.z, e), edge_quant(v.w, e)) ^ e.in_xr4;
+    }
+    for (int i = (n4 << 2) + tid; i < n; i += 256) buf[i] = (uint8_t)(edge_quant(src[i], e) ^ (int)(e.in_xr4 & 0xffu));
+}
+// f32 exit: the `n` bytes of the LDS patch `po` (internal domain) leave as the floats dst[0 .. n), dequantize_i8's expression.  Nothing
+// else is written.
+__device__ __forceinline__ void edge_store_f32(float *dst, const uint8_t *po, int n, const F32Edge &e, int tid) {
+    for (int i = tid; i < n; i += 256) dst[i] = __fmul_rn(e.out_scale, __fsub_rn((float)(int)(int8_t)po[i], e.out_zp_f));
+}
+
 } // namespace k
 } // namespace mf

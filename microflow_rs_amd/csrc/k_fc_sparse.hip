@@ -202,7 +202,7 @@ static void launch_fc_sparse24_t(const int8_t *in, int8_t *out, const FcGemmArgs
     static LaunchState st;
     (void)prepared(st, fc_sparse24<BM, BN, WM, WN>, 64 * WM * WN, lds);
     const int grid = ((a.M + BM - 1) / BM) * (a.N / BN);
-    hipLaunchKernelGGL((fc_sparse24<BM, BN, WM, WN>), dim3(grid), dim3(64 * WM * WN), lds, s, in, out, a);
+    MF_LAUNCH((fc_sparse24<BM, BN, WM, WN>), dim3(grid), dim3(64 * WM * WN), lds, s, in, out, a);
 }
 void launch_fc_sparse24(const int8_t *in, int8_t *out, const FcGemmArgs &a, hipStream_t s) {
     // fc_mfma's tile choice: 256 x 256 tiles where there are enough of them to fill the chip

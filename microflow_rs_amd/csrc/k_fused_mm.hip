@@ -619,7 +619,7 @@ static void launch_dwpw_mm_t(const int8_t *in, int8_t *out, const DwPwArgs &a, i
     DwPwArgs b = a;
     b.dw.qcfg = dq_config(nsteps, grid, dq_est_us((double)batch * (H * W * C + OPIX * N), (double)batch * OPIX * (C + N)));
     b.dw.queue = dq_slot(b.dw.queue, b.dw.qlaunch);
-    hipLaunchKernelGGL((dwpw_mm<H, W, C, S, N, G, NTHR, (DB != 0), CG, CY, ORD, ROWPAD, TS, WPE, MG, XR4, false>), dim3(grid), dim3(NTHR),
+    MF_LAUNCH((dwpw_mm<H, W, C, S, N, G, NTHR, (DB != 0), CG, CY, ORD, ROWPAD, TS, WPE, MG, XR4, false>), dim3(grid), dim3(NTHR),
                        lds, s, in, out, b, batch);
 }
 // the depthwise operator alone (DWONLY instance of the same shape)
@@ -635,7 +635,7 @@ static void launch_dw_mm_t(const int8_t *in, int8_t *out, const DwPwArgs &a, int
     DwPwArgs b = a;
     b.dw.qcfg = dq_config(nsteps, grid, dq_est_us((double)batch * (H * W * C + OPIX * C), (double)batch * OPIX * C));
     b.dw.queue = dq_slot(b.dw.queue, b.dw.qlaunch);
-    hipLaunchKernelGGL((dwpw_mm<H, W, C, S, N, G, NTHR, (DB != 0), CG, CY, ORD, ROWPAD, TS, WPE, MG, XR4, true>), dim3(grid), dim3(NTHR),
+    MF_LAUNCH((dwpw_mm<H, W, C, S, N, G, NTHR, (DB != 0), CG, CY, ORD, ROWPAD, TS, WPE, MG, XR4, true>), dim3(grid), dim3(NTHR),
                        lds, s, in, out, b, batch);
 }
 // Measured per shape against dw3x3_nhwc (v_dot4 taps, no MID round trip): the matrix-pipe form wins on the three
@@ -713,7 +713,7 @@ static void launch_dwpw_rr_t(const int8_t *in, int8_t *out, const DwPwArgs &a, i
     DwPwArgs b = a;
     b.dw.qcfg = dq_config(nsteps, grid, dq_est_us((double)batch * (H * W * C + OPIX * N), (double)batch * OPIX * (C + N)));
     b.dw.queue = dq_slot(b.dw.queue, b.dw.qlaunch);
-    hipLaunchKernelGGL((dwpw_rr<H, W, C, S, N, G, NTHR, DB, CG, CY, ORD, ROWPAD, TS, WPE, MG, XR4>), dim3(grid), dim3(NTHR),
+    MF_LAUNCH((dwpw_rr<H, W, C, S, N, G, NTHR, DB, CG, CY, ORD, ROWPAD, TS, WPE, MG, XR4>), dim3(grid), dim3(NTHR),
                        lds, s, in, out, b, batch);
 }
 const char *dwpw_rr_name(int H, int W, int C, int S, int N) {

@@ -556,10 +556,10 @@ __global__ __launch_bounds__(256) void fc_rowsum(const int8_t *__restrict__ in, 
 bool launch_fc_rowwave(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s) {
     const int grid = grid_for(rows, 4);
     switch (a.N) {
-    case 1: hipLaunchKernelGGL(fc_rowwave<1>, dim3(grid), dim3(256), 0, s, in, out, a, rows); return true;
-    case 2: hipLaunchKernelGGL(fc_rowwave<2>, dim3(grid), dim3(256), 0, s, in, out, a, rows); return true;
-    case 4: hipLaunchKernelGGL(fc_rowwave<4>, dim3(grid), dim3(256), 0, s, in, out, a, rows); return true;
-    case 8: hipLaunchKernelGGL(fc_rowwave<8>, dim3(grid), dim3(256), 0, s, in, out, a, rows); return true;
+    case 1: MF_LAUNCH(fc_rowwave<1>, dim3(grid), dim3(256), 0, s, in, out, a, rows); return true;
+    case 2: MF_LAUNCH(fc_rowwave<2>, dim3(grid), dim3(256), 0, s, in, out, a, rows); return true;
+    case 4: MF_LAUNCH(fc_rowwave<4>, dim3(grid), dim3(256), 0, s, in, out, a, rows); return true;
+    case 8: MF_LAUNCH(fc_rowwave<8>, dim3(grid), dim3(256), 0, s, in, out, a, rows); return true;
     default: return false;
     }
 }
@@ -568,7 +568,7 @@ bool fc_mfma_supported(size_t rows, int N, int K) {
     return rows >= 64 && N % 128 == 0 && K % 128 == 0 && (rows + 127) / 128 * (size_t)(N / 128) < (1u << 30);
 }
 void launch_fc_rowsum(const int8_t *in, int *rowsum, size_t rows, int K, hipStream_t s) {
-    hipLaunchKernelGGL(fc_rowsum, dim3(grid_for(rows, 4)), dim3(256), 0, s, in, rowsum, rows, K);
+    MF_LAUNCH(fc_rowsum, dim3(grid_for(rows, 4)), dim3(256), 0, s, in, rowsum, rows, K);
 }
 template <int BM, int BN, int WM, int WN, bool STAGGER, bool RS, bool RSP = false>
 static void launch_fc_mfma_t(const int8_t *in, int8_t *out, const FcGemmArgs &a, hipStream_t s) {
@@ -576,7 +576,7 @@ static void launch_fc_mfma_t(const int8_t *in, int8_t *out, const FcGemmArgs &a,
     static LaunchState st;
     (void)prepared(st, fc_mfma<BM, BN, WM, WN, STAGGER, RS, RSP>, 64 * WM * WN, lds);
     const int grid = ((a.M + BM - 1) / BM) * (a.N / BN);
-    hipLaunchKernelGGL((fc_mfma<BM, BN, WM, WN, STAGGER, RS, RSP>), dim3(grid), dim3(64 * WM * WN), lds, s, in, out, a);
+    MF_LAUNCH((fc_mfma<BM, BN, WM, WN, STAGGER, RS, RSP>), dim3(grid), dim3(64 * WM * WN), lds, s, in, out, a);
 }
 // the in-launch row sums: 256 x 256 tiles (the instance that fills the chip), a tile row's rows dealt evenly over its tiles
 bool fc_mfma_rowsum_prologue(size_t rows, int N) {
@@ -613,9 +613,9 @@ bool launch_fc_rowwave_softmax(const int8_t *in, int8_t *out, const FcArgs &a, c
                                hipStream_t s) {
     const int grid = grid_for(rows, 4);
     switch (a.N) {
-    case 2: hipLaunchKernelGGL(fc_rowwave_softmax<2>, dim3(grid), dim3(256), 0, s, in, out, a, sm, rows); return true;
-    case 4: hipLaunchKernelGGL(fc_rowwave_softmax<4>, dim3(grid), dim3(256), 0, s, in, out, a, sm, rows); return true;
-    case 8: hipLaunchKernelGGL(fc_rowwave_softmax<8>, dim3(grid), dim3(256), 0, s, in, out, a, sm, rows); return true;
+    case 2: MF_LAUNCH(fc_rowwave_softmax<2>, dim3(grid), dim3(256), 0, s, in, out, a, sm, rows); return true;
+    case 4: MF_LAUNCH(fc_rowwave_softmax<4>, dim3(grid), dim3(256), 0, s, in, out, a, sm, rows); return true;
+    case 8: MF_LAUNCH(fc_rowwave_softmax<8>, dim3(grid), dim3(256), 0, s, in, out, a, sm, rows); return true;
     default: return false;
     }
 }

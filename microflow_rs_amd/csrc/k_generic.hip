@@ -357,33 +357,33 @@ __global__ __launch_bounds__(256) void checksum_i8(const int8_t *__restrict__ in
 // ---- launchers ----
 void launch_conv2d_generic(const int8_t *in, int8_t *out, const ConvArgs &a, size_t batch, hipStream_t s) {
     const size_t total = batch * a.OH * a.OW * a.N;
-    hipLaunchKernelGGL(conv2d_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
+    MF_LAUNCH(conv2d_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
 }
 bool conv1x1_rowwave_supported(const ConvArgs &a) {
     return a.KH == 1 && a.KW == 1 && a.sh == 1 && a.sw == 1 && a.OH == a.H && a.OW == a.W && a.N >= 1 && a.N <= 8 && a.C % 4 == 0;
 }
 void launch_conv1x1_rowwave(const int8_t *in, int8_t *out, const ConvArgs &a, size_t batch, hipStream_t s) {
     const size_t rows = batch * a.H * a.W;
-    hipLaunchKernelGGL(conv1x1_rowwave, dim3(grid_for(rows, 4)), dim3(256), 0, s, in, out, a, rows);
+    MF_LAUNCH(conv1x1_rowwave, dim3(grid_for(rows, 4)), dim3(256), 0, s, in, out, a, rows);
 }
 void launch_dwconv_generic(const int8_t *in, int8_t *out, const ConvArgs &a, size_t batch, hipStream_t s) {
     const size_t total = batch * a.OH * a.OW * a.N;
-    hipLaunchKernelGGL(dwconv_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
+    MF_LAUNCH(dwconv_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
 }
 void launch_avgpool_c4(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s) {
     const size_t total4 = batch * a.OH * a.OW * (a.C / 4);
-    hipLaunchKernelGGL(avgpool_c4, dim3(grid_for(total4)), dim3(256), 0, s, in, out, a, total4);
+    MF_LAUNCH(avgpool_c4, dim3(grid_for(total4)), dim3(256), 0, s, in, out, a, total4);
 }
 void launch_avgpool_generic(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s) {
     const size_t total = batch * a.OH * a.OW * a.C;
-    hipLaunchKernelGGL(avgpool_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
+    MF_LAUNCH(avgpool_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
 }
 void launch_fc_generic(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s) {
     const size_t total = rows * a.N;
-    hipLaunchKernelGGL(fc_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
+    MF_LAUNCH(fc_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
 }
 void launch_softmax(const int8_t *in, int8_t *out, const SoftmaxArgs &a, size_t batch, hipStream_t s) {
-    hipLaunchKernelGGL(softmax_table, dim3(grid_for(batch)), dim3(256), 0, s, in, out, a, batch);
+    MF_LAUNCH(softmax_table, dim3(grid_for(batch)), dim3(256), 0, s, in, out, a, batch);
 }
 // ~0 = the check itself could not run (allocation / launch / copy failed); the sticky error is consumed here
 unsigned long long verify_quant_div(float scale, float rcp, float zp_f, float sat_lo, float sat_hi, hipStream_t s) {
@@ -393,7 +393,7 @@ unsigned long long verify_quant_div(float scale, float rcp, float zp_f, float sa
         return h;
     }
     if (hipMemsetAsync(d, 0, sizeof(h), s) == hipSuccess) {
-        hipLaunchKernelGGL(verify_quant_div_kernel, dim3(256 * 16), dim3(256), 0, s, scale, rcp, zp_f, sat_lo, sat_hi, d);
+        MF_LAUNCH(verify_quant_div_kernel, dim3(256 * 16), dim3(256), 0, s, scale, rcp, zp_f, sat_lo, sat_hi, d);
         if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipStreamSynchronize(s) != hipSuccess) {
             (void)hipGetLastError();
@@ -515,7 +515,7 @@ __global__ __launch_bounds__(256) void verify_fma_form_kernel(const float *A, co
 // all pointers are DEVICE arrays of n entries (bad: zeroed by the caller); returns false when the launch failed
 bool verify_fma_form(const float *A, const float *S, const float *C3, const float *S3, const int *piv, const int *amin, const int *amax,
                      const int *patchP, const int *patchR, int n, float lo, float hi, bool u8, unsigned long long *bad, hipStream_t s) {
-    hipLaunchKernelGGL(verify_fma_form_kernel, dim3(64, n), dim3(256), 0, s, A, S, C3, S3, piv, amin, amax, patchP, patchR, lo, hi,
+    MF_LAUNCH(verify_fma_form_kernel, dim3(64, n), dim3(256), 0, s, A, S, C3, S3, piv, amin, amax, patchP, patchR, lo, hi,
                        u8 ? 0x80u : 0u, bad);
     return hipGetLastError() == hipSuccess;
 }
@@ -578,49 +578,49 @@ unsigned long long selftest_rounding(int mode, bool u8, float lo, float hi, hipS
     return run_selftest(s, [&](unsigned long long *d) {
         const dim3 g(256 * 16), b(256);
         if (mode == 2) {
-            if (u8) hipLaunchKernelGGL((selftest_rounding_kernel<2, 0x80808080u>), g, b, 0, s, lo, hi, d);
-            else hipLaunchKernelGGL((selftest_rounding_kernel<2, 0u>), g, b, 0, s, lo, hi, d);
+            if (u8) MF_LAUNCH((selftest_rounding_kernel<2, 0x80808080u>), g, b, 0, s, lo, hi, d);
+            else MF_LAUNCH((selftest_rounding_kernel<2, 0u>), g, b, 0, s, lo, hi, d);
         } else if (mode == 3) {
-            hipLaunchKernelGGL((selftest_rounding_kernel<3, 0u>), g, b, 0, s, lo, hi, d);
+            MF_LAUNCH((selftest_rounding_kernel<3, 0u>), g, b, 0, s, lo, hi, d);
         } else {
-            if (u8) hipLaunchKernelGGL((selftest_rounding_kernel<1, 0x80808080u>), g, b, 0, s, lo, hi, d);
-            else hipLaunchKernelGGL((selftest_rounding_kernel<1, 0u>), g, b, 0, s, lo, hi, d);
+            if (u8) MF_LAUNCH((selftest_rounding_kernel<1, 0x80808080u>), g, b, 0, s, lo, hi, d);
+            else MF_LAUNCH((selftest_rounding_kernel<1, 0u>), g, b, 0, s, lo, hi, d);
         }
     });
 }
 unsigned long long selftest_cvt_pk(hipStream_t s) { // both modes in one count
     return run_selftest(s, [&](unsigned long long *d) {
-        hipLaunchKernelGGL(selftest_cvt_pk_kernel<1>, dim3(256 * 16), dim3(256), 0, s, d);
-        hipLaunchKernelGGL(selftest_cvt_pk_kernel<0>, dim3(256 * 16), dim3(256), 0, s, d);
+        MF_LAUNCH(selftest_cvt_pk_kernel<1>, dim3(256 * 16), dim3(256), 0, s, d);
+        MF_LAUNCH(selftest_cvt_pk_kernel<0>, dim3(256 * 16), dim3(256), 0, s, d);
     });
 }
 unsigned long long selftest_requant(int mode, bool u8, float A, float S, float lo, float hi, hipStream_t s) {
     return run_selftest(s, [&](unsigned long long *d) {
         const dim3 g(256 * 8), b(256);
         if (mode == 2) {
-            if (u8) hipLaunchKernelGGL((selftest_requant_kernel<2, 0x80808080u>), g, b, 0, s, A, S, lo, hi, d);
-            else hipLaunchKernelGGL((selftest_requant_kernel<2, 0u>), g, b, 0, s, A, S, lo, hi, d);
+            if (u8) MF_LAUNCH((selftest_requant_kernel<2, 0x80808080u>), g, b, 0, s, A, S, lo, hi, d);
+            else MF_LAUNCH((selftest_requant_kernel<2, 0u>), g, b, 0, s, A, S, lo, hi, d);
         } else {
-            if (u8) hipLaunchKernelGGL((selftest_requant_kernel<1, 0x80808080u>), g, b, 0, s, A, S, lo, hi, d);
-            else hipLaunchKernelGGL((selftest_requant_kernel<1, 0u>), g, b, 0, s, A, S, lo, hi, d);
+            if (u8) MF_LAUNCH((selftest_requant_kernel<1, 0x80808080u>), g, b, 0, s, A, S, lo, hi, d);
+            else MF_LAUNCH((selftest_requant_kernel<1, 0u>), g, b, 0, s, A, S, lo, hi, d);
         }
     });
 }
 void launch_quantize(const float *in, int8_t *out, size_t n, float scale, float zp_f, bool u8, hipStream_t s) {
-    hipLaunchKernelGGL(quantize_f32, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, in, out, n, scale, zp_f,
+    MF_LAUNCH(quantize_f32, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, in, out, n, scale, zp_f,
                        u8 ? 0.0f : -128.0f, u8 ? 255.0f : 127.0f, u8 ? 0x80 : 0);
 }
 void launch_xor80(const int8_t *in, int8_t *out, size_t n, hipStream_t s) {
-    hipLaunchKernelGGL(xor80_bytes, dim3(grid_for((n + 15) / 16)), dim3(256), 0, s, in, out, n);
+    MF_LAUNCH(xor80_bytes, dim3(grid_for((n + 15) / 16)), dim3(256), 0, s, in, out, n);
 }
 void launch_dequantize(const int8_t *in, float *out, size_t n, float scale, float zp_f, bool raw_u8, hipStream_t s) {
-    hipLaunchKernelGGL(dequantize_i8, dim3(grid_for(n)), dim3(256), 0, s, in, out, n, scale, zp_f, raw_u8 ? 1 : 0);
+    MF_LAUNCH(dequantize_i8, dim3(grid_for(n)), dim3(256), 0, s, in, out, n, scale, zp_f, raw_u8 ? 1 : 0);
 }
 void launch_synth(int8_t *out, size_t n, uint64_t seed, uint64_t first, hipStream_t s) {
-    hipLaunchKernelGGL(synth_i8, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, out, n, seed, first);
+    MF_LAUNCH(synth_i8, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, out, n, seed, first);
 }
 void launch_checksum(const int8_t *in, size_t n, unsigned long long *result, hipStream_t s) {
-    hipLaunchKernelGGL(checksum_i8, dim3(grid_for(n, 256 * 16, 1024)), dim3(256), 0, s, in, n, result);
+    MF_LAUNCH(checksum_i8, dim3(grid_for(n, 256 * 16, 1024)), dim3(256), 0, s, in, n, result);
 }
 
 } // namespace k

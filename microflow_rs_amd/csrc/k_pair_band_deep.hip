@@ -98,7 +98,7 @@ static void launch_pair_band_deep_t(const int8_t *in, int8_t *out, const PairBan
     const double hbm = (double)a.H * a.W * a.C + (double)a.OH * a.OW * a.N, rq = (double)a.OH * a.OW * (a.C + a.N);
     b.qcfg = dq_config(nsteps, grid, dq_est_us((double)batch * hbm, (double)batch * rq));
     b.queue = dq_slot(b.queue, b.qlaunch);
-    hipLaunchKernelGGL((pair_band_deep_rt<MG, XR4>), dim3(grid), dim3(512), a.lds_bytes, s, in, out, b, batch);
+    MF_LAUNCH((pair_band_deep_rt<MG, XR4>), dim3(grid), dim3(512), a.lds_bytes, s, in, out, b, batch);
 }
 
 void launch_pair_band_deep(const int8_t *in, int8_t *out, const PairBandArgs &a, int batch, hipStream_t s) {

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void pw_mfma(const int8_t *__restrict__ in,
 // ---- launchers ----
 template <int K, int N, int MG, uint32_t XR4>
 static void launch_pw_t(const int8_t *in, int8_t *out, const PwArgs &a, long long npix, int grid, hipStream_t s) {
-    hipLaunchKernelGGL((pw_mfma<K, N, MG, XR4>), dim3(grid), dim3(256), 0, s, in, out, a, npix);
+    MF_LAUNCH((pw_mfma<K, N, MG, XR4>), dim3(grid), dim3(256), 0, s, in, out, a, npix);
 }
 // workgroups of the grid-strided pointwise kernel (r01 sweep, MF_PW_GRID overrides): the wide early
 // layers (K < 64, most pixels) like many short-lived workgroups, the deep late ones few

@@ -737,7 +737,7 @@ static void launch_quad_t(const int8_t *in, int8_t *out, const QuadArgs &a, int 
     const double rq = (double)batch * ((STEM ? GA::H * GA::W * GA::C : 0) + GA::OPIX * (GA::C + GA::N) + GB::OPIX * (GB::C + GB::N));
     b.a.dw.qcfg = dq_config(nsteps, grid, dq_est_us(hbm, rq));
     b.a.dw.queue = dq_slot(b.a.dw.queue, b.a.dw.qlaunch);
-    hipLaunchKernelGGL((quad_rr<Q, STEM, MG, XR4, F32IN>), dim3(grid), dim3(Q::NTHR), lds, s, in, out, b, batch);
+    MF_LAUNCH((quad_rr<Q, STEM, MG, XR4, F32IN>), dim3(grid), dim3(Q::NTHR), lds, s, in, out, b, batch);
 }
 template <typename Q> static bool quad_matches(int H, int W, int C, int S, int N, int H2, int W2, int C2, int S2, int N2) {
     using GA = typename Q::A;

@@ -303,7 +303,7 @@ template <int MG, uint32_t XR4> static void launch_quad_mm_t(const int8_t *in, i
     QuadArgs b = a;
     b.a.dw.qcfg = dq_config(nsteps, grid, dq_est_us((double)batch * (9216 + 4608), (double)batch * (9216 * 2 + 2304 + 4608)));
     b.a.dw.queue = dq_slot(b.a.dw.queue, b.a.dw.qlaunch);
-    hipLaunchKernelGGL((quad_mm_12x12x64<MG, XR4>), dim3(grid), dim3(Q64::NTHR), Q64::LDS, s, in, out, b, batch);
+    MF_LAUNCH((quad_mm_12x12x64<MG, XR4>), dim3(grid), dim3(Q64::NTHR), Q64::LDS, s, in, out, b, batch);
 }
 bool quad_mm_shape(int H, int W, int C, int S, int N, int H2, int W2, int C2, int S2, int N2) {
     return H == 12 && W == 12 && C == 64 && S == 1 && N == 64 && H2 == 12 && W2 == 12 && C2 == 64 && S2 == 2 && N2 == 128;

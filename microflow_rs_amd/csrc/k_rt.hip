@@ -9,6 +9,7 @@
 // epilogue -- but every extent is a kernel argument, a large image is cut into row bands, and the weights of the 1x1
 // convolution live in LDS instead of registers.  Arithmetic contract and helpers: k_common.hpp.
 #include "k_common.hpp"
+#include "k_fc_layer.hpp"
 
 #include <algorithm>
 #include <map>
@@ -764,7 +765,7 @@ static void launch_dw_mm_k(const int8_t *in, int8_t *out, const ConvMmArgs &a, i
     }
     const int nsteps = ((batch + a.G - 1) / a.G) * a.NBANDS;
     const int grid = nsteps < 256 * per_cu ? nsteps : 256 * per_cu;
-    hipLaunchKernelGGL((dw_mm_rt<MG, XR4, KSMAX>), dim3(grid), dim3(256), lds, s, in, out, a, batch);
+    MF_LAUNCH((dw_mm_rt<MG, XR4, KSMAX>), dim3(grid), dim3(256), lds, s, in, out, a, batch);
 }
 template <int MG, uint32_t XR4>
 static void launch_dw_mm_t(const int8_t *in, int8_t *out, const ConvMmArgs &a, int batch, hipStream_t s) {
@@ -864,7 +865,7 @@ static void launch_dw_rt_t(const int8_t *in, int8_t *out, const DwRtArgs &a, int
     const double opix = (double)a.OH * a.OW;
     b.dw.qcfg = dq_config(nsteps, grid, dq_est_us((double)batch * ((double)a.H * a.W * a.C + opix * a.C), (double)batch * opix * a.C));
     b.dw.queue = dq_slot(b.dw.queue, b.dw.qlaunch);
-    hipLaunchKernelGGL((dw3x3_rt<S, R, WZ, MG, XR4>), dim3(grid), dim3(a.NTHR), lds, s, in, out, b, batch);
+    MF_LAUNCH((dw3x3_rt<S, R, WZ, MG, XR4>), dim3(grid), dim3(a.NTHR), lds, s, in, out, b, batch);
 }
 void launch_dw_rt(const int8_t *in, int8_t *out, const DwRtArgs &a, int S, bool wz, int batch, hipStream_t s) {
     const int mg = a.dw.magic;
@@ -904,7 +905,7 @@ static void launch_pw_rt_t(const int8_t *in, int8_t *out, const PwRtArgs &a, lon
     const long long want = (nchunks + 3) / 4;
     const int cap = 256 * per_cu;                    // persistent: the weight image is copied to LDS once per workgroup
     const int grid = (int)(want < cap ? want : cap);
-    hipLaunchKernelGGL((pw_rt_lds<WZ, MG, XR4>), dim3(grid), dim3(256), lds, s, in, out, a, npix);
+    MF_LAUNCH((pw_rt_lds<WZ, MG, XR4>), dim3(grid), dim3(256), lds, s, in, out, a, npix);
 }
 template <int KSC, int MG, uint32_t XR4>
 static void launch_pw_rt_reg_t(const int8_t *in, int8_t *out, const PwRtArgs &a, long long nrows, hipStream_t s) {
@@ -915,7 +916,7 @@ static void launch_pw_rt_reg_t(const int8_t *in, int8_t *out, const PwRtArgs &a,
     // persistent: a workgroup fetches its operand A once; a few waves of workgroups per CU keep the loads deep
     const long long cap = 256LL * per_cu * 2;
     const int grid = (int)(want < cap ? (want < 1 ? 1 : want) : cap);
-    hipLaunchKernelGGL((pw_rt<KSC, MG, XR4>), dim3(grid), dim3(256), 0, s, in, out, a, nrows);
+    MF_LAUNCH((pw_rt<KSC, MG, XR4>), dim3(grid), dim3(256), 0, s, in, out, a, nrows);
 }
 void launch_pw_rt(const int8_t *in, int8_t *out, const PwRtArgs &a, bool wz, long long npix, hipStream_t s) {
     const int mg = a.magic;
@@ -969,8 +970,11 @@ void launch_pw_rt(const int8_t *in, int8_t *out, const PwRtArgs &a, bool wz, lon
 //   step    : G whole images, copied verbatim by LDS-DMA between izp rows (row pitch W: column -1 is patched with a select,
 //             no other padding exists for even W), double buffered, dynamic step queue
 // ------------------------------------------------------------------------
-template <int DM, int MG, uint32_t XR4>
-__global__ __launch_bounds__(256) void dw3x3_stem_rt(const int8_t *__restrict__ in, int8_t *__restrict__ out, DwStemRtArgs p, int batch) {
+// F32IN: the instances that hold a model's f32 entry (dw3x3_stem_rt_f32 below): `in` points to floats; an image's H W floats (a
+// multiple of 16, each image 64-byte aligned where `in` is 16-byte aligned) are loaded as float4s, quantised with quantize_f32's
+// arithmetic (k_fc_layer.hpp edge_quant) and written as the same tile dwords the LDS-DMA would have copied.
+template <int DM, int MG, uint32_t XR4, bool F32IN>
+__device__ __forceinline__ void dw3x3_stem_rt_body(const int8_t *__restrict__ in, int8_t *__restrict__ out, const DwStemRtArgs &p, int batch, const F32Edge &eg) {
     constexpr int GUARD = 16, XS = 32 / DM;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -993,8 +997,16 @@ __global__ __launch_bounds__(256) void dw3x3_stem_rt(const int8_t *__restrict__ 
     auto stage = [&](int st, int buf) {
         for (int gg = 0; gg < G; ++gg) {
             if (st * G + gg >= batch) break;
-            const int8_t *src = in + (size_t)(st * G + gg) * IMG;
             uint8_t *dst = lds + buf * BUF + gg * TILE + GUARD + W;
+            if constexpr (F32IN) {
+                const float4 *fsrc = (const float4 *)((const float *)in + (size_t)(st * G + gg) * IMG);
+                for (int i = tid; i < (IMG >> 2); i += 256) {
+                    const float4 v = fsrc[i];
+                    *(uint32_t *)(dst + 4 * i) = pack4(edge_quant(v.x, eg), edge_quant(v.y, eg), edge_quant(v.z, eg), edge_quant(v.w, eg)) ^ eg.in_xr4;
+                }
+                continue;
+            }
+            const int8_t *src = in + (size_t)(st * G + gg) * IMG;
             for (int c = wave; c < NI; c += 4)
                 if (c * 1024 + lane * 16 < IMG) dma16(src + c * 1024 + lane * 16, dst + c * 1024);
         }
@@ -1045,6 +1057,15 @@ __global__ __launch_bounds__(256) void dw3x3_stem_rt(const int8_t *__restrict__ 
     }
     dq.finish(tid);
 }
+template <int DM, int MG, uint32_t XR4>
+__global__ __launch_bounds__(256) void dw3x3_stem_rt(const int8_t *__restrict__ in, int8_t *__restrict__ out, DwStemRtArgs p, int batch) {
+    dw3x3_stem_rt_body<DM, MG, XR4, false>(in, out, p, batch, F32Edge{});
+}
+template <int DM, int MG, uint32_t XR4>
+__global__ __launch_bounds__(256) void dw3x3_stem_rt_f32(const int8_t *__restrict__ in, int8_t *__restrict__ out, DwStemRtArgs p, F32Edge eg, int batch) {
+    static_assert(MG <= 2, "the boundary quantisation needs round-to-nearest: no single-fma epilogue here");
+    dw3x3_stem_rt_body<DM, MG, XR4, true>(in, out, p, batch, eg);
+}
 
 int conv_rows_lds_bytes(const ConvRowsArgs &a) {
     return a.G * a.TILE + a.KH * a.KG * a.NP * 4 + ((a.KG * 4 + 15) & ~15) + a.NP * 16 + 64;
@@ -1094,7 +1115,7 @@ static void launch_conv_rows_t(const int8_t *in, int8_t *out, const ConvRowsArgs
     }
     const int nsteps = (batch + a.G - 1) / a.G;
     const int grid = nsteps < 256 * per_cu ? nsteps : 256 * per_cu;
-    hipLaunchKernelGGL((conv_rows_lds<WZ, MG, XR4>), dim3(grid), dim3(512), lds, s, in, out, a, batch);
+    MF_LAUNCH((conv_rows_lds<WZ, MG, XR4>), dim3(grid), dim3(512), lds, s, in, out, a, batch);
 }
 bool dw_stem_rt_plan(DwStemRtArgs &a, int H, int W, int DM, int OH, int OW) {
     if ((DM != 4 && DM != 8) || W % 16 != 0 || W < 16 || H < 2 || OH != (H + 1) / 2 || OW != W / 2) return false;
@@ -1110,30 +1131,32 @@ bool dw_stem_rt_plan(DwStemRtArgs &a, int H, int W, int DM, int OH, int OW) {
     return true;
 }
 template <int DM, int MG, uint32_t XR4>
-static void launch_dw_stem_rt_t(const int8_t *in, int8_t *out, const DwStemRtArgs &a_in, int batch, hipStream_t s) {
+static void launch_dw_stem_rt_t(const int8_t *in, int8_t *out, const DwStemRtArgs &a_in, int batch, hipStream_t s, const F32Edge *eg) {
     DwStemRtArgs a = a_in;
     const int lds = 2 * a.G * a.TILE + 64 + 16;
-    static LaunchState st[161];
-    const int per_cu = prepared(st[(lds + 1023) / 1024], dw3x3_stem_rt<DM, MG, XR4>, 256, lds);
+    static LaunchState st[161], stf[161];
+    const int per_cu = eg ? prepared(stf[(lds + 1023) / 1024], dw3x3_stem_rt_f32<DM, MG, XR4>, 256, lds)
+                          : prepared(st[(lds + 1023) / 1024], dw3x3_stem_rt<DM, MG, XR4>, 256, lds);
     const int nsteps = (batch + a.G - 1) / a.G;
     const int grid = nsteps < 256 * per_cu ? nsteps : 256 * per_cu;
     const double out_bytes = (double)batch * a.OH * a.OW * a.DM;
-    a.qcfg = dq_config(nsteps, grid, dq_est_us((double)batch * a.H * a.W + out_bytes, out_bytes));
+    a.qcfg = dq_config(nsteps, grid, dq_est_us((double)batch * a.H * a.W * (eg ? 4 : 1) + out_bytes, out_bytes));
     a.queue = dq_slot(a.queue, a.qlaunch);
-    hipLaunchKernelGGL((dw3x3_stem_rt<DM, MG, XR4>), dim3(grid), dim3(256), lds, s, in, out, a, batch);
+    if (eg) MF_LAUNCH((dw3x3_stem_rt_f32<DM, MG, XR4>), dim3(grid), dim3(256), lds, s, in, out, a, *eg, batch);
+    else MF_LAUNCH((dw3x3_stem_rt<DM, MG, XR4>), dim3(grid), dim3(256), lds, s, in, out, a, batch);
 }
-void launch_dw_stem_rt(const int8_t *in, int8_t *out, const DwStemRtArgs &a, int batch, hipStream_t s) {
+void launch_dw_stem_rt(const int8_t *in, int8_t *out, const DwStemRtArgs &a, int batch, hipStream_t s, const F32Edge *eg) {
     const int mg = a.magic;
 #define MF_RT_GO(DMM)                                                                              \
     do {                                                                                           \
         if (a.xr) {                                                                                \
-            if (mg == 2) launch_dw_stem_rt_t<DMM, 2, 0x80808080u>(in, out, a, batch, s);           \
-            else if (mg) launch_dw_stem_rt_t<DMM, 1, 0x80808080u>(in, out, a, batch, s);           \
-            else launch_dw_stem_rt_t<DMM, 0, 0x80808080u>(in, out, a, batch, s);                   \
+            if (mg == 2) launch_dw_stem_rt_t<DMM, 2, 0x80808080u>(in, out, a, batch, s, eg);       \
+            else if (mg) launch_dw_stem_rt_t<DMM, 1, 0x80808080u>(in, out, a, batch, s, eg);       \
+            else launch_dw_stem_rt_t<DMM, 0, 0x80808080u>(in, out, a, batch, s, eg);               \
         } else {                                                                                   \
-            if (mg == 2) launch_dw_stem_rt_t<DMM, 2, 0u>(in, out, a, batch, s);                    \
-            else if (mg) launch_dw_stem_rt_t<DMM, 1, 0u>(in, out, a, batch, s);                    \
-            else launch_dw_stem_rt_t<DMM, 0, 0u>(in, out, a, batch, s);                            \
+            if (mg == 2) launch_dw_stem_rt_t<DMM, 2, 0u>(in, out, a, batch, s, eg);                \
+            else if (mg) launch_dw_stem_rt_t<DMM, 1, 0u>(in, out, a, batch, s, eg);                \
+            else launch_dw_stem_rt_t<DMM, 0, 0u>(in, out, a, batch, s, eg);                        \
         }                                                                                          \
     } while (0)
     if (a.DM == 8) MF_RT_GO(8); else MF_RT_GO(4);
@@ -1247,7 +1270,7 @@ static void launch_conv_mm_n(const int8_t *in, int8_t *out, const ConvMmArgs &a,
     }
     const int nsteps = ((batch + a.G - 1) / a.G) * a.NBANDS;
     const int grid = nsteps < 256 * per_cu ? nsteps : 256 * per_cu;
-    hipLaunchKernelGGL((conv_mm_rt<WZ, MG, XR4, NTHR>), dim3(grid), dim3(NTHR), lds, s, in, out, a, batch);
+    MF_LAUNCH((conv_mm_rt<WZ, MG, XR4, NTHR>), dim3(grid), dim3(NTHR), lds, s, in, out, a, batch);
 }
 template <bool WZ, int MG, uint32_t XR4>
 static void launch_conv_mm_t(const int8_t *in, int8_t *out, const ConvMmArgs &a, int batch, hipStream_t s) {

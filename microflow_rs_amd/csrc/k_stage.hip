@@ -501,7 +501,7 @@ bool launch_stage(int H, int W, int C, int npairs, const int8_t *in, int8_t *out
         static LaunchState st_;                                                                                    \
         per_cu = prepared(st_, stage_6x6x128<G, NTHR, MG, XR>, NTHR, lds);                                   \
         grid = nsteps < 256 * per_cu ? nsteps : 256 * per_cu;                                                      \
-        hipLaunchKernelGGL((stage_6x6x128<G, NTHR, MG, XR>), dim3(grid), dim3(NTHR), lds, s, in, out, a, batch); \
+        MF_LAUNCH((stage_6x6x128<G, NTHR, MG, XR>), dim3(grid), dim3(NTHR), lds, s, in, out, a, batch); \
     } while (0)
     if (a.mode == 3) { // the single-fma form for every operator of the run (its code does not depend on the element type)
         MF_STAGE_GO(3, 0u);

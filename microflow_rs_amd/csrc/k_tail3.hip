@@ -53,9 +53,11 @@ __device__ long long g_tail3_trace[32];
 // idle) MID buffer, its 1x1 output -- this pair's input -- to X3, which is then never staged from HBM.  Wave w owns channel group
 // w % (C/32) of the front depthwise for every second pixel and output tile w of the front 1x1 (operands resident: 3 + C/128
 // registers x 4; the epilogue constants of the two front operators are read from an LDS copy per phase).  Two more barriers per step.
-template <int H, int W, int C, int N, int NTHR, bool DBUF, int MG, uint32_t XR4, bool FRONT = false>
-__global__ __launch_bounds__(NTHR) void pair3_tail(const int8_t *__restrict__ in, int8_t *__restrict__ out, PairTailArgs p, PairFrontArgs fr,
-                                                   size_t batch) {
+// F32OUT: the instances that hold a model's f32 exit (pair3_tail_f32 below): the finishing threads store the dequantised float,
+// scale * (f32(q) - zp) with the Softmax's stamped parameters (kernels.hpp: F32Edge), instead of the byte.
+template <int H, int W, int C, int N, int NTHR, bool DBUF, int MG, uint32_t XR4, bool FRONT, bool F32OUT>
+__device__ __forceinline__ void pair3_tail_body(const int8_t *__restrict__ in, int8_t *__restrict__ out, const PairTailArgs &p, const PairFrontArgs &fr,
+                                                size_t batch, const F32Edge &eg) {
     constexpr int IMGS = 16, PIX = H * W, IMG = PIX * C, KS = C / 64;
     constexpr int NPIECE = (IMG + 1023) / 1024;            // 1 KiB DMA pieces per image (the last one may be short)
     constexpr int XP = IMG + 16;                           // image pitch in LDS (X3 and MID)
@@ -345,8 +347,12 @@ __global__ __launch_bounds__(NTHR) void pair3_tail(const int8_t *__restrict__ in
             const float qf = __fadd_rn(__fdiv_rn(prob, p.tail.sm_oscale), p.tail.sm_ozp_f);
             const float r = __fadd_rn(qf, __builtin_copysignf(0x1.fffffep-2f, qf));
             const size_t image = blk * IMGS + img;
-            if (image < batch)
-                out[image * N + n] = (int8_t)(((r != r) ? 0 : (int)__builtin_amdgcn_fmed3f(r, p.tail.sm_sat_lo, p.tail.sm_sat_hi)) ^ p.tail.xr);
+            const int yq = ((r != r) ? 0 : (int)__builtin_amdgcn_fmed3f(r, p.tail.sm_sat_lo, p.tail.sm_sat_hi)) ^ p.tail.xr;
+            if constexpr (F32OUT) {
+                if (image < batch) ((float *)out)[image * N + n] = __fmul_rn(eg.out_scale, __fsub_rn((float)(int)(int8_t)yq, eg.out_zp_f));
+            } else {
+                if (image < batch) out[image * N + n] = (int8_t)yq;
+            }
             // (the sums of this buffer are next added to two steps from now, after two more barriers)
             __builtin_amdgcn_wave_barrier();
             src[n] = 0;
@@ -358,6 +364,17 @@ __global__ __launch_bounds__(NTHR) void pair3_tail(const int8_t *__restrict__ in
 #endif
     }
 }
+template <int H, int W, int C, int N, int NTHR, bool DBUF, int MG, uint32_t XR4, bool FRONT = false>
+__global__ __launch_bounds__(NTHR) void pair3_tail(const int8_t *__restrict__ in, int8_t *__restrict__ out, PairTailArgs p, PairFrontArgs fr,
+                                                   size_t batch) {
+    pair3_tail_body<H, W, C, N, NTHR, DBUF, MG, XR4, FRONT, false>(in, out, p, fr, batch, F32Edge{});
+}
+template <int H, int W, int C, int N, int NTHR, bool DBUF, int MG, uint32_t XR4, bool FRONT = false>
+__global__ __launch_bounds__(NTHR) void pair3_tail_f32(const int8_t *__restrict__ in, int8_t *__restrict__ out, PairTailArgs p, PairFrontArgs fr,
+                                                       F32Edge eg, size_t batch) {
+    static_assert(MG <= 2, "the dequantisation needs round-to-nearest: no single-fma epilogue here");
+    pair3_tail_body<H, W, C, N, NTHR, DBUF, MG, XR4, FRONT, true>(in, out, p, fr, batch, eg);
+}
 
 bool pair_tail_supported(int H, int W, int C, int N_pw, int N_head, int ntaps) {
     return H == W && (H == 2 || H == 3 || H == 4) && (C == 256 || C == 128) && N_pw == C && N_head == 2 && ntaps == H * W;
@@ -368,14 +385,20 @@ const char *pair_tail_name(int H, int C) {
     return names[C == 256][H - 2];
 }
 template <int H, int C, bool DBUF, int MG, uint32_t XR4>
-static int launch_pair_tail_t(const int8_t *in, int8_t *out, const PairTailArgs &a, size_t batch, hipStream_t s) {
+static int launch_pair_tail_t(const int8_t *in, int8_t *out, const PairTailArgs &a, size_t batch, hipStream_t s, const F32Edge *eg) {
     constexpr int NTHR = C * 4, XP = H * H * C + 16; // one wave per 16 channels
     constexpr int lds = ((DBUF ? 2 : 1) * 16 + 1 + 16) * XP + 2 * 16 * 4 * 4 + 256 * 4 + 2 * 4 * 4;
     const size_t nblk = (batch + 15) / 16;
-    static LaunchState st;
+    static LaunchState st, stf;
+    if (eg) { // `out` points to batch x 2 floats
+        const int pcu = prepared(stf, pair3_tail_f32<H, H, C, 2, NTHR, DBUF, MG, XR4>, NTHR, lds);
+        const size_t capf = (size_t)256 * pcu;
+        MF_LAUNCH((pair3_tail_f32<H, H, C, 2, NTHR, DBUF, MG, XR4>), dim3((unsigned)(nblk < capf ? nblk : capf)), dim3(NTHR), lds, s, in, out, a, PairFrontArgs{}, *eg, batch);
+        return pcu;
+    }
     const int per_cu = prepared(st, pair3_tail<H, H, C, 2, NTHR, DBUF, MG, XR4>, NTHR, lds);
     const size_t cap = (size_t)256 * per_cu;
-    hipLaunchKernelGGL((pair3_tail<H, H, C, 2, NTHR, DBUF, MG, XR4>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(NTHR), lds, s, in, out, a, PairFrontArgs{}, batch);
+    MF_LAUNCH((pair3_tail<H, H, C, 2, NTHR, DBUF, MG, XR4>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(NTHR), lds, s, in, out, a, PairFrontArgs{}, batch);
     return per_cu;
 }
 // ops 23..30 of person_detect: the front pair (6x6x128 stride 2 -> 3x3x256) + pair3_tail<3,3,256,2> in one launch
@@ -383,35 +406,41 @@ bool pair_front_supported(int H, int W, int C, int S, int N, int tailH, int tail
     return H == 6 && W == 6 && C == 128 && S == 2 && N == 256 && tailH == 3 && tailC == 256;
 }
 template <int MG, uint32_t XR4>
-static void launch_pair_front_tail_t(const int8_t *in, int8_t *out, const PairTailArgs &a, const PairFrontArgs &fr, size_t batch, hipStream_t s) {
+static void launch_pair_front_tail_t(const int8_t *in, int8_t *out, const PairTailArgs &a, const PairFrontArgs &fr, size_t batch, hipStream_t s,
+                                     const F32Edge *eg) {
     constexpr int H = 3, C = 256, NTHR = C * 4, XP = H * H * C + 16, XP1 = 4 * H * H * (C / 2) + 16;
     constexpr int lds = 16 * XP1 + (16 + 16) * XP + 256 + 2 * 16 * 4 * 4 + 256 * 4 + 2 * 4 * 4 + 256 + 3 * (C / 2 + 3 * C) * 4;
     static_assert(lds <= 160 * 1024, "one workgroup per CU");
     const size_t nblk = (batch + 15) / 16;
-    static LaunchState st;
+    static LaunchState st, stf;
+    if (eg) {
+        const size_t capf = (size_t)256 * prepared(stf, pair3_tail_f32<H, H, C, 2, NTHR, false, MG, XR4, true>, NTHR, lds);
+        MF_LAUNCH((pair3_tail_f32<H, H, C, 2, NTHR, false, MG, XR4, true>), dim3((unsigned)(nblk < capf ? nblk : capf)), dim3(NTHR), lds, s, in, out, a, fr, *eg, batch);
+        return;
+    }
     const int per_cu = prepared(st, pair3_tail<H, H, C, 2, NTHR, false, MG, XR4, true>, NTHR, lds);
     const size_t cap = (size_t)256 * per_cu;
-    hipLaunchKernelGGL((pair3_tail<H, H, C, 2, NTHR, false, MG, XR4, true>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(NTHR), lds, s, in, out, a, fr, batch);
+    MF_LAUNCH((pair3_tail<H, H, C, 2, NTHR, false, MG, XR4, true>), dim3((unsigned)(nblk < cap ? nblk : cap)), dim3(NTHR), lds, s, in, out, a, fr, batch);
 }
-void launch_pair_front_tail(const int8_t *in, int8_t *out, const PairTailArgs &a, const PairFrontArgs &fr, size_t batch, hipStream_t s) {
+void launch_pair_front_tail(const int8_t *in, int8_t *out, const PairTailArgs &a, const PairFrontArgs &fr, size_t batch, hipStream_t s, const F32Edge *eg) {
     if (a.tail.xr) {
-        if (a.magic) launch_pair_front_tail_t<1, 0x80808080u>(in, out, a, fr, batch, s);
-        else launch_pair_front_tail_t<0, 0x80808080u>(in, out, a, fr, batch, s);
+        if (a.magic) launch_pair_front_tail_t<1, 0x80808080u>(in, out, a, fr, batch, s, eg);
+        else launch_pair_front_tail_t<0, 0x80808080u>(in, out, a, fr, batch, s, eg);
     } else {
-        if (a.magic) launch_pair_front_tail_t<1, 0u>(in, out, a, fr, batch, s);
-        else launch_pair_front_tail_t<0, 0u>(in, out, a, fr, batch, s);
+        if (a.magic) launch_pair_front_tail_t<1, 0u>(in, out, a, fr, batch, s, eg);
+        else launch_pair_front_tail_t<0, 0u>(in, out, a, fr, batch, s, eg);
     }
 }
-void launch_pair_tail(const int8_t *in, int8_t *out, const PairTailArgs &a, size_t batch, hipStream_t s) {
+void launch_pair_tail(const int8_t *in, int8_t *out, const PairTailArgs &a, size_t batch, hipStream_t s, const F32Edge *eg) {
     int per_cu = 1;
 #define MF_PT_GO(HH, CC, DB)                                                                          \
     do {                                                                                              \
         if (a.tail.xr) {                                                                              \
-            if (a.magic) per_cu = launch_pair_tail_t<HH, CC, DB, 1, 0x80808080u>(in, out, a, batch, s); \
-            else per_cu = launch_pair_tail_t<HH, CC, DB, 0, 0x80808080u>(in, out, a, batch, s);       \
+            if (a.magic) per_cu = launch_pair_tail_t<HH, CC, DB, 1, 0x80808080u>(in, out, a, batch, s, eg);\
+            else per_cu = launch_pair_tail_t<HH, CC, DB, 0, 0x80808080u>(in, out, a, batch, s, eg);   \
         } else {                                                                                      \
-            if (a.magic) per_cu = launch_pair_tail_t<HH, CC, DB, 1, 0u>(in, out, a, batch, s);        \
-            else per_cu = launch_pair_tail_t<HH, CC, DB, 0, 0u>(in, out, a, batch, s);                \
+            if (a.magic) per_cu = launch_pair_tail_t<HH, CC, DB, 1, 0u>(in, out, a, batch, s, eg);    \
+            else per_cu = launch_pair_tail_t<HH, CC, DB, 0, 0u>(in, out, a, batch, s, eg);            \
         }                                                                                             \
     } while (0)
     if (a.C == 256) {
@@ -487,10 +516,10 @@ bool tail_supported(int C, int N, int ntaps) {
 void launch_tail(const int8_t *in, int8_t *out, const TailArgs &a, size_t batch, hipStream_t s) {
     const int grid = grid_for(batch, 4);
     switch (a.N) {
-    case 1: hipLaunchKernelGGL(tail_pool_head_softmax<1>, dim3(grid), dim3(256), 0, s, in, out, a, batch); break;
-    case 2: hipLaunchKernelGGL(tail_pool_head_softmax<2>, dim3(grid), dim3(256), 0, s, in, out, a, batch); break;
-    case 4: hipLaunchKernelGGL(tail_pool_head_softmax<4>, dim3(grid), dim3(256), 0, s, in, out, a, batch); break;
-    default: hipLaunchKernelGGL(tail_pool_head_softmax<8>, dim3(grid), dim3(256), 0, s, in, out, a, batch); break;
+    case 1: MF_LAUNCH(tail_pool_head_softmax<1>, dim3(grid), dim3(256), 0, s, in, out, a, batch); break;
+    case 2: MF_LAUNCH(tail_pool_head_softmax<2>, dim3(grid), dim3(256), 0, s, in, out, a, batch); break;
+    case 4: MF_LAUNCH(tail_pool_head_softmax<4>, dim3(grid), dim3(256), 0, s, in, out, a, batch); break;
+    default: MF_LAUNCH(tail_pool_head_softmax<8>, dim3(grid), dim3(256), 0, s, in, out, a, batch); break;
     }
 }
 

@@ -9,6 +9,27 @@
 namespace mf {
 namespace k {
 
+// Every kernel launch of the library goes through MF_LAUNCH: counted per host thread, so that the model runtime can say how many a
+// call of its own enqueued (mf_model_device_ops; the counter itself lives in ops.hip)
+extern thread_local unsigned long long launches_enqueued;
+#define MF_LAUNCH(...)                      \
+    do {                                    \
+        ++::mf::k::launches_enqueued;       \
+        hipLaunchKernelGGL(__VA_ARGS__);    \
+    } while (0)
+
+// The model boundary inside a launch (M::predict, microflow-macros/src/lib.rs:188-191).  Entry: the launch reads f32 and quantises
+// while it stages, q = sat(roundf(x / in_scale + in_zp_f)) (quantize_f32's arithmetic, k_generic.hip; a u8 model gets the internal
+// byte directly).  Exit: the launch stores scale * (f32(q) - zp_f) (dequantize_i8's expression) as floats instead of its bytes;
+// out_zp_f is the zero point in the internal domain (a u8 model's minus 128: both integers, the difference is the same float).
+struct F32Edge {
+    float in_scale, in_rcp, in_zp_f, in_sat_lo, in_sat_hi;
+    uint32_t in_xr4;
+    int in_fast;         // 1: the 3-instruction division was verified for these parameters (k_common.hpp: quant_div)
+    float out_scale, out_zp_f;
+};
+constexpr int EDGE_IN = 1, EDGE_OUT = 2; // `edge` of the launchers below: which ends of the launch are f32
+
 // Per-channel folded epilogue constants live in HBM (tiny, L2-resident):
 //   A[c]  = fl32(f32(ozp) + c0[c])      S[c] = c1[c or 0]
 //   Kc[c] = -izp * sum_taps w[c] + T * izp * wzp[c]   (FC: c3 - c2[c])
@@ -247,7 +268,8 @@ struct DwStemRtArgs {
     int qcfg;
 };
 bool dw_stem_rt_plan(DwStemRtArgs &a, int H, int W, int DM, int OH, int OW);
-void launch_dw_stem_rt(const int8_t *in, int8_t *out, const DwStemRtArgs &a, int batch, hipStream_t s);
+// (eg != nullptr: the f32 entry -- `in` points to batch x H W floats, 16-byte aligned, quantised with eg's in_* parameters while staged)
+void launch_dw_stem_rt(const int8_t *in, int8_t *out, const DwStemRtArgs &a, int batch, hipStream_t s, const F32Edge *eg = nullptr);
 bool conv_rows_plan(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same);
 void launch_conv_rows(const int8_t *in, int8_t *out, const ConvRowsArgs &a, bool wz, int batch, hipStream_t s);
 // Conv2D with any filter, C % 16 == 0, as an MFMA product over K = KH KW C (k_rt.hip: conv_mm_rt)
@@ -474,6 +496,8 @@ struct DwFcArgs {
 bool dwfc_supported(int H, int W, int KH, int KW, int sh, int sw, int OH, int OW, int DM, int NFC);
 const char *dwfc_name();
 void launch_dwfc(const int8_t *in, int8_t *out, const DwFcArgs &a, size_t batch, hipStream_t s);
+// ... with an f32 end (edge: EDGE_IN | EDGE_OUT): `in` batch x 1960 floats, 16-byte aligned / `out` batch x 4 floats
+void launch_dwfc_f32(const void *in, void *out, const DwFcArgs &a, const F32Edge &e, int edge, size_t batch, hipStream_t s);
 
 // DepthwiseConv2D 3x3 + Conv2D 1x1 on a 3x3x256 tensor + AveragePool2D + head Conv2D + Softmax in one launch
 // (k_tail3.hip: person_detect ops 25..30)
@@ -505,10 +529,11 @@ struct PairFrontArgs {
     float pw_lo, pw_hi;
 };
 bool pair_front_supported(int H, int W, int C, int S, int N, int tailH, int tailC);
-void launch_pair_front_tail(const int8_t *in, int8_t *out, const PairTailArgs &a, const PairFrontArgs &fr, size_t batch, hipStream_t s);
+// (eg != nullptr, here and in launch_pair_tail: the f32 exit -- `out` points to batch x 2 floats, dequantised with eg's out_scale / out_zp_f)
+void launch_pair_front_tail(const int8_t *in, int8_t *out, const PairTailArgs &a, const PairFrontArgs &fr, size_t batch, hipStream_t s, const F32Edge *eg = nullptr);
 bool pair_tail_supported(int H, int W, int C, int N_pw, int N_head, int ntaps);
 const char *pair_tail_name(int H, int C);
-void launch_pair_tail(const int8_t *in, int8_t *out, const PairTailArgs &a, size_t batch, hipStream_t s);
+void launch_pair_tail(const int8_t *in, int8_t *out, const PairTailArgs &a, size_t batch, hipStream_t s, const F32Edge *eg = nullptr);
 
 // a run of identical depthwise + pointwise pairs on a small tensor as one persistent kernel (k_stage.hip)
 struct StagePair {
@@ -654,6 +679,9 @@ constexpr int FC_RT_LDS_MAX = 160 * 1024 - 1024;
 bool fc_rt_plan(FcRtArgs &a, int K, int N); // fills the geometry fields; false: the shape is beyond the budget
 std::vector<int8_t> fc_rt_weight_image(const int8_t *w /*[N][K]*/, int K, int N);
 void launch_fc_rt(const int8_t *in, int8_t *out, const FcRtArgs &a, long long rows, hipStream_t s);
+// fc_rt / fc_chain / pool_fc_chain with an f32 end: `in` points to rows x K floats (16-byte aligned) when edge & EDGE_IN, `out` to
+// rows x N floats when edge & EDGE_OUT; the other end as in the int8 launch
+void launch_fc_rt_f32(const void *in, void *out, const FcRtArgs &a, const F32Edge &e, int edge, long long rows, hipStream_t s);
 // Conv2D of any C and N outside the other Conv2D kernels, (W C) % 4 == 0, as an MFMA product over K' = KH * KWCP with KWCP = KW C
 // rounded up to 16 (k_conv_gemm.hip: conv_gemm_rt); the weights in fc_rt's image, sliced by N across workgroups when they are large
 struct ConvGemmArgs {
@@ -727,6 +755,7 @@ struct FcChainArgs {
 // fills the geometry of a chain whose layers' K, N, S, ... are set in a.l[0 .. L-1]; false: it does not fit the LDS budget
 bool fc_chain_plan(FcChainArgs &a);
 void launch_fc_chain(const int8_t *in, int8_t *out, const FcChainArgs &a, long long rows, hipStream_t s);
+void launch_fc_chain_f32(const void *in, void *out, const FcChainArgs &a, const F32Edge &e, int edge, long long rows, hipStream_t s);
 // The global AveragePool2D of an [H][W][C] image (every pixel in the window, C % 16 == 0) + 1 .. FC_CHAIN_MAX FullyConnected layers
 // (+ a Softmax) in one launch (k_pool_fc.hip: pool_fc_chain).  The pool phase sums the pixels on the matrix pipe straight from HBM
 // and leaves the pooled int8 [R][C] tile in LDS; from there on the step is fc_chain's.
@@ -742,6 +771,7 @@ struct PoolFcArgs {
 // fills the geometry from c.L, c.l[].K / N, c.softmax, P and C; false: C % 16 != 0, or the images and tiles do not fit the LDS budget
 bool pool_fc_plan(PoolFcArgs &a);
 void launch_pool_fc(const int8_t *in, int8_t *out, const PoolFcArgs &a, long long batch, hipStream_t s); // `in` 16-byte aligned
+void launch_pool_fc_f32(const int8_t *in, float *out, const PoolFcArgs &a, const F32Edge &e, long long batch, hipStream_t s); // f32 exit
 
 void launch_softmax(const int8_t *in, int8_t *out, const SoftmaxArgs &a, size_t batch, hipStream_t s);
 // number of float bit patterns (of all 2^32) whose quantised byte differs between quant_div's fast form and the true

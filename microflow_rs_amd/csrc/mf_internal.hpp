@@ -142,7 +142,16 @@ void op_set_generic(OpImpl *op, bool generic);
 // fuse the model-boundary quantize (f32 -> T) into this operator if it has an f32-input kernel
 bool op_set_input_quant(OpImpl *op, float scale, int zp, bool u8);
 bool op_accepts_f32(const OpImpl *op);
-void op_run_f32(OpImpl *op, const float *d_in, size_t batch, int8_t *d_out, void *stream);
+// ... and the mirror image: the model-boundary dequantize (T -> f32, the scale and zero point the operator stamped) inside this
+// operator's launch if it has an f32-output kernel
+bool op_set_output_dequant(OpImpl *op, float scale, int zp, bool u8);
+bool op_emits_f32(const OpImpl *op);
+// the operator's launch with one or both ends in f32: d_in is batch x in_elems floats (16-byte aligned) when in_f32, d_out
+// batch x out_elems floats when out_f32; the other end as op_run's
+void op_run_f32(OpImpl *op, const void *d_in, bool in_f32, size_t batch, void *d_out, bool out_f32, void *stream);
+// kernel launches (and device-side fills and copies) this host thread has enqueued through the library so far; the model runtime adds
+// its own device-to-device copies
+unsigned long long &dev_launch_counter();
 // fused DepthwiseConv2D 3x3 -> Conv2D 1x1 (borrows both operators' device buffers; nullptr when
 // the pair has no fused kernel)
 struct FusedImpl;
@@ -177,8 +186,12 @@ FusedImpl *fused_quad_create(FusedImpl *pair1, FusedImpl *pair2); // two consecu
 FusedImpl *fused_quad_stem_create(OpImpl *stem, FusedImpl *quad); // the one-input-channel stem + a quad in one launch, or nullptr
 void fused_destroy(FusedImpl *f);
 void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream);
+// the model boundary inside a group's launch (as op_set_input_quant / op_set_output_dequant): false when its kernel has no such instance
+bool fused_set_input_quant(FusedImpl *f, float scale, int zp, bool u8);
+bool fused_set_output_dequant(FusedImpl *f, float scale, int zp, bool u8);
 bool fused_accepts_f32(const FusedImpl *f);
-void fused_run_f32(FusedImpl *f, const float *d_in, size_t batch, int8_t *d_out, void *stream);
+bool fused_emits_f32(const FusedImpl *f);
+void fused_run_f32(FusedImpl *f, const void *d_in, bool in_f32, size_t batch, void *d_out, bool out_f32, void *stream);
 const char *fused_kernel_name(const FusedImpl *f);
 int fused_epilogue_mode(const FusedImpl *f); // epilogue mode of the launch (one for all its requantising operators); -1: none
 
@@ -219,6 +232,7 @@ void model_set_autotune(ModelImpl *m, bool enabled);
 // replay the device-resident launch sequence as a hipGraph (captured on the 2nd identical call)
 void model_set_graph(ModelImpl *m, bool enabled);
 uint64_t model_graph_launches(const ModelImpl *m);
+uint64_t model_device_ops(const ModelImpl *m); // kernel launches and device-side copies enqueued so far (a graph replay counts as one)
 // in_f32 or in_i8 (exactly one non-null); out_f32 or out_i8 (exactly one non-null)
 void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t batch,
                float *out_f32, int8_t *out_i8, int mem, int last_op);

@@ -55,6 +55,7 @@ struct Switches {
     bool chain_no_res = false;     // MF_CHAIN_NO_RES     chains reload their operands every step (no register residency)
     bool conv_mm_256 = false;      // MF_CONV_MM_256      round 3's four-wave workgroups for the run-time conv kernel
     bool no_fma_epi = false;       // MF_NO_FMA_EPI       keep the two-rounding requantisation (epilogue modes 1/2) everywhere
+    bool no_f32_boundary = false;  // MF_NO_F32_BOUNDARY  M::predict's quantise / dequantise as separate passes around the FullyConnected launches (fc_rt, fc_chain, pool_fc_chain), not inside them
     bool no_fast_quant_div = false;// MF_NO_FAST_QUANT_DIV  boundary quantisation by IEEE division, not the verified 3-instruction form
     bool dwpw_mm_only = false;     // MF_DWPW_IMPL=mm     every pair on dwpw_mm (LDS intermediate), none on dwpw_rr (registers)
     bool stem_valu = false;        // MF_STEM_IMPL=valu   stem taps on the VALU kernel (dw3x3_stem8), not the matrix-pipe one

@@ -54,6 +54,8 @@ struct ModelImpl {
     int8_t *in_q = nullptr;   // quantized input staging (host-fed or f32 path)
     float *io_f32 = nullptr;  // f32 input / output staging
     size_t io_f32_elems = 0;
+    float *o_f32 = nullptr;   // f32 output staging of a host-fed batch whose last launch dequantises (its input slice is still being
+                              // read): cap_batch x out_elems floats, allocated by the first such call
 
     // hipGraph replay of the device-resident path (mf_model_set_graph): the launch sequence of one
     // (input, output, batch) triple is captured the second time it is seen and replayed afterwards,
@@ -77,6 +79,7 @@ struct ModelImpl {
     GraphKey gkey, gcand;
     bool gvalid = false, gcand_valid = false;
     uint64_t graph_launches = 0;
+    uint64_t device_ops = 0; // kernel launches and device-side copies enqueued so far (mf_model_device_ops)
 
     ~ModelImpl() {
         if (device >= 0) (void)hipSetDevice(device);
@@ -101,8 +104,10 @@ struct ModelImpl {
         }
         if (in_q) (void)hipFree(in_q);
         if (io_f32) (void)hipFree(io_f32);
+        if (o_f32) (void)hipFree(o_f32);
         in_q = nullptr;
         io_f32 = nullptr;
+        o_f32 = nullptr;
         cap_batch = 0;
     }
 };
@@ -438,6 +443,24 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             }
             i = idx.back();
         }
+        // (7) the boundary conversions of M::predict inside the launches at the two ends of the whole model: every launch that can
+        // start a run at operator 0 learns the input's scale and zero point, every one that can end at the last operator the ones
+        // that operator stamped (the stem was told above; a kernel without such an instance says no and keeps the separate pass)
+        {
+            int last_real = (int)n - 1;
+            while (last_real >= 0 && !ops[(size_t)last_real]) --last_real;
+            size_t first_real = 0;
+            while (first_real < n && !ops[first_real]) ++first_real;
+            if (first_real < n && fused[first_real]) (void)fused_set_input_quant(fused[first_real], m->pm.in_scale, m->pm.in_zp, m->pm.u8);
+            if (first_real > 0 && first_real < n) (void)op_set_input_quant(ops[first_real], m->pm.in_scale, m->pm.in_zp, m->pm.u8);
+            if (last_real >= 0) (void)op_set_output_dequant(ops[(size_t)last_real], m->pm.out_scale, m->pm.out_zp, m->pm.u8);
+            for (size_t i = 0; i < n; ++i)
+                if (fused[i] && fused_last[i] == last_real) (void)fused_set_output_dequant(fused[i], m->pm.out_scale, m->pm.out_zp, m->pm.u8);
+            for (const ModelImpl::Stage &st : sg.v) {
+                if (st.first == (int)first_real) (void)fused_set_input_quant(st.f, m->pm.in_scale, m->pm.in_zp, m->pm.u8);
+                if (st.last == last_real) (void)fused_set_output_dequant(st.f, m->pm.out_scale, m->pm.out_zp, m->pm.u8);
+            }
+        }
         // commit (nothing below throws)
         m->stages.swap(sg.v);
         m->device = device;
@@ -472,6 +495,7 @@ void model_set_graph(ModelImpl *m, bool enabled) {
     if (!enabled) m->drop_graph();
 }
 uint64_t model_graph_launches(const ModelImpl *m) { return m->graph_launches; }
+uint64_t model_device_ops(const ModelImpl *m) { return m->device_ops; }
 
 void model_set_generic(ModelImpl *m, bool generic) {
     m->generic = generic;
@@ -480,54 +504,68 @@ void model_set_generic(ModelImpl *m, bool generic) {
         if (o) op_set_generic(o, generic);
 }
 
-// run ops [0..last_op] reading from `src`; returns the buffer holding the result
-// Is the boundary quantize fused into operator 0 for this call?  (peephole: f32 input, fusion on,
-// operator 0 has an f32-input kernel)
-static bool f32_first(const ModelImpl *m, int last_op) {
-    return m->fusion && !m->generic && last_op >= 0 && !m->ops.empty() && m->ops[0] && op_accepts_f32(m->ops[0]);
+// Which launch of a run of ops [0 .. last_op] takes the f32 input itself (the boundary quantize inside it)?  1: the second-level
+// group that starts at the first operator (penta_rr, fc_chain, dwc1_fc_softmax), 2: the first-level group there, 3: that operator alone (the stem kernel, fc_rt: the
+// groups behind it run as usual), 0: none
+static int first_real_op(const ModelImpl *m) { // leading Reshapes alias the input (speech.tflite starts with one)
+    int i = 0;
+    while (i < (int)m->ops.size() && !m->ops[(size_t)i]) ++i;
+    return i;
+}
+static int f32_entry(const ModelImpl *m, int last_op) {
+    const int f = first_real_op(m);
+    if (!m->fusion || m->generic || f > last_op || f >= (int)m->ops.size()) return 0;
+    const ModelImpl::Stage *st0 = stage_at(m, f, last_op);
+    if (st0 && fused_accepts_f32(st0->f)) return 1;
+    if (!st0 && fused_at(m, f) && m->fused_last[(size_t)f] <= last_op && fused_accepts_f32(m->fused[(size_t)f])) return 2;
+    if (!fused_at(m, f) && op_accepts_f32(m->ops[(size_t)f])) return 3;
+    return 0;
 }
 
-// run ops [0..last_op]; `src_f32` != nullptr: operator 0 consumes the f32 input directly.  `final_dst` != nullptr: the
-// launch that produces operator last_op's tensor writes it there instead of into an activation buffer (no copy of
-// the result afterwards: 16 MB per step for the 4096^3 FullyConnected); the return value says where the result is.
+// run ops [0..last_op]; `src_f32` != nullptr (only where f32_entry says so): the first launch consumes the f32 input directly.
+// `final_dst` != nullptr: the launch that produces operator last_op's tensor writes it there instead of into an activation buffer
+// (no copy of the result afterwards: 16 MB per step for the 4096^3 FullyConnected).  `final_f32` != nullptr: that launch stores the
+// dequantised floats there if it has such an instance.  The return value says where the int8 result is; nullptr: it left as floats.
 static const int8_t *run_ops(ModelImpl *m, const int8_t *src, size_t batch, int last_op, hipStream_t stream,
-                             const float *src_f32 = nullptr, int8_t *final_dst = nullptr) {
+                             const float *src_f32 = nullptr, int8_t *final_dst = nullptr, float *final_f32 = nullptr) {
     const int8_t *cur = src;
     int which = 0;
-    int first = 0;
     // the last operator that launches anything (trailing Reshapes alias its output)
     int last_real = last_op;
     while (last_real >= 0 && !m->ops[last_real]) --last_real;
-    if (src_f32) {
-        // the second-level group that starts at operator 0 takes the f32 image itself if it can (penta_rr, k_quad.hip), else the
-        // stem kernel quantises while it stages and the groups behind it run as usual
-        const ModelImpl::Stage *st0 = stage_at(m, 0, last_op);
-        if (st0 && fused_accepts_f32(st0->f)) {
-            int8_t *dst = (final_dst && st0->last >= last_real) ? final_dst : m->act[0];
-            fused_run_f32(st0->f, src_f32, batch, dst, stream);
-            cur = dst;
-            first = st0->last + 1;
-        } else {
-            op_run_f32(m->ops[0], src_f32, batch, (final_dst && last_real == 0) ? final_dst : m->act[0], stream);
-            cur = (final_dst && last_real == 0) ? final_dst : m->act[0];
-            first = 1;
-        }
-        which = 1;
-    }
-    for (int i = first; i <= last_op; ++i) {
+    const int entry = src_f32 ? f32_entry(m, last_op) : 0;
+    if (src_f32 && !entry) fail(MF_ERR_UNSUPPORTED, "no launch takes the f32 input");
+    const int first_real = first_real_op(m);
+    for (int i = 0; i <= last_op; ++i) {
         OpImpl *o = m->ops[i];
         if (!o) continue; // Reshape: alias
+        const bool f32in = src_f32 && i == first_real;
         int8_t *dst = m->act[which];
         if (dst == cur) {
             which ^= 1;
             dst = m->act[which];
         }
         const ModelImpl::Stage *staged = stage_at(m, i, last_op);
-        if (staged && !fused_input_ok(staged->f, cur)) staged = nullptr; // (the operators' own launches take any pointer)
-        const bool grouped = !staged && fused_at(m, i) && m->fused_last[(size_t)i] <= last_op && fused_input_ok(m->fused[(size_t)i], cur);
+        bool grouped;
+        if (f32in) {
+            if (entry != 1) staged = nullptr;
+            grouped = entry == 2;
+        } else {
+            if (staged && !fused_input_ok(staged->f, cur)) staged = nullptr; // (the operators' own launches take any pointer)
+            grouped = !staged && fused_at(m, i) && m->fused_last[(size_t)i] <= last_op && fused_input_ok(m->fused[(size_t)i], cur);
+        }
         const int end = staged ? staged->last : (grouped ? m->fused_last[(size_t)i] : i);
+        const bool f32out = final_f32 && end >= last_real &&
+                            (staged ? fused_emits_f32(staged->f) : grouped ? fused_emits_f32(m->fused[(size_t)i]) : op_emits_f32(o));
         if (final_dst && end >= last_real) dst = final_dst;
-        if (staged) { // several groups in one launch
+        if (f32in || f32out) { // a model boundary inside the launch
+            const void *in = f32in ? (const void *)src_f32 : (const void *)cur;
+            void *out = f32out ? (void *)final_f32 : (void *)dst;
+            if (staged) fused_run_f32(staged->f, in, f32in, batch, out, f32out, stream);
+            else if (grouped) fused_run_f32(m->fused[(size_t)i], in, f32in, batch, out, f32out, stream);
+            else op_run_f32(o, in, f32in, batch, out, f32out, stream);
+            if (f32out) return nullptr;
+        } else if (staged) { // several groups in one launch
             fused_run(staged->f, cur, batch, dst, stream);
         } else if (grouped) { // the whole group in one launch
             fused_run(m->fused[(size_t)i], cur, batch, dst, stream);
@@ -541,6 +579,38 @@ static const int8_t *run_ops(ModelImpl *m, const int8_t *src, size_t batch, int 
     return cur;
 }
 
+// Which of M::predict's two boundary conversions run inside the first / last launch of this call: only with fusion on, the
+// shape-specialised kernels, the whole model, a 16-byte aligned f32 input (float4 loads) and a 4-byte aligned f32 output; and the
+// exit only where the output range does not overlap the input's, which the first launch -- possibly the same one -- is still reading.
+// Otherwise that side keeps its separate pass, with the same bits.
+// can any launch that ends the whole model store floats?
+static bool f32_exit_any(const ModelImpl *m) {
+    int last_real = (int)m->ops.size() - 1;
+    while (last_real >= 0 && !m->ops[(size_t)last_real]) --last_real;
+    if (last_real < 0) return false;
+    if (op_emits_f32(m->ops[(size_t)last_real])) return true;
+    for (size_t i = 0; i < m->fused.size(); ++i)
+        if (m->fused[i] && m->fused_last[i] == last_real && fused_emits_f32(m->fused[i])) return true;
+    for (const ModelImpl::Stage &st : m->stages)
+        if (st.last == last_real && fused_emits_f32(st.f)) return true;
+    return false;
+}
+struct Boundary {
+    bool in = false, out = false;
+};
+static Boundary boundary_plan(const ModelImpl *m, const float *in_f32, const float *out_f32, size_t out_count, const void *in_any, size_t in_bytes,
+                              int last_op) {
+    Boundary b;
+    if (!m->fusion || m->generic || last_op != (int)m->pm.ops.size() - 1) return b;
+    b.in = in_f32 && ((uintptr_t)in_f32 & 15) == 0 && f32_entry(m, last_op) != 0;
+    if (out_f32 && ((uintptr_t)out_f32 & 3) == 0) {
+        const uintptr_t ob = (uintptr_t)out_f32, oe = ob + out_count * sizeof(float);
+        const uintptr_t ib = (uintptr_t)in_any, ie = ib + in_bytes;
+        b.out = !(ob < ie && ib < oe);
+    }
+    return b;
+}
+
 // The whole device-resident sequence (boundary conversion -> ops -> boundary conversion) on
 // `s`: every pointer is a device pointer, nothing synchronizes -- so it can be stream-captured.
 static void enqueue_device(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t batch,
@@ -549,9 +619,11 @@ static void enqueue_device(ModelImpl *m, const float *in_f32, const int8_t *in_i
     const int nops = (int)pm.ops.size();
     const size_t out_elems = last_op == nops - 1 ? pm.out_elems : pm.ops[last_op].out_elems;
     const int8_t *q_in;
-    const bool fuse_q = in_f32 && ((uintptr_t)in_f32 & 15) == 0 && f32_first(m, last_op); // (float4 loads)
+    const Boundary bd = boundary_plan(m, in_f32, out_f32, batch * out_elems, in_f32 ? (const void *)in_f32 : (const void *)in_i8,
+                                      batch * pm.in_elems * (in_f32 ? sizeof(float) : 1), last_op);
+    const bool fuse_q = bd.in;
     if (fuse_q) {
-        q_in = nullptr; // operator 0 quantises while it stages (dw3x3_stem8<.., F32IN>)
+        q_in = nullptr; // the first launch quantises while it stages (dw3x3_stem8<.., F32IN>, fc_chain_f32 ...)
     } else if (in_f32) { // Tensor::quantize(input, scale, zero_point)  (lib.rs:189)
         dev_quantize(m->device, in_f32, batch * pm.in_elems, pm.in_scale, pm.in_zp, pm.u8, m->in_q, s);
         q_in = m->in_q;
@@ -560,6 +632,7 @@ static void enqueue_device(ModelImpl *m, const float *in_f32, const int8_t *in_i
         q_in = m->in_q;
     } else if (((uintptr_t)in_i8 & 15) != 0) { // the fast kernels read 16-byte words: realign an odd caller pointer
         MF_HIP(hipMemcpyAsync(m->in_q, in_i8, batch * pm.in_elems, hipMemcpyDeviceToDevice, s));
+        ++dev_launch_counter();
         q_in = m->in_q;
     } else {
         q_in = in_i8; // consumed in place
@@ -574,11 +647,14 @@ static void enqueue_device(ModelImpl *m, const float *in_f32, const int8_t *in_i
         const uintptr_t ie = ib + batch * pm.in_elems * (in_f32 ? sizeof(float) : 1);
         if (ob < ie && ib < oe) direct = nullptr;
     }
-    const int8_t *res = run_ops(m, q_in, batch, last_op, s, fuse_q ? in_f32 : nullptr, direct);
+    const int8_t *res = run_ops(m, q_in, batch, last_op, s, fuse_q ? in_f32 : nullptr, direct, bd.out ? out_f32 : nullptr);
     if (out_i8) {
         if (pm.u8) dev_xor80(m->device, res, batch * out_elems, out_i8, s);
-        else if (res != out_i8) MF_HIP(hipMemcpyAsync(out_i8, res, batch * out_elems, hipMemcpyDeviceToDevice, s));
-    } else { // .dequantize()  (lib.rs:190) with the parameters the last op stamped on the tensor
+        else if (res != out_i8) {
+            MF_HIP(hipMemcpyAsync(out_i8, res, batch * out_elems, hipMemcpyDeviceToDevice, s));
+            ++dev_launch_counter();
+        }
+    } else if (res) { // .dequantize()  (lib.rs:190) with the parameters the last op stamped on the tensor
         float oscale = pm.out_scale;
         int ozp = pm.out_zp;
         if (last_op != nops - 1) oscale = pm.ops[last_op].out_scale, ozp = pm.ops[last_op].out_zp;
@@ -590,6 +666,15 @@ static void enqueue_device(ModelImpl *m, const float *in_f32, const int8_t *in_i
 static void run_device(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t batch,
                        float *out_f32, int8_t *out_i8, int last_op) {
     hipStream_t s = m->stream;
+    // what this call enqueues, for mf_model_device_ops: the launches and device-to-device copies of an eager pass; one for a call that
+    // launches the graph -- a replay, and also the call that captures it, which records its launches instead of enqueueing them and
+    // then launches the new graph once
+    struct Count {
+        ModelImpl *m;
+        unsigned long long before = dev_launch_counter();
+        bool replay = false;
+        ~Count() { m->device_ops += replay ? 1 : dev_launch_counter() - before; }
+    } count{m};
     if (!m->use_graph) return enqueue_device(m, in_f32, in_i8, batch, out_f32, out_i8, last_op, s);
     ModelImpl::GraphKey k;
     k.in = in_f32 ? (const void *)in_f32 : (const void *)in_i8;
@@ -597,6 +682,7 @@ static void run_device(ModelImpl *m, const float *in_f32, const int8_t *in_i8, s
     k.batch = batch, k.last_op = last_op, k.in_f32 = in_f32 != nullptr, k.out_f32 = out_f32 != nullptr;
     k.epoch = m->epoch;
     if (m->gvalid && m->gkey == k) {
+        count.replay = true;
         MF_HIP(hipGraphLaunch(m->gexec, s));
         ++m->graph_launches;
         return;
@@ -605,6 +691,7 @@ static void run_device(ModelImpl *m, const float *in_f32, const int8_t *in_i8, s
         m->gcand = k, m->gcand_valid = true;
         return enqueue_device(m, in_f32, in_i8, batch, out_f32, out_i8, last_op, s);
     }
+    count.replay = true;
     if (!m->cap_stream) MF_HIP(hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking));
     MF_HIP(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeRelaxed));
     hipGraph_t g = nullptr;
@@ -662,6 +749,14 @@ void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t ba
     float oscale = pm.out_scale;
     int ozp = pm.out_zp;
     if (last_op != nops - 1) oscale = pm.ops[last_op].out_scale, ozp = pm.ops[last_op].out_zp;
+    // (what this call enqueues on the device, for mf_model_device_ops: added on every way out)
+    struct OpsAdded {
+        ModelImpl *m;
+        unsigned long long before = dev_launch_counter();
+        ~OpsAdded() { m->device_ops += dev_launch_counter() - before; }
+    } ops_added{m};
+    if (out_f32 && !m->o_f32 && m->fusion && !m->generic && last_op == nops - 1 && f32_exit_any(m))
+        MF_HIP(hipMalloc((void **)&m->o_f32, m->cap_batch * pm.out_elems * sizeof(float) + 256));
     try {
         if (chunk < batch) { // the copy stream starts after whatever the caller queued on the compute stream
             hipEvent_t e;
@@ -684,12 +779,18 @@ void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t ba
                 MF_HIP(hipEventRecord(e, cs));
                 MF_HIP(hipStreamWaitEvent(s, e, 0));
             }
-            const bool fuse_q = in_f32 && f32_first(m, last_op);
+            // (the f32 result of a last launch that dequantises goes to its own staging slice: the chunk's f32 input slice, which the
+            // separate pass may overwrite, is still being read by that launch)
+            float *fo = m->io_f32 + first * out_elems;
+            float *fo_direct = m->o_f32 ? m->o_f32 + first * out_elems : nullptr;
+            const Boundary bd = boundary_plan(m, in_f32 ? f : nullptr, out_f32 ? fo_direct : nullptr, n * out_elems,
+                                              in_f32 ? (const void *)f : (const void *)q, n * in_bytes, last_op);
+            const bool fuse_q = bd.in;
             if (in_f32 && !fuse_q) // Tensor::quantize(input, scale, zero_point)  (lib.rs:189)
                 dev_quantize(m->device, f, n * pm.in_elems, pm.in_scale, pm.in_zp, pm.u8, q, s);
             else if (!in_f32 && pm.u8)
                 dev_xor80(m->device, q, n * pm.in_elems, q, s); // u8 -> internal i8 domain
-            const int8_t *res = run_ops(m, q, n, last_op, s, fuse_q ? f : nullptr); // predict_inner
+            const int8_t *res = run_ops(m, q, n, last_op, s, fuse_q ? f : nullptr, nullptr, bd.out ? fo_direct : nullptr); // predict_inner
             if (out_i8) {
                 if (pm.u8) { // internal i8 domain -> u8, in place in the scratch buffer holding the result
                     int8_t *tmp = res == q ? m->act[0] : const_cast<int8_t *>(res);
@@ -698,9 +799,8 @@ void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t ba
                 }
                 MF_HIP(hipMemcpyAsync(out_i8 + first * out_elems, res, n * out_elems, hipMemcpyDeviceToHost, s));
             } else { // .dequantize()  (lib.rs:190) with the parameters the last op stamped on the tensor
-                float *fo = m->io_f32 + first * out_elems;
-                dev_dequantize(m->device, res, n * out_elems, oscale, ozp, pm.u8, fo, s);
-                MF_HIP(hipMemcpyAsync(out_f32 + first * out_elems, fo, n * out_bytes, hipMemcpyDeviceToHost, s));
+                if (res) dev_dequantize(m->device, res, n * out_elems, oscale, ozp, pm.u8, fo, s);
+                MF_HIP(hipMemcpyAsync(out_f32 + first * out_elems, res ? fo : fo_direct, n * out_bytes, hipMemcpyDeviceToHost, s));
             }
         }
         MF_HIP(hipStreamSynchronize(s));

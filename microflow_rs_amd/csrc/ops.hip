@@ -931,7 +931,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
                     op->rowsum_rows = 0;
                 }
                 if (inlaunch && op->rowsum_rows != rows) { // the counters sit behind the sums of THIS row count
-                    if (op->rowsum_rows) MF_HIP(hipMemsetAsync(op->d_rowsum, 0, op->rowsum_cap * sizeof(int), s));
+                    if (op->rowsum_rows) {
+                        MF_HIP(hipMemsetAsync(op->d_rowsum, 0, op->rowsum_cap * sizeof(int), s));
+                        ++k::launches_enqueued; // (a device-side fill)
+                    }
                     op->rowsum_rows = rows;
                 }
                 if (inlaunch) g.rs_sums = op->d_rowsum, g.rs_sync = op->d_rowsum + rows;
@@ -1005,8 +1008,28 @@ static bool quant_div_verified(int device, float scale, float rcp, float zp_f, f
     cache[key] = ok;
     return ok;
 }
+void edge_set_in(k::F32Edge &e, int device, float scale, int zp, bool u8) {
+    e.in_scale = scale, e.in_zp_f = (float)zp;
+    e.in_sat_lo = u8 ? 0.0f : -128.0f, e.in_sat_hi = u8 ? 255.0f : 127.0f;
+    e.in_xr4 = u8 ? 0x80808080u : 0u;
+    e.in_rcp = (float)(1.0 / (double)scale);
+    e.in_fast = quant_div_verified(device, scale, e.in_rcp, e.in_zp_f, e.in_sat_lo, e.in_sat_hi) ? 1 : 0;
+}
+void edge_set_out(k::F32Edge &e, float scale, int zp, bool u8) {
+    // f32(q) - f32(zp) with q = stored + 128: both small integers, so the shift moves to zp exactly (as dev_dequantize)
+    e.out_scale = scale, e.out_zp_f = (float)(zp - (u8 ? 128 : 0));
+}
+thread_local unsigned long long k::launches_enqueued = 0;
+unsigned long long &dev_launch_counter() { return k::launches_enqueued; }
+
 bool op_set_input_quant(OpImpl *op, float scale, int zp, bool u8) {
-    if (op->fast != OpImpl::DW_STEM || !(scale == scale)) return false;
+    if (!(scale == scale)) return false;
+    if ((op->fast == OpImpl::FC_RT || op->fast == OpImpl::DW_STEM_RT) && !switches().no_f32_boundary) { // fc_rt_f32 (k_fc_f32.hip), dw3x3_stem_rt_f32 (k_rt.hip)
+        edge_set_in(op->edge, op->device, scale, zp, u8);
+        op->accepts_f32 = true;
+        return true;
+    }
+    if (op->fast != OpImpl::DW_STEM) return false;
     k::DwStemArgs &f = op->stem;
     f.in_scale = scale, f.in_zp_f = (float)zp;
     f.in_sat_lo = u8 ? 0.0f : -128.0f, f.in_sat_hi = u8 ? 255.0f : 127.0f;
@@ -1019,15 +1042,38 @@ bool op_set_input_quant(OpImpl *op, float scale, int zp, bool u8) {
     return true;
 }
 bool op_accepts_f32(const OpImpl *op) { return op->accepts_f32 && !op->force_generic; }
-void op_run_f32(OpImpl *op, const float *d_in, size_t batch, int8_t *d_out, void *stream) {
+bool op_set_output_dequant(OpImpl *op, float scale, int zp, bool u8) {
+    if (op->fast != OpImpl::FC_RT || switches().no_f32_boundary) return false;
+    edge_set_out(op->edge, scale, zp, u8);
+    op->emits_f32 = true;
+    return true;
+}
+bool op_emits_f32(const OpImpl *op) { return op->emits_f32 && !op->force_generic; }
+void op_run_f32(OpImpl *op, const void *d_in, bool in_f32, size_t batch, void *d_out, bool out_f32, void *stream) {
     if (!batch) return;
-    if (!op_accepts_f32(op)) fail(MF_ERR_UNSUPPORTED, "operator has no f32-input kernel");
+    if (!in_f32 && !out_f32) return op_run(op, (const int8_t *)d_in, batch, (int8_t *)d_out, stream);
+    if (in_f32 && !op_accepts_f32(op)) fail(MF_ERR_UNSUPPORTED, "operator has no f32-input kernel");
+    if (out_f32 && !op_emits_f32(op)) fail(MF_ERR_UNSUPPORTED, "operator has no f32-output kernel");
     if (!d_in || !d_out) fail(MF_ERR_INVALID_ARG, "op_run_f32: null device pointer");
+    if ((in_f32 && ((uintptr_t)d_in & 15)) || (out_f32 && ((uintptr_t)d_out & 3))) fail(MF_ERR_INVALID_ARG, "op_run_f32: unaligned device pointer");
     if (batch > 0x7fffffffull / 4) fail(MF_ERR_INVALID_ARG, "batch too large for one launch");
     const OpSpec &sp = op->s;
+    if (op->fast == OpImpl::DW_STEM_RT) { // (entry only: op_set_output_dequant refuses this kernel)
+        MF_HIP(hipSetDevice(op->device));
+        k::launch_dw_stem_rt((const int8_t *)d_in, (int8_t *)d_out, op->stemrt, (int)batch, (hipStream_t)stream, &op->edge);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (op->fast == OpImpl::FC_RT) {
+        MF_HIP(hipSetDevice(op->device));
+        k::launch_fc_rt_f32(d_in, d_out, op->fcrt, op->edge, (in_f32 ? k::EDGE_IN : 0) | (out_f32 ? k::EDGE_OUT : 0), (long long)(batch * sp.M),
+                            (hipStream_t)stream);
+        MF_HIP(hipGetLastError());
+        return;
+    }
     // (never the single-fma epilogue here: that form runs its kernel in round-toward-zero, and this kernel's boundary quantisation
     // needs round-to-nearest)
-    if (!k::launch_dw_stem(sp.H, sp.W, sp.N, sp.sh, (const int8_t *)d_in, d_out, op->stem, (int)batch,
+    if (!k::launch_dw_stem(sp.H, sp.W, sp.N, sp.sh, (const int8_t *)d_in, (int8_t *)d_out, op->stem, (int)batch,
                            (hipStream_t)stream, true))
         fail(MF_ERR_UNSUPPORTED, "f32 stem kernel missing");
     MF_HIP(hipGetLastError());

@@ -50,12 +50,19 @@ inline void act_bounds(int act, float oscale, int ozp, bool u8, int &lo, int &hi
     if (lo > hi) lo = hi; // min(max(y, lo), hi) == hi for every y when lo > hi
 }
 
+// the halves of a launch's boundary block (kernels.hpp: F32Edge).  `zp` is a value of T.  The entry's 3-instruction division is used
+// only where it was verified for these parameters over all 2^32 inputs on the device (ops.hip: a few ms, once per parameter set)
+void edge_set_in(k::F32Edge &e, int device, float scale, int zp, bool u8);
+void edge_set_out(k::F32Edge &e, float scale, int zp, bool u8);
+
 struct OpImpl {
     int device = 0;
     OpSpec s; // pointers inside are NOT valid after create
     size_t in_elems = 0, out_elems = 0;
     bool force_generic = false;
     bool accepts_f32 = false;  // op_set_input_quant succeeded: op_run_f32 may replace quantize + op_run
+    bool emits_f32 = false;    // op_set_output_dequant succeeded: op_run_f32 may replace op_run + dequantize
+    k::F32Edge edge{};         // ... the boundary parameters of the kernels that take them as one block (fc_rt)
     bool finite_consts = true; // A / S all finite (the shape-specialised and fused epilogues assume it)
     std::string generic_name, fast_name;
     enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM, FC_RT,

@@ -78,6 +78,7 @@ Switches switches_parse() {
     s.no_quad_mm = env_set("MF_NO_QUAD_MM");
     s.no_penta = env_set("MF_NO_PENTA");
     s.no_f32_group = env_set("MF_NO_F32_GROUP");
+    s.no_f32_boundary = env_set("MF_NO_F32_BOUNDARY");
     s.quads = (int)env_ll("MF_QUADS", 7);
     s.no_magic = env_set("MF_NO_MAGIC");
     s.no_sat_pack = env_set("MF_NO_SAT_PACK");

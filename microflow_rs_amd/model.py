@@ -115,6 +115,10 @@ class Model:
     def graph_launches(self):
         return int(_lib.lib().mf_model_graph_launches(self._h))
 
+    def device_ops(self):
+        """kernel launches and device-side copies this model has enqueued so far (a graph replay counts as one)"""
+        return int(_lib.lib().mf_model_device_ops(self._h))
+
     def sync(self):
         _lib.check(_lib.lib().mf_model_sync(self._h))
 

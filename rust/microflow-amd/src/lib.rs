@@ -57,6 +57,8 @@ extern "C" {
     pub fn mf_model_predict_quantized(model: *mut mf_model, input: *const i8, batch: usize, output: *mut f32, mem: c_int) -> c_int;
     pub fn mf_model_run_quantized(model: *mut mf_model, input: *const i8, batch: usize, output: *mut i8, mem: c_int) -> c_int;
     pub fn mf_model_set_stream(model: *mut mf_model, stream: *mut c_void) -> c_int;
+    /// diagnostic: kernel launches and device-side copies this handle has enqueued so far
+    pub fn mf_model_device_ops(model: *const mf_model) -> std::os::raw::c_ulonglong;
     pub fn mf_device_count() -> c_int;
     pub fn mf_models_predict(models: *const *mut mf_model, n_models: c_int, input: *const f32, batch: usize,
                              output: *mut f32) -> c_int;

@@ -1,58 +1,98 @@
 #!/usr/bin/env python3
-"""GPU box: M::predict (f32 in HBM -> f32 out) against predict_quantized on person_detect, batch 65 536, median of HIP-event timings.
-usage: time_f32.py [iters]"""
+"""GPU box: M::predict (f32 in HBM -> f32 out) against run_quantized (int8 in, int8 out) on one model at one batch, in the same
+process: median of HIP-event timings, spread = (max - min) / median, and parity (predict's floats are the dequantised bytes of
+run_quantized on the same quantised input).
+
+usage: time_f32.py MODEL BATCH [iters]     one measurement, in this process
+       time_f32.py --all [iters]           the table of profiles/r09/f32_entry.txt: one child process per row, each with its own time limit
+MODEL: person_detect | speech | sine (models/*.tflite), pd_like:SIDE (tools/tflite_writer.person_detect_like(side=SIDE)),
+       mlp:K-N1-N2...[+sm] (tools/tflite_writer.mlp), pool_head:HxWxC-N1...[+sm] (tools/tflite_writer.pool_head)"""
 import os
+import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
-
-import microflow_rs_amd as mf  # noqa: E402
-from microflow_rs_amd import _lib  # noqa: E402
-from microflow_rs_amd.model import synth_i8  # noqa: E402
-
-iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-B = 65536
-m = mf.model(os.path.join(ROOT, "models", "person_detect.tflite"))
-m.prepare(B, device=0)
-L = _lib.lib()
-x = synth_i8(0x4D4643 + 3, 0, B * m.input_elems)
-y = torch.empty(B * m.output_elems, dtype=torch.int8, device="cuda")
-xf = (x.reshape(B, -1).float() - float(m.input_zero_point)) * float(m.input_scale)
-yf = torch.empty((B, m.output_elems), dtype=torch.float32, device="cuda")
-s = torch.cuda.current_stream()
-_lib.check(L.mf_model_set_stream(m._h, s.cuda_stream))
+ROWS = [("person_detect", 65536), ("speech", 4096), ("speech", 65536), ("sine", 65536), ("pd_like:64", 65536), ("mlp:20-33-7+sm", 65536),
+        ("pool_head:7x7x64-10+sm", 65536)]
 
 
-def med(fn):
-    fn()
-    ts = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b))
-    return sorted(ts)[len(ts) // 2]
+def blob(name):
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    if name in ("person_detect", "speech", "sine"):
+        return open(os.path.join(ROOT, "models", name + ".tflite"), "rb").read()
+    import tflite_writer as tw
+    kind, arg = name.split(":", 1)
+    rng = np.random.default_rng(41)
+    if kind == "pd_like":
+        return tw.person_detect_like(rng, side=int(arg))
+    if kind == "mlp":
+        sm = arg.endswith("+sm")
+        return tw.mlp(rng, [int(v) for v in arg.replace("+sm", "").split("-")], softmax=sm)
+    if kind == "pool_head":
+        shape, _, sizes = arg.replace("+sm", "").partition("-")
+        return tw.pool_head(rng, tuple(int(v) for v in shape.split("x")), tuple(int(v) for v in sizes.split("-")), softmax=arg.endswith("+sm"))
+    raise SystemExit("unknown model %r" % name)
 
 
-def wall(fn, n=20):
-    import time
-    fn()
+def one(name, B, iters):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import microflow_rs_amd as mf
+    from microflow_rs_amd import _lib
+    from microflow_rs_amd.model import synth_i8
+    m = mf.Model(blob(name))
+    m.prepare(B, device=0)
+    L = _lib.lib()
+    u8 = m.dtype == np.uint8
+    x = synth_i8(0x4D4643 + 3, 0, B * m.input_elems)
+    if u8:
+        x = x.view(torch.uint8)
+    y = torch.empty(B * m.output_elems, dtype=x.dtype, device="cuda")
+    xf = ((x.reshape(B, -1).float() - float(m.input_zero_point)) * float(m.input_scale)).contiguous()
+    yf = torch.empty((B, m.output_elems), dtype=torch.float32, device="cuda")
+    _lib.check(L.mf_model_set_stream(m._h, torch.cuda.current_stream().cuda_stream))
+
+    def stat(fn):
+        fn(), fn()
+        ts = []
+        for _ in range(iters):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b))
+        ts.sort()
+        med = ts[len(ts) // 2]
+        return med, (ts[-1] - ts[0]) / med
+
+    ti, si = stat(lambda: _lib.check(L.mf_model_run_quantized(m._h, x.data_ptr(), B, y.data_ptr(), _lib.MF_MEM_DEVICE)))
+    tf, sf = stat(lambda: _lib.check(L.mf_model_predict(m._h, xf.data_ptr(), B, yf.data_ptr(), _lib.MF_MEM_DEVICE)))
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(n):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / n * 1e3
+    same = bool(torch.equal(yf.reshape(-1), (y.float() - float(m.output_zero_point)) * float(m.output_scale)))
+    ops = ""
+    if hasattr(m, "device_ops"):
+        a = m.device_ops()
+        _lib.check(L.mf_model_predict(m._h, xf.data_ptr(), B, yf.data_ptr(), _lib.MF_MEM_DEVICE))
+        b = m.device_ops()
+        _lib.check(L.mf_model_run_quantized(m._h, x.data_ptr(), B, y.data_ptr(), _lib.MF_MEM_DEVICE))
+        ops = " | launches predict %d run_quantized %d" % (b - a, m.device_ops() - b)
+        torch.cuda.synchronize()
+    print("%-16s %6d | run_quantized %8.4f ms (spread %4.1f %%) | predict %8.4f ms (spread %4.1f %%, %7.2f M/s) | parity %s%s"
+          % (name, B, ti, 100 * si, tf, 100 * sf, B / tf / 1e3, same, ops), flush=True)
+    return 0 if same else 1
 
 
-ti = med(lambda: _lib.check(L.mf_model_run_quantized(m._h, x.data_ptr(), B, y.data_ptr(), _lib.MF_MEM_DEVICE)))
-tf = med(lambda: _lib.check(L.mf_model_predict(m._h, xf.data_ptr(), B, yf.data_ptr(), _lib.MF_MEM_DEVICE)))
-yq = (yf / float(m.output_scale) + float(m.output_zero_point)).round().to(torch.int8).reshape(-1)
-wi = wall(lambda: _lib.check(L.mf_model_run_quantized(m._h, x.data_ptr(), B, y.data_ptr(), _lib.MF_MEM_DEVICE)))
-wf = wall(lambda: _lib.check(L.mf_model_predict(m._h, xf.data_ptr(), B, yf.data_ptr(), _lib.MF_MEM_DEVICE)))
-print("wall, 20 calls back to back: int8 %.4f ms | f32 %.4f ms" % (wi, wf))
-print("int8 %.4f ms (%.2f M/s) | f32 %.4f ms (%.2f M/s) | same outputs: %s" % (ti, B / ti / 1e3, tf, B / tf / 1e3, bool(torch.equal(yq, y))))
+if __name__ == "__main__":
+    if len(sys.argv) >= 2 and sys.argv[1] == "--all":
+        for name, B in ROWS:
+            # (a failed or timed-out row ends the table: nothing more is started on a card that may be in trouble)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), name, str(B)] + sys.argv[2:3], timeout=240)
+            if r.returncode:
+                sys.exit(r.returncode)
+        sys.exit(0)
+    if len(sys.argv) < 3:
+        raise SystemExit(__doc__)
+    sys.exit(one(sys.argv[1], int(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 20))
