@@ -77,6 +77,13 @@
 #ifndef MF_RR_SPARSE
 #define MF_RR_SPARSE 0
 #endif
+// 1: in the STEM instances (ops 0..4) pair A runs in the BLOCK form (BlkPhase below): the depthwise taps as ONE v_mfma_i32_16x16x64_i8 per
+// channel quad and 2 x 2 output block instead of three per 16 x 16 outputs, the pointwise 8 -> 16 as four "isolating" v_mfma_i32_16x16x32_i8
+// -- 6 matrix instructions per 64 pixels instead of 10, the same requantisation count.  0: the row form (RrPhase) there as well (A/B;
+// the instances without the stem and the single pairs always run the row form).
+#ifndef MF_RR_BLOCK
+#define MF_RR_BLOCK 1
+#endif
 #ifndef MF_RR_SP_PAD
 #define MF_RR_SP_PAD 7
 #endif
@@ -439,6 +446,102 @@ struct RrPhase {
     }
 };
 
+// The BLOCK form of a stride-1 pair with 8 input channels whose input tile this kernel writes itself (the stem phase of quad_rr).
+//   depthwise : column n of a v_mfma_i32_16x16x64_i8 is a 2 x 2 output block (by, bx), its K = 64 the block's 4 x 4 input patch of one
+//               channel quad (lane group g: patch row g = image row 2 by - 1 + g, 4 pixels x 4 channels = 16 bytes), rows m = 4 s + i =
+//               (pixel s of the block, channel i of the quad) against the host-built operand of wimage.cpp build_dw_blk_weights.  The same
+//               nine taps are summed into the same start values as in the row form: bit-identical.  Lane (n, g) ends with the four
+//               channels of pixel g of block n -- one packable dword per quad, 8 bytes = all 8 channels of ONE pixel for both quads.
+//   pointwise : those 8 bytes are the B operand of four v_mfma_i32_16x16x32_i8, one per pixel s of the block, whose A operand holds the
+//               16 x 8 weights in K-bytes 8 s .. 8 s + 7 and zero elsewhere (build_pw_iso_weights): instruction s sees lane group s's
+//               pixel only, and lane (n, g') gets output channels 4 g' .. 4 g' + 3 of pixel (n, s): one set of constants per lane.
+//   tile A    : channel-quad-planar, [quad][row][x][4 bytes] with a one-pixel halo: a patch row is 16 contiguous bytes at an 8-byte
+//               boundary, read as two ds_read_b64.  Row pitch 320 = 64 mod 256: the four patch rows a 32-lane half reads (two block
+//               rows x two lane groups, 8 blocks x 8 bytes each) fall on four different quarters of the 64 banks -- conflict-free
+//               (scripts/model/blk_banks.py); 4 W + 8 = 200 would be 2-way.
+//   unit      : 16 blocks = 2 block rows x 8 block columns; wave w owns block rows 2 w, 2 w + 1 = output rows 4 w .. 4 w + 3 (the rows
+//               its stem phase writes), W / 16 units.
+//   tile B    : four dword stores per unit at pair B's own layout.  Every 32-lane half stores 8 bytes per pixel for 16 pixels 32 bytes
+//               apart in two rows an even number of rows apart: 4-way on the 32 store banks whatever the pads (ROW is a multiple of
+//               16), i.e. 8 instead of 4 cycles per store (MI355X: a 2-way store conflict is free, 4-way costs 2 x).
+template <typename Ge, int NWAVE_, int MG, uint32_t XR4>
+struct BlkPhase {
+    static constexpr int NWAVE = NWAVE_, NU = Ge::W / 16;
+    static constexpr int LP = 4, ROW = 320, PLANE = (Ge::H + 2) * ROW, BYTES = 2 * PLANE;
+    static_assert(Ge::C == 8 && Ge::S == 1 && Ge::N == 16 && Ge::CG == 1, "block form: 8 -> 16 channels, stride 1, one image per step");
+    static_assert(Ge::H == 4 * NWAVE && Ge::W % 16 == 0, "two block rows per wave, whole units per row");
+    static_assert(ROW >= 4 * Ge::W + 2 * LP && ROW % 256 == 64 && BYTES % 16 == 0 && PLANE + 64 * NU + 8 < 65536, "tile A planes");
+    int tbase;      // first byte of this lane's patch row in plane 0, unit 0
+    int dst_lane;   // this lane's dword of pixel 0 of its block in tile B, unit 0
+    v4i Adw[2];
+    long Apw[4];
+    float4 dA[2], dS[2], cA, cS;
+    int4 dK[2], cK;
+    float dlo, dhi, plo, phi;
+
+    template <typename NEXT>
+    __device__ __forceinline__ void init(const DwPwArgs &p, int lane, int wave) {
+        static_assert(NEXT::H == Ge::OH && NEXT::W == Ge::OW && NEXT::C == Ge::N && NEXT::NQ == 1, "pair B consumes this pair's output, unswizzled");
+        const int n = lane & 15, g = lane >> 4, by = 2 * wave + (n >> 3), bcx = n & 7;
+        tbase = (2 * by + g) * ROW + 8 * bcx; // (LP + 4 (2 bx - 1) = 8 bx)
+        dst_lane = (2 * by + 1) * NEXT::ROW + NEXT::LP + 32 * bcx + 4 * g;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            Adw[q] = ((const v4i *)p.dw.wblk)[q * 64 + lane];
+            dA[q] = ((const float4 *)p.dw.A)[q];
+            dS[q] = ((const float4 *)p.dw.S)[q];
+            dK[q] = magic4<MG>(((const int4 *)p.dw.Kc)[q]);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) Apw[s] = ((const long *)p.pw.wiso)[s * 64 + lane];
+        cA = *(const float4 *)(p.pw.A + 4 * g);
+        cS = *(const float4 *)(p.pw.S + 4 * g);
+        cK = magic4<MG>(*(const int4 *)(p.pw.Kc + 4 * g));
+        dlo = p.dw.lo_f, dhi = p.dw.hi_f, plo = p.pw.lo_f, phi = p.pw.hi_f;
+    }
+
+    template <typename NEXT, bool ASMST = false>
+    __device__ __forceinline__ void run(const uint8_t *tb, uint8_t *dst, int) const {
+        static_assert(!ASMST, "the block form stores with plain LDS stores");
+        // the patch rows of all units up front.  Two 8-byte reads each, kept as they are (volatile): fused into one 16-byte read they
+        // would sit 8 bytes off its natural alignment (replayed), paired into ds_read2_b64 they cost four times the cycles
+        typedef unsigned int u32x2_ __attribute__((ext_vector_type(2)));
+        typedef __attribute__((address_space(3))) const volatile u32x2_ lds_cv2;
+        v4i b[NU][2];
+#pragma unroll
+        for (int u = 0; u < NU; ++u)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                lds_u8_t *a = (lds_u8_t *)(tb + tbase) + (q * PLANE + 64 * u);
+                const u32x2_ lo = *(lds_cv2 *)a, hi = *(lds_cv2 *)(a + 8);
+                b[u][q] = v4i{(int)lo[0], (int)lo[1], (int)hi[0], (int)hi[1]};
+            }
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+            v4i acc[2];
+#if MF_QUAD_PRIO
+            __builtin_amdgcn_s_setprio(MF_QUAD_PRIO);
+#endif
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+                acc[q] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Adw[q], b[u][q], v4i{dK[q].x, dK[q].y, dK[q].z, dK[q].w}, 0, 0, 0);
+#if MF_QUAD_PRIO
+            __builtin_amdgcn_s_setprio(0);
+#endif
+            uint32_t d[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) d[q] = requant_pack4<MG, XR4>(acc[q][0], acc[q][1], acc[q][2], acc[q][3], dA[q], dS[q], dlo, dhi);
+            const long bop = (long)(((unsigned long)d[1] << 32) | (unsigned long)d[0]);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const v4i pa = __builtin_amdgcn_mfma_i32_16x16x32_i8(Apw[s], bop, v4i{cK.x, cK.y, cK.z, cK.w}, 0, 0, 0);
+                *(uint32_t *)(dst + dst_lane + 256 * u + (s >> 1) * NEXT::ROW + (s & 1) * 16) =
+                    requant_pack4<MG, XR4>(pa[0], pa[1], pa[2], pa[3], cA, cS, plo, phi);
+            }
+        }
+    }
+};
+
 
 // the two quads of person_detect: pair geometries = the MF_DWRR_SHAPES rows of the single pairs
 #ifndef MF_Q13B_ROWPAD
@@ -477,6 +580,23 @@ struct Quad57 {
 // v_mfma_i32_16x16x32_i8 whose K bytes are two aligned dwords of an image row; the lane's packed dword goes straight into tile A.
 // The stem's output tensor (18 432 B per image, the input of pair A) then never crosses HBM either.  Its per-lane operands are
 // re-read from device memory every step (L2 hits) instead of living in registers next to those of the two pairs.
+// tile-A constants of a phase type (the row form has none of its own: never looked at)
+template <typename P, typename = void> struct blk_or {
+    static constexpr int ROW = 0, LP = 0, PLANE = 0;
+};
+template <typename P> struct blk_or<P, std::void_t<decltype(P::PLANE)>> {
+    static constexpr int ROW = P::ROW, LP = P::LP, PLANE = P::PLANE;
+};
+// the STEM instances run pair A in the block form (not with the inline-asm stores of MF_QUAD_ASM_LDS: the block form has none)
+template <typename Q, bool STEM> constexpr bool quad_blk() {
+    return STEM && MF_RR_BLOCK != 0 && MF_QUAD_ASM_LDS == 0;
+}
+template <typename Q, bool STEM, int MG, uint32_t XR4>
+using QuadPhaseA = std::conditional_t<quad_blk<Q, STEM>(), BlkPhase<typename Q::A, Q::ACT_A, MG, XR4>, RrPhase<typename Q::A, Q::G, Q::ACT_A, MG, XR4, Q::X2A>>;
+template <typename Q, bool STEM> constexpr int quad_buf_a() { // bytes of one tile-A buffer
+    if constexpr (quad_blk<Q, STEM>()) return BlkPhase<typename Q::A, Q::ACT_A, 1, 0u>::BYTES;
+    else return Q::G * Q::A::TILE;
+}
 template <typename Q, bool STEM> constexpr int quad_stem_bytes() {
     return STEM ? 16 + (2 * Q::A::H + 2) * (2 * Q::A::W) : 0;
 }
@@ -493,7 +613,8 @@ __global__ __launch_bounds__(Q::NTHR, Q::WPE) void quad_rr(const int8_t *__restr
     epi_enter<MG>();
     constexpr int G = Q::G, NTHR = Q::NTHR, NWAVE = NTHR / 64;
     constexpr bool DBA = Q::DBA && !STEM; // two tile-A buffers, the next image staged a whole step ahead
-    constexpr int BUF_A = G * GA::TILE, OFF_B = (DBA ? 2 : 1) * BUF_A + 512, BUF_B = G * GB::TILE, OFF_S = OFF_B + BUF_B + 512;
+    constexpr bool BLK = quad_blk<Q, STEM>();
+    constexpr int BUF_A = quad_buf_a<Q, STEM>(), OFF_B = (DBA ? 2 : 1) * BUF_A + 512, BUF_B = G * GB::TILE, OFF_S = OFF_B + BUF_B + 512;
     constexpr int S_GUARD = 16, SW = 2 * GA::W, SH = 2 * GA::H, S_TILE = quad_stem_bytes<Q, STEM>(), OFF_Q = OFF_S + S_TILE;
     constexpr int OFF_F = OFF_Q + 16; // (F32IN) the staged f32 image, verbatim: SH rows of SW floats
     constexpr int OFF_C = OFF_F + (F32IN ? 4 * SH * SW : 0); // (STEM, MF_QUAD_STEM_LDS) the stem's operands: QuadArgs::stem's 152 dwords
@@ -515,7 +636,7 @@ __global__ __launch_bounds__(Q::NTHR, Q::WPE) void quad_rr(const int8_t *__restr
     // tile A's halo holds pair A's input zero point, tile B's pair B's (= the zero point of pair A's output tensor)
     for (int i = tid; i < OFF_B / 16; i += NTHR) ((uint4 *)lds)[i] = make_uint4(p.a.dw.izp4, p.a.dw.izp4, p.a.dw.izp4, p.a.dw.izp4);
     for (int i = tid; i < (BUF_B + 512) / 16; i += NTHR) ((uint4 *)(lds + OFF_B))[i] = make_uint4(p.b.dw.izp4, p.b.dw.izp4, p.b.dw.izp4, p.b.dw.izp4);
-    RrPhase<GA, G, Q::ACT_A, MG, XR4, Q::X2A> pa;
+    QuadPhaseA<Q, STEM, MG, XR4> pa;
     RrPhase<GB, G, Q::ACT_B, MG, XR4, Q::X2B> pb;
     pa.template init<GB>(p.a, lane, wave);
     pb.template init<void>(p.b, lane, wave);
@@ -633,13 +754,16 @@ __global__ __launch_bounds__(Q::NTHR, Q::WPE) void quad_rr(const int8_t *__restr
         // operand: the aligned dwords at columns 4j - 4 and 4j of tile row 2 oy + ky (ky = g; tile row 0 = input row -1)
         const int off0 = S_GUARD + g * SW + 4 * col - 4, off1 = S_GUARD + (2 * oy1 + g) * SW + 4 * j1 - 4, off2 = S_GUARD + (2 + g) * SW + 4 * (8 + col) - 4;
         // result: pixel 2j + (g >> 1) of output row oy -> tile A row oy + 1, 8 bytes per pixel, this lane's 4 channels
-        const int px = (g >> 1) * 8 + cq;
-        const int dst0 = GA::ROW + GA::LP + 16 * col + px, dst1 = (1 + oy1) * GA::ROW + GA::LP + 16 * j1 + px, dst2 = 2 * GA::ROW + GA::LP + 16 * (8 + col) + px;
+        // (block form: tile A is channel-quad-planar -- plane g & 1, 4 bytes per pixel: BlkPhase)
+        using PA = QuadPhaseA<Q, STEM, MG, XR4>;
+        constexpr int A_ROW = BLK ? blk_or<PA>::ROW : GA::ROW, A_LP = BLK ? blk_or<PA>::LP : GA::LP, A_PX = BLK ? 8 : 16;
+        const int px = BLK ? (g & 1) * blk_or<PA>::PLANE + (g >> 1) * 4 : (g >> 1) * 8 + cq;
+        const int dst0 = A_ROW + A_LP + A_PX * col + px, dst1 = (1 + oy1) * A_ROW + A_LP + A_PX * j1 + px, dst2 = 2 * A_ROW + A_LP + A_PX * (8 + col) + px;
 #pragma unroll
         for (int i = 0; i < RPW; ++i) {
             const int rp = wave * RPW + i;
             const uint8_t *t0 = lds + OFF_S + rp * (4 * SW);
-            uint8_t *d0 = lds + rp * (2 * GA::ROW);
+            uint8_t *d0 = lds + rp * (2 * A_ROW);
             long B[3];
 #pragma unroll
             for (int n = 0; n < 3; ++n) {
@@ -723,7 +847,7 @@ __global__ __launch_bounds__(Q::NTHR, Q::WPE) void quad_rr(const int8_t *__restr
 
 template <typename Q, bool STEM, int MG, uint32_t XR4, bool F32IN = false>
 static void launch_quad_t(const int8_t *in, int8_t *out, const QuadArgs &a, int batch, hipStream_t s) {
-    constexpr int lds = ((Q::DBA && !STEM) ? 2 : 1) * Q::G * Q::A::TILE + 512 + Q::G * Q::B::TILE + 512 + quad_stem_bytes<Q, STEM>() + 16 +
+    constexpr int lds = ((Q::DBA && !STEM) ? 2 : 1) * quad_buf_a<Q, STEM>() + 512 + Q::G * Q::B::TILE + 512 + quad_stem_bytes<Q, STEM>() + 16 +
                         (F32IN ? 4 * (2 * Q::A::H) * (2 * Q::A::W) : 0) + (STEM ? 640 : 0);
     static_assert(lds <= 163840, "quad tiles do not fit the LDS");
     static LaunchState st;
@@ -763,6 +887,7 @@ bool launch_quad(int H, int W, int C, int S, int N, int H2, int W2, int C2, int 
                  int batch, hipStream_t s) {
     if (!a.a.dw.wmm || !a.a.pw.wrr || !a.b.dw.wmm || !a.b.pw.wrr) return false;
     if (MF_RR_SPARSE && (!a.a.dw.wsp || !a.b.dw.wsp)) return false; // (no 2:4-sparse form of these taps: the pairs run one by one)
+    if (a.stem && quad_blk<Quad13, true>() && (!a.a.dw.wblk || !a.a.pw.wiso)) return false; // (the block form's operands)
     int mg = std::min(std::min(a.a.dw.magic, a.a.pw.magic), std::min(a.b.dw.magic, a.b.pw.magic));
     if (a.stem) mg = std::min(mg, a.stem_magic);
     if (mg == 0) return false; // (the quads exist for the bit-pattern epilogues only)
@@ -797,6 +922,7 @@ bool launch_quad_f32(int H, int W, int C, int S, int N, int H2, int W2, int C2, 
     if (!a.stem || !a.f32_ok || !(quad_mask() & 4) || !quad_matches<Quad13>(H, W, C, S, N, H2, W2, C2, S2, N2)) return false;
     if (!a.a.dw.wmm || !a.a.pw.wrr || !a.b.dw.wmm || !a.b.pw.wrr) return false;
     if (MF_RR_SPARSE && (!a.a.dw.wsp || !a.b.dw.wsp)) return false;
+    if (quad_blk<Quad13, true>() && (!a.a.dw.wblk || !a.a.pw.wiso)) return false;
     const int mg = std::min(std::min(std::min(a.a.dw.magic, a.a.pw.magic), std::min(a.b.dw.magic, a.b.pw.magic)), a.stem_magic);
     if (mg == 0) return false;
     const int8_t *src = (const int8_t *)in;

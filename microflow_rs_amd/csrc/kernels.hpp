@@ -129,6 +129,8 @@ struct DwFastArgs {
     const void *wmm;    // matrix-pipe form of w (k_fused_mm.hip): [C/16 or 1][3 filter rows][64 lanes] x 16 bytes
     const void *wsp;    // the same taps for v_smfmac_i32_16x16x128_i8 + one v_mfma_i32_16x16x32_i8 (k_quad.hip; wimage.cpp build_dw_sp_weights):
                         // [C/16 or 1][64 lanes] x 32 bytes = {sparse A (16 B), index dword, ninth tap's dense A (8 B), pad}
+    const void *wblk;   // the same taps in the block form (k_quad.hip BlkPhase; wimage.cpp build_dw_blk_weights): [C/4 channel quads][64 lanes]
+                        // x 16 bytes, or nullptr
     const float *A;
     const float *S;
     const int *Kc;
@@ -194,6 +196,8 @@ struct DwPwArgs;
 struct PwArgs {
     const void *wprep;  // [blk][q][tile][kstep][lane] x 16 bytes, MFMA operand-A layout
     const void *wrr;    // register-resident pairs (dwpw_rr): [16-row tile][lane] x 8 bytes, or nullptr
+    const void *wiso;   // K = 8 behind the block-form depthwise (k_quad.hip BlkPhase; wimage.cpp build_pw_iso_weights): [4 sub-pixels][N/16 tiles]
+                        // [lane] x 8 bytes, or nullptr
     const float *A;
     const float *S;
     const int *Kc;

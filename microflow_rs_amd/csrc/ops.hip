@@ -289,7 +289,7 @@ bool route_dw_table(OpImpl &op, const ConvCtx &c) {
     k::DwFastArgs &f = op.dwf;
     f.w = op.conv.w, f.A = op.conv.A, f.S = op.conv.S, f.Kc = op.conv.Kc;
     epi_fields_izp(f, op, c);
-    f.wmm = nullptr, f.wsp = nullptr;
+    f.wmm = nullptr, f.wsp = nullptr, f.wblk = nullptr;
     step_queue(f, op);
     if (s.C == 8 || s.C % 16 == 0) { // matrix-pipe form of the taps for the fused pair kernels
         const std::vector<int8_t> prep = wimage::build_dw_mm_weights(s.weights, s.C);
@@ -299,6 +299,11 @@ bool route_dw_table(OpImpl &op, const ConvCtx &c) {
         if (!sp.empty()) {
             op.d_wsp.upload(sp.data(), sp.size());
             f.wsp = op.d_wsp.p;
+        }
+        if (s.sh == 1) { // the block form of the taps (k_quad.hip BlkPhase): stride 1 only
+            const std::vector<int8_t> blk = wimage::build_dw_blk_weights(s.weights, s.C);
+            op.d_wblk.upload(blk.data(), blk.size());
+            f.wblk = op.d_wblk.p;
         }
         if (dw_taps_on_matrix_pipe() && k::dw_mm_name(s.H, s.W, s.C, s.sh)) op.fast_name = k::dw_mm_name(s.H, s.W, s.C, s.sh);
     }
@@ -373,11 +378,16 @@ bool route_pw_mfma(OpImpl &op, const ConvCtx &c) {
     k::PwArgs &f = op.pw;
     f.wprep = op.d_wprep.p, f.A = op.conv.A, f.S = op.conv.S, f.Kc = op.conv.Kc;
     epi_fields(f, op, c);
-    f.wrr = nullptr;
+    f.wrr = nullptr, f.wiso = nullptr;
     if ((s.C == 8 || s.C == 16 || s.C == 32) && (s.C == 8 ? 2 * s.N : s.N) % 16 == 0) {
         const std::vector<int8_t> rr = wimage::build_pw_rr_weights(s.weights, s.C, s.N);
         op.d_wrr.upload(rr.data(), rr.size());
         f.wrr = op.d_wrr.p;
+    }
+    if (s.C == 8 && s.N % 16 == 0) { // the isolating operands behind a block-form depthwise
+        const std::vector<int8_t> iso = wimage::build_pw_iso_weights(s.weights, s.N);
+        op.d_wiso.upload(iso.data(), iso.size());
+        f.wiso = op.d_wiso.p;
     }
     return true;
 }

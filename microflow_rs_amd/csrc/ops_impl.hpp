@@ -103,7 +103,7 @@ struct OpImpl {
         scratch_used = true;
     }
 
-    DevBuf d_w, d_wzp, d_A, d_S, d_Kc, d_wprep, d_wsp, d_wrr, d_table;
+    DevBuf d_w, d_wzp, d_A, d_S, d_Kc, d_wprep, d_wsp, d_wblk, d_wrr, d_wiso, d_table;
     // host copies of d_w (i8 domain, as uploaded), d_A, d_S, d_Kc, d_wzp and of dw_c1_lds's packed taps: the fused groups
     // (fused.hip) build their own operand images from them.  Kept for the operator's lifetime.
     std::vector<int8_t> h_w;

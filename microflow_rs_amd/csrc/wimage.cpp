@@ -108,6 +108,42 @@ std::vector<int8_t> build_dw_sp_weights(const std::vector<int8_t> &dense /* buil
     return out;
 }
 
+// The block form of the same taps (k_quad.hip BlkPhase): ONE v_mfma_i32_16x16x64_i8 per channel quad computes a 2 x 2 output block
+// per column.  Column n is output block (by, bx); its 64 K-bytes are the block's 4 x 4 input patch -- rows 2 by - 1 .. 2 by + 2,
+// x 2 bx - 1 .. 2 bx + 2 -- of one channel quad: lane group g supplies patch row g, byte 4 xx + j = patch pixel xx, channel 4 q + j.
+// Row m = 4 s + i is output pixel s = (sy, sx) = (s >> 1, s & 1) of the block, channel 4 q + i: lane (m, g) holds
+// w[g - sy][xx - sx][4 q + i] in byte 4 xx + i where both differences are in 0..2, zero elsewhere.  The result lane (n, g') then
+// holds the four channels of pixel g' of block n.  [quad q][lane][16 bytes]; C a multiple of 4.
+std::vector<int8_t> build_dw_blk_weights(const int8_t *w /*[3][3][C]*/, int C) {
+    const int NQ4 = C / 4;
+    std::vector<int8_t> out((size_t)NQ4 * 64 * 16, 0);
+    for (int q = 0; q < NQ4; ++q)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int m = lane & 15, g = lane >> 4, s = m >> 2, i = m & 3, ty = g - (s >> 1);
+            if (ty < 0 || ty > 2) continue;
+            for (int xx = 0; xx < 4; ++xx) {
+                const int tx = xx - (s & 1);
+                if (tx >= 0 && tx <= 2) out[((size_t)q * 64 + lane) * 16 + 4 * xx + i] = w[(ty * 3 + tx) * C + 4 * q + i];
+            }
+        }
+    return out;
+}
+
+// Pointwise weights [N][8] behind the block form: the depthwise result of a lane is the 8 channels of ONE pixel -- pixel g of block n
+// in lane (n, g) -- so the B operand of v_mfma_i32_16x16x32_i8 holds four different pixels in its four K slices.  Operand s of the
+// four "isolating" operands carries the weights in K-bytes 8 s .. 8 s + 7 only (lane group s; zero in the other three groups), so
+// that instruction s sees pixel s alone: row m of tile t is output channel 16 t + m, byte b input channel b.
+// [sub-pixel s][tile t][lane][8 bytes]; N a multiple of 16.
+std::vector<int8_t> build_pw_iso_weights(const int8_t *w /*[N][8]*/, int N) {
+    const int NT = N / 16;
+    std::vector<int8_t> out((size_t)4 * NT * 64 * 8, 0);
+    for (int s = 0; s < 4; ++s)
+        for (int t = 0; t < NT; ++t)
+            for (int m = 0; m < 16; ++m)
+                memcpy(&out[(((size_t)s * NT + t) * 64 + 16 * s + m) * 8], w + (size_t)(16 * t + m) * 8, 8);
+    return out;
+}
+
 // Depthwise weights [KH][KW][C] as operand A of conv_mm_rt's depthwise mode (k_rt.hip) and of dw_gemm_rt (k_dw_gemm.hip): [16-channel
 // group][k step][lane] x 16 bytes; lane (row r, group g) of step ks holds tap t = 4 ks + g: its only non-zero byte is byte r = w[t][16 q
 // + r] (zero for the channels 16 q + r >= C of a last, partial group).  P > 1 (dw_gemm_rt, C <= 8): one group, row r is channel r % C

@@ -14,6 +14,8 @@ namespace wimage {
 std::vector<int8_t> build_pw_weights(const int8_t *w /*[N][K]*/, int K, int N);
 std::vector<int8_t> build_dw_mm_weights(const int8_t *w /*[3][3][C]*/, int C);
 std::vector<int8_t> build_dw_sp_weights(const std::vector<int8_t> &dense /* build_dw_mm_weights */, int NQ);
+std::vector<int8_t> build_dw_blk_weights(const int8_t *w /*[3][3][C]*/, int C);
+std::vector<int8_t> build_pw_iso_weights(const int8_t *w /*[N][8]*/, int N);
 std::vector<int8_t> build_dw_mm_rt_weights(const int8_t *w, int KH, int KW, int C, int KS /* >= (KH KW + 3) / 4: padded with zero steps */,
                                            int P = 1);
 std::vector<int8_t> build_dw_mm_weights_sp(const int8_t *w /*[3][3][C]*/, int C, int S);
