@@ -363,47 +363,129 @@ def inverted_residual_net(rng, input_shape, blocks, elem=INT8, wzp_nonzero=False
     return build_model((1,) + tuple(input_shape), in_q, layers, elem)
 
 
-def person_detect_like(rng, side=96, width=1.0, elem=INT8, wzp_nonzero=False, n_stage=5, classes=2, wmax=None):
+# person_detect_like(quant=...): the head's effective multiplier in_scale * fscale / out_scale (256 products of a byte
+# around the zero point with a full-range weight: accumulators of some 1e5, so about +-100 output steps)
+HEAD_MULT = 1e-3
+PD_SCALES = (0.0235294122, 0.03, 0.02, 0.033, 0.026, 0.0285)
+
+
+def pd_quant_plan(name, elem=INT8, n_stage=5):
+    """The named activation-quantisation plans for person_detect_like(quant=...): one (activation, output scale, output
+    zero point) per conv-like layer (0 = the stem, 1 .. 2 (8 + n_stage) = the pairs, the last = the 1x1 head).
+      shifted  every tensor (0.03, lo + 7), relu6: every clamp is [lo + 7, lo + 207]
+      varied   by layer i: relu6 / relu / none (i % 3), the scale PD_SCALES[i % 6], the zero point lo + (0, 5, 17, 30, 9)[i % 5]
+               behind relu / relu6 and mid + (-6, 4, 11)[(i // 3) % 3] behind none (the activation has period 3, so the
+               index of the third table advances once per period): the periods 6, 5 and 9 leave no two operators of one
+               launch with the same input zero point and clamp
+      stage    as varied, but every input of a pair of the 6x6x128 run (the outputs of ops 12 .. 12 + 2 n_stage - 1) has the
+               zero point lo + 9 and the run alternates relu6 (at a scale of its own per pair) with relu: relu6 then relu in the even
+               pairs, relu then relu6 in the odd ones, so that every pair has its own clamps in one phase or the other
+      one_odd  the shipped quantisation, but ops 3, 7, 10, 17, 25 are relu6 at scale 0.03 (upper bound lo + 200)."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    n = 2 * (8 + n_stage) + 2
+    shipped = [("relu6", PD_SCALES[0], lo)] * (n - 1) + [("none", 0.0125187514, mid - 1)]
+
+    def varied(i):
+        act = ("relu6", "relu", "none")[i % 3]
+        zp = mid + (-6, 4, 11)[(i // 3) % 3] if act == "none" else lo + (0, 5, 17, 30, 9)[i % 5]
+        return (act, PD_SCALES[i % 6], zp)
+
+    if name == "shifted":
+        return [("relu6", 0.03, lo + 7)] * n
+    if name == "varied":
+        return [varied(i) for i in range(n)]
+    if name == "stage":
+        plan = [varied(i) for i in range(n)]
+        run_scales = (0.03, 0.033, 0.026, 0.0285, 0.031, 0.0275, 0.0295, 0.0325)
+        plan[12] = plan[12][:2] + (lo + 9,)
+        for i in range(13, 12 + 2 * n_stage):
+            j = (i - 13) // 2   # relu6 in the depthwise operator of the even pairs and the 1x1 one of the odd pairs
+            plan[i] = ("relu6", run_scales[j % 8], lo + 9) if (i % 2 == 1) == (j % 2 == 0) else ("relu", PD_SCALES[i % 6], lo + 9)
+        return plan
+    if name == "one_odd":
+        return [("relu6", 0.03, lo) if i in (3, 7, 10, 17, 25) else q for i, q in enumerate(shipped)]
+    raise ValueError(name)
+
+
+def person_detect_like(rng, side=96, width=1.0, elem=INT8, wzp_nonzero=False, n_stage=5, classes=2, wmax=None, quant=None, in_q=None):
     """The layer structure of person_detect.tflite (MobileNet-v1 0.25, grey input: a one-channel 3x3 stride-2 stem, then
     depthwise 3x3 + 1x1 pairs with strides 1 2 1 2 1 2 [1 x n_stage] 2 1, AveragePool2D over what is left, a 1x1 head,
     Reshape, Softmax) at another input size / channel width / run length, with random weights.  Activations keep the
     shipped model's quantization (scale 6/255, zero point = the type's minimum, relu6), weights are per-channel.
     `wmax`: weights within +-wmax of the type's middle (trained networks have small weights; None = the full range, the worst
-    case for the accumulator bounds that decide the epilogue form)."""
+    case for the accumulator bounds that decide the epilogue form); a dict {layer index: wmax} narrows single layers and scales
+    their filter scales up by 128 / wmax, so that their outputs stay as spread as their neighbours'.
+
+    `quant` (a list, or a callable over the index of the conv-like layer: 0 = the stem ... the last = the 1x1 head; see
+    pd_quant_plan) gives every conv-like layer its own (activation, output scale, output zero point); the next layer's input
+    quantisation follows from it, and the filter scales are today's draws times out_scale / in_scale: every pair keeps the shipped
+    path's effective multiplier in_scale * fscale / out_scale, so the tensors stay spread; the stem, whose shipped input scale is
+    a third of its output scale, gets three times the shipped one, with which its output reaches both clamp bounds.  The pool
+    keeps its input's zero point, and the head's filter scale is one that leaves its output spread.  `in_q` overrides the model's
+    input quantisation.  This is how the fused table launches, which exist for side 96 and width 1.0 only, are exercised under
+    clamps and zero points the shipped quantisation never has (tests/test_gpu_pd_quant.py, tests/test_pd_quant_host.py).
+    With both None the file is what it always was, byte for byte."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     act_q = (0.0235294122, lo)
-    in_q = (0.00784313772, mid - 1)
+    in_q0 = (0.00784313772, mid - 1)
+    in_q = in_q0 if in_q is None else (float(np.float32(in_q[0])), int(in_q[1]))
     ch = lambda c: max(4, int(round(c * width / 4.0)) * 4)  # noqa: E731
     layers = []
 
-    def conv(op, in_shape, n, k, stride, act, in_scale, out_q):
+    def planned(i, act, out_q):  # layer i's (activation, output quantisation)
+        if quant is None:
+            return act, out_q
+        a, s, z = quant(i) if callable(quant) else quant[i]
+        return a, (float(np.float32(s)), int(z))
+
+    def conv(op, in_shape, n, k, stride, act, in_scale, out_q, rescale=None):
         _, h, w, c = in_shape
         oh, ow = -(-h // stride), -(-w // stride)
         fan = k * k * (1 if op == "depthwise_conv_2d" else c)
         sc = (rng.uniform(0.6, 1.4, n) * 2.2 / (74.0 * np.sqrt(fan))).astype(np.float32)   # keeps the activations spread
+        wm = wmax.get(len(layers)) if isinstance(wmax, dict) else wmax
+        if isinstance(wmax, dict) and wm is not None:   # (narrower weights, the same spread of the outputs)
+            rescale = (rescale or 1.0) * 128.0 / wm
+        if rescale is not None:
+            sc = (sc * np.float32(rescale)).astype(np.float32)
         zp = rng.integers(mid - 12, mid + 12, n) if wzp_nonzero else np.full(n, mid)
         shape = (n, k, k, c) if op == "conv_2d" else (1, k, k, n)
         d = dict(op=op, fscale=sc, fzp=zp, bias=rng.integers(-300, 300, n), bscale=(sc * np.float32(in_scale)).astype(np.float32),
                  bzp=np.zeros(n, np.int64), padding="same", strides=(stride, stride), act=act, out_shape=(1, oh, ow, n), out_q=out_q)
-        d["filters" if op == "conv_2d" else "weights"] = rng.integers(lo, hi, shape) if wmax is None else rng.integers(mid - wmax, mid + wmax + 1, shape)
+        d["filters" if op == "conv_2d" else "weights"] = rng.integers(lo, hi, shape) if wm is None else rng.integers(mid - wm, mid + wm + 1, shape)
         layers.append(d)
         return d["out_shape"]
 
-    shp = conv("depthwise_conv_2d", (1, side, side, 1), ch(8), 3, 2, "relu6", in_q[0], act_q)
+    def layer(op, in_shape, n, k, stride, cur, shipped_in_scale):
+        act, out_q = planned(len(layers), "relu6", act_q)
+        rescale = None
+        if quant is not None:   # today's draw times out_scale / in_scale
+            rescale = out_q[0] / cur[0]
+        elif cur[0] != shipped_in_scale:   # (in_q alone: the shipped multiplier in_scale * fscale / out_scale)
+            rescale = shipped_in_scale / cur[0]
+        return conv(op, in_shape, n, k, stride, act, cur[0], out_q, rescale), out_q
+
+    shp, cur = layer("depthwise_conv_2d", (1, side, side, 1), ch(8), 3, 2, in_q, in_q0[0])
     plan = [(1, 16), (2, 32), (1, 32), (2, 64), (1, 64), (2, 128)] + [(1, 128)] * n_stage + [(2, 256), (1, 256)]
     for stride, n in plan:
-        shp = conv("depthwise_conv_2d", shp, shp[3], 3, stride, "relu6", act_q[0], act_q)
-        shp = conv("conv_2d", shp, ch(n), 1, 1, "relu6", act_q[0], act_q)
+        shp, cur = layer("depthwise_conv_2d", shp, shp[3], 3, stride, cur, act_q[0])
+        shp, cur = layer("conv_2d", shp, ch(n), 1, 1, cur, act_q[0])
+    pool_q = (0.0186093301, lo)
+    if quant is not None:
+        pool_q = (float(np.float32(cur[0] * (0.0186093301 / 0.0235294122))), cur[1])
     layers.append(dict(op="average_pool_2d", filter=(shp[1], shp[2]), padding="valid", strides=(2, 2), act="none",
-                       out_shape=(1, 1, 1, shp[3]), out_q=(0.0186093301, lo)))
+                       out_shape=(1, 1, 1, shp[3]), out_q=pool_q))
     shp = (1, 1, 1, shp[3])
-    head_q = (0.0125187514, mid - 1)
-    sc = (rng.uniform(0.6, 1.4, classes) * 0.002).astype(np.float32)
+    head_act, head_q = planned(len(layers) - 1, "none", (0.0125187514, mid - 1))
+    # (0.002 saturates the head on random weights; the quant path's scale leaves its accumulators a few dozen output steps wide)
+    head_fs = 0.002 if quant is None else HEAD_MULT * head_q[0] / pool_q[0]
+    sc = (rng.uniform(0.6, 1.4, classes) * head_fs).astype(np.float32)
     zp = rng.integers(mid - 12, mid + 12, classes) if wzp_nonzero else np.full(classes, mid)
     layers.append(dict(op="conv_2d", filters=rng.integers(lo, hi, (classes, 1, 1, shp[3])), fscale=sc, fzp=zp,
-                       bias=rng.integers(-300, 300, classes), bscale=(sc * np.float32(0.0186093301)).astype(np.float32),
-                       bzp=np.zeros(classes, np.int64), padding="same", strides=(1, 1), act="none",
+                       bias=rng.integers(-300, 300, classes), bscale=(sc * np.float32(pool_q[0])).astype(np.float32),
+                       bzp=np.zeros(classes, np.int64), padding="same", strides=(1, 1), act=head_act,
                        out_shape=(1, 1, 1, classes), out_q=head_q))
     layers.append(dict(op="reshape", out_shape=(1, classes), out_q=head_q))
     layers.append(dict(op="softmax", out_shape=(1, classes), out_q=(1.0 / 256.0, lo)))
