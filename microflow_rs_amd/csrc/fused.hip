@@ -14,7 +14,7 @@
 namespace mf {
 
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND } kind;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ } kind;
     OpImpl *a, *b, *c;
     k::DwPwArgs dwpw;
     k::TailArgs tail;
@@ -44,6 +44,8 @@ struct FusedImpl {
     k::PoolFcArgs poolfc{};
     // PAIRBAND: one pair too large for chain_rt's LDS plan, walked in row bands (k_pair_band.hip); a = the depthwise, b = the conv
     k::PairBandArgs pairband{};
+    // PAIRWZ: one pair with filter zero points, whole images in LDS (k_pair_wz.hip); a = the depthwise, b = the conv; table and images in stage_w
+    k::PairWzArgs pairwz{};
     // the model's f32 boundary inside this group's launch (fused_set_input_quant / fused_set_output_dequant): FCCHAIN and DWFC both
     // ends, POOLFC and PAIRTAIL the exit
     k::F32Edge edge{};
@@ -272,10 +274,89 @@ static FusedImpl *pair_band_create(OpImpl *dw, OpImpl *pw) {
     return c.release();
 }
 
+// ---- one pair whose filters carry zero points (k_pair_wz.hip): after the table pairs, chain_rt and the band kernels have all declined ----
+// Every other fused launch refuses a filter zero point away from zero in the i8 domain -- every classic asymmetric-uint8 model, and
+// per-channel zero points on i8 -- so such a pair used to run dw3x3_rt<S,wzp> + pw_rt<K,N,wzp> with its intermediate tensor through
+// HBM.  This group takes exactly those pairs (at least one member with a non-zero zero point: a pair without keeps the group it has
+// today), on chain_plan's single-pair plan.  A kind of its own: the stage, quad, tail and chain-partition code all answer "no" to it.
+static FusedImpl *pair_wz_create(OpImpl *dw, OpImpl *pw) {
+    if (switches().no_pair_wz || !dw || !pw || dw->device != pw->device || dw->force_generic || pw->force_generic) return nullptr;
+    const OpSpec &d = dw->s, &q = pw->s;
+    if (d.kind != MF_OP_DEPTHWISE_CONV_2D || q.kind != MF_OP_CONV_2D || d.u8 != q.u8) return nullptr;
+    // geometry as chain_pair_ok: 3x3 SAME, equal strides 1 or 2, one output per channel, the 1x1 at stride 1 on the depthwise output
+    if (d.KH != 3 || d.KW != 3 || d.pad != MF_PAD_SAME || d.sh != d.sw || (d.sh != 1 && d.sh != 2) || d.C != d.N) return nullptr;
+    if (d.W % d.sh != 0) return nullptr;
+    if (q.KH != 1 || q.KW != 1 || q.sh != 1 || q.sw != 1 || q.OH != q.H || q.OW != q.W) return nullptr;
+    if (q.H != d.OH || q.W != d.OW || q.C != d.N) return nullptr;
+    if (d.C % 16 != 0 || d.C < 16 || d.C > 256 || q.N % 16 != 0 || q.N < 16) return nullptr;
+    // the members' own launches: dw3x3_rt or a table kernel, pw_rt or pw_mfma (anything else is a shape class of its own)
+    if (dw->fast != OpImpl::DW_RT && dw->fast != OpImpl::DW_NHWC) return nullptr;
+    if (pw->fast != OpImpl::PW_RT && pw->fast != OpImpl::PW_MFMA) return nullptr;
+    if (dw->h_w.size() != (size_t)9 * d.C || pw->h_w.size() != (size_t)q.N * q.C || dw->h_wzp.size() != (size_t)d.C || pw->h_wzp.size() != (size_t)q.N) return nullptr;
+    if (!dw->finite_consts || !pw->finite_consts) return nullptr;
+    const bool wz = !std::all_of(dw->h_wzp.begin(), dw->h_wzp.end(), [](int32_t z) { return z == 0; }) ||
+                    !std::all_of(pw->h_wzp.begin(), pw->h_wzp.end(), [](int32_t z) { return z == 0; });
+    if (!wz) return nullptr; // (zero filter zero points: the pair keeps exactly the group -- or the two launches -- it has today)
+    const k::DwFastArgs &f = dw->fast == OpImpl::DW_NHWC ? dw->dwf : dw->dwrt.dw;
+    const k::ChainGeom geom{d.H, d.W, d.C, d.sh, d.OH, d.OW, q.N, f.izp4};
+    std::unique_ptr<FusedImpl> c(new FusedImpl{FusedImpl::PAIRWZ, dw, pw, nullptr, {}, {}, ""});
+    k::ChainArgs &a = c->pairwz.c;
+    k::ChainPair t{};
+    if (!k::chain_plan(&geom, 1, &t, a, 150 * 1024)) {
+        if (switches().chain_verbose) fprintf(stderr, "[microflow_amd] no chain plan for the zero-point pair %dx%dx%d s%d -> %d\n", d.H, d.W, d.C, d.sh, q.N);
+        return nullptr;
+    }
+    // chain_plan weighs a step's fixed cost against TWO workgroups per CU while the LDS allows them.  From two k steps on pair_wz_rt's
+    // registers (134 - 179) allow one, which then has the whole LDS: twice the images per step where the plan still fits
+    // (profiles/r09/time_pair_wz.txt: 6x6x128 -> 128 0.106 -> 0.093 ms).  One k step keeps the plan's choice: its resident instances
+    // hold 116 registers, two workgroups per CU (24x24x32 s2 -> 64 ran 0.127 ms so, 0.155 ms with twice the images in one workgroup).
+    for (int gm = a.KSC >= 2 ? switches().pair_wz_gmul : 1; gm > 1; gm /= 2) {
+        k::ChainPair t2{};
+        k::ChainArgs a2{};
+        if (!k::chain_plan(&geom, 1, &t2, a2, 150 * 1024, a.G * gm)) continue;
+        t = t2, a = a2;
+        break;
+    }
+    const int magic = std::min(dw->magic_mode, pw->magic_mode);
+    if (!k::pair_wz_instance(a.KSC, magic)) return nullptr; // (no compiled instance: the pair stays layer-wise)
+    k::pair_wz_split(t); // (the plan's unit ranges are for chain_rt's 8 or 16 waves; pair_wz_rt has 8)
+    a.nwave = 8, a.resident = (t.single_q && !switches().chain_no_res) ? 1 : 0; // (MF_CHAIN_NO_RES: A/B, as chain_rt's)
+    // the depthwise taps in matrix-pipe form, from the weights as uploaded ([3][3][C], i8 domain): route_dw_rt builds no such image
+    // for an operator with filter zero points
+    const std::vector<int8_t> taps = wimage::build_dw_mm_weights(dw->h_w.data(), d.C);
+    t.dw_wmm = keep(*c, taps.data(), taps.size());
+    t.dwA = dw->conv.A, t.dwS = dw->conv.S, t.dwK = dw->conv.Kc, t.dw_lo = dw->conv.lo_f, t.dw_hi = dw->conv.hi_f;
+    const std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(pw->h_w.data(), q.C, q.N, 1, t.TB, t.NBLK); // [N][1][1][C], i8 domain
+    t.pw_w = keep(*c, prep.data(), prep.size());
+    t.pwA = pw->conv.A, t.pwS = pw->conv.S, t.pwK = pw->conv.Kc, t.pw_lo = pw->conv.lo_f, t.pw_hi = pw->conv.hi_f;
+    {
+        std::vector<int> rt;
+        k::chain_rtab(t, rt);
+        t.rtab = (const int *)keep(*c, rt.data(), rt.size() * sizeof(int));
+    }
+    // the two ones images (wimage.cpp): the all-ones filter's tap image -- its three filter rows are the same 1 KiB, the kernel keeps
+    // one -- and the 1x1's tile of ones, zero beyond C
+    const std::vector<int8_t> dones = wimage::build_dw_ones_image();
+    c->pairwz.dw_ones = keep(*c, dones.data(), 1024);
+    const std::vector<int8_t> pones = wimage::build_pw_ones_tile(q.C);
+    c->pairwz.pw_ones = keep(*c, pones.data(), pones.size());
+    c->pairwz.dw_wzp = dw->conv.wzp, c->pairwz.pw_wzp = pw->conv.wzp;
+    a.pairs = (const k::ChainPair *)keep(*c, &t, sizeof(t));
+    a.magic = magic, a.xr = d.u8 ? 0x80 : 0;
+    a.queue = (int *)dw->d_queue.p, a.qlaunch = &dw->q_launches;
+    c->epi_mode = magic;
+    c->name = "pair_wz_rt<" + std::to_string(d.H) + "x" + std::to_string(d.W) + "x" + std::to_string(d.C) + (d.sh == 2 ? "s2" : "") + "-" + std::to_string(q.N) + ";G" + std::to_string(a.G) + ">";
+    if (switches().chain_verbose)
+        fprintf(stderr, "[microflow_amd] zero-point group %s: lds %d B, dbuf %d, %d x %d output tiles, %d k step%s, mode %d\n", c->name.c_str(), a.lds_bytes, a.dbuf, t.NBLK, t.TB, t.KS,
+                t.KS == 1 ? "" : "s", magic);
+    return c.release();
+}
+
 static FusedImpl *pair_create(OpImpl *dw, OpImpl *pw);
 FusedImpl *fused_create(OpImpl *dw, OpImpl *pw) {
     if (FusedImpl *f = pair_create(dw, pw)) return f; // the table pairs, then chain_rt
-    return pair_band_create(dw, pw);
+    if (FusedImpl *f = pair_band_create(dw, pw)) return f;
+    return pair_wz_create(dw, pw); // (only ever a pair with filter zero points, which the two above refuse)
 }
 static FusedImpl *pair_create(OpImpl *dw, OpImpl *pw) {
     const bool chain_all = switches().chain_all; // tests / A-B: the chain kernel on table shapes too
@@ -444,7 +525,7 @@ FusedImpl *fused_pool_fc_create(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl 
     return f;
 }
 bool fused_input_ok(const FusedImpl *f, const int8_t *d_in) {
-    return (f->kind != FusedImpl::POOLFC && f->kind != FusedImpl::PAIRBAND) || ((uintptr_t)d_in & 15) == 0; // (these two read 16-byte words at the pointer)
+    return (f->kind != FusedImpl::POOLFC && f->kind != FusedImpl::PAIRBAND && f->kind != FusedImpl::PAIRWZ) || ((uintptr_t)d_in & 15) == 0; // (these read 16-byte words at the pointer)
 }
 
 // A run of `npairs` identical DepthwiseConv2D 3x3 (stride 1) + Conv2D 1x1 pairs on one small tensor as one persistent
@@ -793,6 +874,13 @@ void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, vo
         if (!fused_input_ok(f, d_in)) fail(MF_ERR_INVALID_ARG, "pair_band_rt: the input pointer is not 16-byte aligned");
         if (f->pairband.KSC == 8) k::launch_pair_band_deep(d_in, d_out, f->pairband, (int)batch, (hipStream_t)stream);
         else k::launch_pair_band(d_in, d_out, f->pairband, (int)batch, (hipStream_t)stream);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (f->kind == FusedImpl::PAIRWZ) {
+        if (batch > 0x7fffffffull / 4) fail(MF_ERR_INVALID_ARG, "batch too large for one launch");
+        if (!fused_input_ok(f, d_in)) fail(MF_ERR_INVALID_ARG, "pair_wz_rt: the input pointer is not 16-byte aligned");
+        k::launch_pair_wz(d_in, d_out, f->pairwz, (int)batch, (hipStream_t)stream);
         MF_HIP(hipGetLastError());
         return;
     }

@@ -417,6 +417,19 @@ void launch_pair_band(const int8_t *in, int8_t *out, const PairBandArgs &a, int 
 bool pair_band_deep_plan(const ChainGeom &g, PairBandArgs &a);
 void launch_pair_band_deep(const int8_t *in, int8_t *out, const PairBandArgs &a, int batch, hipStream_t s);
 
+// ---- one pair whose filters carry zero points, whole images in LDS (k_pair_wz.hip: pair_wz_rt) ----
+// chain_rt's single-pair step plus the reference's two zero-point terms: acc -= wzp[c] * (window sum) in the depthwise,
+// acc[n] -= wzp[n] * (the pixel's sum over its C intermediate bytes) in the 1x1.  Geometry and LDS plan are chain_plan's with n = 1.
+struct PairWzArgs {
+    ChainArgs c;                   // chain_plan's plan of the single pair; c.pairs -> ONE ChainPair, its unit list cut for 8 waves (pair_wz_split)
+    const void *dw_ones;           // build_dw_mm_weights of an all-ones 3x3x16 filter, filter row 0: [lane] x 16 bytes (the three rows are equal)
+    const void *pw_ones;           // fill_ones_tile(C, KS): [k step][lane] x 16 bytes, zero beyond C
+    const int *dw_wzp, *pw_wzp;    // filter zero points per channel, i8 domain ([C], [N]); zeros for a member without
+};
+bool pair_wz_instance(int KSC, int magic); // a compiled kernel exists for this k-step count and epilogue mode
+void pair_wz_split(ChainPair &c);          // the depthwise unit list of a planned pair cut into 8 contiguous ranges (ustart, ucount, single_q)
+void launch_pair_wz(const int8_t *in, int8_t *out, const PairWzArgs &a, int batch, hipStream_t s);
+
 // two consecutive pairs in one launch (k_quad.hip)
 struct QuadArgs {
     DwPwArgs a, b;

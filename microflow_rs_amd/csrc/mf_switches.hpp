@@ -37,6 +37,7 @@ struct Switches {
     bool no_fc_chain = false;      // MF_NO_FC_CHAIN      consecutive FullyConnected layers one launch each, not one fc_chain launch
     bool no_pool_fc = false;       // MF_NO_POOL_FC       global AveragePool2D + FullyConnected (+ Softmax) heads one launch per operator, not one pool_fc_chain launch (k_pool_fc.hip)
     bool no_pair_band = false;     // MF_NO_PAIR_BAND     pairs too large for chain_rt one launch per operator, not one pair_band_rt / pair_band_deep_rt launch (k_pair_band.hip, k_pair_band_deep.hip)
+    bool no_pair_wz = false;       // MF_NO_PAIR_WZ       pairs with filter zero points one launch per operator (dw3x3_rt<S,wzp>, pw_rt<K,N,wzp>), not one pair_wz_rt launch (k_pair_wz.hip)
     bool no_conv_gemm = false;     // MF_NO_CONV_GEMM     Conv2D shapes outside the other Conv2D kernels take conv2d_generic, not conv_gemm_rt (k_conv_gemm.hip)
     bool no_dw_gemm = false;       // MF_NO_DW_GEMM       DepthwiseConv2D shapes outside the other depthwise kernels take dwconv_generic, not dw_gemm_rt / conv_gemm_rt<dw> (k_dw_gemm.hip)
     bool no_dwfc = false;          // MF_NO_DWFC          no depthwise + FC + softmax kernel (k_dwfc.hip, speech)
@@ -70,6 +71,7 @@ struct Switches {
     long long pw_grid = 0;         // MF_PW_GRID          force the pointwise grid
     int pw_rt_ncap = 64;           // MF_PW_RT_NCAP       widest N the run-time pointwise kernel takes
     int dw_rt_threads = 0;         // MF_DW_RT_THREADS    force the run-time depthwise workgroup size
+    int pair_wz_gmul = 2;          // MF_PAIR_WZ_GMUL     pair_wz_rt's images per step from two k steps on, as a multiple of chain_plan's choice where the plan still fits (1, 2, 4)
     // ---- chain planner ----
     int chain_autotune = -1;       // MF_CHAIN_AUTOTUNE   -1 unset (the handle's flag decides), 0 off, 1 on for every handle
     bool chain_tune_g = true;      // MF_CHAIN_TUNE_G=0   autotune keeps the model's images-per-step

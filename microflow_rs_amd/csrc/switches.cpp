@@ -69,6 +69,8 @@ Switches switches_parse() {
     s.no_fc_chain = env_set("MF_NO_FC_CHAIN");
     s.no_pool_fc = env_set("MF_NO_POOL_FC");
     s.no_pair_band = env_set("MF_NO_PAIR_BAND");
+    s.no_pair_wz = env_set("MF_NO_PAIR_WZ");
+    s.pair_wz_gmul = (int)env_ll("MF_PAIR_WZ_GMUL", 2);
     s.no_conv_gemm = env_set("MF_NO_CONV_GEMM");
     s.no_dw_gemm = env_set("MF_NO_DW_GEMM");
     s.no_fc_sparse = env_set("MF_NO_FC_SPARSE");

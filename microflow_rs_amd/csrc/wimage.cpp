@@ -281,6 +281,21 @@ void fill_ones_tile(int8_t *dst, int K, int KS) {
                 if (ks * 64 + (lane >> 4) * 16 + i < K) dst[((size_t)ks * 64 + lane) * 16 + i] = 1;
 }
 
+// pair_wz_rt (k_pair_wz.hip) multiplies a filter zero point with a sum of stored bytes, and takes both sums from the matrix pipe:
+// the window sum per channel is the depthwise product against the image of an all-ones filter (row c meets the nine bytes of
+// channel c; lane group 3 meets zeros, as in every tap image), and a pixel's sum over its C intermediate bytes is the 1x1 product
+// against a tile of ones that ends at C (a padded k step adds nothing).
+std::vector<int8_t> build_dw_ones_image() {
+    const std::vector<int8_t> ones((size_t)9 * 16, 1);
+    return build_dw_mm_weights(ones.data(), 16);
+}
+std::vector<int8_t> build_pw_ones_tile(int C) {
+    const int KS = (C + 63) / 64;
+    std::vector<int8_t> out((size_t)KS * 1024, 0);
+    fill_ones_tile(out.data(), C, KS);
+    return out;
+}
+
 // The one-channel 3x3 stem dw3x3_stem (k_depthwise.hip), weights [3][3][N] with 8 output channels:
 // wrow[ky][c] = bytes (w[ky][0][c], w[ky][1][c], w[ky][2][c], 0)
 void build_stem_rows(const int8_t *w, int N, uint32_t wrow[3][8]) {

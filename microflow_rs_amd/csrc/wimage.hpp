@@ -25,6 +25,9 @@ std::vector<int8_t> build_pw_rt_reg_weights(const int8_t *w /*[N][K]*/, int K, i
 std::vector<int8_t> build_pw_plain_weights(const int8_t *w, int K, int N);
 
 void fill_ones_tile(int8_t *dst /* KS KiB, zeroed */, int K, int KS);
+// pair_wz_rt's two ones images (k_pair_wz.hip): the sums a filter zero point is multiplied with come out of the matrix pipe
+std::vector<int8_t> build_dw_ones_image();     // build_dw_mm_weights of an all-ones 3x3x16 filter: [filter row][lane][16 bytes], three equal rows
+std::vector<int8_t> build_pw_ones_tile(int C); // fill_ones_tile over the (C + 63) / 64 k steps of a 1x1 product: [k step][lane][16 bytes], zero beyond C
 void build_stem_rows(const int8_t *w /*[3][3][N]*/, int N, uint32_t wrow[3][8]);
 void build_stem_mm(const int8_t *w /*[3][3][N]*/, int N, uint32_t *wmm /*[64][pitch]*/, int pitch);
 std::vector<uint32_t> build_conv_rows_pack(const int8_t *w, bool depthwise, int KH, int KW, int C, int N, int KG, int NP);
