@@ -380,111 +380,24 @@ __global__ __launch_bounds__(256) void pw_rt(const int8_t *__restrict__ in, int8
 //   WZ      : filter zero points (conv_2d.rs:57-63): acc -= fzp[n] * (sum of the window), one more v_dot4 per row group
 //             against the byte mask of the real taps.
 // ------------------------------------------------------------------------
+// F32IN: the instances that hold a model's f32 entry (conv_rows_lds_f32 below): `in` points to floats, and dword gofs[e] of a step
+// is the float4 at the same index (W C % 4 == 0: an image is whole float4s; `in` is 16-byte aligned).  The four values are quantised
+// with quantize_f32's arithmetic (k_fc_layer.hpp edge_quant) and the packed dword is written where the int8 dword went.  The floats
+// are loaded BETWEEN the two barriers, without the int8 form's step of lead: sixteen float4s held across the compute loop are 64
+// registers more than __launch_bounds__(512) leaves, and up to four workgroups per CU cover each other's loads.
+// The kernel's statements are k_conv_rows_body.inc, included between the braces of both kernels (as k_pair_band_body.inc): one text,
+// and the int8 instances are compiled exactly as when they were written out here.
 template <bool WZ, int MG, uint32_t XR4>
 __global__ __launch_bounds__(512) void conv_rows_lds(const int8_t *__restrict__ in, int8_t *__restrict__ out, ConvRowsArgs p, int batch) {
-    constexpr int NTHR = 512, MAXE = 16;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    const int tid = threadIdx.x;
-    const int KG = p.KG, KH = p.KH, TWP = p.TWP, TILE = p.TILE, G = p.G, NP = p.NP, NG8 = NP >> 3, N = p.N;
-    const int W_OFF = G * TILE;                          // [KH][KG][NP] weight dwords
-    const int M_OFF = W_OFF + KH * KG * NP * 4;          // [KG] byte masks of the real taps (WZ)
-    const int C_OFF = M_OFF + ((KG * 4 + 15) & ~15);     // A, S, Kc, fzp: [NP] each
-    for (int i = tid; i < G * TILE / 4; i += NTHR) ((uint32_t *)lds)[i] = p.izp4;
-    for (int i = tid; i < KH * KG * NP; i += NTHR) ((uint32_t *)(lds + W_OFF))[i] = p.wpack[i];
-    for (int i = tid; i < KG; i += NTHR) ((uint32_t *)(lds + M_OFF))[i] = p.mask[i];
-    for (int i = tid; i < NP; i += NTHR) {
-        const bool live = i < N;
-        ((float *)(lds + C_OFF))[i] = live ? p.A[i] : 0.0f;
-        ((float *)(lds + C_OFF + NP * 4))[i] = live ? p.S[i] : 0.0f;
-        ((int *)(lds + C_OFF + NP * 8))[i] = (live ? p.Kc[i] : 0) + (MG != 0 ? MF_MAGIC_I : 0);
-        ((int *)(lds + C_OFF + NP * 12))[i] = (WZ && live) ? p.wzp[i] : 0;
-    }
-    // staging map (the same for every step): dword e of this thread is image g, row y, dword x of the step
-    const int ROWD = p.ROWB >> 2, IMGD = p.H * ROWD, STEPD = G * IMGD;
-    int gofs[MAXE], lofs[MAXE];
-#pragma unroll
-    for (int e = 0; e < MAXE; ++e) {
-        const int idx = tid + NTHR * e;
-        const int g = idx / IMGD, r = idx - g * IMGD, y = r / ROWD, x = r - y * ROWD;
-        gofs[e] = idx < STEPD ? idx : -1;
-        lofs[e] = g * TILE + (y + p.shy) * TWP + p.XO + 4 * x;
-    }
-    const int nsteps = (batch + G - 1) / G;
-    uint32_t v[MAXE];
-    auto fetch = [&](int st) {
-        const uint32_t *src = (const uint32_t *)in + (size_t)st * STEPD;
-        const long lim = ((long)batch - (long)st * G) * IMGD; // dwords of the step that exist (a ragged last step)
-#pragma unroll
-        for (int e = 0; e < MAXE; ++e) {
-            // (select the VALUE, not the address: `cond ? src[i] : p.izp4` made the compiler choose between a global and a
-            // kernel-argument address, i.e. a flat load that also counts on lgkmcnt)
-            const bool ok = gofs[e] >= 0 && gofs[e] < lim;
-            const uint32_t got = src[ok ? gofs[e] : 0];
-            v[e] = ok ? got : p.izp4;
-        }
-    };
-    const float inv_ow = 1.0f / (float)p.OW, inv_opix = 1.0f / (float)(p.OH * p.OW);
-    const int OPIX = p.OH * p.OW;
-    int step = blockIdx.x;
-    if (step < nsteps) fetch(step);
-    for (; step < nsteps; step += gridDim.x) {
-        wg_sync();                                 // the previous step's compute is done with the tiles
-#pragma unroll
-        for (int e = 0; e < MAXE; ++e)
-            if (gofs[e] >= 0) *(uint32_t *)(lds + lofs[e]) = v[e];
-        wg_sync();
-        if (step + gridDim.x < nsteps) fetch(step + gridDim.x); // in flight during the compute below
-        const int gvalid = min(G, batch - step * G);
-        for (int po = tid; po < G * OPIX; po += NTHR) {
-            // pixel item -> (image, row, column); exact float divisions (indices < 2^22)
-            const int g = (int)(((float)po + 0.5f) * inv_opix);
-            const int o = po - g * OPIX;
-            const int oy = (int)(((float)o + 0.5f) * inv_ow), ox = o - oy * p.OW;
-            if (g >= gvalid) continue;
-            for (int cgp = 0; cgp < NG8; ++cgp) {        // 8 output channels at a time
-            int acc[8], wsum = 0;
-            const int4 k0 = *(const int4 *)(lds + C_OFF + NP * 8 + cgp * 32), k1 = *(const int4 *)(lds + C_OFF + NP * 8 + cgp * 32 + 16);
-            acc[0] = k0.x, acc[1] = k0.y, acc[2] = k0.z, acc[3] = k0.w, acc[4] = k1.x, acc[5] = k1.y, acc[6] = k1.z, acc[7] = k1.w;
-            const int base0 = g * TILE + (oy * p.sh) * TWP + ox * p.sw * p.C + p.X0;
-            for (int ky = 0; ky < KH; ++ky) {
-                const int base = base0 + ky * TWP;
-                const uint32_t *row = (const uint32_t *)(lds + (base & ~3));
-                const uint32_t sh = (uint32_t)(base & 3);
-                uint32_t lo = row[0];
-                for (int kg = 0; kg < KG; ++kg) {
-                    const uint32_t hi = row[kg + 1];
-                    const uint32_t val = __builtin_amdgcn_alignbyte(hi, lo, sh); // window bytes 4 kg .. 4 kg + 3 of this row
-                    lo = hi;
-                    const uint4 w0 = *(const uint4 *)(lds + W_OFF + ((ky * KG + kg) * NP + cgp * 8) * 4);
-                    const uint4 w1 = *(const uint4 *)(lds + W_OFF + ((ky * KG + kg) * NP + cgp * 8) * 4 + 16);
-                    acc[0] = sdot4(val, w0.x, acc[0]), acc[1] = sdot4(val, w0.y, acc[1]);
-                    acc[2] = sdot4(val, w0.z, acc[2]), acc[3] = sdot4(val, w0.w, acc[3]);
-                    acc[4] = sdot4(val, w1.x, acc[4]), acc[5] = sdot4(val, w1.y, acc[5]);
-                    acc[6] = sdot4(val, w1.z, acc[6]), acc[7] = sdot4(val, w1.w, acc[7]);
-                    if constexpr (WZ) wsum = sdot4(val, ((const uint32_t *)(lds + M_OFF))[kg], wsum);
-                }
-            }
-            if constexpr (WZ) {
-                const int4 z0 = *(const int4 *)(lds + C_OFF + NP * 12 + cgp * 32), z1 = *(const int4 *)(lds + C_OFF + NP * 12 + cgp * 32 + 16);
-                acc[0] -= z0.x * wsum, acc[1] -= z0.y * wsum, acc[2] -= z0.z * wsum, acc[3] -= z0.w * wsum;
-                acc[4] -= z1.x * wsum, acc[5] -= z1.y * wsum, acc[6] -= z1.z * wsum, acc[7] -= z1.w * wsum;
-            }
-            const float4 a0 = *(const float4 *)(lds + C_OFF + cgp * 32), a1 = *(const float4 *)(lds + C_OFF + cgp * 32 + 16);
-            const float4 s0 = *(const float4 *)(lds + C_OFF + NP * 4 + cgp * 32), s1 = *(const float4 *)(lds + C_OFF + NP * 4 + cgp * 32 + 16);
-            const uint32_t d0 = requant_pack4<MG, XR4>(acc[0], acc[1], acc[2], acc[3], a0, s0, p.lo_f, p.hi_f);
-            const uint32_t d1 = requant_pack4<MG, XR4>(acc[4], acc[5], acc[6], acc[7], a1, s1, p.lo_f, p.hi_f);
-            int8_t *dst = out + ((size_t)(step * G + g) * OPIX + o) * N + cgp * 8;
-            if ((N & 7) == 0) {
-                st_out_t<false>(dst, make_uint2(d0, d1));
-            } else {                                     // N not a multiple of 8: byte stores of the channels that exist
-                const int nleft = N - cgp * 8;
-#pragma unroll
-                for (int c = 0; c < 8; ++c)
-                    if (c < nleft) dst[c] = (int8_t)(((c < 4 ? d0 : d1) >> (8 * (c & 3))) & 0xffu);
-            }
-            }
-        }
-    }
+    constexpr bool F32IN = false;
+    constexpr F32Edge eg{};
+#include "k_conv_rows_body.inc"
+}
+template <bool WZ, int MG, uint32_t XR4>
+__global__ __launch_bounds__(512) void conv_rows_lds_f32(const int8_t *__restrict__ in, int8_t *__restrict__ out, ConvRowsArgs p, F32Edge eg, int batch) {
+    static_assert(MG <= 2, "the boundary quantisation needs round-to-nearest: no single-fma epilogue here");
+    constexpr bool F32IN = true;
+#include "k_conv_rows_body.inc"
 }
 
 // ------------------------------------------------------------------------
@@ -1091,8 +1004,8 @@ bool conv_rows_plan(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW,
     a.G = g;
     return conv_rows_lds_bytes(a) <= 96 * 1024;
 }
-template <bool WZ, int MG, uint32_t XR4>
-static void launch_conv_rows_t(const int8_t *in, int8_t *out, const ConvRowsArgs &a, int batch, hipStream_t s) {
+template <bool WZ, int MG, uint32_t XR4, bool F32IN>
+static void launch_conv_rows_t(const int8_t *in, int8_t *out, const ConvRowsArgs &a, int batch, hipStream_t s, const F32Edge *eg) {
     const int lds = conv_rows_lds_bytes(a);
     int per_cu = 1;
     {
@@ -1103,9 +1016,10 @@ static void launch_conv_rows_t(const int8_t *in, int8_t *out, const ConvRowsArgs
         std::lock_guard<std::mutex> lock(mu);
         auto it = cache.find({dev, lds});
         if (it == cache.end()) {
-            (void)hipFuncSetAttribute((const void *)conv_rows_lds<WZ, MG, XR4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+            const void *fn = F32IN ? (const void *)conv_rows_lds_f32<WZ, MG, XR4> : (const void *)conv_rows_lds<WZ, MG, XR4>;
+            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
             int n = 1;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_rows_lds<WZ, MG, XR4>, 512, (size_t)lds) != hipSuccess || n < 1) {
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 512, (size_t)lds) != hipSuccess || n < 1) {
                 (void)hipGetLastError();
                 n = 1;
             }
@@ -1115,7 +1029,8 @@ static void launch_conv_rows_t(const int8_t *in, int8_t *out, const ConvRowsArgs
     }
     const int nsteps = (batch + a.G - 1) / a.G;
     const int grid = nsteps < 256 * per_cu ? nsteps : 256 * per_cu;
-    MF_LAUNCH((conv_rows_lds<WZ, MG, XR4>), dim3(grid), dim3(512), lds, s, in, out, a, batch);
+    if constexpr (F32IN) MF_LAUNCH((conv_rows_lds_f32<WZ, MG, XR4>), dim3(grid), dim3(512), lds, s, in, out, a, *eg, batch);
+    else MF_LAUNCH((conv_rows_lds<WZ, MG, XR4>), dim3(grid), dim3(512), lds, s, in, out, a, batch);
 }
 bool dw_stem_rt_plan(DwStemRtArgs &a, int H, int W, int DM, int OH, int OW) {
     if ((DM != 4 && DM != 8) || W % 16 != 0 || W < 16 || H < 2 || OH != (H + 1) / 2 || OW != W / 2) return false;
@@ -1162,18 +1077,23 @@ void launch_dw_stem_rt(const int8_t *in, int8_t *out, const DwStemRtArgs &a, int
     if (a.DM == 8) MF_RT_GO(8); else MF_RT_GO(4);
 #undef MF_RT_GO
 }
-void launch_conv_rows(const int8_t *in, int8_t *out, const ConvRowsArgs &a, bool wz, int batch, hipStream_t s) {
+template <bool WZ, int MG, uint32_t XR4>
+static void launch_conv_rows_e(const int8_t *in, int8_t *out, const ConvRowsArgs &a, int batch, hipStream_t s, const F32Edge *eg) {
+    if (eg) launch_conv_rows_t<WZ, MG, XR4, true>(in, out, a, batch, s, eg);
+    else launch_conv_rows_t<WZ, MG, XR4, false>(in, out, a, batch, s, nullptr);
+}
+void launch_conv_rows(const int8_t *in, int8_t *out, const ConvRowsArgs &a, bool wz, int batch, hipStream_t s, const F32Edge *eg) {
     const int mg = a.magic;
 #define MF_RT_GO(WZZ)                                                                              \
     do {                                                                                           \
         if (a.xr) {                                                                                \
-            if (mg == 2) launch_conv_rows_t<WZZ, 2, 0x80808080u>(in, out, a, batch, s);            \
-            else if (mg) launch_conv_rows_t<WZZ, 1, 0x80808080u>(in, out, a, batch, s);            \
-            else launch_conv_rows_t<WZZ, 0, 0x80808080u>(in, out, a, batch, s);                    \
+            if (mg == 2) launch_conv_rows_e<WZZ, 2, 0x80808080u>(in, out, a, batch, s, eg);        \
+            else if (mg) launch_conv_rows_e<WZZ, 1, 0x80808080u>(in, out, a, batch, s, eg);        \
+            else launch_conv_rows_e<WZZ, 0, 0x80808080u>(in, out, a, batch, s, eg);                \
         } else {                                                                                   \
-            if (mg == 2) launch_conv_rows_t<WZZ, 2, 0u>(in, out, a, batch, s);                     \
-            else if (mg) launch_conv_rows_t<WZZ, 1, 0u>(in, out, a, batch, s);                     \
-            else launch_conv_rows_t<WZZ, 0, 0u>(in, out, a, batch, s);                             \
+            if (mg == 2) launch_conv_rows_e<WZZ, 2, 0u>(in, out, a, batch, s, eg);                 \
+            else if (mg) launch_conv_rows_e<WZZ, 1, 0u>(in, out, a, batch, s, eg);                 \
+            else launch_conv_rows_e<WZZ, 0, 0u>(in, out, a, batch, s, eg);                         \
         }                                                                                          \
     } while (0)
     if (wz) MF_RT_GO(true); else MF_RT_GO(false);

@@ -274,8 +274,9 @@ struct DwStemRtArgs {
 bool dw_stem_rt_plan(DwStemRtArgs &a, int H, int W, int DM, int OH, int OW);
 // (eg != nullptr: the f32 entry -- `in` points to batch x H W floats, 16-byte aligned, quantised with eg's in_* parameters while staged)
 void launch_dw_stem_rt(const int8_t *in, int8_t *out, const DwStemRtArgs &a, int batch, hipStream_t s, const F32Edge *eg = nullptr);
+int conv_rows_lds_bytes(const ConvRowsArgs &a);
 bool conv_rows_plan(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same);
-void launch_conv_rows(const int8_t *in, int8_t *out, const ConvRowsArgs &a, bool wz, int batch, hipStream_t s);
+void launch_conv_rows(const int8_t *in, int8_t *out, const ConvRowsArgs &a, bool wz, int batch, hipStream_t s, const F32Edge *eg = nullptr);
 // Conv2D with any filter, C % 16 == 0, as an MFMA product over K = KH KW C (k_rt.hip: conv_mm_rt)
 struct ConvMmArgs {
     int H, W, C, N, KH, KW, sh, sw, OH, OW;

@@ -1034,7 +1034,11 @@ unsigned long long &dev_launch_counter() { return k::launches_enqueued; }
 
 bool op_set_input_quant(OpImpl *op, float scale, int zp, bool u8) {
     if (!(scale == scale)) return false;
-    if ((op->fast == OpImpl::FC_RT || op->fast == OpImpl::DW_STEM_RT) && !switches().no_f32_boundary) { // fc_rt_f32 (k_fc_f32.hip), dw3x3_stem_rt_f32 (k_rt.hip)
+    // fc_rt_f32 (k_fc_f32.hip), dw3x3_stem_rt_f32 and conv_rows_lds_f32 (k_rt.hip).  conv_rows_lds takes the floats only where a step is
+    // one image (G == 1: more than 4096 dwords of image): with several small images per step its predict measured slower than the separate
+    // pass (28x28x1, G = 8, +4 %), and conv_gemm_rt has no f32 instance for the same reason (224x224x3 in row bands, +12 %)
+    const bool conv_rows_one_image = op->fast == OpImpl::CONV_ROWS && op->crows.G == 1;
+    if ((op->fast == OpImpl::FC_RT || op->fast == OpImpl::DW_STEM_RT || conv_rows_one_image) && !switches().no_f32_boundary) {
         edge_set_in(op->edge, op->device, scale, zp, u8);
         op->accepts_f32 = true;
         return true;
@@ -1071,6 +1075,12 @@ void op_run_f32(OpImpl *op, const void *d_in, bool in_f32, size_t batch, void *d
     if (op->fast == OpImpl::DW_STEM_RT) { // (entry only: op_set_output_dequant refuses this kernel)
         MF_HIP(hipSetDevice(op->device));
         k::launch_dw_stem_rt((const int8_t *)d_in, (int8_t *)d_out, op->stemrt, (int)batch, (hipStream_t)stream, &op->edge);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (op->fast == OpImpl::CONV_ROWS) { // (entry only, as the stem)
+        MF_HIP(hipSetDevice(op->device));
+        k::launch_conv_rows((const int8_t *)d_in, (int8_t *)d_out, op->crows, op->rt_wz, (int)batch, (hipStream_t)stream, &op->edge);
         MF_HIP(hipGetLastError());
         return;
     }

@@ -5,8 +5,11 @@ run_quantized on the same quantised input).
 
 usage: time_f32.py MODEL BATCH [iters]     one measurement, in this process
        time_f32.py --all [iters]           the table of profiles/r09/f32_entry.txt: one child process per row, each with its own time limit
+       time_f32.py --conv [iters]          the table of profiles/r10/f32_conv_entry.txt (Conv2D-stem models), in the same way
 MODEL: person_detect | speech | sine (models/*.tflite), pd_like:SIDE (tools/tflite_writer.person_detect_like(side=SIDE)),
-       mlp:K-N1-N2...[+sm] (tools/tflite_writer.mlp), pool_head:HxWxC-N1...[+sm] (tools/tflite_writer.pool_head)"""
+       mlp:K-N1-N2...[+sm] (tools/tflite_writer.mlp), pool_head:HxWxC-N1...[+sm] (tools/tflite_writer.pool_head),
+       conv_net:HxWxC-L1-L2... (tools/tflite_writer.conv_net with head=10; a layer is cNkKsS, a KxK Conv2D to N channels at stride S,
+       or dwKsS, a KxK depthwise)"""
 import os
 import subprocess
 import sys
@@ -14,6 +17,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = [("person_detect", 65536), ("speech", 4096), ("speech", 65536), ("sine", 65536), ("pd_like:64", 65536), ("mlp:20-33-7+sm", 65536),
         ("pool_head:7x7x64-10+sm", 65536)]
+# conv_rows_lds: an RGB stem + two depthwise / 1x1 pairs, a LeNet-style greyscale stem; conv_gemm_rt: an ImageNet stem (row bands), a 128 x 128 stem
+CONV_ROWS = [("conv_net:96x96x3-c16k3s2-dw3s1-c32k1s1-dw3s2-c64k1s1", 65536), ("conv_net:28x28x1-c6k5s1", 65536), ("conv_net:224x224x3-c64k7s2", 4096),
+             ("conv_net:128x128x3-c16k3s2", 16384)]
 
 
 def blob(name):
@@ -32,6 +38,16 @@ def blob(name):
     if kind == "pool_head":
         shape, _, sizes = arg.replace("+sm", "").partition("-")
         return tw.pool_head(rng, tuple(int(v) for v in shape.split("x")), tuple(int(v) for v in sizes.split("-")), softmax=arg.endswith("+sm"))
+    if kind == "conv_net":
+        import re
+        shape, *layers = arg.split("-")
+        convs = []
+        for l in layers:
+            f = re.fullmatch(r"(c(\d+)|dw)k?(\d+)s(\d+)", l)
+            if not f:
+                raise SystemExit("conv_net layer %r: cNkKsS or dwKsS" % l)
+            convs.append(("dw", 0, int(f.group(3)), int(f.group(4))) if f.group(1) == "dw" else ("conv", int(f.group(2)), int(f.group(3)), int(f.group(4))))
+        return tw.conv_net(rng, tuple(int(v) for v in shape.split("x")), convs, head=10)
     raise SystemExit("unknown model %r" % name)
 
 
@@ -86,8 +102,8 @@ def one(name, B, iters):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) >= 2 and sys.argv[1] == "--all":
-        for name, B in ROWS:
+    if len(sys.argv) >= 2 and sys.argv[1] in ("--all", "--conv"):
+        for name, B in (ROWS if sys.argv[1] == "--all" else CONV_ROWS):
             # (a failed or timed-out row ends the table: nothing more is started on a card that may be in trouble)
             r = subprocess.run([sys.executable, os.path.abspath(__file__), name, str(B)] + sys.argv[2:3], timeout=240)
             if r.returncode:
