@@ -14,7 +14,7 @@
 namespace mf {
 
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ } kind;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC } kind;
     OpImpl *a, *b, *c;
     k::DwPwArgs dwpw;
     k::TailArgs tail;
@@ -46,6 +46,10 @@ struct FusedImpl {
     k::PairBandArgs pairband{};
     // PAIRWZ: one pair with filter zero points, whole images in LDS (k_pair_wz.hip); a = the depthwise, b = the conv; table and images in stage_w
     k::PairWzArgs pairwz{};
+    // CONV1FC: a one-input-channel convolution + FullyConnected (+ Softmax) in one launch (k_conv1_fc.hip); a = the convolution, b = the
+    // FullyConnected, c = the Softmax or nullptr; the convolution's operand A in stage_w
+    k::Conv1FcArgs conv1fc{};
+    size_t conv1fc_max_batch = 0; // 0: any batch; else the largest batch at which the launch beat the operators' own (fused_batch_ok)
     // the model's f32 boundary inside this group's launch (fused_set_input_quant / fused_set_output_dequant): FCCHAIN and DWFC both
     // ends, POOLFC and PAIRTAIL the exit
     k::F32Edge edge{};
@@ -525,7 +529,83 @@ FusedImpl *fused_pool_fc_create(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl 
     return f;
 }
 bool fused_input_ok(const FusedImpl *f, const int8_t *d_in) {
-    return (f->kind != FusedImpl::POOLFC && f->kind != FusedImpl::PAIRBAND && f->kind != FusedImpl::PAIRWZ) || ((uintptr_t)d_in & 15) == 0; // (these read 16-byte words at the pointer)
+    return (f->kind != FusedImpl::POOLFC && f->kind != FusedImpl::PAIRBAND && f->kind != FusedImpl::PAIRWZ && f->kind != FusedImpl::CONV1FC) || ((uintptr_t)d_in & 15) == 0; // (these read 16-byte words at the pointer)
+}
+
+// A DepthwiseConv2D or Conv2D with one input channel -> [Reshape] -> FullyConnected (one row per inference, reading the flattened
+// output) -> [Softmax over its outputs], as one conv1_fc_rt launch (k_conv1_fc.hip); false for what k::conv1_fc_plan refuses (filter
+// zero points, non-finite constants, the geometry limits, dwc1_fc_softmax's own geometry, the LDS budget).  The FullyConnected's fc_rt
+// image and padded constants are the operator's where it has them; where the operator alone is past fc_rt's own budget (8000 -> 12
+// runs fc_generic) the group builds them from the host copies
+static bool conv1_fc_args(OpImpl *cv, OpImpl *fc, OpImpl *sm, k::Conv1FcArgs &a) {
+    if (switches().no_conv1_fc || !cv || !fc || cv->force_generic || fc->force_generic) return false;
+    const OpSpec &d = cv->s, &q = fc->s;
+    if ((d.kind != MF_OP_DEPTHWISE_CONV_2D && d.kind != MF_OP_CONV_2D) || d.C != 1 || q.kind != MF_OP_FULLY_CONNECTED) return false;
+    if (q.M != 1 || q.u8 != d.u8 || fc->device != cv->device || cv->h_w.empty() || fc->h_w.empty()) return false;
+    const k::FcArgs &g = fc->fc;
+    if ((int)fc->h_A.size() != g.N || (int)fc->h_Kc.size() != g.N || !std::isfinite(g.S) ||
+        !std::all_of(fc->h_A.begin(), fc->h_A.end(), [](float v) { return std::isfinite(v); }))
+        return false;
+    a = k::Conv1FcArgs{};
+    a.H = d.H, a.W = d.W, a.N = d.N, a.KH = d.KH, a.KW = d.KW, a.sh = d.sh, a.sw = d.sw, a.OH = d.OH, a.OW = d.OW;
+    a.pad_same = d.pad == MF_PAD_SAME;
+    a.wz = std::any_of(cv->h_wzp.begin(), cv->h_wzp.end(), [](int32_t z) { return z != 0; }), a.finite = cv->finite_consts;
+    k::FcChainLayer &y = a.fc;
+    y.S = g.S, y.lo_f = g.lo_f, y.hi_f = g.hi_f, y.K = g.K, y.N = g.N, y.wzp = g.wzp;
+    if (fc->fcrt_ok) y.wimg = fc->fcrt.wimg, y.A = fc->fcrt.A, y.Kc = fc->fcrt.Kc; // (else: fused_conv1_fc_create builds them)
+    if (sm) {
+        if (sm->s.kind != MF_OP_SOFTMAX || sm->s.M != 1 || sm->s.N != q.N || sm->s.u8 != d.u8 || sm->device != cv->device) return false;
+        a.softmax = 1, a.sm = sm->sm;
+    }
+    a.A = cv->conv.A, a.S = cv->conv.S, a.Kc = cv->conv.Kc, a.lo_f = cv->conv.lo_f, a.hi_f = cv->conv.hi_f;
+    a.izp4 = 0x01010101u * (uint32_t)(uint8_t)(int8_t)d.izp;
+    a.magic = std::min(cv->magic_mode, 2), a.xr = g.xr; // (the convolution's mode; the FullyConnected's few bytes take mode 0)
+    if (cv->conv.xr != g.xr) return false;
+    return k::conv1_fc_plan(a);
+}
+// The routing rule of DESIGN 4.2d, by measurement (profiles/r10/time_conv1_fc.txt): where the FullyConnected has its own fc_rt launch,
+// conv1_fc_rt beat the three launches at batch 4096 (one step per workgroup: 1.13 - 1.55x) and lost at 65 536 (0.82 - 1.01x), so such
+// a group takes batches up to 4096 only; where the FullyConnected alone runs fc_generic it won at both (2.3 - 3.1x) and takes any
+bool fused_batch_ok(const FusedImpl *f, size_t batch) {
+    return f->kind != FusedImpl::CONV1FC || f->conv1fc_max_batch == 0 || batch <= f->conv1fc_max_batch;
+}
+bool fused_conv1_fc_fits(OpImpl *conv, OpImpl *fc, OpImpl *sm) {
+    k::Conv1FcArgs a;
+    return conv1_fc_args(conv, fc, sm, a);
+}
+FusedImpl *fused_conv1_fc_create(OpImpl *conv, OpImpl *fc, OpImpl *sm) {
+    k::Conv1FcArgs a;
+    if (!conv1_fc_args(conv, fc, sm, a)) return nullptr;
+    const OpSpec &d = conv->s;
+    const bool dw = d.kind == MF_OP_DEPTHWISE_CONV_2D;
+    std::unique_ptr<FusedImpl> f(new FusedImpl{FusedImpl::CONV1FC, conv, fc, sm, {}, {},
+                                               std::string("conv1_fc_rt<") + (dw ? "dw," : "conv,") + std::to_string(d.KH) + "x" + std::to_string(d.KW) +
+                                                   "," + std::to_string(d.N) + (sm ? ">+sm" : ">")});
+    // the taps as uploaded (i8 domain): depthwise [KH][KW][N], Conv2D [N][KH][KW][1]
+    auto w = [&](int ky, int kx, int c) { return dw ? conv->h_w[((size_t)ky * d.KW + kx) * d.N + c] : conv->h_w[((size_t)c * d.KH + ky) * d.KW + kx]; };
+    // operand A: row R = 16 rt + r is (pixel R / N, channel R % N) where a tile holds PP pixels, channel R otherwise; lane group g of k
+    // step ks holds filter row 4 ks + g at bytes pixel * sw .. + KW - 1
+    std::vector<int8_t> wa((size_t)2 * 4 * 64 * 16, 0);
+    for (int rt = 0; rt < a.NRT; ++rt)
+        for (int ks = 0; ks < a.KSC; ++ks)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int R = rt * 16 + (lane & 15), ky = 4 * ks + (lane >> 4);
+                const int px = a.PP > 1 ? R / d.N : 0, c = R - px * d.N;
+                if (px >= a.PP || c >= d.N || ky >= d.KH) continue;
+                for (int kx = 0; kx < d.KW; ++kx) wa[(((size_t)rt * 4 + ks) * 64 + lane) * 16 + (size_t)(px * d.sw + kx)] = w(ky, kx, c);
+            }
+    a.wA = keep(*f, wa.data(), wa.size());
+    if (!fc->fcrt_ok) {
+        const std::vector<int8_t> img = k::fc_rt_weight_image(fc->h_w.data(), a.fc.K, a.fc.N);
+        std::vector<float> pA((size_t)a.fc.NT * 16, 0.0f);
+        std::vector<int32_t> pK((size_t)a.fc.NT * 16, 0);
+        std::copy(fc->h_A.begin(), fc->h_A.end(), pA.begin()), std::copy(fc->h_Kc.begin(), fc->h_Kc.end(), pK.begin());
+        a.fc.wimg = keep(*f, img.data(), img.size());
+        a.fc.A = (const float *)keep(*f, pA.data(), pA.size() * 4), a.fc.Kc = (const int *)keep(*f, pK.data(), pK.size() * 4);
+    }
+    f->conv1fc = a, f->epi_mode = a.magic;
+    f->conv1fc_max_batch = fc->fcrt_ok ? 4096 : 0;
+    return f.release();
 }
 
 // A run of `npairs` identical DepthwiseConv2D 3x3 (stride 1) + Conv2D 1x1 pairs on one small tensor as one persistent
@@ -921,6 +1001,12 @@ void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, vo
     if (f->kind == FusedImpl::POOLFC) { // (any output pointer: the kernel aligns its stores itself)
         if (!fused_input_ok(f, d_in)) fail(MF_ERR_INVALID_ARG, "pool_fc_chain: the input pointer is not 16-byte aligned");
         k::launch_pool_fc(d_in, d_out, f->poolfc, (long long)batch, (hipStream_t)stream);
+        MF_HIP(hipGetLastError());
+        return;
+    }
+    if (f->kind == FusedImpl::CONV1FC) { // (any output pointer: the kernel aligns its stores itself)
+        if (!fused_input_ok(f, d_in)) fail(MF_ERR_INVALID_ARG, "conv1_fc_rt: the input pointer is not 16-byte aligned");
+        k::launch_conv1_fc(d_in, d_out, f->conv1fc, (long long)batch, (hipStream_t)stream);
         MF_HIP(hipGetLastError());
         return;
     }

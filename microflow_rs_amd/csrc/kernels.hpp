@@ -790,6 +790,39 @@ struct PoolFcArgs {
 bool pool_fc_plan(PoolFcArgs &a);
 void launch_pool_fc(const int8_t *in, int8_t *out, const PoolFcArgs &a, long long batch, hipStream_t s); // `in` 16-byte aligned
 void launch_pool_fc_f32(const int8_t *in, float *out, const PoolFcArgs &a, const F32Edge &e, long long batch, hipStream_t s); // f32 exit
+// A DepthwiseConv2D or Conv2D with ONE input channel (N = 4 .. 32 filters of up to 16 x 16, strides 1 or 2 each way, SAME or VALID,
+// zero filter zero points) -> FullyConnected over the flattened [OH][OW][N] tensor (one row per inference, up to 64 outputs, any weight
+// zero point) -> [Softmax] in one launch (k_conv1_fc.hip: conv1_fc_rt).  A step is 16 images = the 16 columns of every matrix
+// instruction; the convolution's output exists only as a band of output rows in LDS, which the FullyConnected consumes band by band.
+struct Conv1FcArgs {
+    // what conv1_fc_plan reads ...
+    int H, W, N, KH, KW, sh, sw, OH, OW, pad_same;
+    int wz, finite;      // the convolution has non-zero filter zero points (internal domain) / every folded constant is finite
+    FcChainLayer fc;     // the FullyConnected: K = OH OW N, N, and for the launch wimg (its fc_rt image), A, Kc, S, lo_f, hi_f, wzp
+    int softmax;
+    // ... and what it fills in
+    int padt, padl;      // SAME: (KH - 1) / 2, (KW - 1) / 2 (src/tensor.rs:193); VALID: 0
+    int XO, PITCH, TROWS, TILE; // an image's tile: TROWS rows of PITCH bytes, image column 0 at byte XO of a row, TILE bytes in all
+    int PP, NRT, KSC;    // output pixels per 16-row tile (N < 16: PP adjacent ones), row tiles, k steps of four filter rows
+    int BH, NB, BP;      // output rows per band, bands, bytes between two images' rows of a band buffer
+    int wres;            // 1: the FullyConnected image is resident in LDS; 0: it does not fit beside the tiles and is read through the L2
+    int woff, toff, tbytes, boff, qoff, aoff, poff, lds; // LDS plan: image, tiles, two band buffers, partial sums, FC row tile, patch
+    uint32_t m_hw4, m_w4; // ceil(2^32 / (H W / 4)), ceil(2^32 / (W / 4)): the staging's divisions as multiplications (0: divisor 1)
+    // the convolution's operands
+    const void *wA;      // [2 row tiles][4 k steps][64 lanes][16 bytes]: row (pixel p, channel c) of k step ks holds filter row
+                         // 4 ks + lane group at bytes p sw .. p sw + KW - 1, zero elsewhere
+    const float *A, *S;  // [N]
+    const int *Kc;       // [N]
+    float lo_f, hi_f;
+    uint32_t izp4;
+    SoftmaxArgs sm;
+    int magic, xr;       // the convolution's epilogue mode (the FullyConnected's few bytes take mode 0), element type
+};
+constexpr int CONV1_FC_BAND_FRONT = 64; // bytes in front of every image's row of a band buffer (a k step may start before the band)
+// fills the geometry; false: outside what the kernel takes (the table in DESIGN 4.2d), dwc1_fc_softmax's own geometry, or the tiles,
+// band buffers and patch do not fit the LDS budget (FC_RT_LDS_MAX)
+bool conv1_fc_plan(Conv1FcArgs &a);
+void launch_conv1_fc(const int8_t *in, int8_t *out, const Conv1FcArgs &a, long long batch, hipStream_t s); // `in` 16-byte aligned
 
 void launch_softmax(const int8_t *in, int8_t *out, const SoftmaxArgs &a, size_t batch, hipStream_t s);
 // number of float bit patterns (of all 2^32) whose quantised byte differs between quant_div's fast form and the true

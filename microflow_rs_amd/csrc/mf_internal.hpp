@@ -167,9 +167,15 @@ FusedImpl *fused_fc_chain_create(OpImpl *const *fcs, int n, OpImpl *sm);
 // launch (k_pool_fc.hip; second level: a fc_rowwave_softmax group inside it stays for run_until pieces)
 bool fused_pool_fc_fits(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm);
 FusedImpl *fused_pool_fc_create(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm);
+// a DepthwiseConv2D / Conv2D with one input channel + the FullyConnected behind it (+ a Softmax over one row: sm, or nullptr) as one
+// conv1_fc_rt launch (k_conv1_fc.hip; second level: the operators and a fc_rowwave_softmax group inside it stay for run_until pieces)
+bool fused_conv1_fc_fits(OpImpl *conv, OpImpl *fc, OpImpl *sm);
+FusedImpl *fused_conv1_fc_create(OpImpl *conv, OpImpl *fc, OpImpl *sm);
 // false: this launch cannot take the group's kernel on this input pointer (pool_fc_chain loads 16-byte words) and the operators run
 // their own launches, as op_run decides for a single operator
 bool fused_input_ok(const FusedImpl *f, const int8_t *d_in);
+// false: at this batch the group's launch measured slower than the operators' own, which run instead (conv1_fc_rt)
+bool fused_batch_ok(const FusedImpl *f, size_t batch);
 // a run of identical depthwise + pointwise pair groups as one persistent kernel (borrows their device buffers:
 // destroy it before them); nullptr when no stage kernel exists for the shape / count
 FusedImpl *fused_stage_create(FusedImpl *const *pairs, int npairs);

@@ -370,6 +370,25 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             while (j < n && m->pm.ops[j].kind == MF_OP_RESHAPE) ++j;
             return j;
         };
+        // (5a) a DepthwiseConv2D or Conv2D with one input channel -> [Reshape] -> FullyConnected (one row per inference) -> [Reshape] ->
+        // [Softmax] -> one conv1_fc_rt launch (fused.hip: fused_conv1_fc_create) at any geometry its plan accepts; speech.tflite's own
+        // geometry is refused there and keeps (5).  Where the FullyConnected + Softmax already are a group of (3), this stage sits over
+        // conv .. softmax and that group stays for mf_model_run_until pieces.  One FullyConnected only: a run behind it is left to (6)
+        for (size_t i = 0; i + 1 < n; ++i) {
+            const int kind = m->pm.ops[i].kind;
+            if (!ops[i] || fused[i] || covered(i) || owned(i) || (kind != MF_OP_DEPTHWISE_CONV_2D && kind != MF_OP_CONV_2D) || m->pm.ops[i].C != 1) continue;
+            const size_t j0 = skip_reshapes(i + 1);
+            if (j0 >= n || !ops[j0] || m->pm.ops[j0].kind != MF_OP_FULLY_CONNECTED || m->pm.ops[j0].M != 1 || covered(j0) || owned(j0)) continue;
+            if (fused[j0]) {
+                if (fused_last[j0] > (int)j0 && m->pm.ops[(size_t)fused_last[j0]].kind == MF_OP_SOFTMAX)
+                    if (FusedImpl *f = fused_conv1_fc_create(ops[i], ops[j0], ops[(size_t)fused_last[j0]])) sg.v.push_back({f, (int)i, fused_last[j0]});
+                continue;
+            }
+            const size_t smi = skip_reshapes(j0 + 1);
+            OpImpl *sm = free_sm(smi) ? ops[smi] : nullptr;
+            if (sm && !fused_conv1_fc_fits(ops[i], ops[j0], sm)) sm = nullptr; // (the two operators without the Softmax)
+            if (FusedImpl *f = fused_conv1_fc_create(ops[i], ops[j0], sm)) sg.v.push_back({f, (int)i, (int)(sm ? smi : j0)});
+        }
         // (5b) AveragePool2D over the whole image -> [Reshape] -> FullyConnected layers (one row per inference) -> [Softmax] -> one
         // pool_fc_chain launch (fused.hip: fused_pool_fc_create), the longest run of layers whose images fit.  Before (6), so that the
         // FullyConnected run behind a pool is offered here first; what does not fit stays for (6) or keeps its own launches.  Where the
@@ -551,7 +570,7 @@ static const int8_t *run_ops(ModelImpl *m, const int8_t *src, size_t batch, int 
             if (entry != 1) staged = nullptr;
             grouped = entry == 2;
         } else {
-            if (staged && !fused_input_ok(staged->f, cur)) staged = nullptr; // (the operators' own launches take any pointer)
+            if (staged && (!fused_input_ok(staged->f, cur) || !fused_batch_ok(staged->f, batch))) staged = nullptr; // (the operators' own launches take any pointer and batch)
             grouped = !staged && fused_at(m, i) && m->fused_last[(size_t)i] <= last_op && fused_input_ok(m->fused[(size_t)i], cur);
         }
         const int end = staged ? staged->last : (grouped ? m->fused_last[(size_t)i] : i);
@@ -850,7 +869,7 @@ void model_time_device(ModelImpl *m, const int8_t *d_in, size_t batch, int8_t *d
                         dst = m->act[which];
                     }
                     const ModelImpl::Stage *st = stage_at(m, i, nops - 1);
-                    if (st && !fused_input_ok(st->f, cur)) st = nullptr;
+                    if (st && (!fused_input_ok(st->f, cur) || !fused_batch_ok(st->f, (size_t)batch))) st = nullptr;
                     if (st) { // timed as one unit (index i), its other ops 0
                         fused_run(st->f, cur, batch, dst, s);
                         for (int j = i; j < st->last; ++j) MF_HIP(hipEventRecord(ev[(size_t)j + 1], s));

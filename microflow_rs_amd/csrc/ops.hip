@@ -684,6 +684,7 @@ void create_fc(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
         }
     }
     op.h_w.assign(s.weights, s.weights + (size_t)s.N * s.K);
+    op.h_A = A, op.h_Kc = Kc; // (a fused group builds its own padded copies where the operator has no fc_rt image: fused.hip conv1_fc)
     op.d_w.upload(s.weights, (size_t)s.N * s.K);
     op.d_A.upload(A.data(), A.size() * 4);
     op.d_Kc.upload(Kc.data(), Kc.size() * 4);

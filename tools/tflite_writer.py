@@ -210,6 +210,56 @@ def speech_like(rng, elem=INT8, fc_wzp=0, per_channel=True, act="relu"):
     return build_model((1, 1960), in_q, layers, elem)
 
 
+def kws_like(rng, shape, stem, classes, elem=INT8, fc_wzp=0, softmax=True, wmax=None, act="relu", stem_wzp=False, reshape=True):
+    """TensorFlow's keyword-spotting "tiny_conv" family at any geometry: input [1, H, W, 1] (shape = (H, W)) -> a one-channel
+    convolution -> Reshape -> FullyConnected(classes) -> optionally a Softmax.  stem = (kind, N, KH, KW, (sh, sw), padding) gives the
+    convolution in full: kind "dw" (DepthwiseConv2D with depth multiplier N, what the converter writes) or "conv" (Conv2D with N
+    filters), padding "same" or "valid".  Per-channel filter quantization with the zero points at the type's middle (stem_wzp:
+    off it), one FullyConnected weight zero point at middle + fc_wzp.  `wmax`: convolution and FullyConnected weights within
+    +-wmax of the middle (None: the full range); the scales keep both operators' outputs spread over the range."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    H, W = (int(v) for v in shape)
+    kind, N, KH, KW, (sh, sw), padding = stem
+    N, KH, KW = int(N), int(KH), int(KW)
+    if padding == "same":
+        OH, OW = -(-H // sh), -(-W // sw)
+    else:
+        OH, OW = (H - KH) // sh + 1, (W - KW) // sw + 1
+    wm = 128 if wmax is None else int(wmax)
+
+    def weights(shp):
+        return rng.integers(lo, hi, shp) if wmax is None else rng.integers(mid - wm, mid + wm + 1, shp)
+
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo, lo + 40)))
+    sc = rng.uniform(0.002, 0.01, N).astype(np.float32)
+    zp = rng.integers(mid - 10, mid + 11, N) if stem_wzp else np.full(N, mid)
+    if stem_wzp and not np.any(zp != mid):
+        zp[0] = mid + 3
+    relu = act in ("relu", "relu6")
+    c_out = (float(np.float32(in_q[0] * float(sc.mean()) * 50.0 * np.sqrt(KH * KW) * wm / 128.0)),
+             int(lo if relu else rng.integers(lo + 20, hi - 20)))
+    d = dict(op="depthwise_conv_2d" if kind == "dw" else "conv_2d", fscale=sc, fzp=zp, bias=rng.integers(-2000, 2000, N),
+             bscale=(sc * np.float32(in_q[0])).astype(np.float32), bzp=np.zeros(N, np.int64), padding=padding, strides=(sh, sw), act=act,
+             out_shape=(1, OH, OW, N), out_q=c_out)
+    if kind == "dw":
+        d["weights"], d["depth_multiplier"] = weights((1, KH, KW, N)), N
+    else:
+        d["filters"] = weights((N, KH, KW, 1))
+    layers = [d]
+    K = OH * OW * N
+    if reshape:
+        layers.append(dict(op="reshape", out_shape=(1, K), out_q=c_out))
+    fsc = np.float32(rng.uniform(0.001, 0.004))
+    f_out = (float(np.float32(c_out[0] * fsc * 40.0 * np.sqrt(K) * wm / 128.0)), int(rng.integers(lo + 60, hi - 60)))
+    layers.append(dict(op="fully_connected", weights=weights((int(classes), K)), wscale=[fsc], wzp=[mid + fc_wzp],
+                       bias=rng.integers(-3000, 3000, int(classes)), bscale=[fsc * np.float32(c_out[0])], bzp=[0], act="none",
+                       out_shape=(1, int(classes)), out_q=f_out))
+    if softmax:
+        layers.append(dict(op="softmax", out_shape=(1, int(classes)), out_q=(1.0 / 256.0, lo)))
+    return build_model((1, H, W, 1), in_q, layers, elem)
+
+
 def mlp(rng, sizes, elem=INT8, wzp_nonzero=False, softmax=False, act="relu", sparse24=()):
     """A FullyConnected-only network: sizes = (K, N1, N2, ...) gives the layers K -> N1 -> N2 ...; every hidden layer has
     the activation `act`, the last one none, optionally followed by a Softmax.  Per-tensor weight quantization (what
