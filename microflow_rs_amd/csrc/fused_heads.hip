@@ -1,0 +1,245 @@
+// fused_heads.hip -- the groups at a network's classifier end: pool + head + Softmax, FullyConnected (+ Softmax) runs, a global pool
+// or a one-input-channel convolution in front of them.  Host code only; the kernels are in k_*.hip.
+#include "fused_impl.hpp"
+
+namespace mf {
+
+FusedImpl *fused_tail_create(OpImpl *pool, OpImpl *conv, OpImpl *sm) {
+    if (!pool || !conv || !sm) return nullptr;
+    const OpSpec &p = pool->s, &c = conv->s, &m = sm->s;
+    if (p.u8 != c.u8 || c.u8 != m.u8) return nullptr;
+    if (!conv->finite_consts || !std::isfinite(p.pool_c0) || !std::isfinite(p.pool_c1)) return nullptr;
+    if (p.kind != MF_OP_AVERAGE_POOL_2D || c.kind != MF_OP_CONV_2D || m.kind != MF_OP_SOFTMAX) return nullptr;
+    if (p.OH != 1 || p.OW != 1) return nullptr;                       // one pooling window
+    if (c.KH != 1 || c.KW != 1 || c.H != 1 || c.W != 1 || c.OH != 1 || c.OW != 1 || c.C != p.C) return nullptr;
+    if (m.M != 1 || m.N != c.N) return nullptr;                       // softmax over the head's N values
+    // the in-range taps of the single window
+    int shy, shx;
+    pool_window_shift(p, shy, shx);
+    std::vector<int> taps;
+    for (int ky = 0; ky < p.KH; ++ky)
+        for (int kx = 0; kx < p.KW; ++kx) {
+            const int iy = ky - shy, ix = kx - shx;
+            if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) taps.push_back((iy * p.W + ix) * p.C);
+        }
+    if (!k::tail_supported(p.C, c.N, (int)taps.size())) return nullptr;
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::TAIL, pool, conv, sm, "tail_pool_head_softmax<" + std::to_string(c.N) + ">");
+    k::TailArgs &t = f->tail;
+    t.H = p.H, t.W = p.W, t.C = p.C, t.N = c.N;
+    t.ntaps = (int)taps.size();
+    for (int i = 0; i < t.ntaps; ++i) t.tap_off[i] = taps[(size_t)i];
+    volatile float inv = 1.0f / (float)t.ntaps; // 1. / view.len as f32 (average_pool_2d.rs:52)
+    t.inv_len = inv;
+    t.pool_c0 = pool->pool.c0, t.pool_c1 = pool->pool.c1, t.pool_lo = pool->pool.lo, t.pool_hi = pool->pool.hi;
+    t.w = conv->conv.w, t.wzp = conv->conv.wzp, t.A = conv->conv.A, t.S = conv->conv.S, t.Kc = conv->conv.Kc;
+    t.lo_f = conv->conv.lo_f, t.hi_f = conv->conv.hi_f;
+    t.exp_table = sm->sm.exp_table, t.sm_oscale = sm->sm.oscale, t.sm_ozp_f = sm->sm.ozp_f;
+    t.pool_bias = pool->pool.bias, t.pool_sat_lo = pool->pool.sat_lo, t.pool_sat_hi = pool->pool.sat_hi;
+    t.sm_sat_lo = sm->sm.sat_lo, t.sm_sat_hi = sm->sm.sat_hi, t.xr = pool->pool.xr;
+    return f.release();
+}
+
+// FullyConnected (one row per inference, the few-outputs row-wave kernel) -> [Reshape] -> Softmax
+// over exactly those outputs
+FusedImpl *fused_fc_softmax_create(OpImpl *fc, OpImpl *sm) {
+    if (!fc || fc->fast != OpImpl::FC_ROWWAVE || fc->s.M != 1 || fc->s.N < 2 || !softmax_over_row(sm, fc->s.N, fc->s.u8, fc->device)) return nullptr;
+    return make_group(FusedImpl::FCSM, fc, sm, nullptr, "fc_rowwave_softmax<" + std::to_string(fc->s.N) + ">").release();
+}
+
+// Consecutive FullyConnected operators (each reading the previous one's [M][N] output) + optionally a Softmax over one row, as
+// one fc_chain launch; nullptr when a member has no fc_rt image or the layers' images and tiles do not fit the LDS budget
+static bool fc_chain_args(OpImpl *const *fcs, int n, OpImpl *sm, k::FcChainArgs &a) {
+    if (switches().no_fc_chain || n < 2 || n > k::FC_CHAIN_MAX || !fcs[0]) return false;
+    // any M, the first layer's (a [M][N] activation matrix per inference)
+    if (!fc_layers_fill(fcs, n, a, fcs[0]->s.M, fcs[0]->s.u8, fcs[0]->device)) return false;
+    for (int l = 0; l < n; ++l)
+        if (fcs[l]->fast == OpImpl::FC_ROWWAVE) return false; // (a few-outputs layer keeps its row-wave kernel, or the FCSM group)
+    if (sm) {
+        if (fcs[0]->s.M != 1 || !softmax_over_row(sm, fcs[n - 1]->s.N, fcs[0]->s.u8, fcs[0]->device)) return false;
+        a.softmax = 1, a.sm = sm->sm;
+    }
+    return k::fc_chain_plan(a);
+}
+bool fused_fc_chain_fits(OpImpl *const *fcs, int n, OpImpl *sm) {
+    k::FcChainArgs a;
+    return fc_chain_args(fcs, n, sm, a);
+}
+FusedImpl *fused_fc_chain_create(OpImpl *const *fcs, int n, OpImpl *sm) {
+    k::FcChainArgs a;
+    if (!fc_chain_args(fcs, n, sm, a)) return nullptr;
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::FCCHAIN, fcs[0], fcs[n - 1], sm, "fc_chain<" + std::to_string(n) + (sm ? ">+sm" : ">"));
+    f->fcchain.args = a, f->fcchain.M = fcs[0]->s.M, f->epi_mode = a.magic;
+    return f.release();
+}
+
+// AveragePool2D over the whole image (one output pixel whose in-range taps are every pixel) -> [Reshape] -> FullyConnected layers
+// with one row per inference, the first reading the C pooled values -> [Softmax over the last layer's outputs], as one pool_fc_chain
+// launch; false when the pool is not the global one, C % 16 != 0, a constant is not finite, a layer has no fc_rt image, or the images
+// and tiles do not fit the LDS budget (k::pool_fc_plan)
+static bool pool_fc_args(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm, k::PoolFcArgs &a) {
+    if (switches().no_pool_fc || !pool || n < 1 || n > k::FC_CHAIN_MAX) return false;
+    const OpSpec &p = pool->s;
+    if (p.kind != MF_OP_AVERAGE_POOL_2D || p.OH != 1 || p.OW != 1 || p.C % 16 != 0) return false;
+    if (!std::isfinite(p.pool_c0) || !std::isfinite(p.pool_c1)) return false;
+    // the in-range taps of the single window must be the whole image
+    int shy, shx;
+    pool_window_shift(p, shy, shx);
+    if (p.KH - 1 - shy < p.H - 1 || p.KW - 1 - shx < p.W - 1) return false;
+    a = k::PoolFcArgs{};
+    k::FcChainArgs &c = a.c;
+    // one row per inference (the pooled pixel), the pool's element type and device
+    if (!fc_layers_fill(fcs, n, c, 1, p.u8, pool->device) || fcs[0]->s.K != p.C) return false;
+    if (sm) {
+        if (!softmax_over_row(sm, fcs[n - 1]->s.N, p.u8, pool->device)) return false;
+        c.softmax = 1, c.sm = sm->sm;
+    }
+    a.P = p.H * p.W, a.C = p.C;
+    a.c0 = pool->pool.c0, a.c1 = pool->pool.c1, a.lo = pool->pool.lo, a.hi = pool->pool.hi, a.bias = pool->pool.bias;
+    a.sat_lo = pool->pool.sat_lo, a.sat_hi = pool->pool.sat_hi;
+    if (pool->pool.xr != c.xr) return false;
+    return k::pool_fc_plan(a);
+}
+bool fused_pool_fc_fits(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm) {
+    k::PoolFcArgs a;
+    return pool_fc_args(pool, fcs, n, sm, a);
+}
+FusedImpl *fused_pool_fc_create(OpImpl *pool, OpImpl *const *fcs, int n, OpImpl *sm) {
+    k::PoolFcArgs a;
+    if (!pool_fc_args(pool, fcs, n, sm, a)) return nullptr;
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::POOLFC, pool, fcs[n - 1], sm, "pool_fc_chain<" + std::to_string(n) + (sm ? ">+sm" : ">"));
+    f->poolfc = a, f->epi_mode = a.c.magic;
+    return f.release();
+}
+
+// A DepthwiseConv2D or Conv2D with one input channel -> [Reshape] -> FullyConnected (one row per inference, reading the flattened
+// output) -> [Softmax over its outputs], as one conv1_fc_rt launch (k_conv1_fc.hip); false for what k::conv1_fc_plan refuses (filter
+// zero points, non-finite constants, the geometry limits, dwc1_fc_softmax's own geometry, the LDS budget).  The FullyConnected's fc_rt
+// image and padded constants are the operator's where it has them; where the operator alone is past fc_rt's own budget (8000 -> 12
+// runs fc_generic) the group builds them from the host copies
+static bool conv1_fc_args(OpImpl *cv, OpImpl *fc, OpImpl *sm, k::Conv1FcArgs &a) {
+    if (switches().no_conv1_fc || !cv || !fc || cv->force_generic || fc->force_generic) return false;
+    const OpSpec &d = cv->s, &q = fc->s;
+    if ((d.kind != MF_OP_DEPTHWISE_CONV_2D && d.kind != MF_OP_CONV_2D) || d.C != 1 || q.kind != MF_OP_FULLY_CONNECTED) return false;
+    if (q.M != 1 || q.u8 != d.u8 || fc->device != cv->device || cv->h_w.empty() || fc->h_w.empty()) return false;
+    const k::FcArgs &g = fc->fc;
+    if ((int)fc->h_A.size() != g.N || (int)fc->h_Kc.size() != g.N || !std::isfinite(g.S) ||
+        !std::all_of(fc->h_A.begin(), fc->h_A.end(), [](float v) { return std::isfinite(v); }))
+        return false;
+    a = k::Conv1FcArgs{};
+    a.H = d.H, a.W = d.W, a.N = d.N, a.KH = d.KH, a.KW = d.KW, a.sh = d.sh, a.sw = d.sw, a.OH = d.OH, a.OW = d.OW;
+    a.pad_same = d.pad == MF_PAD_SAME;
+    a.wz = std::any_of(cv->h_wzp.begin(), cv->h_wzp.end(), [](int32_t z) { return z != 0; }), a.finite = cv->finite_consts;
+    k::FcChainLayer &y = a.fc;
+    y.S = g.S, y.lo_f = g.lo_f, y.hi_f = g.hi_f, y.K = g.K, y.N = g.N, y.wzp = g.wzp;
+    if (fc->fcrt_ok) y.wimg = fc->fcrt.wimg, y.A = fc->fcrt.A, y.Kc = fc->fcrt.Kc; // (else: fused_conv1_fc_create builds them)
+    if (sm) {
+        if (!softmax_over_row(sm, q.N, d.u8, cv->device)) return false;
+        a.softmax = 1, a.sm = sm->sm;
+    }
+    a.A = cv->conv.A, a.S = cv->conv.S, a.Kc = cv->conv.Kc, a.lo_f = cv->conv.lo_f, a.hi_f = cv->conv.hi_f;
+    a.izp4 = 0x01010101u * (uint32_t)(uint8_t)(int8_t)d.izp;
+    a.magic = std::min(cv->magic_mode, 2), a.xr = g.xr; // (the convolution's mode; the FullyConnected's few bytes take mode 0)
+    if (cv->conv.xr != g.xr) return false;
+    return k::conv1_fc_plan(a);
+}
+bool fused_conv1_fc_fits(OpImpl *conv, OpImpl *fc, OpImpl *sm) {
+    k::Conv1FcArgs a;
+    return conv1_fc_args(conv, fc, sm, a);
+}
+FusedImpl *fused_conv1_fc_create(OpImpl *conv, OpImpl *fc, OpImpl *sm) {
+    k::Conv1FcArgs a;
+    if (!conv1_fc_args(conv, fc, sm, a)) return nullptr;
+    const OpSpec &d = conv->s;
+    const bool dw = d.kind == MF_OP_DEPTHWISE_CONV_2D;
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::CONV1FC, conv, fc, sm,
+                                              std::string("conv1_fc_rt<") + (dw ? "dw," : "conv,") + std::to_string(d.KH) + "x" + std::to_string(d.KW) + "," +
+                                                  std::to_string(d.N) + (sm ? ">+sm" : ">"));
+    // the taps as uploaded (i8 domain): depthwise [KH][KW][N], Conv2D [N][KH][KW][1]
+    auto w = [&](int ky, int kx, int c) { return dw ? conv->h_w[((size_t)ky * d.KW + kx) * d.N + c] : conv->h_w[((size_t)c * d.KH + ky) * d.KW + kx]; };
+    // operand A: row R = 16 rt + r is (pixel R / N, channel R % N) where a tile holds PP pixels, channel R otherwise; lane group g of k
+    // step ks holds filter row 4 ks + g at bytes pixel * sw .. + KW - 1
+    std::vector<int8_t> wa((size_t)2 * 4 * 64 * 16, 0);
+    for (int rt = 0; rt < a.NRT; ++rt)
+        for (int ks = 0; ks < a.KSC; ++ks)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int R = rt * 16 + (lane & 15), ky = 4 * ks + (lane >> 4);
+                const int px = a.PP > 1 ? R / d.N : 0, c = R - px * d.N;
+                if (px >= a.PP || c >= d.N || ky >= d.KH) continue;
+                for (int kx = 0; kx < d.KW; ++kx) wa[(((size_t)rt * 4 + ks) * 64 + lane) * 16 + (size_t)(px * d.sw + kx)] = w(ky, kx, c);
+            }
+    a.wA = keep(*f, wa.data(), wa.size());
+    if (!fc->fcrt_ok) {
+        const std::vector<int8_t> img = k::fc_rt_weight_image(fc->h_w.data(), a.fc.K, a.fc.N);
+        std::vector<float> pA((size_t)a.fc.NT * 16, 0.0f);
+        std::vector<int32_t> pK((size_t)a.fc.NT * 16, 0);
+        std::copy(fc->h_A.begin(), fc->h_A.end(), pA.begin()), std::copy(fc->h_Kc.begin(), fc->h_Kc.end(), pK.begin());
+        a.fc.wimg = keep(*f, img.data(), img.size());
+        a.fc.A = (const float *)keep(*f, pA.data(), pA.size() * 4), a.fc.Kc = (const int *)keep(*f, pK.data(), pK.size() * 4);
+    }
+    f->conv1fc.args = a, f->epi_mode = a.magic;
+    // The routing rule of DESIGN 4.2d, by measurement (profiles/r10/time_conv1_fc.txt): where the FullyConnected has its own fc_rt launch,
+    // conv1_fc_rt beat the three launches at batch 4096 (one step per workgroup: 1.13 - 1.55x) and lost at 65 536 (0.82 - 1.01x), so such
+    // a group takes batches up to 4096 only; where the FullyConnected alone runs fc_generic it won at both (2.3 - 3.1x) and takes any
+    f->conv1fc.max_batch = fc->fcrt_ok ? 4096 : 0;
+    return f.release();
+}
+
+// DepthwiseConv2D with one input channel (the dw_c1_lds operator) -> [Reshape] -> FullyConnected + Softmax group, as
+// one kernel (k_dwfc.hip; speech.tflite ops 1..3).  Second level like the stage: the operator and the group inside
+// stay available for mf_model_run_until.  nullptr when the shapes are not the compiled instance.
+FusedImpl *fused_dwfc_create(OpImpl *dw, FusedImpl *fcsm) {
+    const bool off = switches().no_dwfc;
+    if (off || !dw || !fcsm || dw->fast != OpImpl::DW_C1 || fcsm->kind != FusedImpl::FCSM) return nullptr;
+    OpImpl *fc = fcsm->a, *sm = fcsm->b;
+    const OpSpec &d = dw->s, &q = fc->s;
+    using Gm = k::DwFcGeom;
+    if (!k::dwfc_supported(d.H, d.W, d.KH, d.KW, d.sh, d.sw, d.OH, d.OW, d.N, q.N)) return nullptr;
+    if (d.pad != MF_PAD_SAME || d.C != 1 || q.M != 1 || q.K != d.OH * d.OW * d.N || dw->device != fc->device) return nullptr;
+    if (d.u8 != q.u8) return nullptr;
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::DWFC, dw, fc, sm, k::dwfc_name());
+    // both operators' weights as they were uploaded (i8 domain): the depthwise taps from dw_c1_lds's packed form
+    // [ky][4-tap group][8 channels] dwords, the FullyConnected matrix [N][K]
+    const k::DwC1Args &c1 = dw->dwc1;
+    const std::vector<uint32_t> &wp = dw->h_wpack;
+    auto dw_w = [&](int ky, int kx, int c) { return (int8_t)(wp[((size_t)ky * c1.KG + kx / 4) * 8 + c] >> (8 * (kx & 3))); };
+    const std::vector<int8_t> &fc_w = fc->h_w;
+    // operand A: taps of filter row ky = (4k + g) - 2p at byte b = kx + 2s + E0 of the 16-byte window, for row
+    // r = (p, c) of the accumulator tile; zero elsewhere
+    std::vector<int8_t> wa((size_t)4 * 3 * 64 * 16, 0);
+    for (int sft = 0; sft < 4; ++sft)
+        for (int kk = 0; kk < 3; ++kk)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int r = lane & 15, g = lane >> 4, p = r >> 3, c = r & 7;
+                const int ky = 4 * kk + g - Gm::S * p;
+                if (ky < 0 || ky >= Gm::KH) continue;
+                for (int kx = 0; kx < Gm::KW; ++kx)
+                    wa[(((size_t)sft * 3 + kk) * 64 + lane) * 16 + (size_t)(kx + Gm::S * sft + Gm::E0)] =
+                        dw_w(ky, kx, c);
+            }
+    // FullyConnected as operand A of one more MFMA per unit (t, m): lane group g = (p, channel half) holds, for row
+    // n < 4, the weights of the 16 activations it packs -- pixels (2t + p, 4m + s), s = 0..3, channels 4 (g & 1) .. + 3
+    // of the NHWC flattening -- and for row 4 ones (the row sum); nothing for pixel rows beyond the image
+    std::vector<int8_t> wf((size_t)Gm::FCW_BYTES, 0);
+    for (int u = 0; u < Gm::NU; ++u)
+        for (int g = 0; g < 4; ++g) {
+            const int t = u / Gm::NM, m = u % Gm::NM, oy = 2 * t + (g >> 1);
+            if (oy >= Gm::OH) continue;
+            for (int sft = 0; sft < 4; ++sft) {
+                const size_t k0 = ((size_t)oy * Gm::OW + 4 * m + sft) * 8 + 4 * (size_t)(g & 1);
+                for (int b = 0; b < 4; ++b) {
+                    for (int n = 0; n < 4; ++n) wf[(((size_t)u * 4 + g) * 5 + n) * 16 + 4 * sft + b] = fc_w[(size_t)n * q.K + k0 + b];
+                    wf[(((size_t)u * 4 + g) * 5 + 4) * 16 + 4 * sft + b] = 1;
+                }
+            }
+        }
+    f->dwfc.wA = keep(*f, wa.data(), wa.size());
+    f->dwfc.wfc = keep(*f, wf.data(), wf.size());
+    f->dwfc.dwA = c1.A, f->dwfc.dwS = c1.S, f->dwfc.dwKc = c1.Kc, f->dwfc.dw_lo = c1.lo_f, f->dwfc.dw_hi = c1.hi_f;
+    f->dwfc.izp4 = 0x01010101u * (uint32_t)(uint8_t)(int8_t)c1.izp;
+    f->dwfc.magic = c1.magic, f->dwfc.xr = c1.xr;
+    f->epi_mode = c1.magic;
+    f->dwfc.fc = fc->fc, f->dwfc.sm = sm->sm;
+    return f.release();
+}
+
+} // namespace mf

@@ -6,9 +6,11 @@
 //   tflite.cpp    minimal FlatBuffers reader for the ~10 TFLite tables the path needs
 //   hostmath.cpp  f32 constant preparation in the reference's evaluation order
 //   ops.hip       prepared operators: constant folding, kernel routing (one function per route), launches
-//   fused.hip     fused groups of prepared operators as one launch; the chain planner / autotuner
+//   fused.hip     fused groups of prepared operators as one launch: destroy / name / mode, f32 edges, the launch path
+//   fused_pairs.hip, fused_heads.hip, fused_stages.hip   the groups' builders, by family (fused_impl.hpp: the group, shared helpers)
+//   chain_partition.hip   the chain planner / autotuner
 //   wimage.cpp    every operand layout the host builds for the kernels (host only: tests/test_wimage_host.py)
-//   ops_impl.hpp  what ops.hip and fused.hip share (OpImpl, DevBuf)
+//   ops_impl.hpp  what ops.hip and the fused units share (OpImpl, DevBuf)
 //   k_*.hip       the HIP kernels (gfx950), one file per family; k_common.hpp shared helpers
 #pragma once
 #include "mf_switches.hpp"
@@ -233,7 +235,7 @@ void model_set_stream(ModelImpl *m, void *stream);
 void model_sync(ModelImpl *m);
 void model_set_generic(ModelImpl *m, bool generic);
 void model_set_fusion(ModelImpl *m, bool enabled);
-// before model_prepare: measure the run-time-geometry chain candidates at creation (fused.hip fused_chain_partition) instead of planning from the cost model
+// before model_prepare: measure the run-time-geometry chain candidates at creation (chain_partition.hip fused_chain_partition) instead of planning from the cost model
 void model_set_autotune(ModelImpl *m, bool enabled);
 // replay the device-resident launch sequence as a hipGraph (captured on the 2nd identical call)
 void model_set_graph(ModelImpl *m, bool enabled);

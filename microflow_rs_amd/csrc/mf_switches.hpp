@@ -21,7 +21,7 @@ struct ChainPlanSeg {
     int dbuf;  // double buffering of the input tile, a single pair's choice only (-1: the planner's rule, 0 off, 1 on)
 };
 // "len:G:dbuf,len:G:dbuf,..." -> segments; false (and why in `err`) for anything else.  Only the form is checked here: whether a
-// segment can be realised on a given run of pairs is decided where the plan is applied (fused.hip: fused_chain_partition).
+// segment can be realised on a given run of pairs is decided where the plan is applied (chain_partition.hip: fused_chain_partition).
 bool chain_plan_parse(const char *text, std::vector<ChainPlanSeg> &out, std::string &err);
 
 struct Switches {

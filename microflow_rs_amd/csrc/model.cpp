@@ -265,7 +265,7 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             return false;
         };
         // (4) runs of consecutive pair groups on one tensor shape -> a persistent stage kernel, if one exists for that
-        // shape and count (fused.hip: fused_stage_create)
+        // shape and count (fused_stages.hip: fused_stage_create)
         for (size_t i = 0; i + 1 < n; ++i) {
             if (!fused[i] || fused_last[i] != (int)i + 1) continue;
             std::vector<FusedImpl *> run;
@@ -301,7 +301,7 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
                 i += 3;
             }
         }
-        // (4b') the last pair group directly followed by the tail group -> one kernel (fused.hip: fused_pair_tail_create).  Before the
+        // (4b') the last pair group directly followed by the tail group -> one kernel (fused_stages.hip: fused_pair_tail_create).  Before the
         // chain partition below, so that a run-time-geometry pair taken here is not also a candidate there
         for (size_t i = 0; i + 2 < n; ++i) {
             if (!fused[i] || fused_last[i] != (int)i + 1 || covered(i)) continue;
@@ -316,7 +316,7 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
                 }
         }
         // (4c) runs of consecutive run-time-geometry pairs (single-pair chain groups, k_chain.hip): the planner's cost model
-        // decides how the run is cut into chain launches (fused.hip: fused_chain_partition); a pair that is cheapest as two
+        // decides how the run is cut into chain launches (chain_partition.hip: fused_chain_partition); a pair that is cheapest as two
         // separate launches loses its group
         bool chain_runs = false;
         for (size_t i = 0; i + 1 < n; ++i) {
@@ -371,7 +371,7 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             return j;
         };
         // (5a) a DepthwiseConv2D or Conv2D with one input channel -> [Reshape] -> FullyConnected (one row per inference) -> [Reshape] ->
-        // [Softmax] -> one conv1_fc_rt launch (fused.hip: fused_conv1_fc_create) at any geometry its plan accepts; speech.tflite's own
+        // [Softmax] -> one conv1_fc_rt launch (fused_heads.hip: fused_conv1_fc_create) at any geometry its plan accepts; speech.tflite's own
         // geometry is refused there and keeps (5).  Where the FullyConnected + Softmax already are a group of (3), this stage sits over
         // conv .. softmax and that group stays for mf_model_run_until pieces.  One FullyConnected only: a run behind it is left to (6)
         for (size_t i = 0; i + 1 < n; ++i) {
@@ -390,7 +390,7 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             if (FusedImpl *f = fused_conv1_fc_create(ops[i], ops[j0], sm)) sg.v.push_back({f, (int)i, (int)(sm ? smi : j0)});
         }
         // (5b) AveragePool2D over the whole image -> [Reshape] -> FullyConnected layers (one row per inference) -> [Softmax] -> one
-        // pool_fc_chain launch (fused.hip: fused_pool_fc_create), the longest run of layers whose images fit.  Before (6), so that the
+        // pool_fc_chain launch (fused_heads.hip: fused_pool_fc_create), the longest run of layers whose images fit.  Before (6), so that the
         // FullyConnected run behind a pool is offered here first; what does not fit stays for (6) or keeps its own launches.  Where the
         // head's FullyConnected + Softmax already are a group of (3), this stage sits over pool .. softmax and that group stays for
         // mf_model_run_until pieces

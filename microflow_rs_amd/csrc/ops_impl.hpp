@@ -1,5 +1,5 @@
-// ops_impl.hpp -- what the operator unit (ops.hip) and the fused-group unit (fused.hip) share: the prepared operator
-// itself, its device buffers, the wrapping integer arithmetic of the folded constants.  Internal to those two units.
+// ops_impl.hpp -- what the operator unit (ops.hip) and the fused-group units (fused*.hip, chain_partition.hip) share: the prepared operator
+// itself, its device buffers, the wrapping integer arithmetic of the folded constants.  Internal to those units.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -105,7 +105,7 @@ struct OpImpl {
 
     DevBuf d_w, d_wzp, d_A, d_S, d_Kc, d_wprep, d_wsp, d_wblk, d_wrr, d_wiso, d_table;
     // host copies of d_w (i8 domain, as uploaded), d_A, d_S, d_Kc, d_wzp and of dw_c1_lds's packed taps: the fused groups
-    // (fused.hip) build their own operand images from them.  Kept for the operator's lifetime.
+    // (fused_*.hip) build their own operand images from them.  Kept for the operator's lifetime.
     std::vector<int8_t> h_w;
     std::vector<float> h_A, h_S;
     std::vector<int32_t> h_Kc, h_wzp;

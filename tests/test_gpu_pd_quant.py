@@ -115,7 +115,7 @@ def test_routing_and_epilogue_modes(case, O, name):
     assert k[0].startswith("penta_rr") and k[5].startswith("quad_rr") and k[9].startswith("quad_mm"), k
     assert k[L["pair_front_tail"][0]].startswith("pair_front_tail"), k
     if P.MODELS[name][0] == "varied":
-        assert not [n for n in k if n.startswith("stage")], k   # fused.hip fused_stage_create: the izp4 refusal
+        assert not [n for n in k if n.startswith("stage")], k   # fused_stages.hip fused_stage_create: the izp4 refusal
     else:
         assert k[13] == "stage_6x6x128<4,512,%d>" % c.nst, k
     lo, hi = P.limits(c.elem)
