@@ -1,5 +1,9 @@
-// k_conv_rows_body.inc -- the statements of conv_rows_lds<WZ, MG, XR4> and conv_rows_lds_f32<WZ, MG, XR4> (k_rt.hip), included between
-// their braces.  Expects in, out, p (ConvRowsArgs), batch, eg (F32Edge) and the constants WZ, MG, XR4, F32IN in scope.
+// k_conv_rows_body.inc -- the statements of conv_rows_lds<WZ, MG, XR4>, conv_rows_lds_f32<WZ, MG, XR4> and conv_rows_bytes<WZ, MG, XR4>
+// (k_rt.hip), included between their braces.  Expects in, out, p (ConvRowsArgs), batch, eg (F32Edge) and the constants WZ, MG, XR4,
+// F32IN, BYTES in scope.  BYTES: rows that are not whole dwords -- the staging map is conv_rows_bytes_map.hpp's, one packed register
+// per element (el[]), and an element is fetched as the two aligned dwords that hold its bytes (v[], vhi[]): both stay in registers
+// across the compute loop and meet (v_alignbyte, then the input zero point over the bytes past the row) at the tile write, so that
+// the wait for the loads stays where conv_rows_lds has it.  Everything from the second barrier on is the same text for all three.
     constexpr int NTHR = 512, MAXE = 16;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int tid = threadIdx.x;
@@ -20,6 +24,12 @@
     // staging map (the same for every step): dword e of this thread is image g, row y, dword x of the step
     const int ROWD = p.ROWB >> 2, IMGD = p.H * ROWD, STEPD = G * IMGD;
     int gofs[MAXE], lofs[MAXE];
+    uint32_t el[BYTES ? MAXE : 1], vhi[BYTES ? MAXE : 1];
+    const int IMGB = p.H * p.ROWB;                       // (BYTES) bytes of an image
+    if constexpr (BYTES) {
+#pragma unroll
+        for (int e = 0; e < MAXE; ++e) el[e] = rows_bytes_elem(p, tid + NTHR * e);
+    } else {
 #pragma unroll
     for (int e = 0; e < MAXE; ++e) {
         const int idx = tid + NTHR * e;
@@ -27,9 +37,33 @@
         gofs[e] = idx < STEPD ? idx : -1;
         lofs[e] = g * TILE + (y + p.shy) * TWP + p.XO + 4 * x;
     }
+    }
     const int nsteps = (batch + G - 1) / G;
     uint32_t v[MAXE];
     auto fetch = [&](int st) {
+        if constexpr (BYTES) {
+            const size_t sb = (size_t)st * G * IMGB;     // the step's first byte: src is the aligned dword that holds it
+            const uint32_t *src = (const uint32_t *)in + (sb >> 2);
+            const uint32_t low2 = (uint32_t)sb & 3u;
+            const int lim = min(G, batch - st * G) * IMGB; // bytes of the step that exist (a ragged last step)
+#pragma unroll
+            for (int e = 0; e < MAXE; ++e) {
+                // (indices selected, not addresses, as below; src[0] holds the step's first byte, so it is never wholly outside the
+                // batch.  The loaded dwords are not touched here -- which of them count is decided again at the tile write: a select on
+                // them in this place was a wait for the loads ahead of the compute loop)
+                const RowsBytesSrc m = rows_bytes_src(el[e], low2, p.ROWB);
+                const bool ok = el[e] != ROWS_BYTES_NONE && rows_bytes_first(el[e]) < lim;
+                v[e] = src[ok ? m.d0 : 0];
+            }
+#pragma unroll
+            for (int e = 0; e < MAXE; ++e) {       // (the second dwords behind all the first ones: sixteen loads in a row, twice)
+                const RowsBytesSrc m = rows_bytes_src(el[e], low2, p.ROWB);
+                const bool ok = el[e] != ROWS_BYTES_NONE && rows_bytes_first(el[e]) < lim;
+                vhi[e] = src[ok && m.two ? m.d0 + 1 : 0];
+                if (el[e] != ROWS_BYTES_NONE) el[e] = rows_bytes_keep(el[e], m.shift);
+            }
+            return;
+        }
         const uint32_t *src = (const uint32_t *)in + (size_t)st * STEPD;
         const long lim = ((long)batch - (long)st * G) * IMGD; // dwords of the step that exist (a ragged last step)
 #pragma unroll
@@ -63,6 +97,14 @@
                     const uint32_t q = pack4(edge_quant(f[e].x, eg), edge_quant(f[e].y, eg), edge_quant(f[e].z, eg), edge_quant(f[e].w, eg)) ^ eg.in_xr4;
                     if (gofs[h + e] >= 0) *(uint32_t *)(lds + lofs[h + e]) = gofs[h + e] < lim ? q : p.izp4;
                 }
+            }
+        } else if constexpr (BYTES) {
+            const int lim = min(G, batch - step * G) * IMGB;
+#pragma unroll
+            for (int e = 0; e < MAXE; ++e) {
+                // (vhi[e] may be a dword that was not wanted: its bytes then land past the real ones and rows_bytes_merge drops them)
+                const uint32_t got = rows_bytes_merge(__builtin_amdgcn_alignbyte(vhi[e], v[e], rows_bytes_kept(el[e])), rows_bytes_real(el[e], p.ROWB), p.izp4);
+                if (el[e] != ROWS_BYTES_NONE) *(uint32_t *)(lds + rows_bytes_tile(el[e])) = rows_bytes_first(el[e]) < lim ? got : p.izp4;
             }
         } else {
 #pragma unroll

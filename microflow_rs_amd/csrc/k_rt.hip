@@ -10,6 +10,7 @@
 // convolution live in LDS instead of registers.  Arithmetic contract and helpers: k_common.hpp.
 #include "k_common.hpp"
 #include "k_fc_layer.hpp"
+#include "conv_rows_bytes_map.hpp"
 
 #include <algorithm>
 #include <map>
@@ -389,14 +390,26 @@ __global__ __launch_bounds__(256) void pw_rt(const int8_t *__restrict__ in, int8
 // and the int8 instances are compiled exactly as when they were written out here.
 template <bool WZ, int MG, uint32_t XR4>
 __global__ __launch_bounds__(512) void conv_rows_lds(const int8_t *__restrict__ in, int8_t *__restrict__ out, ConvRowsArgs p, int batch) {
-    constexpr bool F32IN = false;
+    constexpr bool F32IN = false, BYTES = false;
     constexpr F32Edge eg{};
 #include "k_conv_rows_body.inc"
 }
 template <bool WZ, int MG, uint32_t XR4>
 __global__ __launch_bounds__(512) void conv_rows_lds_f32(const int8_t *__restrict__ in, int8_t *__restrict__ out, ConvRowsArgs p, F32Edge eg, int batch) {
     static_assert(MG <= 2, "the boundary quantisation needs round-to-nearest: no single-fma epilogue here");
-    constexpr bool F32IN = true;
+    constexpr bool F32IN = true, BYTES = false;
+#include "k_conv_rows_body.inc"
+}
+// conv_rows_bytes: conv_rows_lds for image rows that are NOT whole dwords (ROWB % 4 != 0; routed for one input channel: audio features
+// of 10, 13, 43 ... coefficients per frame).  Tile, weights, constants, compute loop, epilogue and stores are conv_rows_lds's; only the
+// staging differs (conv_rows_bytes_map.hpp, k_conv_rows_body.inc BYTES).  `in` is 16-byte aligned, as for every fast kernel behind
+// mf_op_run (an unaligned pointer takes the shape-generic kernels there), so the aligned dwords of the batch are in's dwords; loads
+// are aligned dwords that hold at least one byte of the batch -- up to three bytes past batch x H x ROWB are READ where that is no
+// multiple of four (the same allocation granule), none is used.  No f32 entry.
+template <bool WZ, int MG, uint32_t XR4>
+__global__ __launch_bounds__(512) void conv_rows_bytes(const int8_t *__restrict__ in, int8_t *__restrict__ out, ConvRowsArgs p, int batch) {
+    constexpr bool F32IN = false, BYTES = true;
+    constexpr F32Edge eg{};
 #include "k_conv_rows_body.inc"
 }
 
@@ -986,7 +999,10 @@ int conv_rows_lds_bytes(const ConvRowsArgs &a) {
 // fills the geometry of a; false: the shape is not for this kernel
 bool conv_rows_plan(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same) {
     const int RWB = KW * C;
-    if (RWB > 64 || KH > 16 || N < 1 || N > 64 || (W * C) % 4 != 0 || C >= 16) return false; // (16 and more channels: conv_mm_rt)
+    // rows that are not whole dwords: conv_rows_bytes, routed for one input channel only (the kernel is written in row bytes; C >= 2
+    // with such rows stays on the generic kernels)
+    const bool bytes = (W * C) % 4 != 0;
+    if (RWB > 64 || KH > 16 || N < 1 || N > 64 || (bytes && (C != 1 || switches().no_conv_rows_bytes)) || C >= 16) return false; // (16 and more channels: conv_mm_rt)
     a.H = H, a.W = W, a.C = C, a.N = N, a.KH = KH, a.KW = KW, a.sh = sh, a.sw = sw, a.OH = OH, a.OW = OW;
     a.ROWB = W * C, a.KG = (RWB + 3) / 4, a.NP = (N + 7) & ~7;
     const int padl = pad_same ? (KW - 1) / 2 : 0, padt = pad_same ? (KH - 1) / 2 : 0;
@@ -997,14 +1013,14 @@ bool conv_rows_plan(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW,
     a.TWP = (std::max(need, a.XO + W * C) + 3 + 4) & ~3;
     const int TH = std::max((OH - 1) * sh + KH, padt + H);
     a.TILE = (TH * a.TWP + 4 + 15) & ~15;
-    const int img_dwords = H * (W * C / 4);
+    const int img_dwords = H * ((W * C + 3) / 4);
     int g = std::min(8, (512 * 16) / std::max(img_dwords, 1));   // 16 prefetched dwords per thread
     while (g > 1 && g * a.TILE > 64 * 1024) --g;
     if (g < 1 || a.TILE > 64 * 1024) return false;
     a.G = g;
     return conv_rows_lds_bytes(a) <= 96 * 1024;
 }
-template <bool WZ, int MG, uint32_t XR4, bool F32IN>
+template <bool WZ, int MG, uint32_t XR4, bool F32IN, bool BYTES = false>
 static void launch_conv_rows_t(const int8_t *in, int8_t *out, const ConvRowsArgs &a, int batch, hipStream_t s, const F32Edge *eg) {
     const int lds = conv_rows_lds_bytes(a);
     int per_cu = 1;
@@ -1016,7 +1032,8 @@ static void launch_conv_rows_t(const int8_t *in, int8_t *out, const ConvRowsArgs
         std::lock_guard<std::mutex> lock(mu);
         auto it = cache.find({dev, lds});
         if (it == cache.end()) {
-            const void *fn = F32IN ? (const void *)conv_rows_lds_f32<WZ, MG, XR4> : (const void *)conv_rows_lds<WZ, MG, XR4>;
+            const void *fn = BYTES ? (const void *)conv_rows_bytes<WZ, MG, XR4>
+                                   : (F32IN ? (const void *)conv_rows_lds_f32<WZ, MG, XR4> : (const void *)conv_rows_lds<WZ, MG, XR4>);
             (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
             int n = 1;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 512, (size_t)lds) != hipSuccess || n < 1) {
@@ -1029,7 +1046,8 @@ static void launch_conv_rows_t(const int8_t *in, int8_t *out, const ConvRowsArgs
     }
     const int nsteps = (batch + a.G - 1) / a.G;
     const int grid = nsteps < 256 * per_cu ? nsteps : 256 * per_cu;
-    if constexpr (F32IN) MF_LAUNCH((conv_rows_lds_f32<WZ, MG, XR4>), dim3(grid), dim3(512), lds, s, in, out, a, *eg, batch);
+    if constexpr (BYTES) MF_LAUNCH((conv_rows_bytes<WZ, MG, XR4>), dim3(grid), dim3(512), lds, s, in, out, a, batch);
+    else if constexpr (F32IN) MF_LAUNCH((conv_rows_lds_f32<WZ, MG, XR4>), dim3(grid), dim3(512), lds, s, in, out, a, *eg, batch);
     else MF_LAUNCH((conv_rows_lds<WZ, MG, XR4>), dim3(grid), dim3(512), lds, s, in, out, a, batch);
 }
 bool dw_stem_rt_plan(DwStemRtArgs &a, int H, int W, int DM, int OH, int OW) {
@@ -1079,7 +1097,8 @@ void launch_dw_stem_rt(const int8_t *in, int8_t *out, const DwStemRtArgs &a, int
 }
 template <bool WZ, int MG, uint32_t XR4>
 static void launch_conv_rows_e(const int8_t *in, int8_t *out, const ConvRowsArgs &a, int batch, hipStream_t s, const F32Edge *eg) {
-    if (eg) launch_conv_rows_t<WZ, MG, XR4, true>(in, out, a, batch, s, eg);
+    if (a.BYTES()) launch_conv_rows_t<WZ, MG, XR4, false, true>(in, out, a, batch, s, nullptr); // (no f32 entry: op_set_input_quant declines)
+    else if (eg) launch_conv_rows_t<WZ, MG, XR4, true>(in, out, a, batch, s, eg);
     else launch_conv_rows_t<WZ, MG, XR4, false>(in, out, a, batch, s, nullptr);
 }
 void launch_conv_rows(const int8_t *in, int8_t *out, const ConvRowsArgs &a, bool wz, int batch, hipStream_t s, const F32Edge *eg) {

@@ -240,7 +240,7 @@ struct PwRtArgs {
 // Conv2D with few input channels / DepthwiseConv2D with one input channel, any filter (k_rt.hip: conv_rows_lds)
 struct ConvRowsArgs {
     int H, W, C, N, KH, KW, sh, sw, OH, OW;
-    int ROWB;            // W * C: image row bytes (a multiple of 4)
+    int ROWB;            // W * C: image row bytes (a multiple of 4, or BYTES())
     int KG, NP;          // dword groups per window row = ceil(KW C / 4); N rounded up to 8
     int shy, XO, X0;     // halo rows above the image; tile byte of image column 0 / of output column 0's window
     int TWP, TILE, G;    // tile row pitch, bytes per image tile, images per step
@@ -253,6 +253,11 @@ struct ConvRowsArgs {
     const int *Kc;
     const int *wzp;
     int magic, xr;
+    // Rows that are not whole dwords (one input channel only: conv_rows_plan): the launch is conv_rows_bytes, whose staging assembles
+    // every tile dword from two aligned source dwords (conv_rows_bytes_map.hpp); a tile row is ceil(ROWB / 4) dwords.  The flag is
+    // ROWB's low bits and not a field of its own: this struct is conv_rows_lds's kernel argument, and a field more would move `batch`
+    // behind it in the 24 existing instances.
+    bool BYTES() const { return (ROWB & 3) != 0; }
 };
 // DepthwiseConv2D 3x3 stride 2 SAME with ONE input channel and 4 or 8 outputs, any H x W with W % 16 == 0 (a MobileNet stem at any
 // resolution / width 0.5; k_rt.hip: dw3x3_stem_rt)
@@ -275,6 +280,7 @@ bool dw_stem_rt_plan(DwStemRtArgs &a, int H, int W, int DM, int OH, int OW);
 // (eg != nullptr: the f32 entry -- `in` points to batch x H W floats, 16-byte aligned, quantised with eg's in_* parameters while staged)
 void launch_dw_stem_rt(const int8_t *in, int8_t *out, const DwStemRtArgs &a, int batch, hipStream_t s, const F32Edge *eg = nullptr);
 int conv_rows_lds_bytes(const ConvRowsArgs &a);
+// (a.BYTES() after a plan that succeeded: launch_conv_rows launches conv_rows_bytes, which has no f32 entry -- eg must be null)
 bool conv_rows_plan(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same);
 void launch_conv_rows(const int8_t *in, int8_t *out, const ConvRowsArgs &a, bool wz, int batch, hipStream_t s, const F32Edge *eg = nullptr);
 // Conv2D with any filter, C % 16 == 0, as an MFMA product over K = KH KW C (k_rt.hip: conv_mm_rt)

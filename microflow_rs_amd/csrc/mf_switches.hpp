@@ -36,7 +36,8 @@ struct Switches {
     bool no_fc_sparse = false;     // MF_NO_FC_SPARSE     FullyConnected weights with 2:4 sparsity on fc_mfma, not fc_sparse24 (k_fc_sparse.hip)
     bool no_fc_chain = false;      // MF_NO_FC_CHAIN      consecutive FullyConnected layers one launch each, not one fc_chain launch
     bool no_conv1_fc = false;      // MF_NO_CONV1_FC      one-input-channel convolution + FullyConnected (+ Softmax) one launch per operator (and fc_rowwave_softmax), not one conv1_fc_rt launch (k_conv1_fc.hip)
-    bool no_pool_fc = false;       // MF_NO_POOL_FC      global AveragePool2D + FullyConnected (+ Softmax) heads one launch per operator, not one pool_fc_chain launch (k_pool_fc.hip)
+    bool no_conv_rows_bytes = false; // MF_NO_CONV_ROWS_BYTES  one-channel convolutions whose image rows are not whole dwords (W % 4 != 0) take the kernels they had before (conv2d_generic, dwconv_generic; dw_c1_lds for a depthwise with up to 8 outputs and no filter zero points), not conv_rows_bytes (k_rt.hip)
+    bool no_pool_fc = false;      // MF_NO_POOL_FC      global AveragePool2D + FullyConnected (+ Softmax) heads one launch per operator, not one pool_fc_chain launch (k_pool_fc.hip)
     bool no_pair_band = false;     // MF_NO_PAIR_BAND     pairs too large for chain_rt one launch per operator, not one pair_band_rt / pair_band_deep_rt launch (k_pair_band.hip, k_pair_band_deep.hip)
     bool no_pair_wz = false;       // MF_NO_PAIR_WZ       pairs with filter zero points one launch per operator (dw3x3_rt<S,wzp>, pw_rt<K,N,wzp>), not one pair_wz_rt launch (k_pair_wz.hip)
     bool no_conv_gemm = false;     // MF_NO_CONV_GEMM     Conv2D shapes outside the other Conv2D kernels take conv2d_generic, not conv_gemm_rt (k_conv_gemm.hip)

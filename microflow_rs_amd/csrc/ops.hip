@@ -461,7 +461,8 @@ bool route_pw_rt(OpImpl &op, const ConvCtx &c) {
 // 8. few input channels (a first convolution; a one-channel depthwise with more than 8 outputs): window rows as dwords.
 // The one route that may REPLACE an earlier one: a one-channel depthwise keeps dw_c1_lds only where the one-launch speech kernel
 // builds on it, k_dwfc.hip (measured on the 96x96 stem: dw_c1_lds 1.22 ms, conv_rows_lds 0.70 ms; MF_DW_C1=lds forces the old
-// kernel).  Steps aside for conv1x1_rowwave.
+// kernel).  Steps aside for conv1x1_rowwave.  One input channel with image rows that are not whole dwords (W % 4 != 0: audio features):
+// the same route, launched as conv_rows_bytes (49x13 -> 8: dw_c1_lds 0.090 ms, dw_rows_lds<bytes> 0.065 ms per 16 384 images).
 bool route_conv_rows(OpImpl &op, const ConvCtx &c) {
     const OpSpec &s = c.s;
     const bool c1_lds = switches().dw_c1_lds, no_rt = switches().no_rt;
@@ -480,7 +481,8 @@ bool route_conv_rows(OpImpl &op, const ConvCtx &c) {
     epi_fields_izp(f, op, c);
     op.fast = OpImpl::CONV_ROWS;
     op.rt_wz = c.wz;
-    op.fast_name = std::string(c.dw ? "dw_rows_lds" : "conv_rows_lds") + (op.rt_wz ? "<wzp>" : "");
+    // (rows that are not whole dwords: the conv_rows_bytes launch, k::ConvRowsArgs::BYTES())
+    op.fast_name = std::string(c.dw ? "dw_rows_lds" : "conv_rows_lds") + (f.BYTES() ? (op.rt_wz ? "<bytes,wzp>" : "<bytes>") : (op.rt_wz ? "<wzp>" : ""));
     return true;
 }
 
@@ -1038,7 +1040,8 @@ bool op_set_input_quant(OpImpl *op, float scale, int zp, bool u8) {
     // fc_rt_f32 (k_fc_f32.hip), dw3x3_stem_rt_f32 and conv_rows_lds_f32 (k_rt.hip).  conv_rows_lds takes the floats only where a step is
     // one image (G == 1: more than 4096 dwords of image): with several small images per step its predict measured slower than the separate
     // pass (28x28x1, G = 8, +4 %), and conv_gemm_rt has no f32 instance for the same reason (224x224x3 in row bands, +12 %)
-    const bool conv_rows_one_image = op->fast == OpImpl::CONV_ROWS && op->crows.G == 1;
+    // (conv_rows_bytes has no f32 instance: a float4 of its input is not a tile dword)
+    const bool conv_rows_one_image = op->fast == OpImpl::CONV_ROWS && op->crows.G == 1 && !op->crows.BYTES();
     if ((op->fast == OpImpl::FC_RT || op->fast == OpImpl::DW_STEM_RT || conv_rows_one_image) && !switches().no_f32_boundary) {
         edge_set_in(op->edge, op->device, scale, zp, u8);
         op->accepts_f32 = true;

@@ -371,6 +371,47 @@ def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, w
     return build_model((1,) + tuple(input_shape), in_q, layers, elem)
 
 
+def ds_cnn(rng, shape=(49, 10), filters=64, blocks=4, classes=12, stem=(10, 4, (2, 2)), elem=INT8, wzp_nonzero=False):
+    """The MLPerf-Tiny keyword spotter's stack (DS-CNN): shape = (frames, coefficients) of ONE channel -- 49 x 10 MFCCs; Conv2D with
+    a stem = (KH, KW, strides) filter (conv_net writes square ones only) to `filters` channels, `blocks` x (depthwise 3x3 + 1x1
+    Conv2D, `filters` channels, stride 1), all SAME and relu; AveragePool2D over the whole image, FullyConnected(classes), Softmax.
+    Per-channel filter quantization; with wzp_nonzero the Conv2D filter zero points sit off the middle (the depthwise kernels keep
+    theirs at the middle, as in conv_net).  Every activation tensor has the input's scale and the filter scales keep a deep stack's
+    outputs spread over the range (conv_net's act_scale form), so that the Softmax at the end still tells the classes apart."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    (H, W), C = shape, 1
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers = in_q, []
+
+    def conv(dw, n, kh, kw, strides):
+        nonlocal q, H, W, C
+        oh, ow = -(-H // strides[0]), -(-W // strides[1])
+        taps = kh * kw * (1 if dw else C)
+        sc = (rng.uniform(0.6, 1.4, n) * 2.2 / (74.0 * np.sqrt(taps))).astype(np.float32)   # (conv_net's act_scale form)
+        zp = rng.integers(mid - 10, mid + 11, n) if wzp_nonzero and not dw else np.full(n, mid)
+        d = dict(op="depthwise_conv_2d" if dw else "conv_2d", fscale=sc, fzp=zp, bias=rng.integers(-500, 500, n),
+                 bscale=(sc * np.float32(q[0])).astype(np.float32), bzp=np.zeros(n, np.int64), padding="same", strides=tuple(strides),
+                 act="relu", out_shape=(1, oh, ow, n), out_q=(q[0], lo))
+        d["weights" if dw else "filters"] = rng.integers(lo, hi, (1, kh, kw, n) if dw else (n, kh, kw, C))
+        layers.append(d)
+        q, H, W, C = d["out_q"], oh, ow, n
+
+    conv(False, filters, stem[0], stem[1], stem[2])
+    for _ in range(blocks):
+        conv(True, filters, 3, 3, (1, 1))
+        conv(False, filters, 1, 1, (1, 1))
+    layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none", out_shape=(1, 1, 1, C), out_q=q))
+    layers.append(dict(op="reshape", out_shape=(1, C), out_q=q))
+    wsc = np.float32(rng.uniform(0.002, 0.02))
+    osc = float(np.float32(q[0] * wsc * 60.0 * np.sqrt(C)))
+    layers.append(dict(op="fully_connected", weights=rng.integers(lo, hi, (classes, C)), wscale=[wsc], wzp=[mid],
+                       bias=rng.integers(-2000, 2000, classes), bscale=[np.float32(q[0]) * wsc], bzp=[0], act="none",
+                       out_shape=(1, classes), out_q=(osc, int(rng.integers(lo + 20, hi - 20)))))
+    layers.append(dict(op="softmax", out_shape=(1, classes), out_q=(1.0 / 256.0, lo)))
+    return build_model((1, int(shape[0]), int(shape[1]), 1), in_q, layers, elem)
+
+
 def inverted_residual_net(rng, input_shape, blocks, elem=INT8, wzp_nonzero=False, head=10):
     """MobileNetV2/V3-style inverted-residual blocks: input_shape = (H, W, C); blocks = [(expand, K, stride, out), ...], each a
     1x1 Conv2D to `expand` channels (relu6) -> KxK depthwise SAME at `stride` (relu6) -> 1x1 Conv2D to `out` channels (no
