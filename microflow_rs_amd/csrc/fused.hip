@@ -18,6 +18,7 @@ int fused_epilogue_mode(const FusedImpl *f) {
 }
 bool fused_input_ok(const FusedImpl *f, const int8_t *d_in) { return !kind_facts(f->kind).in16 || ((uintptr_t)d_in & 15) == 0; }
 bool fused_batch_ok(const FusedImpl *f, size_t batch) {
+    if (f->kind == FusedImpl::BLOCK) return f->block_max_batch == 0 || batch <= f->block_max_batch;
     return f->kind != FusedImpl::CONV1FC || f->conv1fc.max_batch == 0 || batch <= f->conv1fc.max_batch;
 }
 // the f32 entry of a group that starts with the network's first operator (M::predict: the boundary quantisation inside the launch)
@@ -56,6 +57,7 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
         if (f->pairband.KSC == 8) k::launch_pair_band_deep(d_in, d_out, f->pairband, (int)batch, st);
         else k::launch_pair_band(d_in, d_out, f->pairband, (int)batch, st);
         break;
+    case FusedImpl::BLOCK: k::launch_block_band(d_in, d_out, f->block, (int)batch, st); break;
     case FusedImpl::PAIRWZ: k::launch_pair_wz(d_in, d_out, f->pairwz, (int)batch, st); break;
     case FusedImpl::QUAD: {
         const int *q = f->quad.shape;

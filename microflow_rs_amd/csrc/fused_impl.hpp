@@ -17,7 +17,7 @@ namespace mf {
 // One argument block (or a named sub-struct: block + what the launch path needs beside it) per kind; a group uses its own kind's.
 // Plain members, no variant: the chain planner swaps whole groups (std::swap(*groups[i], *trial)).
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC } kind = DWPW;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK } kind = DWPW;
     OpImpl *a = nullptr, *b = nullptr, *c = nullptr;
     std::string name;
     std::vector<std::unique_ptr<DevBuf>> owned; // the group's own operand arrays and tables (keep)
@@ -65,6 +65,9 @@ struct FusedImpl {
         k::Conv1FcArgs args{};
         size_t max_batch = 0; // 0: any batch; else the largest batch at which the launch beat the operators' own (fused_batch_ok)
     } conv1fc;
+    // BLOCK: a 1x1 expand + depthwise 3x3 + 1x1 project block in row bands (k_block_band.hip); a = the expand, b = the depthwise, c = the project
+    k::BlockBandArgs block{};
+    size_t block_max_batch = 0; // 0: any batch; else the largest batch at which the block launch runs (fused_batch_ok): above it the launches it replaces
     // the model's f32 boundary inside this group's launch (fused_set_input_quant / fused_set_output_dequant; KindFacts f32_in / f32_out)
     k::F32Edge edge{};
     bool edge_in = false, edge_out = false;
@@ -93,6 +96,7 @@ inline KindFacts kind_facts(FusedImpl::Kind kind) {
     case FusedImpl::PAIRBAND: return {"pair_band_rt", true, false, false};
     case FusedImpl::PAIRWZ: return {"pair_wz_rt", true, false, false};
     case FusedImpl::CONV1FC: return {"conv1_fc_rt", false, false, false};
+    case FusedImpl::BLOCK: return {"block_band_rt", true, false, false};
     }
     return {nullptr, false, false, false};
 }
@@ -100,7 +104,7 @@ inline KindFacts kind_facts(FusedImpl::Kind kind) {
 // f32 end (`edge`) is limited whatever the kind: batch x 4 bytes per element stay below 2^31
 inline size_t batch_limit(const FusedImpl &f, int edge) {
     if (!kind_facts(f.kind).batch_limit && !edge) return 0;
-    return 0x7fffffffull / 4 / (f.kind == FusedImpl::PAIRBAND ? (size_t)f.pairband.NB : 1);
+    return 0x7fffffffull / 4 / (f.kind == FusedImpl::PAIRBAND ? (size_t)f.pairband.NB : f.kind == FusedImpl::BLOCK ? (size_t)f.block.b.NB : 1);
 }
 
 inline std::unique_ptr<FusedImpl> make_group(FusedImpl::Kind kind, OpImpl *a, OpImpl *b, OpImpl *c, std::string name) {
@@ -144,6 +148,37 @@ inline PairMatch match_dw3x3_pw1x1(const OpImpl *dw, const OpImpl *pw) {
     PairMatch m;
     m.d = &d, m.q = &q, m.f = dw_fast(dw);
     m.geom = k::ChainGeom{d.H, d.W, d.C, d.sh, d.OH, d.OW, q.N, m.f ? m.f->izp4 : 0u};
+    return m;
+}
+// ---- the block block_band_rt starts from (k_block_band.hip) ----
+// A Conv2D 1x1 at stride 1 (the expand, C -> E) on exactly the input of a pair match_dw3x3_pw1x1 accepts (depthwise on E, project
+// E -> N), with the tensor inside the widest: E > C and E > N.  One device, one element type, finite constants, zero filter zero points
+// in the i8 domain on all three, none forced generic, W even at stride 2, and the channel ranges of block_band_plan.  Everything
+// fused_block_create asks short of the plan, the compiled instance and the measured exclusions.
+struct BlockMatch {
+    PairMatch pair;      // the depthwise + project pair (geom.C = E; geom.izp4 = the depthwise's input zero point in every byte)
+    int CI = 0;          // the expand's input channels
+    bool ok = false;
+    explicit operator bool() const { return ok; }
+};
+inline BlockMatch match_expand_block(const OpImpl *ex, const OpImpl *dw, const OpImpl *pw) {
+    BlockMatch no, m;
+    m.pair = match_dw3x3_pw1x1(dw, pw);
+    if (!ex || !m.pair) return no;
+    const OpSpec &e = ex->s, &d = *m.pair.d, &q = *m.pair.q;
+    if (e.kind != MF_OP_CONV_2D || ex->device != dw->device || e.u8 != d.u8 || !ex->finite_consts) return no;
+    if (e.KH != 1 || e.KW != 1 || e.sh != 1 || e.sw != 1 || e.OH != e.H || e.OW != e.W) return no;
+    if (e.H != d.H || e.W != d.W || e.N != d.C) return no; // on exactly the depthwise's input
+    if (ex->force_generic || dw->force_generic || pw->force_generic) return no; // (generic operators stay launches of their own)
+    for (const OpImpl *o : {ex, dw, pw})
+        for (int32_t z : o->h_wzp)
+            if (z != 0) return no;
+    if (d.sh == 2 && d.W % 2 != 0) return no; // (the plan's stride-2 column units)
+    const int C = e.C, E = d.C, N = q.N;
+    if (E <= C || E <= N) return no; // the tensor inside is the widest: what makes the launch pay, and what no chain of pairs has
+    if (E % 16 != 0 || E < 32 || E > 256 || C % 4 != 0 || C < 4 || C > 128 || N % 4 != 0 || N < 4 || N > 256) return no;
+    m.pair.geom.izp4 = 0x01010101u * (uint32_t)(uint8_t)(int8_t)dw->conv.izp; // (whatever kernel the depthwise runs alone)
+    m.CI = C, m.ok = true;
     return m;
 }
 // the pair's ten requantisation constants, from the members' argument blocks (A, S, Kc, lo_f, hi_f), into any block that names them

@@ -276,6 +276,65 @@ static std::unique_ptr<FusedImpl> pair_wz_create(OpImpl *dw, OpImpl *pw) {
     return c;
 }
 
+// ---- a 1x1 expand + depthwise 3x3 + 1x1 project block in row bands (k_block_band.hip): the model's second level, over the pair's group ----
+// Every operand image is built here from the members' host copies and every constant array is the member's own (the project's padded
+// to whole 16-channel tiles where N % 16 != 0), so the block does not depend on which kernels the members run alone.
+static constexpr int BLOCK_LIMIT_STEPS = 512;
+FusedImpl *fused_block_create(OpImpl *ex, OpImpl *dw, OpImpl *pw, bool pair_grouped) {
+    if (switches().no_expand_block) return nullptr;
+    const BlockMatch m = match_expand_block(ex, dw, pw);
+    if (!m) return nullptr;
+    const OpSpec &e = ex->s, &d = *m.pair.d, &q = *m.pair.q;
+    const int CI = m.CI, E = d.C, N = q.N;
+    if (ex->h_w.size() != (size_t)E * CI || dw->h_w.size() != (size_t)9 * E || pw->h_w.size() != (size_t)N * E) return nullptr;
+    if (ex->h_A.size() != (size_t)E || dw->h_A.size() != (size_t)E || pw->h_A.size() != (size_t)N || pw->h_S.size() != (size_t)N || pw->h_Kc.size() != (size_t)N) return nullptr;
+    std::unique_ptr<FusedImpl> c = make_group(FusedImpl::BLOCK, ex, dw, pw, "");
+    k::BlockBandArgs &bb = c->block;
+    k::PairBandArgs &a = bb.b;
+    if (!k::block_band_plan(m.pair.geom, CI, bb)) return nullptr;
+    // Classes measured NOT faster than the launches they replace by more than the spread of the repeats (profiles/r13/time_expand_block.txt,
+    // DESIGN 4.16) keep those launches:
+    //   four k steps of E at stride 1 on a plan that needs more than half a CU's LDS -- eight waves alone on a CU, 6-row bands that
+    //   compute the expand of 8 rows: 56x56x24 -> 144 -> 24 ran 0.624 ms against 0.590 (x0.95);
+    //   four k steps of E and less than one 16-pixel chunk of output per image -- a step is three barriers and a DMA for 36 pixels:
+    //   6x6x32 -> 192 s2 -> 64 ran 0.173 ms against 0.112 (x0.64).
+    if (a.KSC == 4 && ((d.sh == 1 && a.wgs == 1) || d.OH * d.OW < 16)) return nullptr;
+    const int magic = std::min(ex->magic_mode, std::min(dw->magic_mode, pw->magic_mode));
+    if (!k::block_band_instance(a.KSC, bb.KSI, magic)) return nullptr; // (no compiled instance: the block keeps its launches)
+    const std::vector<int8_t> exw = wimage::build_pw_rt_reg_weights(ex->h_w.data(), CI, E, 1, 1, E / 16); // [E][1][1][CI], i8 domain
+    bb.ex_w = keep(*c, exw.data(), exw.size());
+    bb.exA = ex->conv.A, bb.exS = ex->conv.S, bb.exK = ex->conv.Kc, bb.ex_lo = ex->conv.lo_f, bb.ex_hi = ex->conv.hi_f;
+    const std::vector<int8_t> taps = wimage::build_dw_mm_weights(dw->h_w.data(), E); // [3][3][E], i8 domain
+    a.dw_wmm = keep(*c, taps.data(), taps.size());
+    const std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(pw->h_w.data(), E, N, 1, a.TB, a.NBLK); // [N][1][1][E]; rows past N are zero
+    a.pw_w = keep(*c, prep.data(), prep.size());
+    set_pair_consts(a, dw->conv, pw->conv);
+    if (N % 16 != 0) { // a lane fetches the constants of its four channels whether or not they are below N
+        const size_t np = (size_t)a.TB * a.NBLK * 16;
+        auto padded = [&](const auto &src) {
+            auto h = src;
+            h.resize(np, 0);
+            return keep(*c, h.data(), np * 4);
+        };
+        a.pwA = (const float *)padded(pw->h_A), a.pwS = (const float *)padded(pw->h_S), a.pwK = (const int *)padded(pw->h_Kc);
+    }
+    // Classes in which the one launch wins only while the launches it replaces cannot fill the chip (profiles/r13/time_expand_block.txt,
+    // the sweep) run it up to a batch limit and the launches they had above it (fused_batch_ok, as conv1_fc_rt's limit):
+    //   one k step of E (E <= 64), and four k steps at stride 2 with N <= 32: up to one round of the 512 resident workgroups, 512 / NB images;
+    //   a quarter of that where the depthwise + project pair has a launch of its own (pw_rt + chain_rt / pair_band_rt: two launches
+    //   are replaced, not three).
+    if (a.KSC == 1 || (a.KSC == 4 && d.sh == 2 && N <= 32)) c->block_max_batch = (size_t)std::max(1, (pair_grouped ? BLOCK_LIMIT_STEPS / 4 : BLOCK_LIMIT_STEPS) / a.NB);
+    a.magic = magic, a.xr = d.u8 ? 0x80 : 0;
+    a.queue = (int *)ex->d_queue.p, a.qlaunch = &ex->q_launches;
+    c->epi_mode = magic;
+    c->name = "block_band_rt<" + std::to_string(e.H) + "x" + std::to_string(e.W) + "x" + std::to_string(CI) + "-" + std::to_string(E) + (d.sh == 2 ? "s2" : "") + "-" + std::to_string(N) +
+              ";RB" + std::to_string(a.RB) + ";NB" + std::to_string(a.NB) + ">";
+    if (switches().chain_verbose)
+        fprintf(stderr, "[microflow_amd] block group %s: input band %d B, tile %d rows x %d B, MID %d B, lds %d B, %d workgroup%s per CU, %d x %d output tiles, k steps %d / %d, mode %d, batch limit %zu\n",
+                c->name.c_str(), bb.in_bytes, a.TR, a.ROW, a.mid_bytes, a.lds_bytes, a.wgs, a.wgs == 1 ? "" : "s", a.NBLK, a.TB, bb.KSI, a.KSC, magic, c->block_max_batch);
+    return c.release();
+}
+
 // A pair as one launch.  THE ORDER: a table pair or chain_rt (chain_rt first where no table kernel exists or under MF_CHAIN_ALL), then
 // the band kernels, then -- only ever for a pair with filter zero points, which the others refuse -- pair_wz_rt.
 FusedImpl *fused_create(OpImpl *dw, OpImpl *pw) {

@@ -424,6 +424,37 @@ void launch_pair_band(const int8_t *in, int8_t *out, const PairBandArgs &a, int 
 bool pair_band_deep_plan(const ChainGeom &g, PairBandArgs &a);
 void launch_pair_band_deep(const int8_t *in, int8_t *out, const PairBandArgs &a, int batch, hipStream_t s);
 
+// ---- a 1x1 expand + depthwise 3x3 + 1x1 project block, band by band (k_block_band.hip: block_band_rt) ----
+// pair_band_rt's step with the band's depthwise input tile COMPUTED in LDS: the band's (RB - 1) S + 3 input rows of the narrow CI-channel
+// tensor are staged as they lie in HBM, the expand (Conv2D 1x1 CI -> E, its own requantisation) writes the E-channel tile, and the
+// depthwise and project phases are pair_band_rt's on C = E.  The project's N need only be a multiple of 4.
+struct BlockBandArgs {
+    PairBandArgs b;                // the depthwise + project pair on C = E as pair_band_rt takes it (dbuf = 0; N as the model states it,
+                                   // TB NBLK = ceil(N / 16); its constants padded to whole tiles)
+    int CI, KSI;                   // the expand's input channels; 64-deep k steps over them (1 or 2: the kernel instance's)
+    int in_off, in_bytes;          // LDS region of the staged input band: TR W CI bytes + up to 15 in front (the DMA starts at a 16-byte
+                                   // boundary of the tensor) + 64 KSI + 16 behind (the last pixel's whole k steps, the DMA's round-up)
+    uint32_t wmagic;               // ceil(2^32 / W): pixel index -> row = mulhi(index, wmagic), exact for every index of a band (the plan checks)
+    int nfull;                     // N % 16 == 0: every lane of the project's store is inside N
+    const void *ex_w;              // build_pw_rt_reg_weights(CI, E, group 1, TB 1, E / 16): K padded to the k step with zero weights
+    const float *exA, *exS;
+    const int *exK;
+    float ex_lo, ex_hi;
+};
+// the tile rows [lo_r, hi_r) of band `band` that lie inside the image (the others hold the depthwise's input zero point); tile row r is
+// input row S band RB - 1 + r.  The staged bytes of the band are rows lo_r .. hi_r - 1: one contiguous range of the image.
+__host__ __device__ static inline void block_band_rows(int H, int S, int RB, int TR, int band, int &lo_r, int &hi_r) {
+    const int iy0 = S * band * RB - 1;
+    lo_r = iy0 < 0 ? -iy0 : 0;
+    hi_r = H - iy0 < TR ? H - iy0 : TR;
+}
+// fills the geometry and the LDS plan (everything but the operand pointers, clamps and modes); false: a channel count outside the
+// block's ranges (CI 4 .. 128 and N 4 .. 256 in whole fours, E 32 .. 256 in whole sixteens), an odd width at stride 2, or the smallest
+// band does not fit PAIR_BAND_LDS_MAX.  g.C is E; no lower size bound.
+bool block_band_plan(const ChainGeom &g, int CI, BlockBandArgs &a);
+bool block_band_instance(int KSC, int KSI, int magic); // a compiled kernel exists
+void launch_block_band(const int8_t *in, int8_t *out, const BlockBandArgs &a, int batch, hipStream_t s);
+
 // ---- one pair whose filters carry zero points, whole images in LDS (k_pair_wz.hip: pair_wz_rt) ----
 // chain_rt's single-pair step plus the reference's two zero-point terms: acc -= wzp[c] * (window sum) in the depthwise,
 // acc[n] -= wzp[n] * (the pixel's sum over its C intermediate bytes) in the 1x1.  Geometry and LDS plan are chain_plan's with n = 1.

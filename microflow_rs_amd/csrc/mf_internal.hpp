@@ -158,6 +158,7 @@ unsigned long long &dev_launch_counter();
 // the pair has no fused kernel)
 struct FusedImpl;
 FusedImpl *fused_create(OpImpl *dw, OpImpl *pw);
+FusedImpl *fused_block_create(OpImpl *expand, OpImpl *dw, OpImpl *pw, bool pair_grouped = false); // a 1x1 expand + depthwise 3x3 + 1x1 project block in one launch (k_block_band.hip), or nullptr; pair_grouped: the last two have a launch of their own
 // fused tail: AveragePool2D (1x1 output) -> Conv2D 1x1 (N <= 8) -> Softmax (one row of N)
 FusedImpl *fused_tail_create(OpImpl *pool, OpImpl *conv, OpImpl *softmax);
 // fused FullyConnected (row-wave kernel, one row per inference) -> Softmax over its outputs

@@ -347,6 +347,22 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
         // (a forced chain plan that met no run was applied to nothing: the caller must not take the result for that plan's)
         if (!chain_runs && switches().dev && switches_parse().chain_plan_set)
             fail(MF_ERR_UNSUPPORTED, "MF_CHAIN_PLAN segment 0: the model has no run of run-time-geometry pairs");
+        auto owned = [&](size_t i) {
+            for (size_t j = 0; j < i; ++j)
+                if (fused[j] && fused_last[j] >= (int)i) return true;
+            return false;
+        };
+        // (4d) Conv2D 1x1 (expand) -> DepthwiseConv2D 3x3 -> Conv2D 1x1 (project) with the tensor inside the widest -> one block_band_rt
+        // launch (fused_pairs.hip: fused_block_create).  Behind the chain partition, so that a pair a chain of pairs took is not a
+        // candidate; a first-level pair group at i + 1 stays under the stage (mf_model_run_until pieces use it)
+        for (size_t i = 0; i + 2 < n; ++i) {
+            if (!ops[i] || m->pm.ops[i].kind != MF_OP_CONV_2D || fused[i] || covered(i) || owned(i)) continue;
+            if (!ops[i + 1] || !ops[i + 2] || covered(i + 1) || covered(i + 2)) continue;
+            if (FusedImpl *f = fused_block_create(ops[i], ops[i + 1], ops[i + 2], fused[i + 1] != nullptr)) {
+                sg.v.push_back({f, (int)i, (int)i + 2});
+                i += 2;
+            }
+        }
         // (5) DepthwiseConv2D with one input channel -> [Reshape] -> the FullyConnected + Softmax group -> one kernel
         for (size_t i = 0; i + 1 < n; ++i) {
             if (!ops[i] || fused[i] || covered(i) || m->pm.ops[i].kind != MF_OP_DEPTHWISE_CONV_2D) continue;
@@ -355,11 +371,6 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             if (j < n && fused[j] && !covered(j))
                 if (FusedImpl *f = fused_dwfc_create(ops[i], fused[j])) sg.v.push_back({f, (int)i, fused_last[j]});
         }
-        auto owned = [&](size_t i) {
-            for (size_t j = 0; j < i; ++j)
-                if (fused[j] && fused_last[j] >= (int)i) return true;
-            return false;
-        };
         auto free_fc = [&](size_t i) {
             return i < n && ops[i] && m->pm.ops[i].kind == MF_OP_FULLY_CONNECTED && !fused[i] && !covered(i) && !owned(i);
         };
