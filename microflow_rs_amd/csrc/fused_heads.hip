@@ -1,5 +1,5 @@
 // fused_heads.hip -- the groups at a network's classifier end: pool + head + Softmax, FullyConnected (+ Softmax) runs, a global pool
-// or a one-input-channel convolution in front of them.  Host code only; the kernels are in k_*.hip.
+// or a one-input-channel convolution in front of them; and the Conv2D + AveragePool2D stage.  Host code only; the kernels are in k_*.hip.
 #include "fused_impl.hpp"
 
 namespace mf {
@@ -181,6 +181,70 @@ FusedImpl *fused_conv1_fc_create(OpImpl *conv, OpImpl *fc, OpImpl *sm) {
     // conv1_fc_rt beat the three launches at batch 4096 (one step per workgroup: 1.13 - 1.55x) and lost at 65 536 (0.82 - 1.01x), so such
     // a group takes batches up to 4096 only; where the FullyConnected alone runs fc_generic it won at both (2.3 - 3.1x) and takes any
     f->conv1fc.max_batch = fc->fcrt_ok ? 4096 : 0;
+    return f.release();
+}
+
+// A Conv2D directly followed by an AveragePool2D with more than one output pixel on exactly its output, as one conv_pool_rt launch
+// (k_conv_pool.hip): the convolution's bytes stay in LDS.  Same device and element type, finite constants, neither forced generic, and
+// what k::conv_pool_plan accepts.  The weight image, the tables and the padded constants are the group's own, built from the
+// convolution's host copies: alone it may run conv_rows_lds, conv_mm_rt or pw_rt, which keep other images.
+FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool) {
+    if (switches().no_conv_pool || !conv || !pool || conv->force_generic || pool->force_generic) return nullptr;
+    const OpSpec &d = conv->s, &q = pool->s;
+    if (d.kind != MF_OP_CONV_2D || q.kind != MF_OP_AVERAGE_POOL_2D || conv->device != pool->device || d.u8 != q.u8) return nullptr;
+    if (q.H != d.OH || q.W != d.OW || q.C != d.N) return nullptr; // on exactly the convolution's output
+    if (!conv->finite_consts || !std::isfinite(q.pool_c0) || !std::isfinite(q.pool_c1)) return nullptr;
+    if (conv->h_w.size() != (size_t)d.N * d.KH * d.KW * d.C || conv->h_A.size() != (size_t)d.N || conv->h_S.size() != (size_t)d.N ||
+        conv->h_Kc.size() != (size_t)d.N || conv->h_wzp.size() != (size_t)d.N)
+        return nullptr;
+    const bool wz = std::any_of(conv->h_wzp.begin(), conv->h_wzp.end(), [](int32_t z) { return z != 0; });
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::CONVPOOL, conv, pool, nullptr, "");
+    k::ConvPoolArgs &a = f->convpool.args;
+    std::vector<int> tap;
+    std::vector<uint32_t> mask;
+    if (!k::conv_pool_plan(a, tap, mask, d.H, d.W, d.C, d.N, d.KH, d.KW, d.sh, d.sw, d.OH, d.OW, d.pad == MF_PAD_SAME, wz, q.KH, q.KW, q.sh, q.sw, q.OH, q.OW,
+                           q.pad == MF_PAD_SAME))
+        return nullptr;
+    // Classes measured NOT faster than the two launches they replace by more than the spread of the repeats (profiles/r14/time_conv_pool.txt,
+    // DESIGN 4.17) keep those launches:
+    //   one input channel -- a 16-byte operand holds KW real bytes, and conv_rows_lds, which such a convolution runs alone, pads nothing:
+    //   28x28x1 -> 6 5x5 ran x0.52, 96x96x1 -> 8 3x3 x0.19, 12x12x1 -> 8 5x5 x0.86;
+    //   a plan beyond half a CU's LDS -- one workgroup per CU is one wave per SIMD, and a 16-pixel chunk is bound by instruction issue:
+    //   64x64x4 -> 64 in bands x0.67, 48x48x8 -> 96 in bands x0.76, 32x32x32 -> 64 (one image, 126 KiB) x0.74;
+    //   fewer than 16 output channels (half a matrix tile is padding: x0.44 - x0.94 over C = 3 .. 12, 3x3 and 5x5), or fewer than 2400
+    //   real multiply-adds per output pixel, KH KW C N (the chunk's cost is the same, the launches it replaces are cheap: the sweep's
+    //   x0.66 - x1.08, none clearing its spread; from 2400 on x1.14 - x2.81, all clearing it).
+    const bool slow = d.C == 1 || a.lds > 80 * 1024 || d.N < 16 || (long long)d.KH * d.KW * d.C * d.N < 2400;
+    if (slow && !switches().conv_pool_all) return nullptr;
+    k::ConvGemmArgs wg{}; // (what conv_gemm_weight_image reads: the filter and its padded row)
+    wg.N = d.N, wg.C = d.C, wg.KH = d.KH, wg.KW = d.KW, wg.KWCP = a.KWCP;
+    const std::vector<int8_t> img = k::conv_gemm_weight_image(conv->h_w.data(), wg);
+    if (img.size() != (size_t)a.NT * a.KS * 1024) return nullptr;
+    a.wimg = keep(*f, img.data(), img.size());
+    a.tap = (const int *)keep(*f, tap.data(), tap.size() * sizeof(int));
+    a.kmask = (const uint32_t *)keep(*f, mask.data(), mask.size() * 4);
+    const size_t np = (size_t)a.NT * 16; // a lane fetches the constants of its four channels whether or not they are below N
+    auto padded = [&](const auto &src) {
+        auto h = src;
+        h.resize(np, 0);
+        return keep(*f, h.data(), np * 4);
+    };
+    a.A = (const float *)padded(conv->h_A), a.S = (const float *)padded(conv->h_S);
+    a.Kc = (const int *)padded(conv->h_Kc), a.wzp = (const int *)padded(conv->h_wzp);
+    a.izp4 = 0x01010101u * (uint32_t)(uint8_t)(int8_t)d.izp;
+    a.lo_f = conv->conv.lo_f, a.hi_f = conv->conv.hi_f;
+    a.magic = std::min(conv->magic_mode, 2), a.xr = conv->conv.xr;
+    a.pool = pool->pool;
+    if (pool->pool.xr != a.xr) return nullptr;
+    f->convpool.wz = wz;
+    f->epi_mode = a.magic;
+    f->name = "conv_pool_rt<" + std::to_string(d.H) + "x" + std::to_string(d.W) + "x" + std::to_string(d.C) + "-" + std::to_string(d.N) + ";" + std::to_string(d.KH) + "x" +
+              std::to_string(d.KW) + (d.sh != 1 || d.sw != 1 ? "s" + std::to_string(d.sh) : "") + ";p" + std::to_string(q.KH) + "x" + std::to_string(q.KW) +
+              (q.sh != 1 || q.sw != 1 ? "s" + std::to_string(q.sh) : "") +
+              (a.NB == 1 ? ";G" + std::to_string(a.G) : ";PB" + std::to_string(a.PB) + ";NB" + std::to_string(a.NB)) + ">";
+    if (switches().chain_verbose)
+        fprintf(stderr, "[microflow_amd] conv + pool group %s: %d k steps, %d tiles, tile %d rows x %d B, Y %d B per image (%d B per pixel), lds %d B, mode %d\n",
+                f->name.c_str(), a.KS, a.NT, a.RB, a.ROW, a.YIMG, a.NP, a.lds, a.magic);
     return f.release();
 }
 

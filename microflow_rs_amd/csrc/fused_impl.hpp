@@ -17,7 +17,7 @@ namespace mf {
 // One argument block (or a named sub-struct: block + what the launch path needs beside it) per kind; a group uses its own kind's.
 // Plain members, no variant: the chain planner swaps whole groups (std::swap(*groups[i], *trial)).
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK } kind = DWPW;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK, CONVPOOL } kind = DWPW;
     OpImpl *a = nullptr, *b = nullptr, *c = nullptr;
     std::string name;
     std::vector<std::unique_ptr<DevBuf>> owned; // the group's own operand arrays and tables (keep)
@@ -68,6 +68,11 @@ struct FusedImpl {
     // BLOCK: a 1x1 expand + depthwise 3x3 + 1x1 project block in row bands (k_block_band.hip); a = the expand, b = the depthwise, c = the project
     k::BlockBandArgs block{};
     size_t block_max_batch = 0; // 0: any batch; else the largest batch at which the block launch runs (fused_batch_ok): above it the launches it replaces
+    // CONVPOOL: a Conv2D + the AveragePool2D on its output in one launch (k_conv_pool.hip); a = the convolution, b = the pool
+    struct ConvPool {
+        k::ConvPoolArgs args{};
+        bool wz = false; // the convolution has non-zero filter zero points (internal domain)
+    } convpool;
     // the model's f32 boundary inside this group's launch (fused_set_input_quant / fused_set_output_dequant; KindFacts f32_in / f32_out)
     k::F32Edge edge{};
     bool edge_in = false, edge_out = false;
@@ -97,14 +102,16 @@ inline KindFacts kind_facts(FusedImpl::Kind kind) {
     case FusedImpl::PAIRWZ: return {"pair_wz_rt", true, false, false};
     case FusedImpl::CONV1FC: return {"conv1_fc_rt", false, false, false};
     case FusedImpl::BLOCK: return {"block_band_rt", true, false, false};
+    case FusedImpl::CONVPOOL: return {"conv_pool_rt", true, false, false};
     }
     return {nullptr, false, false, false};
 }
-// the most images one launch of the group takes; 0: any size_t.  The band kernels count steps, NB bands per image.  A launch with an
+// the most images one launch of the group takes; 0: any size_t.  The band kernels (conv_pool_rt among them) count steps, NB bands per image.  A launch with an
 // f32 end (`edge`) is limited whatever the kind: batch x 4 bytes per element stay below 2^31
 inline size_t batch_limit(const FusedImpl &f, int edge) {
     if (!kind_facts(f.kind).batch_limit && !edge) return 0;
-    return 0x7fffffffull / 4 / (f.kind == FusedImpl::PAIRBAND ? (size_t)f.pairband.NB : f.kind == FusedImpl::BLOCK ? (size_t)f.block.b.NB : 1);
+    return 0x7fffffffull / 4 / (f.kind == FusedImpl::PAIRBAND ? (size_t)f.pairband.NB : f.kind == FusedImpl::BLOCK ? (size_t)f.block.b.NB :
+                                 f.kind == FusedImpl::CONVPOOL ? (size_t)f.convpool.args.NB : 1);
 }
 
 inline std::unique_ptr<FusedImpl> make_group(FusedImpl::Kind kind, OpImpl *a, OpImpl *b, OpImpl *c, std::string name) {

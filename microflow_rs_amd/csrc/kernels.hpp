@@ -763,6 +763,45 @@ bool conv_gemm_plan(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uint32_t
                     int sw, int OH, int OW, bool pad_same, bool wz); // false: beyond the limits
 std::vector<int8_t> conv_gemm_weight_image(const int8_t *w /*[N][KH][KW][C]*/, const ConvGemmArgs &a);
 void launch_conv_gemm(const int8_t *in, int8_t *out, const ConvGemmArgs &a, bool wz, int batch, hipStream_t s);
+// A Conv2D + the AveragePool2D (more than one output pixel) on exactly its output in one launch (k_conv_pool.hip: conv_pool_rt).  The
+// convolution is conv_gemm_rt's product with the WHOLE weight image resident; its requantised bytes go to an LDS image
+// Y[g][conv row][ox][NP] and the pool (avgpool_generic's arithmetic) reads them there.  A step is G whole images, or one band of PB
+// pooled rows of one image whose convolution rows conv_pool_band gives (overlapping windows recompute the shared rows).
+struct ConvPoolArgs {
+    int H, W, C, N, KH, KW, sh, sw, OH, OW;
+    int padl, padt;      // the convolution's, as ConvGemmArgs
+    int KWCP, KS, NT, TB; // padded filter row, k steps, 16-column tiles (all resident), tiles per block (<= 4)
+    int LP, ROW, RB, TILE; // the input tile as ConvGemmArgs: RB rows of ROW bytes, TILE bytes
+    int PFH, PFW, psh, psw, POH, POW, pshy, pshx; // the pool: window, strides, output, window shift ((K - 1) / 2 under SAME, else 0)
+    int NP;              // bytes between two pixels of Y: N rounded up to 4, one dword more where that many dwords are even (banks)
+    int CB, YIMG;        // the most convolution rows a step holds per image; bytes between two images of Y (CB OW NP)
+    int G, PB, NB;       // images per step (NB == 1); pooled rows per band, bands per image (G == 1)
+    int xoff, yoff, toff, moff, coff, lds; // LDS plan behind the weights (offset 0): tiles, Y, tap table [KS][4], masks [KS][4][16 bytes] (filter
+                         // zero points), the convolution's constants [Kc | A | S | wzp][NT 16], total
+    uint32_t izp4;
+    float lo_f, hi_f;    // the convolution's clamp
+    const void *wimg;    // conv_gemm_weight_image: [NT][KS][64 lanes][16 bytes]
+    const int *tap;      // as ConvGemmArgs
+    const uint32_t *kmask;
+    const float *A;      // [NT * 16], zero beyond N: the convolution's constants
+    const float *S;
+    const int *Kc;
+    const int *wzp;
+    PoolArgs pool;       // the pool operator's block (c0, c1, lo, hi, bias, sat_lo, sat_hi, xr)
+    int magic, xr;       // the convolution's epilogue mode (0 .. 2) and element domain
+};
+// the convolution rows [c0, c1) that band `band` of PB pooled rows reads
+__host__ __device__ static inline void conv_pool_band(int OH, int POH, int PB, int psh, int pshy, int PFH, int band, int &py0, int &py1, int &c0, int &c1) {
+    py0 = band * PB, py1 = py0 + PB < POH ? py0 + PB : POH;
+    c0 = py0 * psh - pshy, c1 = (py1 - 1) * psh - pshy + PFH;
+    c0 = c0 < 0 ? 0 : c0, c1 = c1 > OH ? OH : c1;
+}
+// fills the geometry, the LDS plan and the tables (everything but the operand pointers, constants and modes) inside CONV_GEMM_LDS_MAX;
+// false: (W C) % 4 != 0, KS > CONV_GEMM_KS_MAX, a pool with one output pixel, a degenerate size, or the whole weight image does not
+// fit beside a band of one pooled row
+bool conv_pool_plan(ConvPoolArgs &a, std::vector<int> &tap, std::vector<uint32_t> &mask, int H, int W, int C, int N, int KH, int KW, int sh, int sw,
+                    int OH, int OW, bool pad_same, bool wz, int PFH, int PFW, int psh, int psw, int POH, int POW, bool pool_same);
+void launch_conv_pool(const int8_t *in, int8_t *out, const ConvPoolArgs &a, bool wz, int batch, hipStream_t s);
 // DepthwiseConv2D of any C >= 2 with one output per channel, filters up to 7 x 7, (W C) % 4 == 0, with or without filter zero points
 // (k_dw_gemm.hip: dw_gemm_rt): dw_mm_rt's block-diagonal product with operand B read at its natural alignment
 struct DwGemmArgs {

@@ -159,6 +159,7 @@ unsigned long long &dev_launch_counter();
 struct FusedImpl;
 FusedImpl *fused_create(OpImpl *dw, OpImpl *pw);
 FusedImpl *fused_block_create(OpImpl *expand, OpImpl *dw, OpImpl *pw, bool pair_grouped = false); // a 1x1 expand + depthwise 3x3 + 1x1 project block in one launch (k_block_band.hip), or nullptr; pair_grouped: the last two have a launch of their own
+FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool); // a Conv2D + the AveragePool2D (more than one output pixel) on its output in one launch (k_conv_pool.hip), or nullptr
 // fused tail: AveragePool2D (1x1 output) -> Conv2D 1x1 (N <= 8) -> Softmax (one row of N)
 FusedImpl *fused_tail_create(OpImpl *pool, OpImpl *conv, OpImpl *softmax);
 // fused FullyConnected (row-wave kernel, one row per inference) -> Softmax over its outputs

@@ -473,6 +473,24 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             }
             i = idx.back();
         }
+        // (6a) a Conv2D directly followed by an AveragePool2D with more than one output pixel -> one conv_pool_rt launch (fused_heads.hip:
+        // fused_conv_pool_create).  Behind every peephole above: a global pool stays with the tail and pool_fc_chain groups, the Conv2D of a
+        // depthwise pair with its pair.  A first operator that takes the f32 input inside its own launch keeps that launch (the entry is
+        // predict's quantisation inside a launch; the group has no f32 entry)
+        {
+            size_t first_real = 0;
+            while (first_real < n && !ops[first_real]) ++first_real;
+            auto free_op = [&](size_t i) { return ops[i] && !fused[i] && !covered(i) && !owned(i); };
+            for (size_t i = 0; i + 1 < n; ++i) {
+                if (m->pm.ops[i].kind != MF_OP_CONV_2D || m->pm.ops[i + 1].kind != MF_OP_AVERAGE_POOL_2D || !free_op(i) || !free_op(i + 1)) continue;
+                if (m->pm.ops[i + 1].OH * m->pm.ops[i + 1].OW < 2) continue;
+                if (i == first_real && op_accepts_f32(ops[i])) continue;
+                if (FusedImpl *f = fused_conv_pool_create(ops[i], ops[i + 1])) {
+                    sg.v.push_back({f, (int)i, (int)i + 1});
+                    ++i;
+                }
+            }
+        }
         // (7) the boundary conversions of M::predict inside the launches at the two ends of the whole model: every launch that can
         // start a run at operator 0 learns the input's scale and zero point, every one that can end at the last operator the ones
         // that operator stamped (the stem was told above; a kernel without such an instance says no and keeps the separate pass)

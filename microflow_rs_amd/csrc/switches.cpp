@@ -72,6 +72,8 @@ Switches switches_parse() {
     s.no_conv_rows_bytes = env_set("MF_NO_CONV_ROWS_BYTES");
     s.no_pair_band = env_set("MF_NO_PAIR_BAND");
     s.no_expand_block = env_set("MF_NO_EXPAND_BLOCK");
+    s.no_conv_pool = env_set("MF_NO_CONV_POOL");
+    s.conv_pool_all = env_set("MF_CONV_POOL_ALL");
     s.no_pair_wz = env_set("MF_NO_PAIR_WZ");
     s.pair_wz_gmul = (int)env_ll("MF_PAIR_WZ_GMUL", 2);
     s.no_conv_gemm = env_set("MF_NO_CONV_GEMM");

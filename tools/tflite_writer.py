@@ -371,6 +371,75 @@ def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, w
     return build_model((1,) + tuple(input_shape), in_q, layers, elem)
 
 
+def _same_or_valid(size, k, s, padding):
+    return -(-size // s) if padding == "same" else (size - k) // s + 1
+
+
+def conv_pool_layers(rng, shape, in_q, n, k, stride=1, padding="valid", act="relu", pool=(2, 2), pool_stride=2, pool_padding="valid",
+                     pool_act="none", pool_q="same", elem=INT8, wzp_nonzero=False, wmax=None):
+    """The two layers of one stage, Conv2D k x k (shape = (H, W, C) -> n channels, per-channel filter quantisation, filter zero points
+    off the middle with wzp_nonzero, weights over the full range unless wmax) -> AveragePool2D pool[0] x pool[1]; -> (layers, the
+    stage's output (H, W, C), its quantisation).  pool_q: "same" -- the pool's output has its input's scale and zero point, so the
+    pooled value is the plain mean and lands on .5 ties -- or a factor on the scale (with a random zero point unless the pool has an
+    activation, which pins it to the type's minimum)."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    H, W, C = (int(v) for v in shape)
+    oh, ow = _same_or_valid(H, k, stride, padding), _same_or_valid(W, k, stride, padding)
+    sc = rng.uniform(0.002, 0.01, n).astype(np.float32)
+    zp = rng.integers(mid - 10, mid + 11, n) if wzp_nonzero else np.full(n, mid)
+    span = 128 if wmax is None else wmax
+    osc = float(np.float32(in_q[0] * float(sc.mean()) * 60.0 * np.sqrt(k * k * C) * span / 128.0))
+    ozp = lo if act in ("relu", "relu6") else int(rng.integers(lo + 20, hi - 20))
+    wshape = (n, k, k, C)
+    conv = dict(op="conv_2d", filters=rng.integers(lo, hi, wshape) if wmax is None else rng.integers(mid - wmax, mid + wmax + 1, wshape),
+                fscale=sc, fzp=zp, bias=rng.integers(-500, 500, n), bscale=(sc * np.float32(in_q[0])).astype(np.float32),
+                bzp=np.zeros(n, np.int64), padding=padding, strides=(stride, stride), act=act, out_shape=(1, oh, ow, n), out_q=(osc, ozp))
+    ph, pw = _same_or_valid(oh, pool[0], pool_stride, pool_padding), _same_or_valid(ow, pool[1], pool_stride, pool_padding)
+    if pool_q == "same":
+        pq = (osc, ozp)
+    else:
+        pq = (float(np.float32(osc * pool_q)), lo if pool_act in ("relu", "relu6") else int(rng.integers(lo + 20, hi - 20)))
+    pl = dict(op="average_pool_2d", filter=tuple(pool), padding=pool_padding, strides=(pool_stride, pool_stride), act=pool_act,
+              out_shape=(1, ph, pw, n), out_q=pq)
+    return [conv, pl], (ph, pw, n), pq
+
+
+def conv_pool(rng, shape, n, k, elem=INT8, in_zp=None, **kw):
+    """One Conv2D + AveragePool2D stage as a model of its own (conv_pool_layers' geometry arguments)."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)) if in_zp is None else int(in_zp))
+    layers, _, _ = conv_pool_layers(rng, shape, in_q, n, k, elem=elem, **kw)
+    return build_model((1,) + tuple(int(v) for v in shape), in_q, layers, elem)
+
+
+def lenet(rng, shape=(28, 28, 1), convs=((6, 5), (16, 5)), fcs=(120, 84, 10), elem=INT8, wzp_nonzero=False, softmax=True):
+    """LeNet: per (n, k) of convs a stage Conv2D k x k VALID + relu -> AveragePool2D 2 x 2 stride 2; Reshape; FullyConnected layers
+    (relu between them, none after the last); Softmax.  LeNet-5 on 28 x 28 digits by default; shape = (32, 32, 3) with wider convs is
+    the CIFAR-style stack.  Quantisation as conv_pool_layers and pool_head."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, cur, layers = in_q, tuple(int(v) for v in shape), []
+    for n, k in convs:
+        stage, cur, q = conv_pool_layers(rng, cur, q, int(n), int(k), elem=elem, wzp_nonzero=wzp_nonzero)
+        layers += stage
+    K = cur[0] * cur[1] * cur[2]
+    layers.append(dict(op="reshape", out_shape=(1, K), out_q=q))
+    for i, N in enumerate(int(v) for v in fcs):
+        last = i == len(fcs) - 1
+        a = "none" if last else "relu"
+        wsc = np.float32(rng.uniform(0.002, 0.02))
+        osc = float(np.float32(q[0] * wsc * 60.0 * np.sqrt(K)))
+        ozp = lo if a == "relu" else int(rng.integers(lo + 20, hi - 20))
+        layers.append(dict(op="fully_connected", weights=rng.integers(lo, hi, (N, K)), wscale=[wsc], wzp=[mid + (7 if wzp_nonzero else 0)],
+                           bias=rng.integers(-2000, 2000, N), bscale=[np.float32(q[0]) * wsc], bzp=[0], act=a, out_shape=(1, N), out_q=(osc, ozp)))
+        q, K = (osc, ozp), N
+    if softmax:
+        layers.append(dict(op="softmax", out_shape=(1, K), out_q=(1.0 / 256.0, lo)))
+    return build_model((1,) + tuple(int(v) for v in shape), in_q, layers, elem)
+
+
 def ds_cnn(rng, shape=(49, 10), filters=64, blocks=4, classes=12, stem=(10, 4, (2, 2)), elem=INT8, wzp_nonzero=False):
     """The MLPerf-Tiny keyword spotter's stack (DS-CNN): shape = (frames, coefficients) of ONE channel -- 49 x 10 MFCCs; Conv2D with
     a stem = (KH, KW, strides) filter (conv_net writes square ones only) to `filters` channels, `blocks` x (depthwise 3x3 + 1x1
