@@ -17,6 +17,7 @@
 //     barrier ; the next image's DMA into tile A is issued here and lands during phase B (one staging buffer suffices)
 //     phase B : tile B -> pair B -> HBM
 //     barrier (top of the next step: the DMA has landed, everyone is done with tile B)
+// (ops 5..8 run phase A in the block form, in two sub-phases with a barrier of their own between them: Blk32Phase below.)
 // Column grids, row pads and swizzles are the table rows of the single pairs (kernels.hpp MF_DWRR_SHAPES); the workgroup
 // size is a multiple of four waves (waves go to the SIMDs round-robin per workgroup: anything else loads them unevenly and
 // every barrier waits for the doubled-up ones) over which pair A's unit grid divides; a pair whose grid does not divide runs
@@ -80,9 +81,15 @@
 // 1: in the STEM instances (ops 0..4) pair A runs in the BLOCK form (BlkPhase below): the depthwise taps as ONE v_mfma_i32_16x16x64_i8 per
 // channel quad and 2 x 2 output block instead of three per 16 x 16 outputs, the pointwise 8 -> 16 as four "isolating" v_mfma_i32_16x16x32_i8
 // -- 6 matrix instructions per 64 pixels instead of 10, the same requantisation count.  0: the row form (RrPhase) there as well (A/B;
-// the instances without the stem and the single pairs always run the row form).
+// the instance of ops 1..4 without the stem and the single pairs always run the row form; ops 5..8: MF_Q57_BLOCK).
 #ifndef MF_RR_BLOCK
 #define MF_RR_BLOCK 1
+#endif
+// 1: in the instance of ops 5..8 (Quad57, no stem) pair A runs in the block form as well (Blk32Phase below): the depthwise taps as ONE
+// v_mfma_i32_16x16x64_i8 per channel quad and 16 blocks, gathered from the DMA-staged NHWC tile; the 1x1 behind a workgroup barrier from an
+// NHWC tile of the depthwise result -- 144 matrix instructions per image instead of 288.  0: the row form (A/B).
+#ifndef MF_Q57_BLOCK
+#define MF_Q57_BLOCK 1
 #endif
 #ifndef MF_RR_SP_PAD
 #define MF_RR_SP_PAD 7
@@ -542,6 +549,177 @@ struct BlkPhase {
     }
 };
 
+// The BLOCK form of a stride-1 pair with 32 channels in and out whose input tile is DMA-staged NHWC (pair A of ops 5..8), in two
+// sub-phases with a workgroup barrier between them.
+//   depthwise : the matrix instruction of BlkPhase (column n = a 2 x 2 output block, K = its 4 x 4 patch of one channel quad, operand
+//               build_dw_blk_weights).  A unit is 4 x 4 blocks = 8 x 8 pixels, (H / 8) (W / 8) units per image; wave w runs channel quads
+//               2 w and 2 w + 1 of EVERY unit (the nine units of a 24 x 24 image do not divide over four waves, the eight quads do).
+//   gather    : a lane's 16 K-bytes of one quad are four pixels x four channels, four dwords 32 bytes apart in the tile.  The wave's two
+//               quads are neighbouring dwords of one 16-byte chunk, so ONE ds_read_b64 per patch pixel fetches both: (px0.q, px0.q'),
+//               (px1.q, px1.q') land in the low halves of the two operands, and one v_swap_b32 per pixel pair puts px1.q next to px0.q
+//               -- four reads and two swaps per unit and wave, no other VALU work.
+//   tile A    : [row][x][32 bytes], left pad one pixel, row pitch 800 = 32 + 768 (a row's right halo pixel is the next row's left one:
+//               both hold the input zero point) = 32 mod 256, and the two 16-byte chunks of a pixel change places in the tile rows with
+//               bit 2 set -- on the source side: the DMA lane fetches the other chunk.  All lanes of a read want the same 8 bytes of their
+//               chunk, so the 32 lanes of a half can reach 16 of the 32 bank pairs at best; with this pitch and swizzle they do: 4 cycles
+//               per read, the floor (scripts/model/blk57_banks.py; the row form's pitch 832 unswizzled: 16; four ds_read_b32 per quad: 8
+//               each -- twice the instructions at twice the cycles).
+//   MID       : the requantised depthwise result, [row][x][four 8-byte units], row pitch 768 + 16; lane (n, g') holds pixel g' of block n,
+//               8 bytes for the wave's two quads: one ds_write_b64 per unit into unit w ^ f, f = (bit 2 of x) | (bit 2 of y) << 1.
+//               Conflict-free for the stores and for the reads below (the same script).
+//   pointwise : wave w takes output rows 2 RPW w .. 2 RPW w + 2 RPW - 1 in groups of 2 rows x 8 pixels = the 16 columns of two
+//               v_mfma_i32_16x16x32_i8 (output channels 0..15, 16..31): lane (n, g) reads unit g ^ f of its pixel, channels 8 g .. 8 g + 7,
+//               with one ds_read_b64.  Operand A: pw.wrr, whose K order (byte b of lane group g: channel 4 g + b, 16 + 4 g + b - 4) is that
+//               of the row form's registers; it is brought into channel order with four lane permutes per tile at init.  Rows, constants
+//               and the 8-byte store into tile B are the row form's.
+template <typename Ge, int NWAVE_, int MG, uint32_t XR4, int X2>
+struct Blk32Phase {
+    static constexpr int NWAVE = NWAVE_;
+    static constexpr int LP = 32, ROW = LP + Ge::ROWB, TILE = (Ge::H + 2) * ROW + 32;
+    static constexpr int MROW = Ge::ROWB + 16, MID = Ge::H * MROW;
+    static constexpr int UX = Ge::W / 8, NU = (Ge::H / 8) * UX;             // depthwise units per image
+    static constexpr int RPW = Ge::H / 2 / NWAVE, NPW = RPW * UX;          // pointwise: row pairs and 16-pixel groups per wave
+    static_assert(Ge::C == 32 && Ge::N == 32 && Ge::S == 1 && Ge::CG == 1 && NWAVE == 4, "block form: 32 -> 32 channels, stride 1, two quads per wave");
+    static_assert(Ge::H % 8 == 0 && Ge::W % 8 == 0 && (Ge::H / 2) % NWAVE == 0, "whole units, whole row pairs per wave");
+    static_assert(ROW % 256 == 32 && MROW % 256 == 16 && TILE % 16 == 0 && MID % 16 == 0 && Ge::ROWCH <= 64, "tile A and MID pitches");
+    static_assert((Ge::H / 8) * 8 * ROW + UX * 256 + 128 < 65536 && Ge::H * MROW < 65536, "unit offsets fit the ds offset field");
+    __host__ __device__ static constexpr int swz(int tile_row) { return (tile_row >> 2) & 1; }
+    __host__ __device__ static constexpr int mid_f(int x, int y) { return ((x >> 2) & 1) | (((y >> 2) & 1) << 1); }
+    int tbase;          // this lane's patch row in unit 0: the 8 bytes of the wave's two quads of patch pixel 0
+    int mid_st;         // its 8 result bytes in MID, unit 0
+    int mid_ld[RPW];    // its pointwise operand bytes in MID, pixel group (row pair rp, columns 0..7)
+    int dst_lane;       // its 8 output bytes in tile B, pixel group (0, 0)
+    v4i Adw[2];
+    long Apw[2];
+    float4 dA[2], dS[2], cA[2], cS[2];
+    int4 dK[2], cK[2];
+    float dlo, dhi, plo, phi;
+
+    template <typename NEXT>
+    __device__ __forceinline__ void init(const DwPwArgs &p, int lane, int wave) {
+        static_assert(NEXT::H == Ge::OH && NEXT::W == Ge::OW && NEXT::C == Ge::N && NEXT::NQ == 2, "pair B consumes this pair's output");
+        static_assert(tile_swz<NEXT::TS>(8 * 255) == 0, "x step of a pixel group vs tile B's swizzle");
+        const int n = lane & 15, g = lane >> 4;
+        {
+            const int by = n >> 2, bx = n & 3, r = 2 * by + g;
+            tbase = r * ROW + 64 * bx + 16 * ((wave >> 1) ^ swz(r)) + 8 * (wave & 1); // (LP + 32 (2 bx - 1) = 64 bx)
+            const int y = 2 * by + (g >> 1), x = 2 * bx + (g & 1);
+            mid_st = y * MROW + 32 * x + 8 * (wave ^ mid_f(x, y));
+        }
+        {
+            const int yy = n >> 3, x = n & 7;
+#pragma unroll
+            for (int rp = 0; rp < RPW; ++rp) {
+                const int y = 2 * (RPW * wave + rp) + yy;
+                mid_ld[rp] = y * MROW + 32 * x + 8 * (g ^ mid_f(x, y));
+            }
+            dst_lane = (2 * RPW * wave + yy + 1) * NEXT::ROW + NEXT::LP + x * NEXT::C + 16 * ((g >> 1) ^ tile_swz<NEXT::TS>(x)) + 8 * (g & 1);
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int ch4 = 2 * wave + q;
+            Adw[q] = ((const v4i *)p.dw.wblk)[ch4 * 64 + lane];
+            dA[q] = ((const float4 *)p.dw.A)[ch4];
+            dS[q] = ((const float4 *)p.dw.S)[ch4];
+            dK[q] = magic4<MG>(((const int4 *)p.dw.Kc)[ch4]);
+        }
+        const int n0 = 8 * g;
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            // channel order: K-bytes 8 g .. 8 g + 7 = channel quads 2 g, 2 g + 1; wrr holds quad Q in lane group Q & 3, dword Q >> 2
+            const long w = ((const long *)p.pw.wrr)[m * 64 + lane];
+            const int wlo = (int)(uint32_t)(unsigned long)w, whi = (int)(uint32_t)((unsigned long)w >> 32);
+            const int sa = 4 * (n + 16 * ((2 * g) & 3)), sb = 4 * (n + 16 * ((2 * g + 1) & 3));
+            const int alo = __builtin_amdgcn_ds_bpermute(sa, wlo), ahi = __builtin_amdgcn_ds_bpermute(sa, whi);
+            const int blo = __builtin_amdgcn_ds_bpermute(sb, wlo), bhi = __builtin_amdgcn_ds_bpermute(sb, whi);
+            const uint32_t lo = (uint32_t)(g < 2 ? alo : ahi), hi = (uint32_t)(g < 2 ? blo : bhi);
+            Apw[m] = (long)(((unsigned long)hi << 32) | (unsigned long)lo);
+            cA[m] = *(const float4 *)(p.pw.A + n0 + 4 * m);
+            cS[m] = *(const float4 *)(p.pw.S + n0 + 4 * m);
+            cK[m] = magic4<MG>(*(const int4 *)(p.pw.Kc + n0 + 4 * m));
+        }
+        dlo = p.dw.lo_f, dhi = p.dw.hi_f, plo = p.pw.lo_f, phi = p.pw.hi_f;
+    }
+
+    // depthwise sub-phase: tile A -> MID
+    __device__ __forceinline__ void run_dw(const uint8_t *tb, uint8_t *mid) const {
+        typedef unsigned int u32x2_ __attribute__((ext_vector_type(2)));
+        // (volatile: kept as single 8-byte reads -- paired into ds_read2_b64 they cost four times the cycles, BlkPhase)
+        typedef __attribute__((address_space(3))) const volatile u32x2_ lds_c2;
+        typedef __attribute__((address_space(3))) u32x2_ lds_2;
+        auto load = [&](u32x2_(&b)[4], int u) {
+            lds_u8_t *a = (lds_u8_t *)(tb + tbase) + ((u / UX) * 8 * ROW + (u % UX) * 256);
+#pragma unroll
+            for (int xx = 0; xx < 4; ++xx) b[xx] = *(lds_c2 *)(a + 32 * xx);
+        };
+        // (px0.q, px0.q') (px1.q, px1.q') -> (px0.q, px1.q) (px0.q', px1.q'): the registers stay where the reads put them
+        auto taps = [&](u32x2_(&b)[4], v4i(&acc)[2]) {
+            uint32_t a1 = b[0][1], b0 = b[1][0], c1 = b[2][1], d0 = b[3][0];
+            asm("v_swap_b32 %0, %1" : "+v"(a1), "+v"(b0));
+            asm("v_swap_b32 %0, %1" : "+v"(c1), "+v"(d0));
+            const v4i X = {(int)b[0][0], (int)a1, (int)b[2][0], (int)c1}, Y = {(int)b0, (int)b[1][1], (int)d0, (int)b[3][1]};
+#if MF_QUAD_PRIO
+            __builtin_amdgcn_s_setprio(MF_QUAD_PRIO);
+#endif
+            acc[0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Adw[0], X, v4i{dK[0].x, dK[0].y, dK[0].z, dK[0].w}, 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Adw[1], Y, v4i{dK[1].x, dK[1].y, dK[1].z, dK[1].w}, 0, 0, 0);
+#if MF_QUAD_PRIO
+            __builtin_amdgcn_s_setprio(0);
+#endif
+        };
+        // unit u + 2's reads and unit u + 1's matrix instructions are issued in front of unit u's requantisation
+        u32x2_ b1[4], b2[4];
+        v4i acc[2], accn[2];
+        load(b1, 0);
+        if (NU > 1) load(b2, 1);
+        taps(b1, acc);
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+#pragma unroll
+            for (int xx = 0; xx < 4; ++xx) b1[xx] = b2[xx];
+            if (u + 2 < NU) load(b2, u + 2);
+            if (u + 1 < NU) taps(b1, accn);
+            uint32_t d[2];
+            if constexpr ((X2 & 1) != 0) {
+                requant_pack4x2<MG, XR4>(acc[0], dA[0], dS[0], acc[1], dA[1], dS[1], dlo, dhi, d[0], d[1]);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) d[q] = requant_pack4<MG, XR4>(acc[q][0], acc[q][1], acc[q][2], acc[q][3], dA[q], dS[q], dlo, dhi);
+            }
+            *(lds_2 *)((lds_u8_t *)(mid + mid_st) + ((u / UX) * 8 * MROW + (u % UX) * 256)) = u32x2_{d[0], d[1]};
+            acc[0] = accn[0], acc[1] = accn[1];
+        }
+    }
+
+    // pointwise sub-phase: MID -> tile B (pair B's layout)
+    template <typename NEXT>
+    __device__ __forceinline__ void run_pw(const uint8_t *mid, uint8_t *dst) const {
+        typedef unsigned int u32x2_ __attribute__((ext_vector_type(2)));
+        typedef __attribute__((address_space(3))) const volatile u32x2_ lds_c2;
+        typedef __attribute__((address_space(3))) u32x2_ lds_2;
+        long b[NPW];
+#pragma unroll
+        for (int j = 0; j < NPW; ++j) {
+            const u32x2_ v = *(lds_c2 *)((lds_u8_t *)(mid + mid_ld[j / UX]) + (j % UX) * 256);
+            b[j] = (long)(((unsigned long)v[1] << 32) | (unsigned long)v[0]);
+        }
+#pragma unroll
+        for (int j = 0; j < NPW; ++j) {
+            v4i pa = {cK[0].x, cK[0].y, cK[0].z, cK[0].w}, pb = {cK[1].x, cK[1].y, cK[1].z, cK[1].w};
+            pa = __builtin_amdgcn_mfma_i32_16x16x32_i8(Apw[0], b[j], pa, 0, 0, 0);
+            pb = __builtin_amdgcn_mfma_i32_16x16x32_i8(Apw[1], b[j], pb, 0, 0, 0);
+            uint32_t o[2];
+            if constexpr ((X2 & 2) != 0) {
+                requant_pack4x2<MG, XR4>(pa, cA[0], cS[0], pb, cA[1], cS[1], plo, phi, o[0], o[1]);
+            } else {
+                o[0] = requant_pack4<MG, XR4>(pa[0], pa[1], pa[2], pa[3], cA[0], cS[0], plo, phi);
+                o[1] = requant_pack4<MG, XR4>(pb[0], pb[1], pb[2], pb[3], cA[1], cS[1], plo, phi);
+            }
+            *(lds_2 *)((lds_u8_t *)(dst + dst_lane) + ((j / UX) * 2 * NEXT::ROW + (j % UX) * 8 * NEXT::C)) = u32x2_{o[0], o[1]};
+        }
+    }
+};
+
 
 // the two quads of person_detect: pair geometries = the MF_DWRR_SHAPES rows of the single pairs
 #ifndef MF_Q13B_ROWPAD
@@ -591,11 +769,23 @@ template <typename P> struct blk_or<P, std::void_t<decltype(P::PLANE)>> {
 template <typename Q, bool STEM> constexpr bool quad_blk() {
     return STEM && MF_RR_BLOCK != 0 && MF_QUAD_ASM_LDS == 0;
 }
+// the instance of ops 5..8 runs pair A in the block form of a 32-channel pair (Blk32Phase), with one staging buffer
+template <typename Q, bool STEM> constexpr bool quad_blk32() {
+    return !STEM && MF_Q57_BLOCK != 0 && MF_QUAD_ASM_LDS == 0 && !Q::DBA && Q::G == 1 && Q::A::C == 32 && Q::A::N == 32 && Q::A::S == 1 && Q::ACT_A == 4 &&
+           Q::NTHR == 256;
+}
 template <typename Q, bool STEM, int MG, uint32_t XR4>
-using QuadPhaseA = std::conditional_t<quad_blk<Q, STEM>(), BlkPhase<typename Q::A, Q::ACT_A, MG, XR4>, RrPhase<typename Q::A, Q::G, Q::ACT_A, MG, XR4, Q::X2A>>;
+using QuadPhaseA = std::conditional_t<quad_blk<Q, STEM>(), BlkPhase<typename Q::A, Q::ACT_A, MG, XR4>,
+                                      std::conditional_t<quad_blk32<Q, STEM>(), Blk32Phase<typename Q::A, 4, MG, XR4, Q::X2A>,
+                                                         RrPhase<typename Q::A, Q::G, Q::ACT_A, MG, XR4, Q::X2A>>>;
 template <typename Q, bool STEM> constexpr int quad_buf_a() { // bytes of one tile-A buffer
     if constexpr (quad_blk<Q, STEM>()) return BlkPhase<typename Q::A, Q::ACT_A, 1, 0u>::BYTES;
+    else if constexpr (quad_blk32<Q, STEM>()) return Blk32Phase<typename Q::A, 4, 1, 0u, 0>::TILE;
     else return Q::G * Q::A::TILE;
+}
+template <typename Q, bool STEM> constexpr int quad_mid_bytes() { // the depthwise result between Blk32Phase's two sub-phases
+    if constexpr (quad_blk32<Q, STEM>()) return Blk32Phase<typename Q::A, 4, 1, 0u, 0>::MID;
+    else return 0;
 }
 template <typename Q, bool STEM> constexpr int quad_stem_bytes() {
     return STEM ? 16 + (2 * Q::A::H + 2) * (2 * Q::A::W) : 0;
@@ -618,6 +808,9 @@ __global__ __launch_bounds__(Q::NTHR, Q::WPE) void quad_rr(const int8_t *__restr
     constexpr int S_GUARD = 16, SW = 2 * GA::W, SH = 2 * GA::H, S_TILE = quad_stem_bytes<Q, STEM>(), OFF_Q = OFF_S + S_TILE;
     constexpr int OFF_F = OFF_Q + 16; // (F32IN) the staged f32 image, verbatim: SH rows of SW floats
     constexpr int OFF_C = OFF_F + (F32IN ? 4 * SH * SW : 0); // (STEM, MF_QUAD_STEM_LDS) the stem's operands: QuadArgs::stem's 152 dwords
+    constexpr bool BLK32 = quad_blk32<Q, STEM>();
+    constexpr int OFF_M = OFF_C + (STEM ? 640 : 0);          // (BLK32) the depthwise result of pair A
+    static_assert(!BLK32 || (OFF_M % 16 == 0 && OFF_M + quad_mid_bytes<Q, STEM>() <= 80 * 1024), "two workgroups per CU");
     // (the f32 instance and the two-rounding epilogue forms sit on the 168-register step, where the copy's LDS pointer costs spills: they
     // keep the device-memory reads unless MF_QUAD_STEM_LDS is 2)
     constexpr bool ASMST = MF_QUAD_ASM_LDS == 2 || (MF_QUAD_ASM_LDS == 1 && STEM);
@@ -659,6 +852,17 @@ __global__ __launch_bounds__(Q::NTHR, Q::WPE) void quad_rr(const int8_t *__restr
             for (int k = 0; k < (NI + NWAVE - 1) / NWAVE; ++k) {
                 const int r = k * NWAVE + wave;
                 if (r < NI) dma16(in + ((size_t)st * (SH * SW) + r * 1024 + lane * 16), lds + OFF_S + S_GUARD + SW + r * 1024);
+            }
+            return;
+        }
+        if constexpr (BLK32) { // the block form's tile A: its own row pitch, the 16-byte chunks of a pixel swapped by tile row
+            using PA = QuadPhaseA<Q, STEM, MG, XR4>;
+            static_assert(GA::H % NWAVE == 0, "whole rows per wave");
+#pragma unroll
+            for (int k = 0; k < GA::H / NWAVE; ++k) {
+                const int y = k * NWAVE + wave;
+                if (st < batch && lane < GA::ROWCH)
+                    dma16(in + ((size_t)st * GA::IMG + y * GA::ROWB + (lane ^ PA::swz(y + 1)) * 16), lds + (y + 1) * PA::ROW + PA::LP);
             }
             return;
         }
@@ -831,10 +1035,20 @@ __global__ __launch_bounds__(Q::NTHR, Q::WPE) void quad_rr(const int8_t *__restr
             if constexpr (DBA) { // the other buffer was last read in the previous step's phase A: refill it now, a whole step ahead
                 if (dq.nxt < nsteps && !((MF_QUAD_KO & 8) && ko_steps > 0)) stage(dq.nxt, cur ^ 1);
             }
-            if (Q::ACT_A == NWAVE || wave < Q::ACT_A) pa.template run<GB, ASMST>(lds + (DBA ? cur * BUF_A : 0), lds + OFF_B, gvalid); // pair A: tile A -> tile B
-            if (!(MF_QUAD_KO & 16)) quad_barrier<ASMST>(); // tile B is complete; tile A is free
-            if constexpr (!DBA) {
-                if (dq.nxt < nsteps && !((MF_QUAD_KO & 8) && ko_steps > 0)) stage(dq.nxt); // lands during phase B
+            if constexpr (BLK32) {
+                // pair A in two sub-phases.  Tile A is dead behind the first: the next image's DMAs are issued there and have the pointwise
+                // sub-phase and phase B to land.  They are still issued in front of phase B's output stores: the counted wait above holds
+                pa.run_dw(lds, lds + OFF_M);                    // tile A -> MID
+                if (!(MF_QUAD_KO & 16)) quad_barrier<ASMST>(); // MID is complete; tile A is free
+                if (dq.nxt < nsteps && !((MF_QUAD_KO & 8) && ko_steps > 0)) stage(dq.nxt);
+                pa.template run_pw<GB>(lds + OFF_M, lds + OFF_B); // MID -> tile B
+                if (!(MF_QUAD_KO & 16)) quad_barrier<ASMST>(); // tile B is complete
+            } else {
+                if (Q::ACT_A == NWAVE || wave < Q::ACT_A) pa.template run<GB, ASMST>(lds + (DBA ? cur * BUF_A : 0), lds + OFF_B, gvalid); // pair A: tile A -> tile B
+                if (!(MF_QUAD_KO & 16)) quad_barrier<ASMST>(); // tile B is complete; tile A is free
+                if constexpr (!DBA) {
+                    if (dq.nxt < nsteps && !((MF_QUAD_KO & 8) && ko_steps > 0)) stage(dq.nxt); // lands during phase B
+                }
             }
             if (Q::ACT_B == NWAVE || wave < Q::ACT_B)
                 pb.template run<void>(lds + OFF_B, (uint8_t *)out + (size_t)step * G * GB::OPIX * GB::N, gvalid); // pair B: tile B -> HBM
@@ -848,8 +1062,9 @@ __global__ __launch_bounds__(Q::NTHR, Q::WPE) void quad_rr(const int8_t *__restr
 template <typename Q, bool STEM, int MG, uint32_t XR4, bool F32IN = false>
 static void launch_quad_t(const int8_t *in, int8_t *out, const QuadArgs &a, int batch, hipStream_t s) {
     constexpr int lds = ((Q::DBA && !STEM) ? 2 : 1) * quad_buf_a<Q, STEM>() + 512 + Q::G * Q::B::TILE + 512 + quad_stem_bytes<Q, STEM>() + 16 +
-                        (F32IN ? 4 * (2 * Q::A::H) * (2 * Q::A::W) : 0) + (STEM ? 640 : 0);
+                        (F32IN ? 4 * (2 * Q::A::H) * (2 * Q::A::W) : 0) + (STEM ? 640 : 0) + quad_mid_bytes<Q, STEM>();
     static_assert(lds <= 163840, "quad tiles do not fit the LDS");
+    static_assert(!quad_blk32<Q, STEM>() || lds <= 80 * 1024, "the block form of ops 5..8 keeps two workgroups per CU");
     static LaunchState st;
     const int per_cu = prepared(st, quad_rr<Q, STEM, MG, XR4, F32IN>, Q::NTHR, lds);
     const int nsteps = (batch + Q::G - 1) / Q::G;
@@ -888,6 +1103,7 @@ bool launch_quad(int H, int W, int C, int S, int N, int H2, int W2, int C2, int 
     if (!a.a.dw.wmm || !a.a.pw.wrr || !a.b.dw.wmm || !a.b.pw.wrr) return false;
     if (MF_RR_SPARSE && (!a.a.dw.wsp || !a.b.dw.wsp)) return false; // (no 2:4-sparse form of these taps: the pairs run one by one)
     if (a.stem && quad_blk<Quad13, true>() && (!a.a.dw.wblk || !a.a.pw.wiso)) return false; // (the block form's operands)
+    if (!a.stem && quad_blk32<Quad57, false>() && quad_matches<Quad57>(H, W, C, S, N, H2, W2, C2, S2, N2) && !a.a.dw.wblk) return false;
     int mg = std::min(std::min(a.a.dw.magic, a.a.pw.magic), std::min(a.b.dw.magic, a.b.pw.magic));
     if (a.stem) mg = std::min(mg, a.stem_magic);
     if (mg == 0) return false; // (the quads exist for the bit-pattern epilogues only)

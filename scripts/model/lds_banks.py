@@ -21,6 +21,8 @@ def cycles(addrs, kind):
         groups, width, banks = HALF_GROUPS, 2, 64
     elif kind in ("read_b32", "write_b32"):
         groups, width, banks = HALF_GROUPS, 1, 32
+    elif kind == "write_b64":
+        groups, width, banks = [list(range(16 * i, 16 * i + 16)) for i in range(4)], 2, 32
     else:
         raise ValueError(kind)
     total = 0
@@ -37,4 +39,4 @@ def cycles(addrs, kind):
 
 
 def ideal(kind):
-    return {"read_b128": 4, "read_b64": 2, "read_b32": 2, "write_b32": 2}[kind]
+    return {"read_b128": 4, "read_b64": 2, "read_b32": 2, "write_b32": 2, "write_b64": 4}[kind]
