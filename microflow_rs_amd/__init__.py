@@ -4,7 +4,8 @@ CPU fallback: every compute entry point raises if the library or a GPU is missin
 from ._lib import MicroflowError, lib, lib_path  # noqa: F401
 from .model import Model, model, run_sharded  # noqa: F401
 from . import ops  # noqa: F401
+from .windows import Windows, gather_windows  # noqa: F401
 from .tensor import (FusedActivation, Tensor2D, Tensor4D, TensorViewPadding)  # noqa: F401
 
-__all__ = ["model", "Model", "run_sharded", "ops", "Tensor2D", "Tensor4D", "FusedActivation",
+__all__ = ["model", "Model", "run_sharded", "ops", "Windows", "gather_windows", "Tensor2D", "Tensor4D", "FusedActivation",
            "TensorViewPadding", "MicroflowError", "lib", "lib_path"]

@@ -43,8 +43,15 @@ class OpDesc(C.Structure):
                 ("out_elems", C.c_size_t), ("kernel", C.c_char_p)]
 
 
+class WindowsDesc(C.Structure):
+    """mf_windows (include/microflow_amd.h, section 5)"""
+    _fields_ = [(n, C.c_size_t) for n in ("n_sources", "src_stride", "src_rows", "src_row_elems", "src_pitch",
+                                          "win_rows", "win_row_elems", "hop_rows", "hop_elems")]
+
+
 _i8p, _f32p, _i32p = C.POINTER(C.c_int8), C.POINTER(C.c_float), C.POINTER(C.c_int32)
 _vp = C.c_void_p
+_szp, _wp = C.POINTER(C.c_size_t), C.POINTER(WindowsDesc)
 
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against
 # the declarations in include/microflow_amd.h
@@ -123,12 +130,20 @@ SIGNATURES = {
     "mf_selftest_cvt_pk": (C.c_int, [C.c_int, C.POINTER(C.c_uint64)]),
     "mf_model_time_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_int, C.c_int,
                                        C.POINTER(C.c_float), _vp]),
+    "mf_windows_count": (C.c_int, [_wp, _szp, _szp]),
+    "mf_window_gather": (C.c_int, [C.c_int, _vp, C.c_int, _wp, C.c_size_t, C.c_size_t, _vp, _vp]),
+    "mf_window_gather_quantize": (C.c_int, [C.c_int, _vp, _wp, C.c_size_t, C.c_size_t, C.c_float, C.c_int8, _vp, _vp]),
+    "mf_model_run_windows": (C.c_int, [_vp, _vp, _wp, C.c_size_t, C.c_size_t, _vp, C.c_int]),
+    "mf_model_predict_windows": (C.c_int, [_vp, _vp, _wp, C.c_size_t, C.c_size_t, _vp, C.c_int]),
+    "mf_model_predict_quantized_windows": (C.c_int, [_vp, _vp, _wp, C.c_size_t, C.c_size_t, _vp, C.c_int]),
+    "mf_model_set_window_chunk": (C.c_int, [_vp, C.c_size_t]),
 }
 
 # T = u8 instantiations: the i8 signature with every int8_t value parameter as uint8_t
 for _n in ("mf_preprocess_fully_connected", "mf_preprocess_average_pool_2d",
            "mf_fully_connected_create", "mf_conv_2d_create", "mf_depthwise_conv_2d_create",
-           "mf_average_pool_2d_create", "mf_softmax_create", "mf_quantize", "mf_dequantize"):
+           "mf_average_pool_2d_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
+           "mf_window_gather_quantize"):
     _r, _a = SIGNATURES[_n]
     SIGNATURES[_n + "_u8"] = (_r, [C.c_uint8 if t is C.c_int8 else t for t in _a])
 

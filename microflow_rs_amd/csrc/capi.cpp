@@ -550,6 +550,74 @@ int mf_model_run_until(mf_model *model, const int8_t *input, size_t batch, int l
     })
 }
 
+// ---- 5. sliding windows -------------------------------------------------------------
+// (a description is validated by windows_spec.cpp before anything asks for a device)
+static mf::WindowsGeom windows_checked(const mf_windows *w, size_t input_elems, size_t first, size_t count) {
+    mf::WindowsGeom g;
+    const char *err = "";
+    if (mf::windows_check(w, input_elems, &g, &err) != MF_OK) mf::fail(MF_ERR_INVALID_ARG, err);
+    if (mf::windows_range_check(g, first, count, &err) != MF_OK) mf::fail(MF_ERR_INVALID_ARG, err);
+    return g;
+}
+int mf_windows_count(const mf_windows *w, size_t *per_source, size_t *total) {
+    MF_TRY({
+        const mf::WindowsGeom g = windows_checked(w, 0, 0, 0);
+        if (per_source) *per_source = g.per_source;
+        if (total) *total = g.total;
+    })
+}
+int mf_window_gather(int device, const void *d_src, int elem_bytes, const mf_windows *w, size_t first, size_t count, void *d_dst,
+                     void *stream) {
+    MF_TRY({
+        const mf::WindowsGeom g = windows_checked(w, 0, first, count);
+        if (elem_bytes != 1) mf::fail(MF_ERR_INVALID_ARG, "invalid argument: elem_bytes must be 1");
+        MF_NEED(count == 0 || (d_src && d_dst));
+        mf::dev_window_gather(device, d_src, *w, g, first, count, false, (int8_t *)d_dst, stream);
+    })
+}
+static void gather_quantize(int device, const float *d_src, const mf_windows *w, size_t first, size_t count, float scale, int zp,
+                            bool u8, void *d_dst, void *stream) {
+    const mf::WindowsGeom g = windows_checked(w, 0, first, count);
+    MF_NEED(count == 0 || (d_src && d_dst));
+    if ((uintptr_t)d_src & 3) mf::fail(MF_ERR_INVALID_ARG, "invalid argument: d_src must be 4-byte aligned");
+    const bool fast = mf::dev_quant_div_fast(device, scale, zp, u8);
+    // (real bytes of T out, as mf_quantize / mf_quantize_u8: no move into the internal domain)
+    mf::dev_window_gather_quantize(device, d_src, *w, g, first, count, scale, zp, u8, fast, false, (int8_t *)d_dst, stream);
+}
+int mf_window_gather_quantize(int device, const float *d_src, const mf_windows *w, size_t first, size_t count, float scale,
+                              int8_t zero_point, int8_t *d_dst, void *stream) {
+    MF_TRY({ gather_quantize(device, d_src, w, first, count, scale, zero_point, false, d_dst, stream); })
+}
+int mf_window_gather_quantize_u8(int device, const float *d_src, const mf_windows *w, size_t first, size_t count, float scale,
+                                 uint8_t zero_point, uint8_t *d_dst, void *stream) {
+    MF_TRY({ gather_quantize(device, d_src, w, first, count, scale, zero_point, true, d_dst, stream); })
+}
+int mf_model_run_windows(mf_model *model, const int8_t *src, const mf_windows *w, size_t first, size_t count, int8_t *out, int mem) {
+    MF_TRY({
+        MF_NEED(model && model->impl);
+        mf::model_run_windows(model->impl, nullptr, src, w, first, count, nullptr, out, mem);
+    })
+}
+int mf_model_predict_windows(mf_model *model, const float *src, const mf_windows *w, size_t first, size_t count, float *out, int mem) {
+    MF_TRY({
+        MF_NEED(model && model->impl);
+        mf::model_run_windows(model->impl, src, nullptr, w, first, count, out, nullptr, mem);
+    })
+}
+int mf_model_predict_quantized_windows(mf_model *model, const int8_t *src, const mf_windows *w, size_t first, size_t count, float *out,
+                                       int mem) {
+    MF_TRY({
+        MF_NEED(model && model->impl);
+        mf::model_run_windows(model->impl, nullptr, src, w, first, count, out, nullptr, mem);
+    })
+}
+int mf_model_set_window_chunk(mf_model *model, size_t windows) {
+    MF_TRY({
+        MF_NEED(model && model->impl);
+        mf::model_set_window_chunk(model->impl, windows);
+    })
+}
+
 // ---- 4. measurement helpers -------------------------------------------------------
 int mf_synth_i8(int device, uint64_t seed, uint64_t first_byte, size_t n, int8_t *d_output,
                 void *stream) {

@@ -644,6 +644,13 @@ __device__ __forceinline__ float quant_div(float x, float scale, float rcp, bool
     if (!(__builtin_fabsf(q) <= 3.0e38f)) q = __fdiv_rn(x, scale);
     return q;
 }
+// One value of the boundary quantisation, q = sat(roundf(x / scale + f32(zp))) (src/quantize.rs:16-18; NaN -> 0 as Rust's `as T`):
+// what the separate pass (k_generic.hip quantize_f32, fast = false) and the window gather (k_windows.hip) both evaluate.
+__device__ __forceinline__ int quant_byte(float x, float scale, float rcp, bool fast, float zp_f, float sat_lo, float sat_hi) {
+    const float t = __fadd_rn(quant_div(x, scale, rcp, fast), zp_f);
+    const float r = __fadd_rn(t, __builtin_copysignf(0x1.fffffep-2f, t));
+    return (r != r) ? 0 : (int)__builtin_amdgcn_fmed3f(r, sat_lo, sat_hi);
+}
 
 // 4 x 4 transpose between four registers and the four 16-lane groups of a wave: on return register i of lane
 // group g holds what register g of lane group i held (v_permlane32_swap: lanes 32..63 of the first <-> lanes 0..31 of

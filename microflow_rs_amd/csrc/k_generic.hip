@@ -269,17 +269,13 @@ __global__ __launch_bounds__(256) void quantize_f32(const float *__restrict__ in
         const float xs[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float t = __fadd_rn(__fdiv_rn(xs[k], scale), zp_f);
-            const float r = __fadd_rn(t, __builtin_copysignf(0x1.fffffep-2f, t));
-            q[k] = (r != r) ? 0 : (int)__builtin_amdgcn_fmed3f(r, sat_lo, sat_hi);
+            q[k] = quant_byte(xs[k], scale, 0.0f, false, zp_f, sat_lo, sat_hi);
         }
         ((uint32_t *)out)[i] = pack4(q[0], q[1], q[2], q[3]) ^ (0x01010101u * (uint32_t)xr);
     }
     for (size_t i = (n4 << 2) + (size_t)blockIdx.x * 256 + threadIdx.x; i < n;
          i += (size_t)gridDim.x * 256) {
-        const float t = __fadd_rn(__fdiv_rn(in[i], scale), zp_f);
-        const float r = __fadd_rn(t, __builtin_copysignf(0x1.fffffep-2f, t));
-        const int qi = (r != r) ? 0 : (int)__builtin_amdgcn_fmed3f(r, sat_lo, sat_hi);
+        const int qi = quant_byte(in[i], scale, 0.0f, false, zp_f, sat_lo, sat_hi);
         out[i] = (int8_t)(qi ^ xr);
     }
 }

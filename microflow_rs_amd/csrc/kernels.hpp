@@ -915,6 +915,24 @@ bool verify_fma_form(const float *A, const float *S, const float *C3, const floa
 void launch_quantize(const float *in, int8_t *out, size_t n, float scale, float zp_f, bool u8, hipStream_t s);
 void launch_xor80(const int8_t *in, int8_t *out, size_t n, hipStream_t s);
 void launch_dequantize(const int8_t *in, float *out, size_t n, float scale, float zp_f, bool raw_u8, hipStream_t s);
+// ---- sliding windows of a larger source, gathered into a dense batch (k_windows.hip) ----
+// Window w = first + (dense index) of a validated mf_windows (windows_spec.cpp) starts at source element
+//   (w / (ny nx)) src_stride + ((w / nx) % ny) hop_row_stride + (w % nx) hop_elems
+// and is WR rows of WE elements, src_pitch apart; the launch writes `total` = count x E bytes.  Rows that lie back to back in the
+// source (src_pitch == win_row_elems) are handed over as ONE row of E elements.
+struct WinArgs {
+    size_t src_stride, src_pitch, hop_row_stride, hop_elems;
+    size_t ny, nx, first, total;
+    uint32_t E, WE, WR;      // elements per window, per window row; rows
+    int narrow;              // first + count and total are below 2^32: the index divisions run in 32 bits
+    uint32_t xr4;            // 0, or 0x80808080: real u8 bytes in (gather) / u8 model (quantise), the internal i8 domain out
+    // gather-quantise only: quant_byte's parameters (k_common.hpp)
+    float scale, rcp, zp_f, sat_lo, sat_hi;
+    int fast;
+};
+// src: elem_bytes 1 at any byte address; dst at any byte address (16-byte stores wherever the destination allows them)
+void launch_window_gather(const void *src, int8_t *dst, const WinArgs &a, hipStream_t s);
+void launch_window_gather_quantize(const float *src, int8_t *dst, const WinArgs &a, hipStream_t s); // src 4-byte aligned
 void launch_synth(int8_t *out, size_t n, uint64_t seed, uint64_t first, hipStream_t s);
 void launch_checksum(const int8_t *in, size_t n, unsigned long long *result, hipStream_t s);
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/microflow_amd.h"
+#include "windows_spec.hpp"
 
 namespace mf {
 
@@ -213,6 +214,14 @@ void dev_dequantize(int device, const int8_t *d_in, size_t n, float scale, int z
 void dev_dequantize_u8_raw(int device, const uint8_t *d_in, size_t n, float scale, int zp, float *d_out,
                            void *stream); // real u8 bytes in
 void dev_xor80(int device, const int8_t *d_in, size_t n, int8_t *d_out, void *stream);
+// windows [first, first + count) of a validated description (windows_spec.hpp) as a dense batch at d_dst (k_windows.hip); flip80:
+// every byte ^ 0x80 on the way (a u8 model's internal domain).  The quantising form evaluates dev_quantize's arithmetic per element;
+// `fast`: quant_div's 3-instruction division, only where dev_quant_div_fast said so for (scale, zp, u8)
+void dev_window_gather(int device, const void *d_src, const mf_windows &w, const WindowsGeom &g, size_t first, size_t count, bool flip80,
+                       int8_t *d_dst, void *stream);
+void dev_window_gather_quantize(int device, const float *d_src, const mf_windows &w, const WindowsGeom &g, size_t first, size_t count,
+                                float scale, int zp, bool u8, bool fast, bool flip80, int8_t *d_dst, void *stream);
+bool dev_quant_div_fast(int device, float scale, int zp, bool u8); // verified on the device once per parameter set and process
 void dev_synth_i8(int device, uint64_t seed, uint64_t first, size_t n, int8_t *d_out, void *stream);
 uint64_t dev_checksum_i8(int device, const int8_t *d_in, size_t n, void *stream);
 // exhaustive check of the 3-instruction boundary-quantisation division (k_common.hpp: quant_div): mismatching bytes
@@ -246,6 +255,11 @@ uint64_t model_device_ops(const ModelImpl *m); // kernel launches and device-sid
 // in_f32 or in_i8 (exactly one non-null); out_f32 or out_i8 (exactly one non-null)
 void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t batch,
                float *out_f32, int8_t *out_i8, int mem, int last_op);
+// model_run over windows [first, first + count) of a source (include/microflow_amd.h, section 5): src_f32 or src_i8 (exactly one
+// non-null), out_f32 or out_i8 (exactly one non-null).  Validates before it looks at the device.
+void model_run_windows(ModelImpl *m, const float *src_f32, const int8_t *src_i8, const mf_windows *w, size_t first, size_t count,
+                       float *out_f32, int8_t *out_i8, int mem);
+void model_set_window_chunk(ModelImpl *m, size_t windows);
 void model_time_device(ModelImpl *m, const int8_t *d_in, size_t batch, int8_t *d_out, int warmup,
                        int iters, float *avg_ms, float *per_op_ms);
 

@@ -81,9 +81,20 @@ struct ModelImpl {
     uint64_t graph_launches = 0;
     uint64_t device_ops = 0; // kernel launches and device-side copies enqueued so far (mf_model_device_ops)
 
+    // sliding windows (model_run_windows): its own buffers, which no captured graph refers to
+    size_t win_chunk = 0;     // windows per step (0: window_chunk_default)
+    int8_t *win_q = nullptr;  // the gathered chunk: win_chunk x in_elems bytes, 16-byte aligned (what fused_input_ok asks)
+    void *win_src = nullptr;  // a host-fed source, as it is
+    void *win_out = nullptr;  // the results of a host-fed call, chunk after chunk, until they have crossed back
+    size_t win_q_cap = 0, win_src_cap = 0, win_out_cap = 0; // bytes
+    int win_fast = -1;        // quant_div's fast form verified for the model's input (scale, zero point, type): -1 not asked yet
+
     ~ModelImpl() {
         if (device >= 0) (void)hipSetDevice(device);
         drop_graph();
+        if (win_q) (void)hipFree(win_q);
+        if (win_src) (void)hipFree(win_src);
+        if (win_out) (void)hipFree(win_out);
         if (cap_stream) (void)hipStreamDestroy(cap_stream);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (const Stage &st : stages) fused_destroy(st.f); // they borrow the groups' buffers: first
@@ -852,6 +863,140 @@ void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t ba
             }
         }
         MF_HIP(hipStreamSynchronize(s));
+    } catch (...) {
+        if (m->copy_stream) (void)hipStreamSynchronize(m->copy_stream);
+        (void)hipStreamSynchronize(s);
+        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+        throw;
+    }
+    for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+}
+
+// ---- sliding windows (include/microflow_amd.h, section 5) ----
+// Windows run chunk by chunk: the gather (k_windows.hip) writes a dense chunk into win_q -- quantising an f32 source, moving a u8
+// source into the internal domain on the way, so neither boundary pass runs -- and run_ops takes it from there as it takes any
+// resident batch; the f32 exit stays inside the last launch where the model has one.  Always eager: nothing here looks at or
+// changes the graph kept for model_run's triples, and under set_graph the chunk never outgrows the activation buffers (growing
+// them would drop that graph).
+// The chunk: the sweep (profiles/r16/windows.txt) found every model faster the larger the chunk, up to the whole batch
+// -- a chunk is a gather and a whole launch sequence, and the persistent step-queue kernels want tens of thousands of inputs
+// -- and no step down where the staged bytes outgrow the 256 MiB Infinity Cache.  128 MiB (half that cache) is where the
+// curves have flattened to within a few per cent of the whole batch, and what bounds the staging buffer.
+constexpr size_t WINDOW_CHUNK_BYTES = 128u << 20;
+static size_t window_chunk_default(const ParsedModel &pm) {
+    const size_t per = (WINDOW_CHUNK_BYTES / std::max<size_t>(pm.in_elems, 1)) & ~(size_t)255;
+    return std::max<size_t>(per, 256);
+}
+void model_set_window_chunk(ModelImpl *m, size_t windows) { m->win_chunk = windows; }
+static void window_buffer(ModelImpl *m, void **p, size_t *cap, size_t bytes) {
+    if (*cap >= bytes && *p) return;
+    MF_HIP(hipStreamSynchronize(m->stream)); // an earlier call's launches may still read the old one
+    if (*p) (void)hipFree(*p);
+    *p = nullptr, *cap = 0;
+    MF_HIP(hipMalloc(p, bytes + 256));
+    *cap = bytes;
+}
+
+void model_run_windows(ModelImpl *m, const float *src_f32, const int8_t *src_i8, const mf_windows *w, size_t first, size_t count,
+                       float *out_f32, int8_t *out_i8, int mem) {
+    // ---- arguments: all of it before the device is looked at ----
+    const ParsedModel &pm = m->pm;
+    WindowsGeom g;
+    const char *err = "";
+    if (windows_check(w, pm.in_elems, &g, &err) != MF_OK) fail(MF_ERR_INVALID_ARG, err);
+    if (windows_range_check(g, first, count, &err) != MF_OK) fail(MF_ERR_INVALID_ARG, err);
+    if (mem != MF_MEM_HOST && mem != MF_MEM_DEVICE) fail(MF_ERR_INVALID_ARG, "bad mem kind");
+    const size_t esz = src_f32 ? sizeof(float) : 1, osz = out_f32 ? sizeof(float) : 1;
+    size_t lo = 0, span = 0;
+    windows_span(*w, g, first, count, &lo, &span);
+    if (count) {
+        if ((src_f32 == nullptr) == (src_i8 == nullptr) || (out_f32 == nullptr) == (out_i8 == nullptr)) fail(MF_ERR_INVALID_ARG, "null buffer");
+        if (((uintptr_t)src_f32 & 3) || ((uintptr_t)out_f32 & 3)) fail(MF_ERR_INVALID_ARG, "src / out: f32 buffers must be 4-byte aligned");
+        const uintptr_t sb = (src_f32 ? (uintptr_t)src_f32 : (uintptr_t)src_i8) + lo * esz, se = sb + span * esz;
+        const uintptr_t ob = out_f32 ? (uintptr_t)out_f32 : (uintptr_t)out_i8, oe = ob + count * pm.out_elems * osz;
+        if (ob < se && sb < oe) fail(MF_ERR_INVALID_ARG, "src and out overlap");
+    }
+    if (!m->prepared) {
+        if (dev_count() <= 0) fail(MF_ERR_NO_DEVICE, "no HIP device available: libmicroflow_amd has no CPU fallback");
+        fail(MF_ERR_INVALID_ARG, "model not prepared: call mf_model_prepare first");
+    }
+    if (!count) return;
+
+    MF_HIP(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const bool host = mem == MF_MEM_HOST;
+    const int last_op = (int)pm.ops.size() - 1;
+    size_t chunk = std::min(count, m->win_chunk ? m->win_chunk : window_chunk_default(pm));
+    if (m->use_graph && m->cap_batch) chunk = std::min(chunk, m->cap_batch);
+    ensure_capacity(m, chunk);
+    window_buffer(m, (void **)&m->win_q, &m->win_q_cap, chunk * pm.in_elems);
+    if (src_f32 && m->win_fast < 0) m->win_fast = dev_quant_div_fast(m->device, pm.in_scale, pm.in_zp, pm.u8) ? 1 : 0;
+
+    // the source as the gather sees it: a host source crosses once, whole sources from the first window's to the last window's
+    const void *d_src = src_f32 ? (const void *)src_f32 : (const void *)src_i8;
+    size_t d_first = first;
+    if (host) {
+        window_buffer(m, &m->win_src, &m->win_src_cap, span * esz);
+        window_buffer(m, &m->win_out, &m->win_out_cap, count * pm.out_elems * osz);
+        MF_HIP(hipMemcpyAsync(m->win_src, (const char *)d_src + lo * esz, span * esz, hipMemcpyHostToDevice, s));
+        d_src = m->win_src;
+        d_first = first - (first / g.per_source) * g.per_source;
+    }
+    const bool many = chunk < count;
+    if (host && many && !m->copy_stream) MF_HIP(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
+    std::vector<hipEvent_t> evs;
+    struct OpsAdded {
+        ModelImpl *m;
+        unsigned long long before = dev_launch_counter();
+        ~OpsAdded() { m->device_ops += dev_launch_counter() - before; }
+    } ops_added{m};
+    try {
+        for (size_t done = 0; done < count; done += chunk) {
+            const size_t n = std::min(chunk, count - done);
+            if (src_f32)
+                dev_window_gather_quantize(m->device, (const float *)d_src, *w, g, d_first + done, n, pm.in_scale, pm.in_zp, pm.u8,
+                                           m->win_fast == 1, pm.u8, m->win_q, s);
+            else
+                dev_window_gather(m->device, d_src, *w, g, d_first + done, n, pm.u8, m->win_q, s);
+            // where this chunk's results go on the device: the caller's buffer, or win_out on their way to the host
+            const size_t off = done * pm.out_elems;
+            float *t_f32 = out_f32 ? (host ? (float *)m->win_out : out_f32) + off : nullptr;
+            int8_t *t_i8 = out_i8 ? (host ? (int8_t *)m->win_out : out_i8) + off : nullptr;
+            const void *from; // (host) where the chunk's results lie when its launches are through
+            if (t_f32) {
+                const int8_t *res = run_ops(m, m->win_q, n, last_op, s, nullptr, nullptr, (m->fusion && !m->generic) ? t_f32 : nullptr);
+                if (res) dev_dequantize(m->device, res, n * pm.out_elems, pm.out_scale, pm.out_zp, pm.u8, t_f32, s);
+                from = t_f32;
+            } else if (pm.u8) {
+                const int8_t *res = run_ops(m, m->win_q, n, last_op, s);
+                dev_xor80(m->device, res, n * pm.out_elems, t_i8, s);
+                from = t_i8;
+            } else {
+                const int8_t *res = run_ops(m, m->win_q, n, last_op, s, nullptr, ((uintptr_t)t_i8 & 15) == 0 ? t_i8 : nullptr);
+                from = res; // (an activation buffer where the slice is not aligned for the last launch's 16-byte stores)
+                if (!host && res != t_i8) {
+                    MF_HIP(hipMemcpyAsync(t_i8, res, n * pm.out_elems, hipMemcpyDeviceToDevice, s));
+                    ++dev_launch_counter();
+                }
+            }
+            if (!host) continue;
+            char *h_out = (out_f32 ? (char *)out_f32 : (char *)out_i8) + off * osz;
+            const bool in_win_out = from == (const void *)t_f32 || from == (const void *)t_i8;
+            if (many && in_win_out) { // the slice is not written again: it crosses on the copy stream while the next chunk runs
+                hipEvent_t e;
+                MF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                evs.push_back(e);
+                MF_HIP(hipEventRecord(e, s));
+                MF_HIP(hipStreamWaitEvent(m->copy_stream, e, 0));
+                MF_HIP(hipMemcpyAsync(h_out, from, n * pm.out_elems * osz, hipMemcpyDeviceToHost, m->copy_stream));
+            } else {
+                MF_HIP(hipMemcpyAsync(h_out, from, n * pm.out_elems * osz, hipMemcpyDeviceToHost, s));
+            }
+        }
+        if (host) {
+            MF_HIP(hipStreamSynchronize(s));
+            if (many) MF_HIP(hipStreamSynchronize(m->copy_stream));
+        }
     } catch (...) {
         if (m->copy_stream) (void)hipStreamSynchronize(m->copy_stream);
         (void)hipStreamSynchronize(s);

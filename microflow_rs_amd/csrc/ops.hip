@@ -1131,6 +1131,45 @@ void dev_xor80(int device, const int8_t *d_in, size_t n, int8_t *d_out, void *st
     k::launch_xor80(d_in, d_out, n, (hipStream_t)stream);
     MF_HIP(hipGetLastError());
 }
+// the kernel's view of a validated description: windows [first, first + count)
+static k::WinArgs win_args(const mf_windows &w, const WindowsGeom &g, size_t first, size_t count) {
+    k::WinArgs a{};
+    const size_t E = w.win_rows * w.win_row_elems;
+    if (E > 0x7fffffffull) fail(MF_ERR_INVALID_ARG, "invalid window description: win_rows * win_row_elems is 2^31 or more");
+    if (count > ~(size_t)0 / E) fail(MF_ERR_INVALID_ARG, "invalid window description: count * input_elems overflows");
+    a.src_stride = w.n_sources > 1 ? w.src_stride : 0, a.src_pitch = w.src_pitch;
+    a.hop_row_stride = w.hop_rows * w.src_pitch, a.hop_elems = w.hop_elems;
+    a.ny = g.ny, a.nx = g.nx, a.first = first, a.total = count * E;
+    a.E = (uint32_t)E, a.WE = (uint32_t)w.win_row_elems, a.WR = (uint32_t)w.win_rows;
+    if (w.src_pitch == w.win_row_elems) a.WE = a.E, a.WR = 1; // the window's rows lie back to back: one run
+    a.narrow = (first + count <= 0xffffffffull && a.total <= 0xffffffffull && g.nx <= 0xffffffffull && g.ny <= 0xffffffffull) ? 1 : 0;
+    return a;
+}
+void dev_window_gather(int device, const void *d_src, const mf_windows &w, const WindowsGeom &g, size_t first, size_t count, bool flip80,
+                       int8_t *d_dst, void *stream) {
+    dev_require(device);
+    if (!count) return;
+    k::WinArgs a = win_args(w, g, first, count);
+    a.xr4 = flip80 ? 0x80808080u : 0u;
+    k::launch_window_gather(d_src, d_dst, a, (hipStream_t)stream);
+    MF_HIP(hipGetLastError());
+}
+bool dev_quant_div_fast(int device, float scale, int zp, bool u8) {
+    dev_require(device);
+    return quant_div_verified(device, scale, (float)(1.0 / (double)scale), (float)zp, u8 ? 0.0f : -128.0f, u8 ? 255.0f : 127.0f);
+}
+void dev_window_gather_quantize(int device, const float *d_src, const mf_windows &w, const WindowsGeom &g, size_t first, size_t count,
+                                float scale, int zp, bool u8, bool fast, bool flip80, int8_t *d_dst, void *stream) {
+    dev_require(device);
+    if (!count) return;
+    k::WinArgs a = win_args(w, g, first, count);
+    a.xr4 = flip80 ? 0x80808080u : 0u;
+    a.scale = scale, a.rcp = (float)(1.0 / (double)scale), a.zp_f = (float)zp;
+    a.sat_lo = u8 ? 0.0f : -128.0f, a.sat_hi = u8 ? 255.0f : 127.0f;
+    a.fast = fast ? 1 : 0;
+    k::launch_window_gather_quantize(d_src, d_dst, a, (hipStream_t)stream);
+    MF_HIP(hipGetLastError());
+}
 void dev_synth_i8(int device, uint64_t seed, uint64_t first, size_t n, int8_t *d_out, void *stream) {
     dev_require(device);
     if (!n) return;

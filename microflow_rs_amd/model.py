@@ -208,6 +208,77 @@ class Model:
         _lib.check(_lib.lib().mf_model_run_quantized(self._h, p, batch, o, mem))
         return fin()
 
+    # ---- sliding windows of a larger source (windows.py; include/microflow_amd.h section 5) ----
+    def set_window_chunk(self, windows=0):
+        """windows gathered per step by the *_windows calls; 0 = the library's choice (mf_model_set_window_chunk)"""
+        _lib.check(_lib.lib().mf_model_set_window_chunk(self._h, int(windows)))
+        return self
+
+    def _win_io(self, src, np_dtype, windows, first, count, out_torch_dtype, out_np_dtype, out):
+        """The source (a numpy array: host memory; a cuda tensor: in place, at whatever byte offset it starts) and the result
+        buffer of a *_windows call, with _io's dtype and device checks."""
+        import torch
+        from .windows import _range
+        first, count = _range(windows, first, count)
+        if isinstance(src, torch.Tensor) and not src.is_cuda:
+            src = src.numpy()
+        if np_dtype != np.float32:  # quantized source: the other 1-byte integer type is a caller bug
+            got = src.dtype if isinstance(src, np.ndarray) else getattr(src, "dtype", None)
+            other = {np.int8: (np.dtype(np.uint8), torch.uint8), np.uint8: (np.dtype(np.int8), torch.int8)}[np_dtype]
+            if got is not None and got in other:
+                raise TypeError("model element type is %s, got %s" % (np.dtype(np_dtype).name, got))
+        shape = (count,) + tuple(self.output_shape)
+        if not isinstance(src, torch.Tensor):
+            a = np.ascontiguousarray(src, dtype=np_dtype).reshape(-1)
+            if a.size < windows.source_elems:
+                raise ValueError("source has %d elements, the description needs %d" % (a.size, windows.source_elems))
+            res = np.empty((count, self.output_elems), out_np_dtype)
+            return (a.ctypes.data_as(C.c_void_p), first, count, _lib.MF_MEM_HOST, res.ctypes.data_as(C.c_void_p),
+                    (lambda: res.reshape(shape)), a)
+        want = torch.float32 if np_dtype == np.float32 else self._tdtype()
+        if src.dtype != want:
+            raise TypeError("device source must be a %s tensor, got %s (no implicit cast of device memory)" % (want, src.dtype))
+        if self._device is None and not self._prepared:
+            self._device = src.device.index
+        if self._device is not None and src.device.index != self._device:
+            raise ValueError("source lives on cuda:%s but the model belongs to cuda:%s" % (src.device.index, self._device))
+        xt = src.contiguous().reshape(-1)
+        if xt.numel() < windows.source_elems:
+            raise ValueError("source has %d elements, the description needs %d" % (xt.numel(), windows.source_elems))
+        if out is None:
+            out = torch.empty((count, self.output_elems), dtype=out_torch_dtype, device=xt.device)
+        elif (not out.is_cuda or out.dtype != out_torch_dtype or out.numel() != count * self.output_elems
+              or not out.is_contiguous()):
+            raise ValueError("out= must be a contiguous cuda tensor of %d %s values" % (count * self.output_elems, out_torch_dtype))
+        _lib.check(_lib.lib().mf_model_set_stream(self._h, torch.cuda.current_stream(xt.device).cuda_stream))
+        return xt.data_ptr(), first, count, _lib.MF_MEM_DEVICE, out.data_ptr(), (lambda: out.reshape(shape)), xt
+
+    def _windows_call(self, fn, src, np_dtype, windows, first, count, out_torch_dtype, out_np_dtype, out):
+        p, first, count, mem, o, fin, keep = self._win_io(src, np_dtype, windows, first, count, out_torch_dtype, out_np_dtype, out)
+        d = windows.desc()
+        L = _lib.lib()
+        # (a description the library refuses is refused before a device is asked for: only a valid call prepares the model)
+        _lib.check(L.mf_windows_count(C.byref(d), None, None))
+        if windows.window_elems == self.input_elems and first + count <= windows.total:
+            self._ensure(max(1, min(count, 256)))
+        _lib.check(getattr(L, fn)(self._h, p, C.byref(d), first, count, o, mem))
+        return fin()
+
+    def run_windows(self, src, windows, first=0, count=None, out=None):
+        """run_quantized over windows [first, first + count) of `src` (mf_model_run_windows): [count, *output_shape] of T"""
+        return self._windows_call("mf_model_run_windows", src, self.dtype, windows, first, count, self._tdtype(), self.dtype, out)
+
+    def predict_windows(self, src, windows, first=0, count=None, out=None):
+        """predict over windows of an f32 source (mf_model_predict_windows)"""
+        import torch
+        return self._windows_call("mf_model_predict_windows", src, np.float32, windows, first, count, torch.float32, np.float32, out)
+
+    def predict_quantized_windows(self, src, windows, first=0, count=None, out=None):
+        """predict_quantized over windows of a T source (mf_model_predict_quantized_windows)"""
+        import torch
+        return self._windows_call("mf_model_predict_quantized_windows", src, self.dtype, windows, first, count, torch.float32,
+                                  np.float32, out)
+
     def run_until(self, xq, last_op):
         """int8 output of op `last_op` for the whole batch (per-layer parity localisation)."""
         import torch

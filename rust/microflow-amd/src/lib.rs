@@ -44,6 +44,22 @@ pub struct mf_model_info {
     pub element_type: c_int,
 }
 
+/// A set of sliding windows of a larger source (include/microflow_amd.h, section 5): per source
+/// `(src_rows - win_rows) / hop_rows + 1` by `(src_row_elems - win_row_elems) / hop_elems + 1` windows, no padding.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct mf_windows {
+    pub n_sources: usize,
+    pub src_stride: usize,
+    pub src_rows: usize,
+    pub src_row_elems: usize,
+    pub src_pitch: usize,
+    pub win_rows: usize,
+    pub win_row_elems: usize,
+    pub hop_rows: usize,
+    pub hop_elems: usize,
+}
+
 pub const MF_OK: c_int = 0;
 pub const MF_MEM_HOST: c_int = 0;
 
@@ -64,6 +80,21 @@ extern "C" {
                              output: *mut f32) -> c_int;
     pub fn mf_models_predict_quantized(models: *const *mut mf_model, n_models: c_int, input: *const i8, batch: usize,
                                        output: *mut f32) -> c_int;
+    // sliding windows (section 5 of the header)
+    pub fn mf_windows_count(w: *const mf_windows, per_source: *mut usize, total: *mut usize) -> c_int;
+    pub fn mf_window_gather(device: c_int, d_src: *const c_void, elem_bytes: c_int, w: *const mf_windows, first: usize,
+                            count: usize, d_dst: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn mf_window_gather_quantize(device: c_int, d_src: *const f32, w: *const mf_windows, first: usize, count: usize,
+                                     scale: f32, zero_point: i8, d_dst: *mut i8, stream: *mut c_void) -> c_int;
+    pub fn mf_window_gather_quantize_u8(device: c_int, d_src: *const f32, w: *const mf_windows, first: usize, count: usize,
+                                        scale: f32, zero_point: u8, d_dst: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn mf_model_run_windows(model: *mut mf_model, src: *const i8, w: *const mf_windows, first: usize, count: usize,
+                                out: *mut i8, mem: c_int) -> c_int;
+    pub fn mf_model_predict_windows(model: *mut mf_model, src: *const f32, w: *const mf_windows, first: usize, count: usize,
+                                    out: *mut f32, mem: c_int) -> c_int;
+    pub fn mf_model_predict_quantized_windows(model: *mut mf_model, src: *const i8, w: *const mf_windows, first: usize,
+                                              count: usize, out: *mut f32, mem: c_int) -> c_int;
+    pub fn mf_model_set_window_chunk(model: *mut mf_model, windows: usize) -> c_int;
 }
 
 /// One prepared model on one GPU.  Not `Sync`: the C handle is single-threaded; the macro
@@ -124,6 +155,18 @@ impl Model {
         check(unsafe {
             mf_model_predict_quantized(self.raw, input.as_ptr() as *const i8, batch, out.as_mut_ptr(), MF_MEM_HOST)
         });
+        out
+    }
+    /// `predict` over every window of `src` that `w` describes: the source crosses to the device once, as it is, and
+    /// the windows are gathered there.  Panics on a description the library refuses (a zero hop, a window larger than
+    /// the source or not the model's input size ...), like a shape mismatch would.
+    pub fn predict_windows(&mut self, src: &[f32], w: &mf_windows) -> Vec<f32> {
+        let (mut per, mut total) = (0usize, 0usize);
+        check(unsafe { mf_windows_count(w, &mut per, &mut total) });
+        let stride = if w.n_sources > 1 { w.src_stride } else { 0 };
+        assert!(src.len() >= (w.n_sources - 1) * stride + (w.src_rows - 1) * w.src_pitch + w.src_row_elems);
+        let mut out = vec![0f32; total * self.info.output_elems];
+        check(unsafe { mf_model_predict_windows(self.raw, src.as_ptr(), w, 0, total, out.as_mut_ptr(), MF_MEM_HOST) });
         out
     }
 }
