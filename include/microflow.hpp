@@ -7,7 +7,7 @@
 //
 //   microflow::Tensor2D / Tensor4D                      src/tensor.rs:27-47
 //   microflow::FusedActivation, TensorViewPadding       src/activation.rs:6-13, src/tensor.rs:9-15
-//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / average_pool_2d /
+//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / average_pool_2d / max_pool_2d (ours) /
 //                   softmax / reshape                    src/ops/*.rs
 //   microflow::Model  (what #[model("x.tflite")] generates: predict, predict_quantized)
 //                                                        microflow-macros/src/lib.rs:185-203
@@ -176,6 +176,22 @@ inline Tensor4D average_pool_2d(const Tensor4D &input, std::array<int, 2> filter
                                     output_scale[0], output_zero_point[0], (int)options.fused_activation,
                                     (int)options.view_padding, options.strides[0], options.strides[1], output_shape[0],
                                     output_shape[1], constants[0], constants[1], &op));
+    Tensor4D out;
+    out.buffer = detail::run(op, input.buffer, (size_t)input.batches);
+    out.batches = input.batches, out.rows = output_shape[0], out.cols = output_shape[1], out.chans = input.chans;
+    out.scale = {output_scale[0]}, out.zero_point = {output_zero_point[0]};
+    return out;
+}
+
+// MaxPool2D: no counterpart in the reference (microflow_amd.h states the contract); average_pool_2d's arguments.
+inline Tensor4D max_pool_2d(const Tensor4D &input, std::array<int, 2> filter_shape, std::array<float, 1> output_scale,
+                            std::array<int8_t, 1> output_zero_point, AveragePool2DOptions options,
+                            std::array<float, 2> constants, std::array<int, 2> output_shape, int device = 0) {
+    mf_op *op = nullptr;
+    check(mf_max_pool_2d_create(device, input.rows, input.cols, input.chans, filter_shape[0], filter_shape[1],
+                                output_scale[0], output_zero_point[0], (int)options.fused_activation,
+                                (int)options.view_padding, options.strides[0], options.strides[1], output_shape[0],
+                                output_shape[1], constants[0], constants[1], &op));
     Tensor4D out;
     out.buffer = detail::run(op, input.buffer, (size_t)input.batches);
     out.batches = input.batches, out.rows = output_shape[0], out.cols = output_shape[1], out.chans = input.chans;

@@ -13,6 +13,7 @@ MF_OK, MF_ERR_INVALID_MODEL, MF_ERR_UNSUPPORTED, MF_ERR_INVALID_ARG = 0, 1, 2, 3
 MF_ERR_NO_DEVICE, MF_ERR_HIP, MF_ERR_OOM = 4, 5, 6
 MF_MEM_HOST, MF_MEM_DEVICE = 0, 1
 MF_ELEM_I8, MF_ELEM_U8 = 0, 1
+MF_OP_AVERAGE_POOL_2D, MF_OP_MAX_POOL_2D = 1, 17   # mf_op_kind of the two pools (TFLite builtin codes)
 STATUS_NAMES = {0: "MF_OK", 1: "MF_ERR_INVALID_MODEL", 2: "MF_ERR_UNSUPPORTED",
                 3: "MF_ERR_INVALID_ARG", 4: "MF_ERR_NO_DEVICE", 5: "MF_ERR_HIP", 6: "MF_ERR_OOM"}
 
@@ -81,6 +82,9 @@ SIGNATURES = {
     "mf_average_pool_2d_create": (C.c_int, [C.c_int] * 6 + [C.c_float, C.c_int8, C.c_int, C.c_int,
                                                             C.c_int, C.c_int, C.c_int, C.c_int,
                                                             C.c_float, C.c_float, C.POINTER(_vp)]),
+    "mf_max_pool_2d_create": (C.c_int, [C.c_int] * 6 + [C.c_float, C.c_int8, C.c_int, C.c_int,
+                                                        C.c_int, C.c_int, C.c_int, C.c_int,
+                                                        C.c_float, C.c_float, C.POINTER(_vp)]),
     "mf_softmax_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int8,
                                     C.POINTER(_vp)]),
     "mf_op_run": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
@@ -142,7 +146,7 @@ SIGNATURES = {
 # T = u8 instantiations: the i8 signature with every int8_t value parameter as uint8_t
 for _n in ("mf_preprocess_fully_connected", "mf_preprocess_average_pool_2d",
            "mf_fully_connected_create", "mf_conv_2d_create", "mf_depthwise_conv_2d_create",
-           "mf_average_pool_2d_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
+           "mf_average_pool_2d_create", "mf_max_pool_2d_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
            "mf_window_gather_quantize"):
     _r, _a = SIGNATURES[_n]
     SIGNATURES[_n + "_u8"] = (_r, [C.c_uint8 if t is C.c_int8 else t for t in _a])

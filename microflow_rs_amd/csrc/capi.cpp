@@ -174,16 +174,20 @@ static void create_conv(int device, bool u8, bool dw, int H, int W, int Cin, int
     s.c0 = c0, s.c1 = c1, s.nc1 = nc1;
     wrap_op(mf::op_create(device, s), op);
 }
-static void create_pool(int device, bool u8, int H, int W, int C, int FH, int FW, float output_scale,
+static void create_pool(int device, bool u8, bool mx, int H, int W, int C, int FH, int FW, float output_scale,
                         int ozp, int act, int pad, int sh, int sw, int OH, int OW, float c0, float c1,
                         mf_op **op) {
     MF_NEED(op);
     mf::OpSpec s;
-    s.kind = MF_OP_AVERAGE_POOL_2D, s.u8 = u8;
+    s.kind = mx ? MF_OP_MAX_POOL_2D : MF_OP_AVERAGE_POOL_2D, s.u8 = u8;
     s.H = H, s.W = W, s.C = C, s.N = C, s.KH = FH, s.KW = FW;
     s.oscale = output_scale, s.ozp = ozp, s.act = check_act_arg(act);
     s.pad = check_pad_arg(pad), s.sh = sh, s.sw = sw, s.OH = OH, s.OW = OW;
     s.pool_c0 = c0, s.pool_c1 = c1;
+    // (a geometry MaxPool2D has no value for is a bad argument whether or not there is a device to create the operator on)
+    if (mx && H > 0 && W > 0 && FH > 0 && FW > 0 && sh > 0 && sw > 0 && OH > 0 && OW > 0 &&
+        mf::h_pool_window_empty(H, W, FH, FW, sh, sw, s.pad == MF_PAD_SAME, OH, OW))
+        mf::fail(MF_ERR_INVALID_ARG, "max_pool_2d: a window has no in-bounds tap");
     wrap_op(mf::op_create(device, s), op);
 }
 static void create_softmax(int device, bool u8, int rows, int cols, float input_scale,
@@ -268,7 +272,7 @@ int mf_average_pool_2d_create(int device, int H, int W, int C, int FH, int FW, f
                               int stride_h, int stride_w, int OH, int OW, float c0, float c1,
                               mf_op **op) {
     MF_TRY({
-        create_pool(device, false, H, W, C, FH, FW, output_scale, output_zero_point, fused_activation,
+        create_pool(device, false, false, H, W, C, FH, FW, output_scale, output_zero_point, fused_activation,
                     view_padding, stride_h, stride_w, OH, OW, c0, c1, op);
     })
 }
@@ -277,7 +281,24 @@ int mf_average_pool_2d_create_u8(int device, int H, int W, int C, int FH, int FW
                                  int stride_h, int stride_w, int OH, int OW, float c0, float c1,
                                  mf_op **op) {
     MF_TRY({
-        create_pool(device, true, H, W, C, FH, FW, output_scale, output_zero_point, fused_activation,
+        create_pool(device, true, false, H, W, C, FH, FW, output_scale, output_zero_point, fused_activation,
+                    view_padding, stride_h, stride_w, OH, OW, c0, c1, op);
+    })
+}
+
+int mf_max_pool_2d_create(int device, int H, int W, int C, int FH, int FW, float output_scale,
+                          int8_t output_zero_point, int fused_activation, int view_padding,
+                          int stride_h, int stride_w, int OH, int OW, float c0, float c1, mf_op **op) {
+    MF_TRY({
+        create_pool(device, false, true, H, W, C, FH, FW, output_scale, output_zero_point, fused_activation,
+                    view_padding, stride_h, stride_w, OH, OW, c0, c1, op);
+    })
+}
+int mf_max_pool_2d_create_u8(int device, int H, int W, int C, int FH, int FW, float output_scale,
+                             uint8_t output_zero_point, int fused_activation, int view_padding,
+                             int stride_h, int stride_w, int OH, int OW, float c0, float c1, mf_op **op) {
+    MF_TRY({
+        create_pool(device, true, true, H, W, C, FH, FW, output_scale, output_zero_point, fused_activation,
                     view_padding, stride_h, stride_w, OH, OW, c0, c1, op);
     })
 }

@@ -58,7 +58,10 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
         else k::launch_pair_band(d_in, d_out, f->pairband, (int)batch, st);
         break;
     case FusedImpl::BLOCK: k::launch_block_band(d_in, d_out, f->block, (int)batch, st); break;
-    case FusedImpl::CONVPOOL: k::launch_conv_pool(d_in, d_out, f->convpool.args, f->convpool.wz, (int)batch, st); break;
+    case FusedImpl::CONVPOOL:
+        if (f->convpool.mx) k::launch_conv_maxpool(d_in, d_out, f->convpool.args, f->convpool.wz, (int)batch, st);
+        else k::launch_conv_pool(d_in, d_out, f->convpool.args, f->convpool.wz, (int)batch, st);
+        break;
     case FusedImpl::PAIRWZ: k::launch_pair_wz(d_in, d_out, f->pairwz, (int)batch, st); break;
     case FusedImpl::QUAD: {
         const int *q = f->quad.shape;

@@ -185,13 +185,15 @@ FusedImpl *fused_conv1_fc_create(OpImpl *conv, OpImpl *fc, OpImpl *sm) {
 }
 
 // A Conv2D directly followed by an AveragePool2D with more than one output pixel on exactly its output, as one conv_pool_rt launch
-// (k_conv_pool.hip): the convolution's bytes stay in LDS.  Same device and element type, finite constants, neither forced generic, and
+// (k_conv_pool.hip) -- or by a MaxPool2D, as one conv_maxpool_rt launch (k_conv_maxpool.hip: the same kernel text, plan and
+// conditions; its own name and its own measured exclusions): the convolution's bytes stay in LDS. Same device and element type, finite constants, neither forced generic, and
 // what k::conv_pool_plan accepts.  The weight image, the tables and the padded constants are the group's own, built from the
 // convolution's host copies: alone it may run conv_rows_lds, conv_mm_rt or pw_rt, which keep other images.
 FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool) {
     if (switches().no_conv_pool || !conv || !pool || conv->force_generic || pool->force_generic) return nullptr;
     const OpSpec &d = conv->s, &q = pool->s;
-    if (d.kind != MF_OP_CONV_2D || q.kind != MF_OP_AVERAGE_POOL_2D || conv->device != pool->device || d.u8 != q.u8) return nullptr;
+    const bool mx = q.kind == MF_OP_MAX_POOL_2D;
+    if (d.kind != MF_OP_CONV_2D || (q.kind != MF_OP_AVERAGE_POOL_2D && !mx) || conv->device != pool->device || d.u8 != q.u8) return nullptr;
     if (q.H != d.OH || q.W != d.OW || q.C != d.N) return nullptr; // on exactly the convolution's output
     if (!conv->finite_consts || !std::isfinite(q.pool_c0) || !std::isfinite(q.pool_c1)) return nullptr;
     if (conv->h_w.size() != (size_t)d.N * d.KH * d.KW * d.C || conv->h_A.size() != (size_t)d.N || conv->h_S.size() != (size_t)d.N ||
@@ -215,6 +217,11 @@ FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool) {
     //   real multiply-adds per output pixel, KH KW C N (the chunk's cost is the same, the launches it replaces are cheap: the sweep's
     //   x0.66 - x1.08, none clearing its spread; from 2400 on x1.14 - x2.81, all clearing it).
     const bool slow = d.C == 1 || a.lds > 80 * 1024 || d.N < 16 || (long long)d.KH * d.KW * d.C * d.N < 2400;
+    // With a MaxPool2D behind the convolution the classes were measured anew (profiles/r17/time_conv_maxpool_all.txt and
+    // time_conv_maxpool_sweep.txt) and fall the same way, since phase A is the same and the two launches the group replaces
+    // differ by the pool alone: C = 1 x0.51 / x0.19 / x0.86; beyond 80 KiB x0.68 / x0.76 / x0.75; N = 8 x0.44 - x0.95; below 2400
+    // multiply-adds per output pixel x0.66 - x1.10 with one shape of eleven clearing its spread (16x16x8 -> 32 3x3, 2304: x1.10 against
+    // 8.1 %, while 16x16x4 -> 64 at the same 2304 does not: x1.07 against 10.6 %); from 2400 on x1.15 - x2.82, all clearing it.
     if (slow && !switches().conv_pool_all) return nullptr;
     k::ConvGemmArgs wg{}; // (what conv_gemm_weight_image reads: the filter and its padded row)
     wg.N = d.N, wg.C = d.C, wg.KH = d.KH, wg.KW = d.KW, wg.KWCP = a.KWCP;
@@ -236,9 +243,9 @@ FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool) {
     a.magic = std::min(conv->magic_mode, 2), a.xr = conv->conv.xr;
     a.pool = pool->pool;
     if (pool->pool.xr != a.xr) return nullptr;
-    f->convpool.wz = wz;
+    f->convpool.wz = wz, f->convpool.mx = mx;
     f->epi_mode = a.magic;
-    f->name = "conv_pool_rt<" + std::to_string(d.H) + "x" + std::to_string(d.W) + "x" + std::to_string(d.C) + "-" + std::to_string(d.N) + ";" + std::to_string(d.KH) + "x" +
+    f->name = std::string(mx ? "conv_maxpool_rt<" : "conv_pool_rt<") + std::to_string(d.H) + "x" + std::to_string(d.W) + "x" + std::to_string(d.C) + "-" + std::to_string(d.N) + ";" + std::to_string(d.KH) + "x" +
               std::to_string(d.KW) + (d.sh != 1 || d.sw != 1 ? "s" + std::to_string(d.sh) : "") + ";p" + std::to_string(q.KH) + "x" + std::to_string(q.KW) +
               (q.sh != 1 || q.sw != 1 ? "s" + std::to_string(q.sh) : "") +
               (a.NB == 1 ? ";G" + std::to_string(a.G) : ";PB" + std::to_string(a.PB) + ";NB" + std::to_string(a.NB)) + ">";

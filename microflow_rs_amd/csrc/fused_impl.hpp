@@ -68,10 +68,12 @@ struct FusedImpl {
     // BLOCK: a 1x1 expand + depthwise 3x3 + 1x1 project block in row bands (k_block_band.hip); a = the expand, b = the depthwise, c = the project
     k::BlockBandArgs block{};
     size_t block_max_batch = 0; // 0: any batch; else the largest batch at which the block launch runs (fused_batch_ok): above it the launches it replaces
-    // CONVPOOL: a Conv2D + the AveragePool2D on its output in one launch (k_conv_pool.hip); a = the convolution, b = the pool
+    // CONVPOOL: a Conv2D + the AveragePool2D (k_conv_pool.hip) or MaxPool2D (mx; k_conv_maxpool.hip) on its output in one launch;
+    // a = the convolution, b = the pool
     struct ConvPool {
         k::ConvPoolArgs args{};
         bool wz = false; // the convolution has non-zero filter zero points (internal domain)
+        bool mx = false; // the pool is a MaxPool2D: conv_maxpool_rt
     } convpool;
     // the model's f32 boundary inside this group's launch (fused_set_input_quant / fused_set_output_dequant; KindFacts f32_in / f32_out)
     k::F32Edge edge{};

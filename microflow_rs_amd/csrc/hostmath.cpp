@@ -168,4 +168,11 @@ void h_preprocess_pool(float iscale, int izp, float oscale, int ozp, float *c0, 
     *c1 = (float)ozp - q;
 }
 
+// MaxPool2D has no value for a window without an in-bounds tap.  Along one axis output o reads taps o * s - shift .. + K - 1 with
+// shift <= (K - 1) / 2, so the first window always holds tap 0 and the last one is the only one that can start behind the input.
+bool h_pool_window_empty(int H, int W, int KH, int KW, int sh, int sw, bool same, int OH, int OW) {
+    const long long shy = same ? (KH - 1) / 2 : 0, shx = same ? (KW - 1) / 2 : 0;
+    return (long long)(OH - 1) * sh - shy >= H || (long long)(OW - 1) * sw - shx >= W;
+}
+
 } // namespace mf

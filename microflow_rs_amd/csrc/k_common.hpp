@@ -206,6 +206,21 @@ __device__ __forceinline__ uint32_t pack4(int a, int b, int c, int d) {
     return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
 }
 
+// MaxPool2D's epilogue (maxpool_generic, maxpool_c4, conv_maxpool_rt): average_pool_2d.rs:56 with x := f32(m), m the window's max in
+// the internal i8 domain (monotone in T's value for both element types; p.bias brings it back to T's) --
+// y = roundf(c0 * x + c1) in two roundings, `as T`, the fused activation's clamp.
+__device__ __forceinline__ int maxpool_requant(int m, const PoolArgs &p) {
+    const float x = (float)(m + p.bias);
+    const float y = __fadd_rn(__fmul_rn(p.c0, x), p.c1);
+    const float r = __fadd_rn(y, __builtin_copysignf(0x1.fffffep-2f, y));
+    int q = (r != r) ? 0 : (int)__builtin_amdgcn_fmed3f(r, p.sat_lo, p.sat_hi); // NaN converts to 0 like Rust's `as`
+    q = max(q, p.lo);
+    return min(q, p.hi);
+}
+// two signed 16-bit lanes: v_pk_max_i16 orders a pair of bytes by its high byte first, which is how the packed max pools keep four
+// running byte maxima in two registers (k_generic.hip maxpool_c4)
+typedef short mf_short2 __attribute__((ext_vector_type(2)));
+
 // ------------------------------------------------------------------------
 // The epilogue of the fast kernels: four accumulators -> one packed dword.
 //

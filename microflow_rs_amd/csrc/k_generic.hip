@@ -202,6 +202,66 @@ __global__ __launch_bounds__(256) void avgpool_c4(const int8_t *__restrict__ in,
     }
 }
 
+// MaxPool2D (TFLite builtin 17; the reference has no such operator -- the contract is DESIGN section 2's, the arithmetic k_common.hpp's
+// maxpool_requant): the window is placed as average_pool_2d places it, m = the max over the IN-BOUNDS taps only (no filled halo takes
+// part; a geometry with an empty window is refused at create time).
+__global__ __launch_bounds__(256) void maxpool_generic(const int8_t *__restrict__ in, int8_t *__restrict__ out, PoolArgs p,
+                                                       size_t total) {
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const int c = (int)(idx % p.C);
+        size_t t = idx / p.C;
+        const int ox = (int)(t % p.OW);
+        t /= p.OW;
+        const int oy = (int)(t % p.OH);
+        const size_t img = t / p.OH;
+        const int8_t *ip = in + img * (size_t)p.H * p.W * p.C;
+        const int shy = p.pad_same ? (p.KH - 1) / 2 : 0, shx = p.pad_same ? (p.KW - 1) / 2 : 0;
+        int m = -128; // (the internal i8 domain is monotone in T's value for both element types)
+        for (int ky = 0; ky < p.KH; ++ky) {
+            const int iy = oy * p.sh + ky - shy;
+            for (int kx = 0; kx < p.KW; ++kx) {
+                const int ix = ox * p.sw + kx - shx;
+                if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) m = max(m, (int)ip[((size_t)iy * p.W + ix) * p.C + c]);
+            }
+        }
+        out[idx] = (int8_t)(maxpool_requant(m, p) ^ p.xr);
+    }
+}
+
+// The same operator with 4 channels per thread (C % 4 == 0): avgpool_c4's work split, loads and stores.  gfx950 has no packed
+// 8-bit max, but a signed 16-bit max orders a pair of bytes by its HIGH byte first, so two v_pk_max_i16 per tap -- one on the dword
+// as loaded (bytes 1 and 3 lead their halves), one on the dword shifted left by 8 (bytes 0 and 2 lead) -- keep the four running
+// maxima in the high bytes of the halves; what lands in the low bytes only breaks ties between equal high bytes and is dropped.
+__global__ __launch_bounds__(256) void maxpool_c4(const int8_t *__restrict__ in, int8_t *__restrict__ out, PoolArgs p,
+                                                  size_t total4) {
+    const int C4 = p.C >> 2;
+    const int shy = p.pad_same ? (p.KH - 1) / 2 : 0, shx = p.pad_same ? (p.KW - 1) / 2 : 0;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total4; idx += (size_t)gridDim.x * 256) {
+        const int c4 = (int)(idx % C4);
+        size_t t = idx / C4;
+        const int ox = (int)(t % p.OW);
+        t /= p.OW;
+        const int oy = (int)(t % p.OH);
+        const size_t img = t / p.OH;
+        const int8_t *ip = in + img * (size_t)p.H * p.W * p.C + 4 * c4;
+        mf_short2 odd = {(short)-32768, (short)-32768}, even = odd; // -128 in the high bytes
+        for (int ky = 0; ky < p.KH; ++ky) {
+            const int iy = oy * p.sh + ky - shy;
+            for (int kx = 0; kx < p.KW; ++kx) {
+                const int ix = ox * p.sw + kx - shx;
+                if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) {
+                    const uint32_t v = *(const uint32_t *)(ip + ((size_t)iy * p.W + ix) * p.C);
+                    odd = __builtin_elementwise_max(odd, __builtin_bit_cast(mf_short2, v));
+                    even = __builtin_elementwise_max(even, __builtin_bit_cast(mf_short2, v << 8));
+                }
+            }
+        }
+        const int q0 = maxpool_requant((int)even.x >> 8, p), q1 = maxpool_requant((int)odd.x >> 8, p);
+        const int q2 = maxpool_requant((int)even.y >> 8, p), q3 = maxpool_requant((int)odd.y >> 8, p);
+        ((uint32_t *)out)[idx] = pack4(q0, q1, q2, q3) ^ (0x01010101u * (uint32_t)p.xr);
+    }
+}
+
 // microflow::ops::fully_connected  (src/ops/fully_connected.rs:24-82), any M/K/N.
 // in [batch*M][K], w [N][K], out [batch*M][N].
 __global__ __launch_bounds__(256) void fc_generic(const int8_t *__restrict__ in,
@@ -373,6 +433,14 @@ void launch_avgpool_c4(const int8_t *in, int8_t *out, const PoolArgs &a, size_t 
 void launch_avgpool_generic(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s) {
     const size_t total = batch * a.OH * a.OW * a.C;
     MF_LAUNCH(avgpool_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
+}
+void launch_maxpool_c4(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s) {
+    const size_t total4 = batch * a.OH * a.OW * (a.C / 4);
+    MF_LAUNCH(maxpool_c4, dim3(grid_for(total4)), dim3(256), 0, s, in, out, a, total4);
+}
+void launch_maxpool_generic(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s) {
+    const size_t total = batch * a.OH * a.OW * a.C;
+    MF_LAUNCH(maxpool_generic, dim3(grid_for(total)), dim3(256), 0, s, in, out, a, total);
 }
 void launch_fc_generic(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s) {
     const size_t total = rows * a.N;

@@ -696,6 +696,8 @@ bool conv1x1_rowwave_supported(const ConvArgs &a); // 1x1 filter, stride 1, N <=
 void launch_conv1x1_rowwave(const int8_t *in, int8_t *out, const ConvArgs &a, size_t batch, hipStream_t s);
 void launch_avgpool_generic(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s);
 void launch_avgpool_c4(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s); // C % 4 == 0
+void launch_maxpool_generic(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s); // MaxPool2D: no window may be empty
+void launch_maxpool_c4(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s); // C % 4 == 0
 void launch_fc_generic(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s);
 bool launch_fc_rowwave(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s);
 bool launch_fc_rowwave_softmax(const int8_t *in, int8_t *out, const FcArgs &a, const SoftmaxArgs &sm, size_t rows,
@@ -802,6 +804,8 @@ __host__ __device__ static inline void conv_pool_band(int OH, int POH, int PB, i
 bool conv_pool_plan(ConvPoolArgs &a, std::vector<int> &tap, std::vector<uint32_t> &mask, int H, int W, int C, int N, int KH, int KW, int sh, int sw,
                     int OH, int OW, bool pad_same, bool wz, int PFH, int PFW, int psh, int psw, int POH, int POW, bool pool_same);
 void launch_conv_pool(const int8_t *in, int8_t *out, const ConvPoolArgs &a, bool wz, int batch, hipStream_t s);
+// the same launch with a MaxPool2D behind the convolution (k_conv_maxpool.hip: conv_maxpool_rt; a.pool holds the max pool's arguments)
+void launch_conv_maxpool(const int8_t *in, int8_t *out, const ConvPoolArgs &a, bool wz, int batch, hipStream_t s);
 // DepthwiseConv2D of any C >= 2 with one output per channel, filters up to 7 x 7, (W C) % 4 == 0, with or without filter zero points
 // (k_dw_gemm.hip: dw_gemm_rt): dw_mm_rt's block-diagonal product with operand B read at its natural alignment
 struct DwGemmArgs {

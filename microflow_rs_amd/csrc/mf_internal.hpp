@@ -48,6 +48,8 @@ void h_preprocess_conv(float iscale, int n, const int32_t *bias, const float *bs
                        const int32_t *bzp, int nbz, const float *fscale, int nfq, float oscale,
                        float *c0, float *c1);
 void h_preprocess_pool(float iscale, int izp, float oscale, int ozp, float *c0, float *c1);
+// true: some window of this (positive) pool geometry has no in-bounds tap -- MaxPool2D refuses it
+bool h_pool_window_empty(int H, int W, int KH, int KW, int sh, int sw, bool same, int OH, int OW);
 
 // ---- single-fma requantisation: host search (epi_fma.cpp) -------------------
 // y_u8(acc) = v_cvt_pk_u8_f32(v_fma_f32(S, bits_as_f32(0x4B400000 + acc + d), C))  -- k_common.hpp, epilogue mode 3
@@ -160,7 +162,7 @@ unsigned long long &dev_launch_counter();
 struct FusedImpl;
 FusedImpl *fused_create(OpImpl *dw, OpImpl *pw);
 FusedImpl *fused_block_create(OpImpl *expand, OpImpl *dw, OpImpl *pw, bool pair_grouped = false); // a 1x1 expand + depthwise 3x3 + 1x1 project block in one launch (k_block_band.hip), or nullptr; pair_grouped: the last two have a launch of their own
-FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool); // a Conv2D + the AveragePool2D (more than one output pixel) on its output in one launch (k_conv_pool.hip), or nullptr
+FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool); // a Conv2D + the AveragePool2D (k_conv_pool.hip) or MaxPool2D (k_conv_maxpool.hip) with more than one output pixel on its output in one launch, or nullptr
 // fused tail: AveragePool2D (1x1 output) -> Conv2D 1x1 (N <= 8) -> Softmax (one row of N)
 FusedImpl *fused_tail_create(OpImpl *pool, OpImpl *conv, OpImpl *softmax);
 // fused FullyConnected (row-wave kernel, one row per inference) -> Softmax over its outputs

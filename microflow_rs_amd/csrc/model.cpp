@@ -230,7 +230,7 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             s.nc1 = (int)po.c1.size();
             s.c2 = po.c2.empty() ? nullptr : po.c2.data();
             s.c3 = po.c3;
-            if (po.kind == MF_OP_AVERAGE_POOL_2D) s.pool_c0 = po.c0[0], s.pool_c1 = po.c1[0];
+            if (po.kind == MF_OP_AVERAGE_POOL_2D || po.kind == MF_OP_MAX_POOL_2D) s.pool_c0 = po.c0[0], s.pool_c1 = po.c1[0];
             ops.push_back(nullptr); // reserve the slot first: a throwing push_back must not leak the operator
             ops.back() = op_create(device, s);
             cur_scale = po.out_scale;
@@ -484,7 +484,8 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             }
             i = idx.back();
         }
-        // (6a) a Conv2D directly followed by an AveragePool2D with more than one output pixel -> one conv_pool_rt launch (fused_heads.hip:
+        // (6a) a Conv2D directly followed by an AveragePool2D or a MaxPool2D with more than one output pixel -> one conv_pool_rt /
+        // conv_maxpool_rt launch (fused_heads.hip:
         // fused_conv_pool_create).  Behind every peephole above: a global pool stays with the tail and pool_fc_chain groups, the Conv2D of a
         // depthwise pair with its pair.  A first operator that takes the f32 input inside its own launch keeps that launch (the entry is
         // predict's quantisation inside a launch; the group has no f32 entry)
@@ -493,7 +494,8 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
             while (first_real < n && !ops[first_real]) ++first_real;
             auto free_op = [&](size_t i) { return ops[i] && !fused[i] && !covered(i) && !owned(i); };
             for (size_t i = 0; i + 1 < n; ++i) {
-                if (m->pm.ops[i].kind != MF_OP_CONV_2D || m->pm.ops[i + 1].kind != MF_OP_AVERAGE_POOL_2D || !free_op(i) || !free_op(i + 1)) continue;
+                const int pk = m->pm.ops[i + 1].kind; // (an AveragePool2D: conv_pool_rt; a MaxPool2D: conv_maxpool_rt)
+                if (m->pm.ops[i].kind != MF_OP_CONV_2D || (pk != MF_OP_AVERAGE_POOL_2D && pk != MF_OP_MAX_POOL_2D) || !free_op(i) || !free_op(i + 1)) continue;
                 if (m->pm.ops[i + 1].OH * m->pm.ops[i + 1].OW < 2) continue;
                 if (i == first_real && op_accepts_f32(ops[i])) continue;
                 if (FusedImpl *f = fused_conv_pool_create(ops[i], ops[i + 1])) {

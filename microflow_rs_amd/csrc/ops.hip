@@ -643,12 +643,16 @@ void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
 }
 
 void create_pool(OpImpl &op, const OpSpec &s, int lo, int hi, int xr) {
+    const bool mx = s.kind == MF_OP_MAX_POOL_2D;
+    const std::string nm = mx ? "max_pool_2d" : "average_pool_2d";
     if (s.H <= 0 || s.W <= 0 || s.C <= 0 || s.KH <= 0 || s.KW <= 0 || s.OH <= 0 || s.OW <= 0 ||
         s.sh <= 0 || s.sw <= 0)
-        fail(MF_ERR_INVALID_ARG, "average_pool_2d: bad arguments");
+        fail(MF_ERR_INVALID_ARG, nm + ": bad arguments");
+    if (mx && h_pool_window_empty(s.H, s.W, s.KH, s.KW, s.sh, s.sw, s.pad == MF_PAD_SAME, s.OH, s.OW))
+        fail(MF_ERR_INVALID_ARG, nm + ": a window has no in-bounds tap");
     if (s.pad == MF_PAD_VALID &&
         ((s.OH - 1) * s.sh + s.KH > s.H || (s.OW - 1) * s.sw + s.KW > s.W))
-        fail(MF_ERR_INVALID_ARG, "average_pool_2d: VALID view leaves the input");
+        fail(MF_ERR_INVALID_ARG, nm + ": VALID view leaves the input");
     op.in_elems = (size_t)s.H * s.W * s.C;
     op.out_elems = (size_t)s.OH * s.OW * s.C;
     k::PoolArgs &a = op.pool;
@@ -657,8 +661,9 @@ void create_pool(OpImpl &op, const OpSpec &s, int lo, int hi, int xr) {
     a.c0 = s.pool_c0, a.c1 = s.pool_c1, a.lo = lo, a.hi = hi;
     a.bias = s.u8 ? 128 : 0, a.xr = xr;
     a.sat_lo = s.u8 ? 0.0f : -128.0f, a.sat_hi = s.u8 ? 255.0f : 127.0f;
-    op.generic_name = "avgpool_generic";
-    if (s.C % 4 == 0) op.fast = OpImpl::POOL_C4, op.fast_name = "avgpool_c4"; // 4 channels per thread, dword loads
+    op.generic_name = mx ? "maxpool_generic" : "avgpool_generic";
+    // 4 channels per thread, dword loads
+    if (s.C % 4 == 0) op.fast = mx ? OpImpl::MAXPOOL_C4 : OpImpl::POOL_C4, op.fast_name = mx ? "maxpool_c4" : "avgpool_c4";
 }
 
 void create_fc(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
@@ -782,7 +787,8 @@ OpImpl *op_create(int device, const OpSpec &spec) {
     switch (s.kind) {
     case MF_OP_CONV_2D:
     case MF_OP_DEPTHWISE_CONV_2D: create_conv(*op, s, dom, lo, hi, xr); break;
-    case MF_OP_AVERAGE_POOL_2D: create_pool(*op, s, lo, hi, xr); break;
+    case MF_OP_AVERAGE_POOL_2D:
+    case MF_OP_MAX_POOL_2D: create_pool(*op, s, lo, hi, xr); break;
     case MF_OP_FULLY_CONNECTED: create_fc(*op, s, dom, lo, hi, xr); break;
     case MF_OP_SOFTMAX: create_softmax(*op, s, xr); break;
     default: fail(MF_ERR_UNSUPPORTED, "unsupported operator kind " + std::to_string(s.kind));
@@ -863,6 +869,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             break;
         case OpImpl::POOL_C4:
             k::launch_avgpool_c4(d_in, d_out, op->pool, batch, s);
+            done = true;
+            break;
+        case OpImpl::MAXPOOL_C4:
+            k::launch_maxpool_c4(d_in, d_out, op->pool, batch, s);
             done = true;
             break;
         case OpImpl::DW_C1:
@@ -967,6 +977,7 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
         case MF_OP_CONV_2D: k::launch_conv2d_generic(d_in, d_out, op->conv, batch, s); break;
         case MF_OP_DEPTHWISE_CONV_2D: k::launch_dwconv_generic(d_in, d_out, op->conv, batch, s); break;
         case MF_OP_AVERAGE_POOL_2D: k::launch_avgpool_generic(d_in, d_out, op->pool, batch, s); break;
+        case MF_OP_MAX_POOL_2D: k::launch_maxpool_generic(d_in, d_out, op->pool, batch, s); break;
         case MF_OP_FULLY_CONNECTED: k::launch_fc_generic(d_in, d_out, op->fc, batch * sp.M, s); break;
         case MF_OP_SOFTMAX: k::launch_softmax(d_in, d_out, op->sm, batch, s); break;
         default: fail(MF_ERR_UNSUPPORTED, "op_run: bad kind");

@@ -337,13 +337,15 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
                               po.c1.data());
             break;
         }
-        case MF_OP_AVERAGE_POOL_2D: { // microflow-macros/src/ops/average_pool_2d.rs:47-66
-            require_elem(in, "AveragePool2D", pm.u8), require_elem(out, "AveragePool2D", pm.u8);
-            need_quant(in, "AveragePool2D"), need_quant(out, "AveragePool2D");
+        case MF_OP_AVERAGE_POOL_2D:  // microflow-macros/src/ops/average_pool_2d.rs:47-66
+        case MF_OP_MAX_POOL_2D: {    // (not in the reference: the same options table, checks and constants; include/microflow_amd.h)
+            const char *nm = code == MF_OP_MAX_POOL_2D ? "MaxPool2D" : "AveragePool2D";
+            require_elem(in, nm, pm.u8), require_elem(out, nm, pm.u8);
+            need_quant(in, nm), need_quant(out, nm);
             if (in.shape.size() != 4 || out.shape.size() != 4)
-                fail(MF_ERR_UNSUPPORTED, "AveragePool2D: unsupported tensors");
+                fail(MF_ERR_UNSUPPORTED, std::string(nm) + ": unsupported tensors");
             if (in.shape[0] != 1 || out.shape[0] != 1)
-                fail(MF_ERR_UNSUPPORTED, "AveragePool2D: tensor batch must be 1");
+                fail(MF_ERR_UNSUPPORTED, std::string(nm) + ": tensor batch must be 1");
             set_shapes(po, in, out, pm.u8);
             po.H = in.shape[1], po.W = in.shape[2], po.C = in.shape[3], po.N = po.C;
             po.OH = out.shape[1], po.OW = out.shape[2];
@@ -357,6 +359,9 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             if (po.sh <= 0 || po.sw <= 0 || po.KH <= 0 || po.KW <= 0)
                 fail(MF_ERR_INVALID_MODEL, "invalid model: bad pool geometry");
             if (out.shape[3] != po.C) fail(MF_ERR_INVALID_MODEL, "invalid model: pool channels");
+            if (code == MF_OP_MAX_POOL_2D && (po.H <= 0 || po.W <= 0 || po.OH <= 0 || po.OW <= 0 ||
+                                              h_pool_window_empty(po.H, po.W, po.KH, po.KW, po.sh, po.sw, po.pad == MF_PAD_SAME, po.OH, po.OW)))
+                fail(MF_ERR_INVALID_MODEL, "invalid model: a MaxPool2D window has no in-bounds tap");
             po.c0.resize(1), po.c1.resize(1);
             h_preprocess_pool(in.scale[0], zp_of(in.zp[0], pm.u8), out.scale[0], zp_of(out.zp[0], pm.u8), po.c0.data(),
                               po.c1.data());

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 
-OP_NAMES = {1: "average_pool_2d", 3: "conv_2d", 4: "depthwise_conv_2d", 9: "fully_connected",
+OP_NAMES = {1: "average_pool_2d", 3: "conv_2d", 4: "depthwise_conv_2d", 9: "fully_connected", 17: "max_pool_2d",
             22: "reshape", 25: "softmax"}
 
 

@@ -5,6 +5,7 @@ names, argument order and meaning, executed by the HIP kernels behind the C ABI.
     conv_2d(input, filters, output_scale, output_zero_point, options, constants, output_shape)
     depthwise_conv_2d(input, weights, output_scale, output_zero_point, options, constants, output_shape)
     average_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)
+    max_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)   (not in the reference)
     softmax(input, output_scale, output_zero_point)
     reshape(input, output_shape)
 
@@ -242,6 +243,31 @@ def average_pool_2d(input: Tensor4D, filter_shape, output_scale, output_zero_poi
     shp = tuple(input.buffer.shape)
     op = prepare_average_pool_2d(shp[-3:], filter_shape, output_scale[0], output_zero_point[0],
                                  options, constants, output_shape, dtype=_elem(input.buffer))
+    return Tensor4D(op(input.buffer), list(output_scale), list(output_zero_point))
+
+
+MaxPool2DOptions = AveragePool2DOptions
+
+
+def prepare_max_pool_2d(in_hwc, filter_shape, output_scale, output_zero_point, options,
+                        constants, out_hw, dtype=np.int8):
+    H, W, Cc = in_hwc
+    h = C.c_void_p()
+    _lib.check(_fn("mf_max_pool_2d_create", dtype)(
+        _device(), H, W, Cc, filter_shape[0], filter_shape[1], float(output_scale),
+        int(output_zero_point), int(options.fused_activation), int(options.view_padding),
+        options.strides[0], options.strides[1], out_hw[0], out_hw[1], float(constants[0]),
+        float(constants[1]), C.byref(h)))
+    return PreparedOp(h, (H, W, Cc), (out_hw[0], out_hw[1], Cc), dtype)
+
+
+def max_pool_2d(input: Tensor4D, filter_shape, output_scale, output_zero_point,
+                options: MaxPool2DOptions, constants, output_shape) -> Tensor4D:
+    """MaxPool2D (TFLite builtin 17; the reference has none): average_pool_2d's window placement and constants, the max over the
+    in-bounds taps, then roundf(c0 * f32(max) + c1) and the fused activation (include/microflow_amd.h)."""
+    shp = tuple(input.buffer.shape)
+    op = prepare_max_pool_2d(shp[-3:], filter_shape, output_scale[0], output_zero_point[0],
+                             options, constants, output_shape, dtype=_elem(input.buffer))
     return Tensor4D(op(input.buffer), list(output_scale), list(output_zero_point))
 
 

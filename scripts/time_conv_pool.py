@@ -2,7 +2,7 @@
 """GPU box: Conv2D + AveragePool2D stages as one conv_pool_rt launch (k_conv_pool.hip) against the same model with fusion off (the
 convolution's own launch + avgpool_c4 / avgpool_generic: what ran before the group existed), in the same process, back to back.
 
-    python scripts/time_conv_pool.py [--reps 20] [--repeats 3] [--sweep] [--only 3]
+    python scripts/time_conv_pool.py [--reps 20] [--repeats 3] [--sweep] [--pool max] [--yardsticks] [--only 3]
 
 One line per case: per path the median over --repeats of the median of --reps runs (each run timed with HIP events after warm-up)
 and the spread of those repeats ((max - min) / median), the ratio fusion off / default, whether the ratio clears the larger of the
@@ -10,7 +10,12 @@ two spreads, hbm_frac = batch x (H W C + POH POW N) bytes (the least the stage m
 (the MI355X spec figure; a plain copy reaches 5.3 - 5.6 TB/s, profiles/r03/hbm_copy_ceiling.txt), and whether the two paths gave
 the same bytes.  Under MF_DEV=1 MF_CONV_POOL_ALL=1 the classes the route excludes run as one launch too (what the exclusions are
 read off); under MF_DEV=1 MF_NO_CONV_POOL=1 the first column is the routing the group replaces.  Every case runs in a child
-process of its own under a time limit; the first that fails or runs into its limit ends the run, and nothing more is started."""
+process of its own under a time limit; the first that fails or runs into its limit ends the run, and nothing more is started.
+
+--pool max writes the stages with a MaxPool2D (one conv_maxpool_rt launch, k_conv_maxpool.hip, against the convolution's own launch +
+maxpool_c4 / maxpool_generic).  --yardsticks times, per case and in one process, what the max-pool paths are expected to match: the
+stage's default path with an AveragePool2D against the same stage with a MaxPool2D (the same weights), and -- the first two lines --
+avgpool_c4 against maxpool_c4 alone on 16x16x64 2x2 s2 and 48x48x8 3x3 s2 SAME at batch 65 536."""
 import argparse
 import os
 import subprocess
@@ -59,14 +64,63 @@ def median_ms(fn, reps, warm=3):
     return float(np.median(ts))
 
 
-def one(idx, reps, repeats, cases):
+POOL_OPS = [("16x16x64 p2x2s2", (16, 16, 64), (2, 2), "valid", (8, 8)), ("48x48x8 p3x3s2 same", (48, 48, 8), (3, 3), "same", (24, 24))]
+
+
+def _model(tw, idx, shape, N, K, kw, pool):
+    rng = np.random.default_rng(idx)
+    return tw.lenet(rng, shape, pool=pool) if N is None else tw.conv_pool(rng, shape, N, K, wmax=32, pool_op=pool, **kw)
+
+
+def _alternate(runs, reps, repeats):
+    """-> per run (median of the repeats' medians, spread of the repeats); the runs alternate inside every repeat"""
+    ts = [[] for _ in runs]
+    for _ in range(repeats):
+        for t, fn in zip(ts, runs):
+            t.append(median_ms(fn, reps))
+    return [(float(np.median(t)), (max(t) - min(t)) / float(np.median(t))) for t in ts]
+
+
+def yardstick(idx, reps, repeats, cases):
+    """avg against max in one process: the two pool operators alone (idx < len(POOL_OPS)), else the stage's default path"""
+    import torch
+    import microflow_rs_amd as mf
+    import tflite_writer as tw
+    assert torch.cuda.is_available(), "needs the GPU"
+    if idx < len(POOL_OPS):
+        label, (H, W, C), filt, pad, out_hw = POOL_OPS[idx]
+        batch = 65536
+        opts = mf.ops.AveragePool2DOptions(mf.FusedActivation(0), mf.TensorViewPadding(0 if pad == "same" else 1), (2, 2))
+        ops = [f((H, W, C), filt, 0.05, -3, opts, (1.0, 0.0), out_hw) for f in (mf.ops.prepare_average_pool_2d, mf.ops.prepare_max_pool_2d)]
+        x = torch.randint(-128, 128, (batch, H, W, C), dtype=torch.int8, device="cuda")
+        names = [o.kernel for o in ops]
+        runs = [lambda o=o: o(x) for o in ops]
+        hb = batch * (H * W * C + out_hw[0] * out_hw[1] * C)
+    else:
+        label, shape, N, K, kw, batch = cases[idx - len(POOL_OPS)]
+        ms = [mf.Model(_model(tw, idx - len(POOL_OPS), shape, N, K, kw, pool)) for pool in ("avg", "max")]
+        for m in ms:
+            m.prepare(batch)
+        x = torch.randint(-128, 128, (batch, ms[0].input_elems), dtype=torch.int8, device="cuda")
+        outs = [m.run_quantized(x).clone() for m in ms]
+        names = ["+".join(n for n in (m.op(i)["kernel"] for i in range(m.num_ops)) if n and not n.startswith("(")) for m in ms]
+        runs = [lambda m=m, o=o: m.run_quantized(x, out=o) for m, o in zip(ms, outs)]
+        hb = batch * (ms[0].input_elems + ms[0].output_elems)
+    (avg, s_avg), (mx, s_mx) = _alternate(runs, reps, repeats)
+    spread = max(s_avg, s_mx)
+    print("%-22s batch %6d  avg %8.4f ms (spread %4.1f %%)  max %8.4f ms (spread %4.1f %%)  max / avg %5.3f  %-22s max path %.2f TB/s\n"
+          "    avg: %s\n    max: %s" % (label, batch, avg, 100 * s_avg, mx, 100 * s_mx, mx / avg,
+                                       "within the larger spread" if mx / avg - 1.0 <= spread else "SLOWER by more", hb / (mx * 1e-3) / 1e12, names[0], names[1]),
+          flush=True)
+
+
+def one(idx, reps, repeats, cases, pool="avg"):
     import torch
     import microflow_rs_amd as mf
     import tflite_writer as tw
     assert torch.cuda.is_available(), "needs the GPU"
     label, shape, N, K, kw, batch = cases[idx]
-    rng = np.random.default_rng(idx)
-    m = mf.Model(tw.lenet(rng, shape) if N is None else tw.conv_pool(rng, shape, N, K, wmax=32, **kw))
+    m = mf.Model(_model(tw, idx, shape, N, K, kw, pool))
     m.prepare(batch)
     x = torch.randint(-128, 128, (batch, m.input_elems), dtype=torch.int8, device="cuda")
     out = m.run_quantized(x).clone()
@@ -99,14 +153,17 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--sweep", action="store_true", help="the few-channel sweep instead of the cases")
+    ap.add_argument("--pool", choices=("avg", "max"), default="avg", help="the stages' pool operator")
+    ap.add_argument("--yardsticks", action="store_true", help="avg against max in one process: the two pool operators alone, then every case's default path")
     ap.add_argument("--only", type=int, default=-1, help="run this case in this process (what the parent starts per case)")
     a = ap.parse_args()
     cases = SWEEP if a.sweep else CASES
     if a.only >= 0:
-        return one(a.only, a.reps, a.repeats, cases)
-    for idx in range(len(cases)):
+        return yardstick(a.only, a.reps, a.repeats, cases) if a.yardsticks else one(a.only, a.reps, a.repeats, cases, a.pool)
+    for idx in range(len(cases) + (len(POOL_OPS) if a.yardsticks else 0)):
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--reps", str(a.reps), "--repeats", str(a.repeats), "--only", str(idx)] + (["--sweep"] if a.sweep else []),
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--reps", str(a.reps), "--repeats", str(a.repeats), "--only", str(idx), "--pool", a.pool] +
+                               (["--sweep"] if a.sweep else []) + (["--yardsticks"] if a.yardsticks else []),
                                timeout=STEP_TIMEOUT)
         except subprocess.TimeoutExpired:
             sys.exit("case %d ran into its %d s limit: nothing more is started" % (idx, STEP_TIMEOUT))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes small .tflite models made of the six operators MicroFlow supports
-(microflow-macros/src/lib.rs:138-148), for randomized model-level tests: parser + constant
+(microflow-macros/src/lib.rs:138-148) and MaxPool2D, for randomized model-level tests: parser + constant
 preparation + kernel routing + run, product vs oracle.  Only the fields the MicroFlow front
 end reads are written (tflite.fbs field ids as used by microflow-macros/src/ops/*.rs).
 
@@ -13,6 +13,7 @@ Each layer dict (all quantization parameters are given, nothing is derived):
                       out_shape (1,OH,OW,N), out_q (scale, zp)
     depthwise_conv_2d weights int8 [1,KH,KW,C] + the same fields
     average_pool_2d   filter (h,w), padding, strides, act, out_shape, out_q
+    max_pool_2d       the same fields
     fully_connected   weights int8 [N,K], wscale, wzp, bias int32 [N], bscale, bzp, act, out_shape (M,N), out_q
     reshape           out_shape
     softmax           out_shape, out_q
@@ -24,10 +25,10 @@ import numpy as np
 from make_fc_model import FB, Table, TableVec, Vec, emit, prune_2_4
 
 INT32, UINT8, INT8 = 2, 3, 9
-OPCODES = {"average_pool_2d": 1, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "reshape": 22,
+OPCODES = {"average_pool_2d": 1, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "max_pool_2d": 17, "reshape": 22,
            "softmax": 25}
 # BuiltinOptions union type ids (tflite.fbs)
-OPT_TYPE = {"conv_2d": 1, "depthwise_conv_2d": 2, "average_pool_2d": 5, "fully_connected": 8, "softmax": 9,
+OPT_TYPE = {"conv_2d": 1, "depthwise_conv_2d": 2, "average_pool_2d": 5, "max_pool_2d": 5, "fully_connected": 8, "softmax": 9,
             "reshape": 17}
 ACT = {None: 0, "none": 0, "relu": 1, "relu6": 3, 0: 0, 1: 1, 3: 3}
 PAD = {"same": 0, "valid": 1, 0: 0, 1: 1}
@@ -81,7 +82,7 @@ def build_model(input_shape, input_q, layers, elem=INT8):
                 opts = Table({0: ("i8", PAD[L["padding"]]), 1: ("i32", L["strides"][1]), 2: ("i32", L["strides"][0]),
                               3: ("i32", L.get("depth_multiplier", 1)), 4: ("i8", ACT[L.get("act")])})
             ins = [cur, tw, tb]
-        elif op == "average_pool_2d":
+        elif op in ("average_pool_2d", "max_pool_2d"):
             out = add_tensor(L["out_shape"], elem, 0, *L["out_q"])
             # Pool2DOptions { padding:0 stride_w:1 stride_h:2 filter_width:3 filter_height:4 act:5 }
             opts = Table({0: ("i8", PAD[L["padding"]]), 1: ("i32", L["strides"][1]), 2: ("i32", L["strides"][0]),
@@ -376,12 +377,16 @@ def _same_or_valid(size, k, s, padding):
 
 
 def conv_pool_layers(rng, shape, in_q, n, k, stride=1, padding="valid", act="relu", pool=(2, 2), pool_stride=2, pool_padding="valid",
-                     pool_act="none", pool_q="same", elem=INT8, wzp_nonzero=False, wmax=None):
+                     pool_act="none", pool_q="same", elem=INT8, wzp_nonzero=False, wmax=None, pool_op="avg"):
     """The two layers of one stage, Conv2D k x k (shape = (H, W, C) -> n channels, per-channel filter quantisation, filter zero points
-    off the middle with wzp_nonzero, weights over the full range unless wmax) -> AveragePool2D pool[0] x pool[1]; -> (layers, the
+    off the middle with wzp_nonzero, weights over the full range unless wmax) -> AveragePool2D (pool_op="avg") or MaxPool2D ("max")
+    pool[0] x pool[1]; -> (layers, the
     stage's output (H, W, C), its quantisation).  pool_q: "same" -- the pool's output has its input's scale and zero point, so the
     pooled value is the plain mean and lands on .5 ties -- or a factor on the scale (with a random zero point unless the pool has an
-    activation, which pins it to the type's minimum)."""
+    activation, which pins it to the type's minimum).  `pool` is the window; pool="avg" | "max" names the operator instead (as lenet's
+    argument does) and leaves the window at 2 x 2 -- with another window the operator goes in pool_op."""
+    if isinstance(pool, str):
+        pool, pool_op = (2, 2), pool
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     H, W, C = (int(v) for v in shape)
@@ -400,29 +405,29 @@ def conv_pool_layers(rng, shape, in_q, n, k, stride=1, padding="valid", act="rel
         pq = (osc, ozp)
     else:
         pq = (float(np.float32(osc * pool_q)), lo if pool_act in ("relu", "relu6") else int(rng.integers(lo + 20, hi - 20)))
-    pl = dict(op="average_pool_2d", filter=tuple(pool), padding=pool_padding, strides=(pool_stride, pool_stride), act=pool_act,
+    pl = dict(op={"avg": "average_pool_2d", "max": "max_pool_2d"}[pool_op], filter=tuple(pool), padding=pool_padding, strides=(pool_stride, pool_stride), act=pool_act,
               out_shape=(1, ph, pw, n), out_q=pq)
     return [conv, pl], (ph, pw, n), pq
 
 
 def conv_pool(rng, shape, n, k, elem=INT8, in_zp=None, **kw):
-    """One Conv2D + AveragePool2D stage as a model of its own (conv_pool_layers' geometry arguments)."""
+    """One Conv2D + AveragePool2D (or MaxPool2D: pool="max", or pool_op="max" beside a window) stage as a model of its own
+    (conv_pool_layers' geometry arguments)."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)) if in_zp is None else int(in_zp))
     layers, _, _ = conv_pool_layers(rng, shape, in_q, n, k, elem=elem, **kw)
     return build_model((1,) + tuple(int(v) for v in shape), in_q, layers, elem)
 
 
-def lenet(rng, shape=(28, 28, 1), convs=((6, 5), (16, 5)), fcs=(120, 84, 10), elem=INT8, wzp_nonzero=False, softmax=True):
-    """LeNet: per (n, k) of convs a stage Conv2D k x k VALID + relu -> AveragePool2D 2 x 2 stride 2; Reshape; FullyConnected layers
-    (relu between them, none after the last); Softmax.  LeNet-5 on 28 x 28 digits by default; shape = (32, 32, 3) with wider convs is
-    the CIFAR-style stack.  Quantisation as conv_pool_layers and pool_head."""
+def lenet_layers(rng, shape=(28, 28, 1), convs=((6, 5), (16, 5)), fcs=(120, 84, 10), elem=INT8, wzp_nonzero=False, softmax=True, pool="avg"):
+    """lenet's (input shape, input quantisation, layer dicts): what build_model takes, for tests that write parts of the stack as
+    models of their own."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
     q, cur, layers = in_q, tuple(int(v) for v in shape), []
     for n, k in convs:
-        stage, cur, q = conv_pool_layers(rng, cur, q, int(n), int(k), elem=elem, wzp_nonzero=wzp_nonzero)
+        stage, cur, q = conv_pool_layers(rng, cur, q, int(n), int(k), elem=elem, wzp_nonzero=wzp_nonzero, pool_op=pool)
         layers += stage
     K = cur[0] * cur[1] * cur[2]
     layers.append(dict(op="reshape", out_shape=(1, K), out_q=q))
@@ -437,7 +442,15 @@ def lenet(rng, shape=(28, 28, 1), convs=((6, 5), (16, 5)), fcs=(120, 84, 10), el
         q, K = (osc, ozp), N
     if softmax:
         layers.append(dict(op="softmax", out_shape=(1, K), out_q=(1.0 / 256.0, lo)))
-    return build_model((1,) + tuple(int(v) for v in shape), in_q, layers, elem)
+    return (1,) + tuple(int(v) for v in shape), in_q, layers
+
+
+def lenet(rng, shape=(28, 28, 1), convs=((6, 5), (16, 5)), fcs=(120, 84, 10), elem=INT8, wzp_nonzero=False, softmax=True, pool="avg"):
+    """LeNet: per (n, k) of convs a stage Conv2D k x k VALID + relu -> AveragePool2D (pool="avg") or MaxPool2D ("max") 2 x 2 stride 2;
+    Reshape; FullyConnected layers (relu between them, none after the last); Softmax.  LeNet-5 on 28 x 28 digits by default;
+    shape = (32, 32, 3) with wider convs is the CIFAR-style stack.  Quantisation as conv_pool_layers and pool_head."""
+    in_shape, in_q, layers = lenet_layers(rng, shape, convs, fcs, elem, wzp_nonzero, softmax, pool)
+    return build_model(in_shape, in_q, layers, elem)
 
 
 def ds_cnn(rng, shape=(49, 10), filters=64, blocks=4, classes=12, stem=(10, 4, (2, 2)), elem=INT8, wzp_nonzero=False):
