@@ -202,7 +202,7 @@ FusedImpl *fused_quad_stem_create(OpImpl *stem, FusedImpl *quad) {
     }
     a.stem = (const uint32_t *)keep(*f, tab.data(), tab.size() * 4);
     a.stem_izp4 = sa.izp4, a.stem_lo = sa.lo_f, a.stem_hi = sa.hi_f, a.stem_magic = sa.magic;
-    // the f32 entry (model.cpp sets the stem's input quantisation before the groups are built): same launch, f32 image in
+    // the f32 entry (model_groups.cpp sets the stem's input quantisation before the groups are built): same launch, f32 image in
     a.in_scale = sa.in_scale, a.in_zp_f = sa.in_zp_f, a.in_sat_lo = sa.in_sat_lo, a.in_sat_hi = sa.in_sat_hi;
     a.in_rcp = sa.in_rcp, a.in_xr4 = sa.in_xr4, a.in_fast = sa.in_fast, a.f32_ok = stem->accepts_f32 ? 1 : 0;
     f->epi_mode = std::min(std::min(pair_mode(a.a), pair_mode(a.b)), sa.magic);

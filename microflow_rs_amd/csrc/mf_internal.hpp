@@ -3,6 +3,7 @@
 // Layering:
 //   capi.cpp      extern "C" boundary (include/microflow_amd.h), error translation
 //   model.cpp     .tflite -> ParsedModel -> prepared device ops -> launch sequence
+//   model_groups.cpp   the grouping rules: which operators run as one launch (model_groups.hpp: ModelGroups, the owner of all three tiers)
 //   tflite.cpp    minimal FlatBuffers reader for the ~10 TFLite tables the path needs
 //   hostmath.cpp  f32 constant preparation in the reference's evaluation order
 //   ops.hip       prepared operators: constant folding, kernel routing (one function per route), launches

@@ -17,8 +17,11 @@
 #include <vector>
 
 #include "mf_internal.hpp"
+#include "model_groups.hpp"
 
 namespace mf {
+
+using Stage = ModelGroups::Stage;
 
 #define MF_HIP(call)                                                                          \
     do {                                                                                      \
@@ -34,19 +37,7 @@ struct ModelImpl {
     bool prepared = false;
     bool generic = false;
     hipStream_t stream = nullptr;
-    std::vector<OpImpl *> ops; // nullptr for Reshape
-    // fused[i] != nullptr: ops i .. fused_last[i] run as ONE kernel (depthwise + 1x1 conv pairs;
-    // the pool -> head conv -> [reshape] -> softmax tail)
-    std::vector<FusedImpl *> fused;
-    std::vector<int> fused_last;
-    // second level: ops first .. last (several first-level groups / operators) as ONE kernel: a run of identical pair
-    // groups (k_stage.hip), a one-input-channel depthwise + FullyConnected + Softmax (k_dwfc.hip), the last pair + the
-    // tail (k_tail3.hip).  They do not overlap; what is inside stays available for mf_model_run_until.
-    struct Stage {
-        FusedImpl *f;
-        int first, last;
-    };
-    std::vector<Stage> stages;
+    ModelGroups g; // operators, first-level groups, second-level stages (model_groups.hpp); empty until prepared
     bool fusion = true;
     bool autotune = false; // model_set_autotune: time the run-time-geometry chain candidates at creation
     size_t cap_batch = 0;
@@ -97,9 +88,7 @@ struct ModelImpl {
         if (win_out) (void)hipFree(win_out);
         if (cap_stream) (void)hipStreamDestroy(cap_stream);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        for (const Stage &st : stages) fused_destroy(st.f); // they borrow the groups' buffers: first
-        for (FusedImpl *f : fused) fused_destroy(f);
-        for (OpImpl *o : ops) op_destroy(o);
+        g.clear();
         free_buffers();
     }
     void drop_graph() {
@@ -130,46 +119,107 @@ ModelImpl *model_create(const uint8_t *buf, size_t len) {
 }
 void model_destroy(ModelImpl *m) { delete m; }
 const ParsedModel &model_parsed(const ModelImpl *m) { return m->pm; }
+
+// ---- which launch runs operator i ----
+// The launch that starts at an operator: a second-level stage or a first-level group (f) over operators i .. last, or the
+// operator's own (f == nullptr, last == i).  last < 0: no launch
+struct Launch {
+    FusedImpl *f;
+    int last;
+};
 static bool fused_at(const ModelImpl *m, int i) {
-    return m->fusion && !m->generic && i >= 0 && i < (int)m->fused.size() && m->fused[(size_t)i];
+    return m->fusion && !m->generic && i >= 0 && i < (int)m->g.fused.size() && m->g.fused[(size_t)i];
 }
 // the second-level group that starts at op i and ends at or before last_op, if any
-static const ModelImpl::Stage *stage_at(const ModelImpl *m, int i, int last_op) {
+static const Stage *stage_at(const ModelImpl *m, int i, int last_op) {
     if (!m->fusion || m->generic) return nullptr;
-    for (const ModelImpl::Stage &st : m->stages)
+    for (const Stage &st : m->g.stages)
         if (st.first == i && st.last <= last_op) return &st;
     return nullptr;
+}
+// ... and the first-level group
+static FusedImpl *group_at(const ModelImpl *m, int i, int last_op) {
+    return fused_at(m, i) && m->g.fused_last[(size_t)i] <= last_op ? m->g.fused[(size_t)i] : nullptr;
+}
+// The launch of a run that ends at last_op, at operator i, on this input pointer and batch: the stage, else the group, else the
+// operator (the operators' own launches take any pointer and batch; a group is not asked about the batch)
+static Launch launch_at(const ModelImpl *m, int i, int last_op, const int8_t *d_in, size_t batch) {
+    const Stage *st = stage_at(m, i, last_op);
+    if (st && fused_input_ok(st->f, d_in) && fused_batch_ok(st->f, batch)) return {st->f, st->last};
+    FusedImpl *f = group_at(m, i, last_op);
+    if (f && fused_input_ok(f, d_in)) return {f, m->g.fused_last[(size_t)i]};
+    return {nullptr, i};
+}
+// the stage a run from operator 0 uses for op i: the covering one that starts first
+static const Stage *covering_stage(const ModelImpl *m, int i) {
+    const Stage *best = nullptr;
+    if (m->fusion && !m->generic)
+        for (const Stage &st : m->g.stages)
+            if (i >= st.first && i <= st.last && (!best || st.first < best->first)) best = &st;
+    return best;
 }
 // index of the fused group that swallows op i (without being its first op), or -1
 static int fused_owner(const ModelImpl *m, int i) {
     for (int j = i - 1; j >= 0 && j >= i - 4; --j)
-        if (fused_at(m, j) && m->fused_last[(size_t)j] >= i) return j;
+        if (fused_at(m, j) && m->g.fused_last[(size_t)j] >= i) return j;
     return -1;
 }
 const char *model_op_kernel(const ModelImpl *m, int i) {
-    if (!m->prepared || i < 0 || i >= (int)m->ops.size() || !m->ops[i]) return "";
-    if (m->fusion && !m->generic) { // the stage a run from operator 0 uses for op i: the covering one that starts first
-        const ModelImpl::Stage *best = nullptr;
-        for (const ModelImpl::Stage &st : m->stages)
-            if (i >= st.first && i <= st.last && (!best || st.first < best->first)) best = &st;
-        if (best) return best->first == i ? fused_kernel_name(best->f) : "(fused into the previous operator)";
-    }
-    if (fused_at(m, i)) return fused_kernel_name(m->fused[(size_t)i]);
+    if (!m->prepared || i < 0 || i >= (int)m->g.ops.size() || !m->g.ops[i]) return "";
+    if (const Stage *best = covering_stage(m, i)) return best->first == i ? fused_kernel_name(best->f) : "(fused into the previous operator)";
+    if (fused_at(m, i)) return fused_kernel_name(m->g.fused[(size_t)i]);
     if (fused_owner(m, i) >= 0) return "(fused into the previous operator)";
-    return op_kernel_name(m->ops[i]);
+    return op_kernel_name(m->g.ops[i]);
 }
 
-int model_op_epilogue_mode(const ModelImpl *m, int i) {
-    if (!m->prepared || i < 0 || i >= (int)m->ops.size() || !m->ops[i]) return -1;
-    if (m->fusion && !m->generic) {
-        const ModelImpl::Stage *best = nullptr;
-        for (const ModelImpl::Stage &st : m->stages)
-            if (i >= st.first && i <= st.last && (!best || st.first < best->first)) best = &st;
-        if (best && best->first == i) return fused_epilogue_mode(best->f);
-        if (!best && fused_at(m, i)) return fused_epilogue_mode(m->fused[(size_t)i]);
-    }
-    return op_epilogue_mode(m->ops[i]);
+int model_op_epilogue_mode(const ModelImpl *m, int i) { // (a swallowed operator answers with its own launch's mode)
+    if (!m->prepared || i < 0 || i >= (int)m->g.ops.size() || !m->g.ops[i]) return -1;
+    const Stage *best = covering_stage(m, i);
+    if (best && best->first == i) return fused_epilogue_mode(best->f);
+    if (!best && fused_at(m, i)) return fused_epilogue_mode(m->g.fused[(size_t)i]);
+    return op_epilogue_mode(m->g.ops[i]);
 }
+
+// ---- small helpers of the run paths ----
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t ab = (uintptr_t)a, ae = ab + a_bytes, bb = (uintptr_t)b, be = bb + b_bytes;
+    return ab < be && bb < ae;
+}
+// operator last_op's tensor as a run that ends there returns it: the scale and zero point the operator stamped on it, elements per inference
+struct OutQuant {
+    float scale;
+    int zp;
+    size_t elems;
+};
+static OutQuant out_quant(const ParsedModel &pm, int last_op) {
+    if (last_op == (int)pm.ops.size() - 1) return {pm.out_scale, pm.out_zp, pm.out_elems};
+    const ParsedOp &po = pm.ops[(size_t)last_op];
+    return {po.out_scale, po.out_zp, po.out_elems};
+}
+// What a call enqueues on the device, for mf_model_device_ops, added on every way out: its launches and device-to-device copies;
+// one for a call that launches a graph (replay)
+struct LaunchCount {
+    ModelImpl *m;
+    unsigned long long before = dev_launch_counter();
+    bool replay = false;
+    ~LaunchCount() { m->device_ops += replay ? 1 : dev_launch_counter() - before; }
+};
+// events of one call, destroyed on every way out
+struct EventList {
+    std::vector<hipEvent_t> v;
+    EventList() = default;
+    EventList(const EventList &) = delete;
+    EventList &operator=(const EventList &) = delete;
+    ~EventList() {
+        for (hipEvent_t e : v)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipEvent_t add(unsigned flags) {
+        v.push_back(nullptr); // the slot first: a throwing push_back must not leak the event
+        MF_HIP(hipEventCreateWithFlags(&v.back(), flags));
+        return v.back();
+    }
+};
 
 static void ensure_capacity(ModelImpl *m, size_t batch) {
     if (batch <= m->cap_batch) return;
@@ -191,343 +241,11 @@ void model_prepare(ModelImpl *m, int device, size_t max_batch) {
     if (m->prepared && m->device != device)
         fail(MF_ERR_INVALID_ARG, "model already prepared on another device");
     if (!m->prepared) {
-        // Everything is built in locals and committed only when all of it exists: a failure half way
+        // Everything is built in a local and committed only when all of it exists: a failure half way
         // (a HIP error, OOM, a geometry the operator rejects) leaves the model unprepared and retryable,
         // on this or another device.
-        struct Pending {
-            std::vector<OpImpl *> ops;
-            std::vector<FusedImpl *> fused;
-            ~Pending() {
-                for (FusedImpl *f : fused) fused_destroy(f);
-                for (OpImpl *o : ops) op_destroy(o);
-            }
-        } pend;
-        std::vector<OpImpl *> &ops = pend.ops;
-        // predict_inner's running tensor: every op stamps its output scale / zero point on
-        // it (Tensor::new(output, output_scale, output_zero_point)); Reshape keeps them.
-        float cur_scale = m->pm.in_scale;
-        int cur_zp = m->pm.in_zp;
-        for (const ParsedOp &po : m->pm.ops) {
-            if (po.kind == MF_OP_RESHAPE) {
-                ops.push_back(nullptr);
-                continue;
-            }
-            OpSpec s;
-            s.kind = po.kind;
-            s.u8 = m->pm.u8;
-            s.M = po.M, s.K = po.K, s.N = po.N;
-            s.H = po.H, s.W = po.W, s.C = po.C, s.KH = po.KH, s.KW = po.KW;
-            s.sh = po.sh ? po.sh : 1, s.sw = po.sw ? po.sw : 1, s.pad = po.pad;
-            s.OH = po.OH, s.OW = po.OW, s.act = po.act;
-            s.izp = cur_zp;          // input.zero_point[0] of the running tensor (conv_2d.rs:56)
-            s.in_scale = cur_scale;  // input.scale[0] of the running tensor (softmax.rs:20)
-            s.oscale = po.out_scale, s.ozp = po.out_zp;
-            s.weights = po.weights.empty() ? nullptr : po.weights.data();
-            s.wzp = po.wzp.empty() ? nullptr : po.wzp.data();
-            s.nq = (int)po.wzp.size();
-            s.c0 = po.c0.empty() ? nullptr : po.c0.data();
-            s.c1 = po.c1.empty() ? nullptr : po.c1.data();
-            s.nc1 = (int)po.c1.size();
-            s.c2 = po.c2.empty() ? nullptr : po.c2.data();
-            s.c3 = po.c3;
-            if (po.kind == MF_OP_AVERAGE_POOL_2D || po.kind == MF_OP_MAX_POOL_2D) s.pool_c0 = po.c0[0], s.pool_c1 = po.c1[0];
-            ops.push_back(nullptr); // reserve the slot first: a throwing push_back must not leak the operator
-            ops.back() = op_create(device, s);
-            cur_scale = po.out_scale;
-            cur_zp = po.out_zp;
-        }
-        // peephole (0): the boundary quantize of M::predict folds into operator 0 when that is the stem
-        if (!ops.empty() && ops[0]) (void)op_set_input_quant(ops[0], m->pm.in_scale, m->pm.in_zp, m->pm.u8);
-        // peepholes.  (1) DepthwiseConv2D 3x3 directly followed by a 1x1 Conv2D -> one fused kernel.
-        // (2) AveragePool2D (1x1 output) -> Conv2D 1x1 -> [Reshape] -> Softmax -> one tail kernel.
-        // (3) FullyConnected (few outputs, one row) -> [Reshape] -> Softmax -> one kernel.
-        const size_t n = ops.size();
-        std::vector<FusedImpl *> &fused = pend.fused;
-        fused.assign(n, nullptr);
-        std::vector<int> fused_last(n, -1);
-        for (size_t i = 0; i + 1 < n; ++i) {
-            if (m->pm.ops[i].kind == MF_OP_DEPTHWISE_CONV_2D && m->pm.ops[i + 1].kind == MF_OP_CONV_2D) {
-                if ((fused[i] = fused_create(ops[i], ops[i + 1]))) fused_last[i] = (int)i + 1;
-            } else if (m->pm.ops[i].kind == MF_OP_AVERAGE_POOL_2D && m->pm.ops[i + 1].kind == MF_OP_CONV_2D) {
-                size_t j = i + 2;
-                while (j < n && m->pm.ops[j].kind == MF_OP_RESHAPE) ++j;
-                if (j < n && m->pm.ops[j].kind == MF_OP_SOFTMAX &&
-                    (fused[i] = fused_tail_create(ops[i], ops[i + 1], ops[j])))
-                    fused_last[i] = (int)j;
-            } else if (m->pm.ops[i].kind == MF_OP_FULLY_CONNECTED) { // (3) FC -> [Reshape] -> Softmax
-                size_t j = i + 1;
-                while (j < n && m->pm.ops[j].kind == MF_OP_RESHAPE) ++j;
-                if (j < n && m->pm.ops[j].kind == MF_OP_SOFTMAX &&
-                    (fused[i] = fused_fc_softmax_create(ops[i], ops[j])))
-                    fused_last[i] = (int)j;
-            }
-            if (fused[i]) i = (size_t)fused_last[i]; // groups do not overlap
-        }
-        // second level (the guard destroys what was built if anything below throws)
-        struct StageGuard {
-            std::vector<ModelImpl::Stage> v;
-            ~StageGuard() {
-                for (const ModelImpl::Stage &st : v) fused_destroy(st.f);
-            }
-        } sg;
-        auto covered = [&](size_t i) {
-            for (const ModelImpl::Stage &st : sg.v)
-                if ((int)i >= st.first && (int)i <= st.last) return true;
-            return false;
-        };
-        // (4) runs of consecutive pair groups on one tensor shape -> a persistent stage kernel, if one exists for that
-        // shape and count (fused_stages.hip: fused_stage_create)
-        for (size_t i = 0; i + 1 < n; ++i) {
-            if (!fused[i] || fused_last[i] != (int)i + 1) continue;
-            std::vector<FusedImpl *> run;
-            size_t a = i;
-            while (a + 1 < n && fused[a] && fused_last[a] == (int)a + 1 && m->pm.ops[a].H == m->pm.ops[i].H &&
-                   m->pm.ops[a].W == m->pm.ops[i].W && m->pm.ops[a].C == m->pm.ops[i].C &&
-                   m->pm.ops[a + 1].N == m->pm.ops[i].C && m->pm.ops[a].sh == 1) {
-                run.push_back(fused[a]);
-                a += 2;
-            }
-            // the longest prefix of the run a stage kernel accepts (differing zero points, a run longer than the kernel's
-            // limit ...); what is left forms the next run
-            size_t used = 0;
-            for (size_t k = run.size(); k >= 2 && !used; --k)
-                if (FusedImpl *f = fused_stage_create(run.data(), (int)k)) {
-                    sg.v.push_back({f, (int)i, (int)(i + 2 * k) - 1});
-                    used = k;
-                }
-            if (used) i += 2 * used - 1;             // continue with the pair after the stage
-            else if (!run.empty()) i = a - 1;        // no stage for any prefix: continue after the run
-        }
-        // (4b) two consecutive pair groups whose shapes have a quad kernel (k_quad.hip: a VALU-bound stride-1 pair with the
-        // HBM-bound stride-2 pair behind it; the tensor between them stays in LDS)
-        for (size_t i = 0; i + 3 < n; ++i) {
-            if (!fused[i] || fused_last[i] != (int)i + 1 || covered(i) || covered(i + 2)) continue;
-            if (!fused[i + 2] || fused_last[i + 2] != (int)i + 3) continue;
-            if (FusedImpl *f = fused_quad_create(fused[i], fused[i + 2])) {
-                sg.v.push_back({f, (int)i, (int)i + 3});
-                // ... and with the stem in front of it: ops i - 1 .. i + 3 in one launch.  Both stay: a run that does not
-                // start at the stem (mf_model_run_until pieces, the f32 entry whose stem kernel quantises) uses the quad
-                if (i >= 1 && ops[i - 1] && !fused[i - 1] && !covered(i - 1))
-                    if (FusedImpl *g = fused_quad_stem_create(ops[i - 1], f)) sg.v.push_back({g, (int)i - 1, (int)i + 3});
-                i += 3;
-            }
-        }
-        // (4b') the last pair group directly followed by the tail group -> one kernel (fused_stages.hip: fused_pair_tail_create).  Before the
-        // chain partition below, so that a run-time-geometry pair taken here is not also a candidate there
-        for (size_t i = 0; i + 2 < n; ++i) {
-            if (!fused[i] || fused_last[i] != (int)i + 1 || covered(i)) continue;
-            const size_t j = i + 2;
-            if (fused[j] && !covered(j))
-                if (FusedImpl *f = fused_pair_tail_create(fused[i], fused[j])) {
-                    sg.v.push_back({f, (int)i, fused_last[j]});
-                    // ... and with the pair group in front of it: ops i - 2 .. the tail's end in one launch.  Both stay (a run that
-                    // ends before the tail uses the pair groups, mf_model_run_until pieces that start at i the pair + tail stage)
-                    if (i >= 2 && fused[i - 2] && fused_last[i - 2] == (int)i - 1 && !covered(i - 2))
-                        if (FusedImpl *g = fused_front_pair_tail_create(fused[i - 2], f)) sg.v.push_back({g, (int)i - 2, fused_last[j]});
-                }
-        }
-        // (4c) runs of consecutive run-time-geometry pairs (single-pair chain groups, k_chain.hip): the planner's cost model
-        // decides how the run is cut into chain launches (chain_partition.hip: fused_chain_partition); a pair that is cheapest as two
-        // separate launches loses its group
-        bool chain_runs = false;
-        for (size_t i = 0; i + 1 < n; ++i) {
-            if (!fused_is_chain_single(fused[i]) || fused_last[i] != (int)i + 1 || covered(i)) continue;
-            chain_runs = true;
-            std::vector<FusedImpl *> run;
-            size_t a = i;
-            while (a + 1 < n && fused_is_chain_single(fused[a]) && fused_last[a] == (int)a + 1 && !covered(a)) {
-                run.push_back(fused[a]);
-                a += 2;
-            }
-            const int rn = (int)run.size();
-            std::vector<int> seg((size_t)rn, 0);
-            std::unique_ptr<bool[]> unf(new bool[(size_t)rn]);
-            std::vector<int> segG((size_t)rn, 0);
-            fused_chain_partition(run.data(), rn, seg.data(), unf.get(), segG.data(), m->autotune);
-            for (int k = 0; k < rn; ++k) {
-                const size_t at = i + 2 * (size_t)k;
-                if (seg[(size_t)k] >= 2) {
-                    if (FusedImpl *f = fused_chain_create(run.data() + k, seg[(size_t)k], segG[(size_t)k])) sg.v.push_back({f, (int)at, (int)(at + 2 * (size_t)seg[(size_t)k]) - 1});
-                } else if (seg[(size_t)k] == 1 && unf[(size_t)k]) {
-                    fused_destroy(fused[at]);
-                    fused[at] = nullptr, fused_last[at] = -1;
-                }
-            }
-            i = a - 1;
-        }
-        // (a forced chain plan that met no run was applied to nothing: the caller must not take the result for that plan's)
-        if (!chain_runs && switches().dev && switches_parse().chain_plan_set)
-            fail(MF_ERR_UNSUPPORTED, "MF_CHAIN_PLAN segment 0: the model has no run of run-time-geometry pairs");
-        auto owned = [&](size_t i) {
-            for (size_t j = 0; j < i; ++j)
-                if (fused[j] && fused_last[j] >= (int)i) return true;
-            return false;
-        };
-        // (4d) Conv2D 1x1 (expand) -> DepthwiseConv2D 3x3 -> Conv2D 1x1 (project) with the tensor inside the widest -> one block_band_rt
-        // launch (fused_pairs.hip: fused_block_create).  Behind the chain partition, so that a pair a chain of pairs took is not a
-        // candidate; a first-level pair group at i + 1 stays under the stage (mf_model_run_until pieces use it)
-        for (size_t i = 0; i + 2 < n; ++i) {
-            if (!ops[i] || m->pm.ops[i].kind != MF_OP_CONV_2D || fused[i] || covered(i) || owned(i)) continue;
-            if (!ops[i + 1] || !ops[i + 2] || covered(i + 1) || covered(i + 2)) continue;
-            if (FusedImpl *f = fused_block_create(ops[i], ops[i + 1], ops[i + 2], fused[i + 1] != nullptr)) {
-                sg.v.push_back({f, (int)i, (int)i + 2});
-                i += 2;
-            }
-        }
-        // (5) DepthwiseConv2D with one input channel -> [Reshape] -> the FullyConnected + Softmax group -> one kernel
-        for (size_t i = 0; i + 1 < n; ++i) {
-            if (!ops[i] || fused[i] || covered(i) || m->pm.ops[i].kind != MF_OP_DEPTHWISE_CONV_2D) continue;
-            size_t j = i + 1;
-            while (j < n && m->pm.ops[j].kind == MF_OP_RESHAPE) ++j;
-            if (j < n && fused[j] && !covered(j))
-                if (FusedImpl *f = fused_dwfc_create(ops[i], fused[j])) sg.v.push_back({f, (int)i, fused_last[j]});
-        }
-        auto free_fc = [&](size_t i) {
-            return i < n && ops[i] && m->pm.ops[i].kind == MF_OP_FULLY_CONNECTED && !fused[i] && !covered(i) && !owned(i);
-        };
-        auto free_sm = [&](size_t i) {
-            return i < n && ops[i] && m->pm.ops[i].kind == MF_OP_SOFTMAX && !fused[i] && !covered(i) && !owned(i);
-        };
-        auto skip_reshapes = [&](size_t j) {
-            while (j < n && m->pm.ops[j].kind == MF_OP_RESHAPE) ++j;
-            return j;
-        };
-        // (5a) a DepthwiseConv2D or Conv2D with one input channel -> [Reshape] -> FullyConnected (one row per inference) -> [Reshape] ->
-        // [Softmax] -> one conv1_fc_rt launch (fused_heads.hip: fused_conv1_fc_create) at any geometry its plan accepts; speech.tflite's own
-        // geometry is refused there and keeps (5).  Where the FullyConnected + Softmax already are a group of (3), this stage sits over
-        // conv .. softmax and that group stays for mf_model_run_until pieces.  One FullyConnected only: a run behind it is left to (6)
-        for (size_t i = 0; i + 1 < n; ++i) {
-            const int kind = m->pm.ops[i].kind;
-            if (!ops[i] || fused[i] || covered(i) || owned(i) || (kind != MF_OP_DEPTHWISE_CONV_2D && kind != MF_OP_CONV_2D) || m->pm.ops[i].C != 1) continue;
-            const size_t j0 = skip_reshapes(i + 1);
-            if (j0 >= n || !ops[j0] || m->pm.ops[j0].kind != MF_OP_FULLY_CONNECTED || m->pm.ops[j0].M != 1 || covered(j0) || owned(j0)) continue;
-            if (fused[j0]) {
-                if (fused_last[j0] > (int)j0 && m->pm.ops[(size_t)fused_last[j0]].kind == MF_OP_SOFTMAX)
-                    if (FusedImpl *f = fused_conv1_fc_create(ops[i], ops[j0], ops[(size_t)fused_last[j0]])) sg.v.push_back({f, (int)i, fused_last[j0]});
-                continue;
-            }
-            const size_t smi = skip_reshapes(j0 + 1);
-            OpImpl *sm = free_sm(smi) ? ops[smi] : nullptr;
-            if (sm && !fused_conv1_fc_fits(ops[i], ops[j0], sm)) sm = nullptr; // (the two operators without the Softmax)
-            if (FusedImpl *f = fused_conv1_fc_create(ops[i], ops[j0], sm)) sg.v.push_back({f, (int)i, (int)(sm ? smi : j0)});
-        }
-        // (5b) AveragePool2D over the whole image -> [Reshape] -> FullyConnected layers (one row per inference) -> [Softmax] -> one
-        // pool_fc_chain launch (fused_heads.hip: fused_pool_fc_create), the longest run of layers whose images fit.  Before (6), so that the
-        // FullyConnected run behind a pool is offered here first; what does not fit stays for (6) or keeps its own launches.  Where the
-        // head's FullyConnected + Softmax already are a group of (3), this stage sits over pool .. softmax and that group stays for
-        // mf_model_run_until pieces
-        for (size_t i = 0; i + 1 < n; ++i) {
-            if (!ops[i] || fused[i] || covered(i) || owned(i) || m->pm.ops[i].kind != MF_OP_AVERAGE_POOL_2D) continue;
-            const size_t j0 = skip_reshapes(i + 1);
-            if (j0 < n && fused[j0] && !covered(j0) && m->pm.ops[j0].kind == MF_OP_FULLY_CONNECTED && fused_last[j0] > (int)j0 &&
-                m->pm.ops[(size_t)fused_last[j0]].kind == MF_OP_SOFTMAX) {
-                OpImpl *fc = ops[j0];
-                if (FusedImpl *f = fused_pool_fc_create(ops[i], &fc, 1, ops[(size_t)fused_last[j0]])) sg.v.push_back({f, (int)i, fused_last[j0]});
-                continue;
-            }
-            if (!free_fc(j0) || m->pm.ops[j0].M != 1) continue;
-            std::vector<size_t> idx{j0};
-            for (;;) {
-                const size_t j = skip_reshapes(idx.back() + 1);
-                if (!free_fc(j) || m->pm.ops[j].M != 1 || m->pm.ops[j].K != m->pm.ops[idx.back()].N) break;
-                idx.push_back(j);
-            }
-            std::vector<OpImpl *> run;
-            for (size_t j : idx) run.push_back(ops[j]);
-            for (size_t len = run.size(); len >= 1; --len) {
-                const size_t smi = skip_reshapes(idx[len - 1] + 1);
-                OpImpl *sm = free_sm(smi) ? ops[smi] : nullptr;
-                if (sm && !fused_pool_fc_fits(ops[i], run.data(), (int)len, sm)) sm = nullptr; // (the layers without their Softmax)
-                if (FusedImpl *f = fused_pool_fc_create(ops[i], run.data(), (int)len, sm)) {
-                    sg.v.push_back({f, (int)i, (int)(sm ? smi : idx[len - 1])});
-                    break;
-                }
-            }
-        }
-        // (6) runs of consecutive FullyConnected operators (Reshapes between them keeping the [M][N] rows; + a Softmax over one row at
-        // the end) that no group above took -> fc_chain launches (k_fc_rt.hip), cut greedily into the longest chains whose weights fit
-        // the LDS budget; a layer that fits no chain keeps its own launch
-        for (size_t i = 0; i < n; ++i) {
-            if (!free_fc(i)) continue;
-            std::vector<size_t> idx{i};
-            for (;;) {
-                size_t j = idx.back() + 1;
-                while (j < n && m->pm.ops[j].kind == MF_OP_RESHAPE) ++j;
-                if (!free_fc(j) || m->pm.ops[j].M != m->pm.ops[idx.back()].M || m->pm.ops[j].K != m->pm.ops[idx.back()].N) break;
-                idx.push_back(j);
-            }
-            size_t smi = idx.back() + 1;
-            while (smi < n && m->pm.ops[smi].kind == MF_OP_RESHAPE) ++smi;
-            OpImpl *sm = (smi < n && ops[smi] && m->pm.ops[smi].kind == MF_OP_SOFTMAX && !fused[smi] && !covered(smi) && !owned(smi)) ? ops[smi] : nullptr;
-            std::vector<OpImpl *> run;
-            for (size_t j : idx) run.push_back(ops[j]);
-            size_t pos = 0;
-            while (pos < run.size()) {
-                int best = 0;
-                bool best_sm = false;
-                for (size_t len = 2; pos + len <= run.size(); ++len) {
-                    const bool end = pos + len == run.size();
-                    if (fused_fc_chain_fits(run.data() + pos, (int)len, end ? sm : nullptr)) {
-                        best = (int)len, best_sm = end && sm;
-                    } else {
-                        if (end && sm && fused_fc_chain_fits(run.data() + pos, (int)len, nullptr)) best = (int)len, best_sm = false;
-                        break;
-                    }
-                }
-                if (best >= 2) {
-                    if (FusedImpl *f = fused_fc_chain_create(run.data() + pos, best, best_sm ? sm : nullptr))
-                        sg.v.push_back({f, (int)idx[pos], (int)(best_sm ? smi : idx[pos + (size_t)best - 1])});
-                    pos += (size_t)best;
-                } else {
-                    ++pos;
-                }
-            }
-            i = idx.back();
-        }
-        // (6a) a Conv2D directly followed by an AveragePool2D or a MaxPool2D with more than one output pixel -> one conv_pool_rt /
-        // conv_maxpool_rt launch (fused_heads.hip:
-        // fused_conv_pool_create).  Behind every peephole above: a global pool stays with the tail and pool_fc_chain groups, the Conv2D of a
-        // depthwise pair with its pair.  A first operator that takes the f32 input inside its own launch keeps that launch (the entry is
-        // predict's quantisation inside a launch; the group has no f32 entry)
-        {
-            size_t first_real = 0;
-            while (first_real < n && !ops[first_real]) ++first_real;
-            auto free_op = [&](size_t i) { return ops[i] && !fused[i] && !covered(i) && !owned(i); };
-            for (size_t i = 0; i + 1 < n; ++i) {
-                const int pk = m->pm.ops[i + 1].kind; // (an AveragePool2D: conv_pool_rt; a MaxPool2D: conv_maxpool_rt)
-                if (m->pm.ops[i].kind != MF_OP_CONV_2D || (pk != MF_OP_AVERAGE_POOL_2D && pk != MF_OP_MAX_POOL_2D) || !free_op(i) || !free_op(i + 1)) continue;
-                if (m->pm.ops[i + 1].OH * m->pm.ops[i + 1].OW < 2) continue;
-                if (i == first_real && op_accepts_f32(ops[i])) continue;
-                if (FusedImpl *f = fused_conv_pool_create(ops[i], ops[i + 1])) {
-                    sg.v.push_back({f, (int)i, (int)i + 1});
-                    ++i;
-                }
-            }
-        }
-        // (7) the boundary conversions of M::predict inside the launches at the two ends of the whole model: every launch that can
-        // start a run at operator 0 learns the input's scale and zero point, every one that can end at the last operator the ones
-        // that operator stamped (the stem was told above; a kernel without such an instance says no and keeps the separate pass)
-        {
-            int last_real = (int)n - 1;
-            while (last_real >= 0 && !ops[(size_t)last_real]) --last_real;
-            size_t first_real = 0;
-            while (first_real < n && !ops[first_real]) ++first_real;
-            if (first_real < n && fused[first_real]) (void)fused_set_input_quant(fused[first_real], m->pm.in_scale, m->pm.in_zp, m->pm.u8);
-            if (first_real > 0 && first_real < n) (void)op_set_input_quant(ops[first_real], m->pm.in_scale, m->pm.in_zp, m->pm.u8);
-            if (last_real >= 0) (void)op_set_output_dequant(ops[(size_t)last_real], m->pm.out_scale, m->pm.out_zp, m->pm.u8);
-            for (size_t i = 0; i < n; ++i)
-                if (fused[i] && fused_last[i] == last_real) (void)fused_set_output_dequant(fused[i], m->pm.out_scale, m->pm.out_zp, m->pm.u8);
-            for (const ModelImpl::Stage &st : sg.v) {
-                if (st.first == (int)first_real) (void)fused_set_input_quant(st.f, m->pm.in_scale, m->pm.in_zp, m->pm.u8);
-                if (st.last == last_real) (void)fused_set_output_dequant(st.f, m->pm.out_scale, m->pm.out_zp, m->pm.u8);
-            }
-        }
-        // commit (nothing below throws)
-        m->stages.swap(sg.v);
+        m->g = build_groups(m->pm, device, m->autotune);
         m->device = device;
-        m->ops.swap(pend.ops);
-        m->fused.swap(pend.fused);
-        m->fused_last.swap(fused_last);
         m->prepared = true;
         model_set_generic(m, m->generic);
     }
@@ -561,26 +279,71 @@ uint64_t model_device_ops(const ModelImpl *m) { return m->device_ops; }
 void model_set_generic(ModelImpl *m, bool generic) {
     m->generic = generic;
     m->drop_graph();
-    for (OpImpl *o : m->ops)
+    for (OpImpl *o : m->g.ops)
         if (o) op_set_generic(o, generic);
 }
 
-// Which launch of a run of ops [0 .. last_op] takes the f32 input itself (the boundary quantize inside it)?  1: the second-level
-// group that starts at the first operator (penta_rr, fc_chain, dwc1_fc_softmax), 2: the first-level group there, 3: that operator alone (the stem kernel, fc_rt: the
-// groups behind it run as usual), 0: none
-static int first_real_op(const ModelImpl *m) { // leading Reshapes alias the input (speech.tflite starts with one)
-    int i = 0;
-    while (i < (int)m->ops.size() && !m->ops[(size_t)i]) ++i;
-    return i;
+// Which launch of a run of ops [0 .. last_op] takes the f32 input itself (the boundary quantize inside it)?  The second-level
+// group that starts at the first operator (penta_rr, fc_chain, dwc1_fc_softmax), else the first-level group there, else that operator alone (the stem kernel, fc_rt: the
+// groups behind it run as usual); last < 0: none.  A stage there that does not take f32 blocks the group, a group the operator
+static Launch f32_entry(const ModelImpl *m, int last_op) {
+    const Launch none{nullptr, -1};
+    const int f = m->g.first_real;
+    if (!m->fusion || m->generic || f > last_op || f >= (int)m->g.ops.size()) return none;
+    const Stage *st0 = stage_at(m, f, last_op);
+    if (st0 && fused_accepts_f32(st0->f)) return {st0->f, st0->last};
+    FusedImpl *g = group_at(m, f, last_op);
+    if (!st0 && g && fused_accepts_f32(g)) return {g, m->g.fused_last[(size_t)f]};
+    if (!fused_at(m, f) && op_accepts_f32(m->g.ops[(size_t)f])) return {nullptr, f};
+    return none;
 }
-static int f32_entry(const ModelImpl *m, int last_op) {
-    const int f = first_real_op(m);
-    if (!m->fusion || m->generic || f > last_op || f >= (int)m->ops.size()) return 0;
-    const ModelImpl::Stage *st0 = stage_at(m, f, last_op);
-    if (st0 && fused_accepts_f32(st0->f)) return 1;
-    if (!st0 && fused_at(m, f) && m->fused_last[(size_t)f] <= last_op && fused_accepts_f32(m->fused[(size_t)f])) return 2;
-    if (!fused_at(m, f) && op_accepts_f32(m->ops[(size_t)f])) return 3;
-    return 0;
+// the last operator at or before last_op that launches anything (trailing Reshapes alias its output)
+static int last_real_upto(const ModelImpl *m, int last_op) {
+    while (last_op >= 0 && !m->g.ops[(size_t)last_op]) --last_op;
+    return last_op;
+}
+
+// A run of ops [0 .. last_op] in flight: where the running tensor is, and what the two ends of the run ask for (run_ops)
+struct Run {
+    const int8_t *cur; // the running tensor
+    size_t batch;
+    int last_op, last_real;
+    hipStream_t stream;
+    const float *src_f32 = nullptr;
+    Launch entry{nullptr, -1}; // with src_f32: the launch that takes it (f32_entry)
+    int8_t *final_dst = nullptr;
+    float *final_f32 = nullptr;
+    int which = 0;         // the activation buffer the next launch writes, unless it is reading it
+    bool left_f32 = false; // the last launch stored floats at final_f32: there is no int8 result
+};
+// The launch of the run at operator i (not a Reshape): picks the destination of the ping-pong, selects the launch, runs it -- the int8
+// form or, with a model boundary inside it, the f32-edge form -- and returns the last operator it covered
+static int run_step(ModelImpl *m, Run &r, int i) {
+    OpImpl *o = m->g.ops[(size_t)i];
+    const bool f32in = r.src_f32 && i == m->g.first_real;
+    int8_t *dst = m->act[r.which];
+    if (dst == r.cur) {
+        r.which ^= 1;
+        dst = m->act[r.which];
+    }
+    const Launch l = f32in ? r.entry : launch_at(m, i, r.last_op, r.cur, r.batch);
+    const bool ends = l.last >= r.last_real;
+    const bool f32out = r.final_f32 && ends && (l.f ? fused_emits_f32(l.f) : op_emits_f32(o));
+    if (r.final_dst && ends) dst = r.final_dst;
+    if (f32in || f32out) { // a model boundary inside the launch
+        const void *in = f32in ? (const void *)r.src_f32 : (const void *)r.cur;
+        void *out = f32out ? (void *)r.final_f32 : (void *)dst;
+        if (l.f) fused_run_f32(l.f, in, f32in, r.batch, out, f32out, r.stream);
+        else op_run_f32(o, in, f32in, r.batch, out, f32out, r.stream);
+        r.left_f32 = f32out;
+    } else if (l.f) { // several groups, or the whole group, in one launch
+        fused_run(l.f, r.cur, r.batch, dst, r.stream);
+    } else {
+        op_run(o, r.cur, r.batch, dst, r.stream);
+    }
+    r.cur = dst;
+    r.which ^= 1;
+    return l.last;
 }
 
 // run ops [0..last_op]; `src_f32` != nullptr (only where f32_entry says so): the first launch consumes the f32 input directly.
@@ -589,73 +352,30 @@ static int f32_entry(const ModelImpl *m, int last_op) {
 // dequantised floats there if it has such an instance.  The return value says where the int8 result is; nullptr: it left as floats.
 static const int8_t *run_ops(ModelImpl *m, const int8_t *src, size_t batch, int last_op, hipStream_t stream,
                              const float *src_f32 = nullptr, int8_t *final_dst = nullptr, float *final_f32 = nullptr) {
-    const int8_t *cur = src;
-    int which = 0;
-    // the last operator that launches anything (trailing Reshapes alias its output)
-    int last_real = last_op;
-    while (last_real >= 0 && !m->ops[last_real]) --last_real;
-    const int entry = src_f32 ? f32_entry(m, last_op) : 0;
-    if (src_f32 && !entry) fail(MF_ERR_UNSUPPORTED, "no launch takes the f32 input");
-    const int first_real = first_real_op(m);
-    for (int i = 0; i <= last_op; ++i) {
-        OpImpl *o = m->ops[i];
-        if (!o) continue; // Reshape: alias
-        const bool f32in = src_f32 && i == first_real;
-        int8_t *dst = m->act[which];
-        if (dst == cur) {
-            which ^= 1;
-            dst = m->act[which];
-        }
-        const ModelImpl::Stage *staged = stage_at(m, i, last_op);
-        bool grouped;
-        if (f32in) {
-            if (entry != 1) staged = nullptr;
-            grouped = entry == 2;
-        } else {
-            if (staged && (!fused_input_ok(staged->f, cur) || !fused_batch_ok(staged->f, batch))) staged = nullptr; // (the operators' own launches take any pointer and batch)
-            grouped = !staged && fused_at(m, i) && m->fused_last[(size_t)i] <= last_op && fused_input_ok(m->fused[(size_t)i], cur);
-        }
-        const int end = staged ? staged->last : (grouped ? m->fused_last[(size_t)i] : i);
-        const bool f32out = final_f32 && end >= last_real &&
-                            (staged ? fused_emits_f32(staged->f) : grouped ? fused_emits_f32(m->fused[(size_t)i]) : op_emits_f32(o));
-        if (final_dst && end >= last_real) dst = final_dst;
-        if (f32in || f32out) { // a model boundary inside the launch
-            const void *in = f32in ? (const void *)src_f32 : (const void *)cur;
-            void *out = f32out ? (void *)final_f32 : (void *)dst;
-            if (staged) fused_run_f32(staged->f, in, f32in, batch, out, f32out, stream);
-            else if (grouped) fused_run_f32(m->fused[(size_t)i], in, f32in, batch, out, f32out, stream);
-            else op_run_f32(o, in, f32in, batch, out, f32out, stream);
-            if (f32out) return nullptr;
-        } else if (staged) { // several groups in one launch
-            fused_run(staged->f, cur, batch, dst, stream);
-        } else if (grouped) { // the whole group in one launch
-            fused_run(m->fused[(size_t)i], cur, batch, dst, stream);
-        } else {
-            op_run(o, cur, batch, dst, stream);
-        }
-        i = end;
-        cur = dst;
-        which ^= 1;
-    }
-    return cur;
+    Run r{src, batch, last_op, last_real_upto(m, last_op), stream, src_f32};
+    if (src_f32) r.entry = f32_entry(m, last_op);
+    if (src_f32 && r.entry.last < 0) fail(MF_ERR_UNSUPPORTED, "no launch takes the f32 input");
+    r.final_dst = final_dst, r.final_f32 = final_f32;
+    for (int i = 0; i <= last_op && !r.left_f32; ++i)
+        if (m->g.ops[(size_t)i]) i = run_step(m, r, i); // (a Reshape is an alias)
+    return r.left_f32 ? nullptr : r.cur;
 }
 
+// Can any launch that ends the whole model -- the last real operator's own, a group or a stage that ends there -- store floats?
+static bool f32_exit_any(const ModelImpl *m) {
+    const ModelGroups &g = m->g;
+    if (g.last_real < 0) return false;
+    if (op_emits_f32(g.ops[(size_t)g.last_real])) return true;
+    for (size_t i = 0; i < g.fused.size(); ++i)
+        if (g.fused[i] && g.fused_last[i] == g.last_real && fused_emits_f32(g.fused[i])) return true;
+    for (const Stage &st : g.stages)
+        if (st.last == g.last_real && fused_emits_f32(st.f)) return true;
+    return false;
+}
 // Which of M::predict's two boundary conversions run inside the first / last launch of this call: only with fusion on, the
 // shape-specialised kernels, the whole model, a 16-byte aligned f32 input (float4 loads) and a 4-byte aligned f32 output; and the
 // exit only where the output range does not overlap the input's, which the first launch -- possibly the same one -- is still reading.
 // Otherwise that side keeps its separate pass, with the same bits.
-// can any launch that ends the whole model store floats?
-static bool f32_exit_any(const ModelImpl *m) {
-    int last_real = (int)m->ops.size() - 1;
-    while (last_real >= 0 && !m->ops[(size_t)last_real]) --last_real;
-    if (last_real < 0) return false;
-    if (op_emits_f32(m->ops[(size_t)last_real])) return true;
-    for (size_t i = 0; i < m->fused.size(); ++i)
-        if (m->fused[i] && m->fused_last[i] == last_real && fused_emits_f32(m->fused[i])) return true;
-    for (const ModelImpl::Stage &st : m->stages)
-        if (st.last == last_real && fused_emits_f32(st.f)) return true;
-    return false;
-}
 struct Boundary {
     bool in = false, out = false;
 };
@@ -663,12 +383,8 @@ static Boundary boundary_plan(const ModelImpl *m, const float *in_f32, const flo
                               int last_op) {
     Boundary b;
     if (!m->fusion || m->generic || last_op != (int)m->pm.ops.size() - 1) return b;
-    b.in = in_f32 && ((uintptr_t)in_f32 & 15) == 0 && f32_entry(m, last_op) != 0;
-    if (out_f32 && ((uintptr_t)out_f32 & 3) == 0) {
-        const uintptr_t ob = (uintptr_t)out_f32, oe = ob + out_count * sizeof(float);
-        const uintptr_t ib = (uintptr_t)in_any, ie = ib + in_bytes;
-        b.out = !(ob < ie && ib < oe);
-    }
+    b.in = in_f32 && ((uintptr_t)in_f32 & 15) == 0 && f32_entry(m, last_op).last >= 0;
+    b.out = out_f32 && ((uintptr_t)out_f32 & 3) == 0 && !ranges_overlap(out_f32, out_count * sizeof(float), in_any, in_bytes);
     return b;
 }
 
@@ -677,11 +393,12 @@ static Boundary boundary_plan(const ModelImpl *m, const float *in_f32, const flo
 static void enqueue_device(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t batch,
                            float *out_f32, int8_t *out_i8, int last_op, hipStream_t s) {
     const ParsedModel &pm = m->pm;
-    const int nops = (int)pm.ops.size();
-    const size_t out_elems = last_op == nops - 1 ? pm.out_elems : pm.ops[last_op].out_elems;
+    const OutQuant oq = out_quant(pm, last_op);
+    const size_t out_elems = oq.elems;
+    const void *in_any = in_f32 ? (const void *)in_f32 : (const void *)in_i8;
+    const size_t in_bytes = batch * pm.in_elems * (in_f32 ? sizeof(float) : 1);
     const int8_t *q_in;
-    const Boundary bd = boundary_plan(m, in_f32, out_f32, batch * out_elems, in_f32 ? (const void *)in_f32 : (const void *)in_i8,
-                                      batch * pm.in_elems * (in_f32 ? sizeof(float) : 1), last_op);
+    const Boundary bd = boundary_plan(m, in_f32, out_f32, batch * out_elems, in_any, in_bytes, last_op);
     const bool fuse_q = bd.in;
     if (fuse_q) {
         q_in = nullptr; // the first launch quantises while it stages (dw3x3_stem8<.., F32IN>, fc_chain_f32 ...)
@@ -702,12 +419,7 @@ static void enqueue_device(ModelImpl *m, const float *in_f32, const int8_t *in_i
     // the caller's input, which the first launch may still be reading (in_i8 is consumed in place): a model that is ONE
     // launch would then read and write the same memory.  Overlapping buffers take the activation buffer + copy path.
     int8_t *direct = (out_i8 && !pm.u8 && ((uintptr_t)out_i8 & 15) == 0) ? out_i8 : nullptr; // (16-byte vector stores)
-    if (direct) {
-        const uintptr_t ob = (uintptr_t)out_i8, oe = ob + batch * out_elems;
-        const uintptr_t ib = (uintptr_t)(in_f32 ? (const void *)in_f32 : (const void *)in_i8);
-        const uintptr_t ie = ib + batch * pm.in_elems * (in_f32 ? sizeof(float) : 1);
-        if (ob < ie && ib < oe) direct = nullptr;
-    }
+    if (direct && ranges_overlap(out_i8, batch * out_elems, in_any, in_bytes)) direct = nullptr;
     const int8_t *res = run_ops(m, q_in, batch, last_op, s, fuse_q ? in_f32 : nullptr, direct, bd.out ? out_f32 : nullptr);
     if (out_i8) {
         if (pm.u8) dev_xor80(m->device, res, batch * out_elems, out_i8, s);
@@ -716,10 +428,7 @@ static void enqueue_device(ModelImpl *m, const float *in_f32, const int8_t *in_i
             ++dev_launch_counter();
         }
     } else if (res) { // .dequantize()  (lib.rs:190) with the parameters the last op stamped on the tensor
-        float oscale = pm.out_scale;
-        int ozp = pm.out_zp;
-        if (last_op != nops - 1) oscale = pm.ops[last_op].out_scale, ozp = pm.ops[last_op].out_zp;
-        dev_dequantize(m->device, res, batch * out_elems, oscale, ozp, pm.u8, out_f32, s);
+        dev_dequantize(m->device, res, batch * out_elems, oq.scale, oq.zp, pm.u8, out_f32, s);
     }
 }
 
@@ -730,12 +439,7 @@ static void run_device(ModelImpl *m, const float *in_f32, const int8_t *in_i8, s
     // what this call enqueues, for mf_model_device_ops: the launches and device-to-device copies of an eager pass; one for a call that
     // launches the graph -- a replay, and also the call that captures it, which records its launches instead of enqueueing them and
     // then launches the new graph once
-    struct Count {
-        ModelImpl *m;
-        unsigned long long before = dev_launch_counter();
-        bool replay = false;
-        ~Count() { m->device_ops += replay ? 1 : dev_launch_counter() - before; }
-    } count{m};
+    LaunchCount count{m};
     if (!m->use_graph) return enqueue_device(m, in_f32, in_i8, batch, out_f32, out_i8, last_op, s);
     ModelImpl::GraphKey k;
     k.in = in_f32 ? (const void *)in_f32 : (const void *)in_i8;
@@ -785,10 +489,10 @@ void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t ba
     const int nops = (int)pm.ops.size();
     if (last_op < 0) last_op = nops - 1;
     if (last_op >= nops) fail(MF_ERR_INVALID_ARG, "op index out of range");
-    if (!batch) return;
     MF_HIP(hipSetDevice(m->device));
     ensure_capacity(m, batch);
-    const size_t out_elems = last_op == nops - 1 ? pm.out_elems : pm.ops[last_op].out_elems;
+    const OutQuant oq = out_quant(pm, last_op); // (host path) .dequantize() takes the parameters the last op stamped on the tensor
+    const size_t out_elems = oq.elems;
     const bool host = mem == MF_MEM_HOST;
     hipStream_t s = m->stream;
     if (!host) return run_device(m, in_f32, in_i8, batch, out_f32, out_i8, last_op);
@@ -806,23 +510,13 @@ void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t ba
         if (batch > per + per / 2) chunk = per;
     }
     if (chunk < batch && !m->copy_stream) MF_HIP(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
-    std::vector<hipEvent_t> evs;
-    float oscale = pm.out_scale;
-    int ozp = pm.out_zp;
-    if (last_op != nops - 1) oscale = pm.ops[last_op].out_scale, ozp = pm.ops[last_op].out_zp;
-    // (what this call enqueues on the device, for mf_model_device_ops: added on every way out)
-    struct OpsAdded {
-        ModelImpl *m;
-        unsigned long long before = dev_launch_counter();
-        ~OpsAdded() { m->device_ops += dev_launch_counter() - before; }
-    } ops_added{m};
+    EventList evs;
+    LaunchCount ops_added{m};
     if (out_f32 && !m->o_f32 && m->fusion && !m->generic && last_op == nops - 1 && f32_exit_any(m))
         MF_HIP(hipMalloc((void **)&m->o_f32, m->cap_batch * pm.out_elems * sizeof(float) + 256));
     try {
         if (chunk < batch) { // the copy stream starts after whatever the caller queued on the compute stream
-            hipEvent_t e;
-            MF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            evs.push_back(e);
+            hipEvent_t e = evs.add(hipEventDisableTiming);
             MF_HIP(hipEventRecord(e, s));
             MF_HIP(hipStreamWaitEvent(m->copy_stream, e, 0));
         }
@@ -834,9 +528,7 @@ void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t ba
             if (in_f32) MF_HIP(hipMemcpyAsync(f, in_f32 + first * pm.in_elems, n * in_bytes, hipMemcpyHostToDevice, cs));
             else MF_HIP(hipMemcpyAsync(q, in_i8 + first * pm.in_elems, n * in_bytes, hipMemcpyHostToDevice, cs));
             if (cs != s) {
-                hipEvent_t e;
-                MF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                evs.push_back(e);
+                hipEvent_t e = evs.add(hipEventDisableTiming);
                 MF_HIP(hipEventRecord(e, cs));
                 MF_HIP(hipStreamWaitEvent(s, e, 0));
             }
@@ -860,7 +552,7 @@ void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t ba
                 }
                 MF_HIP(hipMemcpyAsync(out_i8 + first * out_elems, res, n * out_elems, hipMemcpyDeviceToHost, s));
             } else { // .dequantize()  (lib.rs:190) with the parameters the last op stamped on the tensor
-                if (res) dev_dequantize(m->device, res, n * out_elems, oscale, ozp, pm.u8, fo, s);
+                if (res) dev_dequantize(m->device, res, n * out_elems, oq.scale, oq.zp, pm.u8, fo, s);
                 MF_HIP(hipMemcpyAsync(out_f32 + first * out_elems, res ? fo : fo_direct, n * out_bytes, hipMemcpyDeviceToHost, s));
             }
         }
@@ -868,10 +560,8 @@ void model_run(ModelImpl *m, const float *in_f32, const int8_t *in_i8, size_t ba
     } catch (...) {
         if (m->copy_stream) (void)hipStreamSynchronize(m->copy_stream);
         (void)hipStreamSynchronize(s);
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
         throw;
     }
-    for (hipEvent_t e : evs) (void)hipEventDestroy(e);
 }
 
 // ---- sliding windows (include/microflow_amd.h, section 5) ----
@@ -914,9 +604,9 @@ void model_run_windows(ModelImpl *m, const float *src_f32, const int8_t *src_i8,
     if (count) {
         if ((src_f32 == nullptr) == (src_i8 == nullptr) || (out_f32 == nullptr) == (out_i8 == nullptr)) fail(MF_ERR_INVALID_ARG, "null buffer");
         if (((uintptr_t)src_f32 & 3) || ((uintptr_t)out_f32 & 3)) fail(MF_ERR_INVALID_ARG, "src / out: f32 buffers must be 4-byte aligned");
-        const uintptr_t sb = (src_f32 ? (uintptr_t)src_f32 : (uintptr_t)src_i8) + lo * esz, se = sb + span * esz;
-        const uintptr_t ob = out_f32 ? (uintptr_t)out_f32 : (uintptr_t)out_i8, oe = ob + count * pm.out_elems * osz;
-        if (ob < se && sb < oe) fail(MF_ERR_INVALID_ARG, "src and out overlap");
+        const void *sb = (const void *)((src_f32 ? (uintptr_t)src_f32 : (uintptr_t)src_i8) + lo * esz);
+        const void *ob = out_f32 ? (const void *)out_f32 : (const void *)out_i8;
+        if (ranges_overlap(ob, count * pm.out_elems * osz, sb, span * esz)) fail(MF_ERR_INVALID_ARG, "src and out overlap");
     }
     if (!m->prepared) {
         if (dev_count() <= 0) fail(MF_ERR_NO_DEVICE, "no HIP device available: libmicroflow_amd has no CPU fallback");
@@ -946,12 +636,8 @@ void model_run_windows(ModelImpl *m, const float *src_f32, const int8_t *src_i8,
     }
     const bool many = chunk < count;
     if (host && many && !m->copy_stream) MF_HIP(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
-    std::vector<hipEvent_t> evs;
-    struct OpsAdded {
-        ModelImpl *m;
-        unsigned long long before = dev_launch_counter();
-        ~OpsAdded() { m->device_ops += dev_launch_counter() - before; }
-    } ops_added{m};
+    EventList evs;
+    LaunchCount ops_added{m};
     try {
         for (size_t done = 0; done < count; done += chunk) {
             const size_t n = std::min(chunk, count - done);
@@ -985,9 +671,7 @@ void model_run_windows(ModelImpl *m, const float *src_f32, const int8_t *src_i8,
             char *h_out = (out_f32 ? (char *)out_f32 : (char *)out_i8) + off * osz;
             const bool in_win_out = from == (const void *)t_f32 || from == (const void *)t_i8;
             if (many && in_win_out) { // the slice is not written again: it crosses on the copy stream while the next chunk runs
-                hipEvent_t e;
-                MF_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                evs.push_back(e);
+                hipEvent_t e = evs.add(hipEventDisableTiming);
                 MF_HIP(hipEventRecord(e, s));
                 MF_HIP(hipStreamWaitEvent(m->copy_stream, e, 0));
                 MF_HIP(hipMemcpyAsync(h_out, from, n * pm.out_elems * osz, hipMemcpyDeviceToHost, m->copy_stream));
@@ -1002,10 +686,8 @@ void model_run_windows(ModelImpl *m, const float *src_f32, const int8_t *src_i8,
     } catch (...) {
         if (m->copy_stream) (void)hipStreamSynchronize(m->copy_stream);
         (void)hipStreamSynchronize(s);
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
         throw;
     }
-    for (hipEvent_t e : evs) (void)hipEventDestroy(e);
 }
 
 void model_time_device(ModelImpl *m, const int8_t *d_in, size_t batch, int8_t *d_out, int warmup,
@@ -1016,9 +698,8 @@ void model_time_device(ModelImpl *m, const int8_t *d_in, size_t batch, int8_t *d
     ensure_capacity(m, batch);
     const int nops = (int)m->pm.ops.size();
     hipStream_t s = m->stream;
-    hipEvent_t e0, e1;
-    MF_HIP(hipEventCreate(&e0));
-    MF_HIP(hipEventCreate(&e1));
+    EventList evs; // e0, e1, then the sweep's nops + 1
+    const hipEvent_t e0 = evs.add(hipEventDefault), e1 = evs.add(hipEventDefault);
     for (int i = 0; i < warmup; ++i) model_run(m, nullptr, d_in, batch, nullptr, d_out, MF_MEM_DEVICE, -1);
     MF_HIP(hipEventRecord(e0, s));
     for (int i = 0; i < iters; ++i) model_run(m, nullptr, d_in, batch, nullptr, d_out, MF_MEM_DEVICE, -1);
@@ -1027,58 +708,36 @@ void model_time_device(ModelImpl *m, const int8_t *d_in, size_t batch, int8_t *d
     float ms = 0;
     MF_HIP(hipEventElapsedTime(&ms, e0, e1));
     if (avg_ms) *avg_ms = ms / (float)iters;
+    if (!per_op_ms) return;
 
-    if (per_op_ms) { // second sweep: one event pair per op, on the same stream
-        std::vector<hipEvent_t> ev((size_t)nops + 1);
-        for (auto &e : ev) MF_HIP(hipEventCreate(&e));
-        std::vector<std::vector<float>> samples((size_t)nops); // per operator: one duration per iteration
-        for (int it = 0; it < iters; ++it) {
-            const int8_t *cur = d_in;
-            int which = 0;
-            MF_HIP(hipEventRecord(ev[0], s));
-            for (int i = 0; i < nops; ++i) {
-                OpImpl *o = m->ops[i];
-                if (o) {
-                    int8_t *dst = m->act[which];
-                    if (dst == cur) {
-                        which ^= 1;
-                        dst = m->act[which];
-                    }
-                    const ModelImpl::Stage *st = stage_at(m, i, nops - 1);
-                    if (st && (!fused_input_ok(st->f, cur) || !fused_batch_ok(st->f, (size_t)batch))) st = nullptr;
-                    if (st) { // timed as one unit (index i), its other ops 0
-                        fused_run(st->f, cur, batch, dst, s);
-                        for (int j = i; j < st->last; ++j) MF_HIP(hipEventRecord(ev[(size_t)j + 1], s));
-                        i = st->last;
-                    } else if (fused_at(m, i) && fused_input_ok(m->fused[(size_t)i], cur)) { // the group is timed as one unit (index i), its other ops 0
-                        fused_run(m->fused[(size_t)i], cur, batch, dst, s);
-                        for (int j = i; j < m->fused_last[(size_t)i]; ++j) MF_HIP(hipEventRecord(ev[(size_t)j + 1], s));
-                        i = m->fused_last[(size_t)i];
-                    } else {
-                        op_run(o, cur, batch, dst, s);
-                    }
-                    cur = dst;
-                    which ^= 1;
-                }
-                MF_HIP(hipEventRecord(ev[(size_t)i + 1], s));
+    // second sweep: one event pair per op, on the same stream; run_ops' steps with an event behind each (these launches are not
+    // added to mf_model_device_ops)
+    for (int i = 0; i <= nops; ++i) evs.add(hipEventDefault);
+    const hipEvent_t *ev = evs.v.data() + 2;
+    std::vector<std::vector<float>> samples((size_t)nops); // per operator: one duration per iteration
+    for (int it = 0; it < iters; ++it) {
+        Run r{d_in, batch, nops - 1, m->g.last_real, s};
+        MF_HIP(hipEventRecord(ev[0], s));
+        for (int i = 0; i < nops; ++i) {
+            if (m->g.ops[(size_t)i]) { // a stage or a group is timed as one unit (index i), its other ops 0
+                const int end = run_step(m, r, i);
+                for (; i < end; ++i) MF_HIP(hipEventRecord(ev[(size_t)i + 1], s));
             }
-            MF_HIP(hipEventSynchronize(ev[(size_t)nops]));
-            for (int i = 0; i < nops; ++i) {
-                float t = 0;
-                MF_HIP(hipEventElapsedTime(&t, ev[(size_t)i], ev[(size_t)i + 1]));
-                samples[(size_t)i].push_back(t);
-            }
+            MF_HIP(hipEventRecord(ev[(size_t)i + 1], s));
         }
-        for (int i = 0; i < nops; ++i) { // median over the iterations
-            std::vector<float> &v = samples[(size_t)i];
-            std::sort(v.begin(), v.end());
-            const size_t n = v.size();
-            per_op_ms[i] = n % 2 ? v[n / 2] : 0.5f * (v[n / 2 - 1] + v[n / 2]);
+        MF_HIP(hipEventSynchronize(ev[(size_t)nops]));
+        for (int i = 0; i < nops; ++i) {
+            float t = 0;
+            MF_HIP(hipEventElapsedTime(&t, ev[(size_t)i], ev[(size_t)i + 1]));
+            samples[(size_t)i].push_back(t);
         }
-        for (auto &e : ev) (void)hipEventDestroy(e);
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    for (int i = 0; i < nops; ++i) { // median over the iterations
+        std::vector<float> &v = samples[(size_t)i];
+        std::sort(v.begin(), v.end());
+        const size_t n = v.size();
+        per_op_ms[i] = n % 2 ? v[n / 2] : 0.5f * (v[n / 2 - 1] + v[n / 2]);
+    }
 }
 
 } // namespace mf

@@ -1,0 +1,50 @@
+// model_groups.hpp -- what model_prepare builds for a parsed model (model_groups.cpp) and the model runtime launches (model.cpp):
+// the prepared operators, the first-level groups over them and the second-level stages over those.
+#pragma once
+#include <utility>
+#include <vector>
+
+#include "mf_internal.hpp"
+
+namespace mf {
+
+// The single owner of all three tiers.  Move-only; destroys stages first, then first-level groups, then operators.
+struct ModelGroups {
+    std::vector<OpImpl *> ops; // nullptr for Reshape
+    // fused[i] != nullptr: ops i .. fused_last[i] run as ONE kernel (depthwise + 1x1 conv pairs;
+    // the pool -> head conv -> [reshape] -> softmax tail)
+    std::vector<FusedImpl *> fused;
+    std::vector<int> fused_last;
+    // second level: ops first .. last (several first-level groups / operators) as ONE kernel: a run of identical pair
+    // groups (k_stage.hip), a one-input-channel depthwise + FullyConnected + Softmax (k_dwfc.hip), the last pair + the
+    // tail (k_tail3.hip).  They do not overlap; what is inside stays available for mf_model_run_until.
+    struct Stage {
+        FusedImpl *f;
+        int first, last;
+    };
+    std::vector<Stage> stages;
+    // the first / last operator that launches anything (leading Reshapes alias the input -- speech.tflite starts with one --
+    // trailing ones the output): ops.size() / -1 where there is none
+    int first_real = 0, last_real = -1;
+
+    ModelGroups() = default;
+    ModelGroups(const ModelGroups &) = delete;
+    ModelGroups &operator=(const ModelGroups &) = delete;
+    ModelGroups(ModelGroups &&o) noexcept { swap(o); }
+    ModelGroups &operator=(ModelGroups &&o) noexcept {
+        swap(o);
+        return *this;
+    }
+    ~ModelGroups() { clear(); }
+    void clear(); // stages borrow the groups' buffers, groups the operators': in that order
+    void swap(ModelGroups &o) noexcept {
+        ops.swap(o.ops), fused.swap(o.fused), fused_last.swap(o.fused_last), stages.swap(o.stages);
+        std::swap(first_real, o.first_real), std::swap(last_real, o.last_real);
+    }
+};
+
+// Operators and every group the grouping rules find, built in a local: a failure half way (a HIP error, OOM, a geometry an
+// operator rejects) destroys what exists and throws.  autotune: time the run-time-geometry chain candidates on the device
+ModelGroups build_groups(const ParsedModel &pm, int device, bool autotune);
+
+} // namespace mf
