@@ -153,7 +153,10 @@ static void rule_4b_quads(GroupBuilder &b) {
         if (FusedImpl *f = fused_quad_create(b.g.fused[i], b.g.fused[i + 2])) {
             b.add_stage(f, i, i + 3);
             // ... and with the stem in front of it: ops i - 1 .. i + 3 in one launch.  Both stay: a run that does not
-            // start at the stem (mf_model_run_until pieces, the f32 entry whose stem kernel quantises) uses the quad
+            // start at the stem (mf_model_run_until pieces, the f32 entry whose stem kernel quantises) uses the quad.
+            // (The stem test does not ask owned(i - 1), and need not: fused_quad_stem_create takes a one-channel depthwise stem only,
+            // and a depthwise operator is never a later member of a first-level group -- (1) starts at one, (2) and (3) hold none.  The
+            // operator that CAN sit there owned, the 1x1 of a pair group at i - 2, is refused by its kind)
             if (i >= 1 && b.g.ops[i - 1] && !b.g.fused[i - 1] && !b.covered(i - 1))
                 if (FusedImpl *g = fused_quad_stem_create(b.g.ops[i - 1], f)) b.add_stage(g, i - 1, i + 3);
             i += 3;
@@ -228,7 +231,10 @@ static void rule_4d_expand_blocks(GroupBuilder &b) {
     }
 }
 
-// (5) DepthwiseConv2D with one input channel -> [Reshape] -> the FullyConnected + Softmax group -> one kernel
+// (5) DepthwiseConv2D with one input channel -> [Reshape] -> the FullyConnected + Softmax group -> one kernel.
+// (The test on operator i does not ask owned(i), and need not: no operator sequence makes a depthwise operator a later member of a
+// first-level group -- (1) starts at the depthwise, (2) is pool + Conv2D + Softmax, (3) FullyConnected + Softmax -- so owned(i) is
+// false for every i that passes the kind test.  The group at j is a group's FIRST operator, which owned() does not concern)
 static void rule_5_dwfc(GroupBuilder &b) {
     for (size_t i = 0; i + 1 < b.n; ++i) {
         if (!b.g.ops[i] || b.g.fused[i] || b.covered(i) || b.kind(i) != MF_OP_DEPTHWISE_CONV_2D) continue;

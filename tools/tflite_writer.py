@@ -342,23 +342,9 @@ def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, w
         in_q = (float(np.float32(act_scale)), in_q[1])
     q, layers = in_q, []
     for op, n, k, s in convs:
-        oh, ow = -(-H // s), -(-W // s)
-        dw = op == "dw"
-        n = C if dw else n
-        sc = rng.uniform(0.002, 0.01, n).astype(np.float32)
-        zp = rng.integers(mid - 10, mid + 11, n) if wzp_nonzero and not dw else np.full(n, mid)
-        taps = k * k * (1 if dw else C)
-        osc = float(np.float32(q[0] * float(sc.mean()) * 60.0 * np.sqrt(taps)))
-        if act_scale is not None:
-            sc = (rng.uniform(0.6, 1.4, n) * 2.2 / (74.0 * np.sqrt(taps)) * (128.0 / (wmax or 128))).astype(np.float32)
-            osc = float(np.float32(act_scale))
-        d = dict(op="depthwise_conv_2d" if dw else "conv_2d", fscale=sc, fzp=zp, bias=rng.integers(-500, 500, n),
-                 bscale=(sc * np.float32(q[0])).astype(np.float32), bzp=np.zeros(n, np.int64), padding="same", strides=(s, s),
-                 act="relu6", out_shape=(1, oh, ow, n), out_q=(osc, lo))
-        wshape = (1, k, k, n) if dw else (n, k, k, C)
-        d["weights" if dw else "filters"] = rng.integers(lo, hi, wshape) if wmax is None else rng.integers(mid - wmax, mid + wmax + 1, wshape)
+        d = _conv_layer(rng, (H, W, C), q, op == "dw", n, k, s, elem=elem, wzp="conv" if wzp_nonzero else "none", wmax=wmax, act_scale=act_scale)
         layers.append(d)
-        q, H, W, C = d["out_q"], oh, ow, n
+        q, (_, H, W, C) = d["out_q"], d["out_shape"]
     if head:
         layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none",
                            out_shape=(1, 1, 1, C), out_q=q))
@@ -374,6 +360,49 @@ def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, w
 
 def _same_or_valid(size, k, s, padding):
     return -(-size // s) if padding == "same" else (size - k) // s + 1
+
+
+def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", elem=INT8, wzp="none", wmax=None, act_scale=None):
+    """conv_net's per-layer form, one layer dict: a k x k Conv2D to n channels, or (dw) a k x k depthwise, on a tensor shape = (H, W, C)
+    of quantisation q; per-channel filter quantisation; the output scale keeps the outputs spread, or is act_scale with
+    person_detect_like's filter scales; the output zero point is the type's minimum behind relu / relu6 and a random one without an
+    activation.  wzp: filter zero points off the middle -- "conv": Conv2D only, conv_net's draw; "all": the depthwise ones too, both
+    with inverted_residual_net's draw, which never lands on the middle."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    H, W, C = (int(v) for v in shape)
+    oh, ow = _same_or_valid(H, k, stride, padding), _same_or_valid(W, k, stride, padding)
+    n = C if dw else int(n)
+    sc = rng.uniform(0.002, 0.01, n).astype(np.float32)
+    if wzp == "all":
+        zp = rng.integers(mid - 12, mid + 13, n)
+        zp[zp == mid] = mid + 5
+    else:
+        zp = rng.integers(mid - 10, mid + 11, n) if wzp == "conv" and not dw else np.full(n, mid)
+    taps = k * k * (1 if dw else C)
+    osc = float(np.float32(q[0] * float(sc.mean()) * 60.0 * np.sqrt(taps)))
+    if act_scale is not None:
+        sc = (rng.uniform(0.6, 1.4, n) * 2.2 / (74.0 * np.sqrt(taps)) * (128.0 / (wmax or 128))).astype(np.float32)
+        osc = float(np.float32(act_scale))
+    ozp = lo if act in ("relu", "relu6") else int(rng.integers(lo + 20, hi - 20))
+    d = dict(op="depthwise_conv_2d" if dw else "conv_2d", fscale=sc, fzp=zp, bias=rng.integers(-500, 500, n),
+             bscale=(sc * np.float32(q[0])).astype(np.float32), bzp=np.zeros(n, np.int64), padding=padding, strides=(stride, stride),
+             act=act, out_shape=(1, oh, ow, n), out_q=(osc, ozp))
+    wshape = (1, k, k, n) if dw else (n, k, k, C)
+    d["weights" if dw else "filters"] = rng.integers(lo, hi, wshape) if wmax is None else rng.integers(mid - wmax, mid + wmax + 1, wshape)
+    return d
+
+
+def _fc_layer(rng, K, N, q, act="none", elem=INT8, wzp_off=0):
+    """lenet's FullyConnected form, one layer dict: K -> N on one row, per-tensor weight quantisation with the zero point at the
+    middle + wzp_off, an output scale that keeps the outputs spread"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    wsc = np.float32(rng.uniform(0.002, 0.02))
+    osc = float(np.float32(q[0] * wsc * 60.0 * np.sqrt(K)))
+    ozp = lo if act in ("relu", "relu6") else int(rng.integers(lo + 20, hi - 20))
+    return dict(op="fully_connected", weights=rng.integers(lo, hi, (N, K)), wscale=[wsc], wzp=[mid + wzp_off],
+                bias=rng.integers(-2000, 2000, N), bscale=[np.float32(q[0]) * wsc], bzp=[0], act=act, out_shape=(1, N), out_q=(osc, ozp))
 
 
 def conv_pool_layers(rng, shape, in_q, n, k, stride=1, padding="valid", act="relu", pool=(2, 2), pool_stride=2, pool_padding="valid",
@@ -423,7 +452,6 @@ def lenet_layers(rng, shape=(28, 28, 1), convs=((6, 5), (16, 5)), fcs=(120, 84, 
     """lenet's (input shape, input quantisation, layer dicts): what build_model takes, for tests that write parts of the stack as
     models of their own."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
-    mid = (lo + hi) // 2
     in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
     q, cur, layers = in_q, tuple(int(v) for v in shape), []
     for n, k in convs:
@@ -432,14 +460,8 @@ def lenet_layers(rng, shape=(28, 28, 1), convs=((6, 5), (16, 5)), fcs=(120, 84, 
     K = cur[0] * cur[1] * cur[2]
     layers.append(dict(op="reshape", out_shape=(1, K), out_q=q))
     for i, N in enumerate(int(v) for v in fcs):
-        last = i == len(fcs) - 1
-        a = "none" if last else "relu"
-        wsc = np.float32(rng.uniform(0.002, 0.02))
-        osc = float(np.float32(q[0] * wsc * 60.0 * np.sqrt(K)))
-        ozp = lo if a == "relu" else int(rng.integers(lo + 20, hi - 20))
-        layers.append(dict(op="fully_connected", weights=rng.integers(lo, hi, (N, K)), wscale=[wsc], wzp=[mid + (7 if wzp_nonzero else 0)],
-                           bias=rng.integers(-2000, 2000, N), bscale=[np.float32(q[0]) * wsc], bzp=[0], act=a, out_shape=(1, N), out_q=(osc, ozp)))
-        q, K = (osc, ozp), N
+        layers.append(_fc_layer(rng, K, N, q, "none" if i == len(fcs) - 1 else "relu", elem, 7 if wzp_nonzero else 0))
+        q, K = layers[-1]["out_q"], N
     if softmax:
         layers.append(dict(op="softmax", out_shape=(1, K), out_q=(1.0 / 256.0, lo)))
     return (1,) + tuple(int(v) for v in shape), in_q, layers
@@ -663,3 +685,105 @@ def person_detect_like(rng, side=96, width=1.0, elem=INT8, wzp_nonzero=False, n_
     layers.append(dict(op="reshape", out_shape=(1, classes), out_q=head_q))
     layers.append(dict(op="softmax", out_shape=(1, classes), out_q=(1.0 / 256.0, lo)))
     return build_model((1, side, side, 1), in_q, layers, elem)
+
+
+def stack_layers(rng, input_shape, segments, elem=INT8, wzp="none", act_scale=None):
+    """A model written segment by segment, for compositions no generator above has; -> (input shape, input quantisation, layer
+    dicts), what build_model takes.  input_shape = (H, W, C); a segment is one of
+        ("conv", N, K, stride, padding="same", act="relu6")     Conv2D K x K
+        ("dw", K, stride, act="relu6")                          depthwise K x K SAME
+        ("avgpool" | "maxpool", window, stride, padding="valid")  the pool (window: one side, or (h, w))
+        ("gap",)                                                AveragePool2D over the whole image + Reshape to (1, C)
+        ("flatten",)                                            Reshape to (1, H W C)
+        ("fc", N, act="none")                                   FullyConnected, one row
+        ("softmax",)
+    Per-channel filter quantisation, per-tensor FullyConnected; conv_net's output scales, or its act_scale form (every activation
+    tensor at that scale) with act_scale; the output zero point behind relu / relu6 is the type's minimum; a pool keeps its input's
+    quantisation.  A Conv2D directly followed by a pool is conv_pool_layers' stage (without act_scale, which that form does not have).
+    wzp: "none"; "conv" -- Conv2D filter zero points off the middle; "all" -- depthwise and FullyConnected ones too, as
+    inverted_residual_net(wzp_nonzero=True) and mlp(wzp_nonzero=True) draw them."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    if wzp not in ("none", "conv", "all"):
+        raise ValueError(wzp)
+    H, W, C = (int(v) for v in input_shape)
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    if act_scale is not None:
+        in_q = (float(np.float32(act_scale)), in_q[1])
+    q, layers, flat = in_q, [], None       # flat: the row length once the tensor is [1, K]
+    segs = [tuple(s) for s in segments]
+
+    def pool_args(seg):
+        kind, window, stride = seg[:3]
+        return (window, window) if np.isscalar(window) else tuple(window), int(stride), seg[3] if len(seg) > 3 else "valid"
+
+    def image():
+        if flat is not None:
+            raise ValueError("a %s segment behind a flatten / gap" % segs[i][0])
+
+    i = 0
+    while i < len(segs):
+        seg = segs[i]
+        kind = seg[0]
+        nxt = segs[i + 1] if i + 1 < len(segs) else None
+        if kind == "conv":
+            image()
+            n, k, stride = seg[1:4]
+            padding, act = (seg[4] if len(seg) > 4 else "same"), (seg[5] if len(seg) > 5 else "relu6")
+            if nxt and nxt[0] in ("avgpool", "maxpool") and act_scale is None:
+                window, pstride, ppad = pool_args(nxt)
+                stage, (H, W, C), q = conv_pool_layers(rng, (H, W, C), q, int(n), int(k), stride=int(stride), padding=padding, act=act, pool=window,
+                                                       pool_stride=pstride, pool_padding=ppad, elem=elem, wzp_nonzero=wzp != "none",
+                                                       pool_op=nxt[0][:3])
+                layers += stage
+                i += 2
+                continue
+            d = _conv_layer(rng, (H, W, C), q, False, n, int(k), int(stride), padding, act, elem, wzp, act_scale=act_scale)
+            layers.append(d)
+            q, (_, H, W, C) = d["out_q"], d["out_shape"]
+        elif kind == "dw":
+            image()
+            k, stride = seg[1:3]
+            d = _conv_layer(rng, (H, W, C), q, True, C, int(k), int(stride), "same", seg[3] if len(seg) > 3 else "relu6", elem,
+                            wzp if wzp == "all" else "none", act_scale=act_scale)
+            layers.append(d)
+            q, (_, H, W, C) = d["out_q"], d["out_shape"]
+        elif kind in ("avgpool", "maxpool"):
+            image()
+            window, stride, padding = pool_args(seg)
+            oh, ow = _same_or_valid(H, window[0], stride, padding), _same_or_valid(W, window[1], stride, padding)
+            layers.append(dict(op={"avgpool": "average_pool_2d", "maxpool": "max_pool_2d"}[kind], filter=window, padding=padding,
+                               strides=(stride, stride), act="none", out_shape=(1, oh, ow, C), out_q=q))
+            H, W = oh, ow
+        elif kind == "gap":
+            image()
+            layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none", out_shape=(1, 1, 1, C), out_q=q))
+            layers.append(dict(op="reshape", out_shape=(1, C), out_q=q))
+            H, W, flat = 1, 1, C
+        elif kind == "flatten":
+            image()
+            flat = H * W * C
+            layers.append(dict(op="reshape", out_shape=(1, flat), out_q=q))
+        elif kind == "fc":
+            if flat is None:
+                raise ValueError("an fc segment needs a flatten or a gap in front of it")
+            off = (int(rng.integers(-20, 21)) or 7) if wzp == "all" else 0
+            d = _fc_layer(rng, flat, int(seg[1]), q, seg[2] if len(seg) > 2 else "none", elem, off)
+            layers.append(d)
+            q, flat = d["out_q"], int(seg[1])
+        elif kind == "softmax":
+            if flat is None:
+                raise ValueError("a softmax segment needs a flatten or a gap in front of it")
+            layers.append(dict(op="softmax", out_shape=(1, flat), out_q=(1.0 / 256.0, lo)))
+            q = layers[-1]["out_q"]
+        else:
+            raise ValueError(kind)
+        if min(H, W) < 1:
+            raise ValueError("segment %d (%s) leaves no pixel" % (i, kind))
+        i += 1
+    return (1,) + tuple(int(v) for v in input_shape), in_q, layers
+
+
+def stack(rng, input_shape, segments, elem=INT8, wzp="none", act_scale=None):
+    """stack_layers' model as a flatbuffer"""
+    in_shape, in_q, layers = stack_layers(rng, input_shape, segments, elem, wzp, act_scale)
+    return build_model(in_shape, in_q, layers, elem)
