@@ -7,7 +7,7 @@
 //
 //   microflow::Tensor2D / Tensor4D                      src/tensor.rs:27-47
 //   microflow::FusedActivation, TensorViewPadding       src/activation.rs:6-13, src/tensor.rs:9-15
-//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / average_pool_2d / max_pool_2d (ours) /
+//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / average_pool_2d / max_pool_2d (ours) / add (ours) /
 //                   softmax / reshape                    src/ops/*.rs
 //   microflow::Model  (what #[model("x.tflite")] generates: predict, predict_quantized)
 //                                                        microflow-macros/src/lib.rs:185-203
@@ -85,6 +85,21 @@ inline std::vector<int8_t> run(mf_op *op, const std::vector<int8_t> &in, size_t 
     check(mf_op_run(op, (const int8_t *)din.p, batch, (int8_t *)dout.p, nullptr));
     std::vector<int8_t> out(out_n);
     if (hipMemcpy(out.data(), dout.p, out_n, 2 /*D2H*/) != 0) throw Error(MF_ERR_HIP, "hipMemcpy D2H failed");
+    return out;
+}
+// ... an operator with two inputs (ADD)
+inline std::vector<int8_t> run2(mf_op *op, const std::vector<int8_t> &a, const std::vector<int8_t> &b, size_t batch) {
+    struct Guard {
+        mf_op *o;
+        ~Guard() { mf_op_destroy(o); }
+    } g{op};
+    const size_t n = mf_op_input_elems(op) * batch;
+    if (a.size() != n || b.size() != n) throw Error(MF_ERR_INVALID_ARG, "input size does not match the operator");
+    DeviceBuffer da(n), db(n), dout(n);
+    if (hipMemcpy(da.p, a.data(), n, 1 /*H2D*/) != 0 || hipMemcpy(db.p, b.data(), n, 1) != 0) throw Error(MF_ERR_HIP, "hipMemcpy H2D failed");
+    check(mf_op_run2(op, (const int8_t *)da.p, (const int8_t *)db.p, batch, (int8_t *)dout.p, nullptr));
+    std::vector<int8_t> out(n);
+    if (hipMemcpy(out.data(), dout.p, n, 2 /*D2H*/) != 0) throw Error(MF_ERR_HIP, "hipMemcpy D2H failed");
     return out;
 }
 } // namespace detail
@@ -195,6 +210,23 @@ inline Tensor4D max_pool_2d(const Tensor4D &input, std::array<int, 2> filter_sha
     Tensor4D out;
     out.buffer = detail::run(op, input.buffer, (size_t)input.batches);
     out.batches = input.batches, out.rows = output_shape[0], out.cols = output_shape[1], out.chans = input.chans;
+    out.scale = {output_scale[0]}, out.zero_point = {output_zero_point[0]};
+    return out;
+}
+
+// ADD: no counterpart in the reference (microflow_amd.h states the contract).  Two tensors of one shape, per-tensor quantisation;
+// constants = {ca, cb} of mf_preprocess_add.  The operand order is kept.
+struct AddOptions {
+    FusedActivation fused_activation = FusedActivation::None;
+};
+inline Tensor4D add(const Tensor4D &a, const Tensor4D &b, std::array<float, 1> output_scale, std::array<int8_t, 1> output_zero_point,
+                    AddOptions options, std::array<float, 2> constants, int device = 0) {
+    mf_op *op = nullptr;
+    check(mf_add_create(device, (size_t)a.rows * a.cols * a.chans, a.scale[0], a.zero_point[0], b.scale[0], b.zero_point[0],
+                        output_scale[0], output_zero_point[0], (int)options.fused_activation, constants[0], constants[1], &op));
+    Tensor4D out;
+    out.buffer = detail::run2(op, a.buffer, b.buffer, (size_t)a.batches);
+    out.batches = a.batches, out.rows = a.rows, out.cols = a.cols, out.chans = a.chans;
     out.scale = {output_scale[0]}, out.zero_point = {output_zero_point[0]};
     return out;
 }

@@ -1,6 +1,7 @@
 // capi.cpp -- the extern "C" boundary declared in include/microflow_amd.h.
 // Nothing crosses it but plain pointers, sizes and status codes; C++ exceptions are
 // translated to mf_status + a thread-local message.
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
@@ -109,6 +110,29 @@ int mf_preprocess_average_pool_2d_u8(float input_scale, uint8_t input_zero_point
     MF_TRY({
         MF_NEED(c0 && c1);
         mf::h_preprocess_pool(input_scale, input_zero_point, output_scale, output_zero_point, c0, c1);
+    })
+}
+
+int mf_preprocess_add(float a_scale, float b_scale, float output_scale, float *ca, float *cb) {
+    MF_TRY({
+        MF_NEED(ca && cb);
+        mf::h_preprocess_add(a_scale, b_scale, output_scale, ca, cb);
+    })
+}
+
+int mf_add_fma_form(float ca, float cb, int a_zero_point, int b_zero_point, float output_scale, int output_zero_point,
+                    int fused_activation, int is_u8, float *k1, int *admitted) {
+    MF_TRY({
+        MF_NEED(k1 && admitted);
+        const int act = fused_activation;
+        if (act != MF_ACT_NONE && act != MF_ACT_RELU && act != MF_ACT_RELU6) mf::fail(MF_ERR_UNSUPPORTED, "unsupported fused activation");
+        const bool u8 = is_u8 != 0;
+        int lo = u8 ? 0 : -128, hi = u8 ? 255 : 127; // (ops_impl.hpp: act_bounds)
+        if (act != MF_ACT_NONE) lo = output_zero_point;
+        if (act == MF_ACT_RELU6) hi = mf::h_quantize_t(6.0f, output_scale, output_zero_point, u8);
+        if (lo > hi) lo = hi;
+        const int off = u8 ? 0 : 128;
+        *admitted = mf::h_add_fma_form(ca, cb, off + a_zero_point, off + b_zero_point, output_zero_point, lo, hi, k1) ? 1 : 0;
     })
 }
 
@@ -312,6 +336,39 @@ int mf_softmax_create_u8(int device, int rows, int cols, float input_scale, floa
     MF_TRY({ create_softmax(device, true, rows, cols, input_scale, output_scale, output_zero_point, op); })
 }
 
+// ADD (include/microflow_amd.h: the library's own contract).  Bad scales are a bad argument whether or not there is a device
+static void create_add(int device, bool u8, size_t elems, float sa, int za, float sb, int zb, float so, int zo, int act, float ca,
+                       float cb, mf_op **op) {
+    MF_NEED(op && elems > 0);
+    for (float v : {sa, sb, so})
+        if (!(v > 0.0f) || !std::isfinite(v)) mf::fail(MF_ERR_INVALID_ARG, "add: scales must be finite and positive");
+    mf::OpSpec s;
+    s.kind = MF_OP_ADD, s.u8 = u8;
+    s.add_elems = elems, s.add_za = za, s.add_zb = zb, s.add_ca = ca, s.add_cb = cb;
+    s.oscale = so, s.ozp = zo, s.act = check_act_arg(act);
+    wrap_op(mf::op_create(device, s), op);
+}
+int mf_add_create(int device, size_t elems, float a_scale, int8_t a_zero_point, float b_scale, int8_t b_zero_point,
+                  float output_scale, int8_t output_zero_point, int fused_activation, float ca, float cb, mf_op **op) {
+    MF_TRY({
+        create_add(device, false, elems, a_scale, a_zero_point, b_scale, b_zero_point, output_scale, output_zero_point,
+                   fused_activation, ca, cb, op);
+    })
+}
+int mf_add_create_u8(int device, size_t elems, float a_scale, uint8_t a_zero_point, float b_scale, uint8_t b_zero_point,
+                     float output_scale, uint8_t output_zero_point, int fused_activation, float ca, float cb, mf_op **op) {
+    MF_TRY({
+        create_add(device, true, elems, a_scale, a_zero_point, b_scale, b_zero_point, output_scale, output_zero_point,
+                   fused_activation, ca, cb, op);
+    })
+}
+
+int mf_op_run2(mf_op *op, const int8_t *d_a, const int8_t *d_b, size_t batch, int8_t *d_output, void *stream) {
+    MF_TRY({
+        MF_NEED(op && op->impl);
+        mf::op_run2(op->impl, d_a, d_b, batch, d_output, stream, true);
+    })
+}
 int mf_op_run(mf_op *op, const int8_t *d_input, size_t batch, int8_t *d_output, void *stream) {
     MF_TRY({
         MF_NEED(op && op->impl);
@@ -436,6 +493,18 @@ int mf_model_get_op_constants(const mf_model *model, int index, float *c0, float
         if (c1 && !o.c1.empty()) std::memcpy(c1, o.c1.data(), o.c1.size() * sizeof(float));
         if (c2 && !o.c2.empty()) std::memcpy(c2, o.c2.data(), o.c2.size() * sizeof(int32_t));
         if (c3) *c3 = o.c3;
+    })
+}
+
+int mf_model_get_op_skip(const mf_model *model, int index, int *source, int *running_input) {
+    MF_TRY({
+        MF_NEED(model && model->impl);
+        const mf::ParsedModel &pm = mf::model_parsed(model->impl);
+        MF_NEED(index >= 0 && index < (int)pm.ops.size());
+        const mf::ParsedOp &o = pm.ops[(size_t)index];
+        if (o.kind != MF_OP_ADD) mf::fail(MF_ERR_INVALID_ARG, "mf_model_get_op_skip: the operator is no ADD");
+        if (source) *source = o.skip_src;
+        if (running_input) *running_input = o.run_input;
     })
 }
 

@@ -175,4 +175,35 @@ bool h_pool_window_empty(int H, int W, int KH, int KW, int sh, int sw, bool same
     return (long long)(OH - 1) * sh - shy >= H || (long long)(OW - 1) * sw - shx >= W;
 }
 
+// ADD's two constants: each one f32 division (this unit is built without contraction)
+void h_preprocess_add(float sa, float sb, float so, float *ca, float *cb) {
+    *ca = sa / so;
+    *cb = sb / so;
+}
+
+// One element's tail on the host, the device's instructions one by one (k_add.hip add_one): roundf as y + copysign(0.49999997, y)
+// truncated, NaN -> 0, the clamp
+static int add_tail(float y, int lo, int hi) {
+    float r = y + std::copysign(0x1.fffffep-2f, y);
+    if (r != r) r = 0.0f;
+    r = std::fmin(std::fmax(r, (float)lo), (float)hi);
+    return (int)r;
+}
+bool h_add_fma_form(float ca, float cb, int ka, int kb, int zo, int lo, int hi, float *k1) {
+    *k1 = 0.0f;
+    if (!std::isfinite(ca) || !std::isfinite(cb) || std::fabs(ca) > 0x1p100f || std::fabs(cb) > 0x1p100f) return false;
+    const float k = (float)((double)zo - (double)ca * ka - (double)cb * kb);
+    if (!std::isfinite(k)) return false;
+    const float zo_f = (float)zo;
+    for (int ua = 0; ua < 256; ++ua) {
+        const float ta = ca * (float)(ua - ka), fa = std::fmaf(ca, (float)ua, k);
+        for (int ub = 0; ub < 256; ++ub) {
+            const float y = (zo_f + ta) + cb * (float)(ub - kb);
+            if (add_tail(y, lo, hi) != add_tail(std::fmaf(cb, (float)ub, fa), lo, hi)) return false;
+        }
+    }
+    *k1 = k;
+    return true;
+}
+
 } // namespace mf

@@ -63,6 +63,16 @@ struct PoolArgs {
     float sat_lo, sat_hi; // `as T` saturation: [-128,127] or [0,255]
     int xr;
 };
+// ADD (k_add.hip).  A stored byte u (0 .. 255) holds the value v = (u ^ xin) - off of T: i8 and the internal domain of u8 have
+// xin = 0x80 (off = 128 resp. 0), real u8 bytes xin = 0.  ka = f32(off + za), so f32(u ^ xin) - ka is f32(v - za): both are integers
+// below 2^24 and the f32 subtraction is exact.
+struct AddArgs {
+    float ca, cb, ka, kb;
+    float zo_f;
+    float lo_f, hi_f;     // `as T` saturation and the fused activation as one clamp, values of T (ops_impl.hpp: act_bounds)
+    float k1;             // the gated form (add_c16<fma>): y = fma(cb, f32(ub), fma(ca, f32(ua), k1)), k1 = zo - ca ka - cb kb folded on the host
+    uint32_t xin4, xout4; // per dword: input bytes ^ xin4 are offset values; result bytes (value & 0xff) ^ xout4 are stored
+};
 struct FcArgs {
     int K, N;
     int wzp;
@@ -698,6 +708,10 @@ void launch_avgpool_generic(const int8_t *in, int8_t *out, const PoolArgs &a, si
 void launch_avgpool_c4(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s); // C % 4 == 0
 void launch_maxpool_generic(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s); // MaxPool2D: no window may be empty
 void launch_maxpool_c4(const int8_t *in, int8_t *out, const PoolArgs &a, size_t batch, hipStream_t s); // C % 4 == 0
+// ADD over n bytes (k_add.hip).  out may be exactly a or exactly b.  c16: all three pointers 16-byte aligned; cus: the device's CU count
+// fma: the gated form, only where the host checked it identical over all 65 536 byte pairs (hostmath.cpp: h_add_fma_form)
+void launch_add_c16(const int8_t *a, const int8_t *b, int8_t *out, const AddArgs &p, size_t n, int cus, bool fma, hipStream_t s);
+void launch_add_generic(const int8_t *a, const int8_t *b, int8_t *out, const AddArgs &p, size_t n, hipStream_t s);
 void launch_fc_generic(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s);
 bool launch_fc_rowwave(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s);
 bool launch_fc_rowwave_softmax(const int8_t *in, int8_t *out, const FcArgs &a, const SoftmaxArgs &sm, size_t rows,

@@ -51,6 +51,12 @@ void h_preprocess_conv(float iscale, int n, const int32_t *bias, const float *bs
 void h_preprocess_pool(float iscale, int izp, float oscale, int ozp, float *c0, float *c1);
 // true: some window of this (positive) pool geometry has no in-bounds tap -- MaxPool2D refuses it
 bool h_pool_window_empty(int H, int W, int KH, int KW, int sh, int sw, bool same, int OH, int OW);
+// ADD (not in the reference; include/microflow_amd.h states the contract): ca = sa / so, cb = sb / so, two f32 divisions
+void h_preprocess_add(float sa, float sb, float so, float *ca, float *cb);
+// ADD's gated form y = fma(cb, f32(ub), fma(ca, f32(ua), k1)) with k1 = zo - ca ka - cb kb (ua, ub: bytes 0 .. 255 whose values are
+// ua - ka, ub - kb).  true, with *k1: the constants are finite and the form gives the text's byte -- through the same rounding and
+// the clamp [lo, hi] -- for ALL 65 536 (ua, ub) pairs.  Host only, exhaustive
+bool h_add_fma_form(float ca, float cb, int ka, int kb, int zo, int lo, int hi, float *k1);
 
 // ---- single-fma requantisation: host search (epi_fma.cpp) -------------------
 // y_u8(acc) = v_cvt_pk_u8_f32(v_fma_f32(S, bits_as_f32(0x4B400000 + acc + d), C))  -- k_common.hpp, epilogue mode 3
@@ -96,6 +102,12 @@ struct ParsedOp {
     std::vector<float> c0, c1;
     std::vector<int32_t> c2;
     int32_t c3 = 0;
+    // ADD only: the tensor beside the running one.  skip_src: the operator whose output it is (-1: the model input; -2: no ADD);
+    // run_input: which of the ADD's two inputs (0 = a, 1 = b) the running tensor is; (a_*, b_*): the operands' quantisation by
+    // input position, zero points as values of T.  c0[0] = ca, c1[0] = cb
+    int skip_src = -2, run_input = 0;
+    float a_scale = 0, b_scale = 0;
+    int a_zp = 0, b_zp = 0;
 };
 struct ParsedModel {
     bool u8 = false; // element type T of every quantized tensor: INT8 (false) or UINT8 (true)
@@ -104,7 +116,16 @@ struct ParsedModel {
     float in_scale = 0, out_scale = 0;
     int in_zp = 0, out_zp = 0;
     size_t in_elems = 0, out_elems = 0, max_elems = 0;
+    size_t max_fork_elems = 0; // the largest tensor an operator produces for a later ADD to read beside the running one (0: none)
+    bool input_skip = false;   // some ADD reads the model input beside the running tensor
     std::vector<ParsedOp> ops;
+    // the operator that launches the tensor ADD i reads beside the running one: skip_src with the Reshapes (aliases) in front of it
+    // skipped; -1: the model input
+    int skip_real(size_t i) const {
+        int s = ops[i].skip_src;
+        while (s >= 0 && ops[(size_t)s].kind == MF_OP_RESHAPE) --s;
+        return s;
+    }
 };
 ParsedModel parse_tflite(const uint8_t *buf, size_t len);
 
@@ -132,10 +153,17 @@ struct OpSpec {
     const int32_t *c2 = nullptr;
     int32_t c3 = 0;
     float pool_c0 = 0, pool_c1 = 0;
+    // ADD: elements per inference, the operands' zero points (values of T) and the two constants
+    size_t add_elems = 0;
+    int add_za = 0, add_zb = 0;
+    float add_ca = 0, add_cb = 0;
 };
 OpImpl *op_create(int device, const OpSpec &spec);
 void op_destroy(OpImpl *op);
 void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream);
+// an ADD: out = a + b over batch x elems bytes.  d_out may be exactly d_a or exactly d_b (in place); any other overlap is refused.
+// external: a u8 operator exchanges real u8 bytes (the ABI's view, in the same launch), else the internal domain
+void op_run2(OpImpl *op, const int8_t *d_a, const int8_t *d_b, size_t batch, int8_t *d_out, void *stream, bool external);
 // the ABI's view: a u8 operator exchanges real u8 bytes (two extra byte passes)
 void op_run_external(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream);
 size_t op_in_elems(const OpImpl *op);

@@ -6,6 +6,8 @@
 //   weights + folded constants : resident per op (person_detect: ~0.3 MB)
 //   act[0], act[1]             : ping-pong activation buffers, batch x max tensor bytes
 //   in_q / io_f32              : staging for host-fed batches
+//   fork[0], fork[1]           : models with an ADD only -- where a tensor that a later ADD reads beside the running one is
+//                                written, batch x largest such tensor; the ping-pong never writes there, so no skip is ever copied
 // Every op reads one buffer and writes the other; Reshape is an alias (the 2D<->4D
 // maps of src/tensor.rs:103-141 are the identity in NHWC memory).
 #include <hip/hip_runtime.h>
@@ -42,6 +44,8 @@ struct ModelImpl {
     bool autotune = false; // model_set_autotune: time the run-time-geometry chain candidates at creation
     size_t cap_batch = 0;
     int8_t *act[2] = {nullptr, nullptr};
+    int8_t *fork[2] = {nullptr, nullptr}; // skip tensors (pm.max_fork_elems != 0): two, for an ADD whose sum is the next skip
+    std::vector<char> forks;  // per operator: its tensor (through the Reshapes behind it) is read by a later ADD beside the running one
     int8_t *in_q = nullptr;   // quantized input staging (host-fed or f32 path)
     float *io_f32 = nullptr;  // f32 input / output staging
     size_t io_f32_elems = 0;
@@ -102,6 +106,10 @@ struct ModelImpl {
             if (p) (void)hipFree(p);
             p = nullptr;
         }
+        for (auto &p : fork) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+        }
         if (in_q) (void)hipFree(in_q);
         if (io_f32) (void)hipFree(io_f32);
         if (o_f32) (void)hipFree(o_f32);
@@ -115,6 +123,9 @@ struct ModelImpl {
 ModelImpl *model_create(const uint8_t *buf, size_t len) {
     std::unique_ptr<ModelImpl> m(new ModelImpl);
     m->pm = parse_tflite(buf, len);
+    m->forks.assign(m->pm.ops.size(), 0);
+    for (size_t i = 0; i < m->pm.ops.size(); ++i)
+        if (m->pm.ops[i].kind == MF_OP_ADD && m->pm.skip_real(i) >= 0) m->forks[(size_t)m->pm.skip_real(i)] = 1;
     return m.release();
 }
 void model_destroy(ModelImpl *m) { delete m; }
@@ -230,6 +241,8 @@ static void ensure_capacity(ModelImpl *m, size_t batch) {
     const ParsedModel &pm = m->pm;
     const size_t act_bytes = ((batch * pm.max_elems + 255) / 256) * 256 + 256;
     for (auto &p : m->act) MF_HIP(hipMalloc((void **)&p, act_bytes));
+    if (pm.max_fork_elems)
+        for (auto &p : m->fork) MF_HIP(hipMalloc((void **)&p, ((batch * pm.max_fork_elems + 255) / 256) * 256 + 256));
     MF_HIP(hipMalloc((void **)&m->in_q, ((batch * pm.in_elems + 255) / 256) * 256 + 256));
     m->io_f32_elems = batch * std::max(pm.in_elems, pm.out_elems);
     MF_HIP(hipMalloc((void **)&m->io_f32, m->io_f32_elems * sizeof(float) + 256));
@@ -289,7 +302,7 @@ void model_set_generic(ModelImpl *m, bool generic) {
 static Launch f32_entry(const ModelImpl *m, int last_op) {
     const Launch none{nullptr, -1};
     const int f = m->g.first_real;
-    if (!m->fusion || m->generic || f > last_op || f >= (int)m->g.ops.size()) return none;
+    if (!m->fusion || m->generic || f > last_op || f >= (int)m->g.ops.size() || m->pm.input_skip) return none;
     const Stage *st0 = stage_at(m, f, last_op);
     if (st0 && fused_accepts_f32(st0->f)) return {st0->f, st0->last};
     FusedImpl *g = group_at(m, f, last_op);
@@ -306,6 +319,7 @@ static int last_real_upto(const ModelImpl *m, int last_op) {
 // A run of ops [0 .. last_op] in flight: where the running tensor is, and what the two ends of the run ask for (run_ops)
 struct Run {
     const int8_t *cur; // the running tensor
+    const int8_t *skip; // the live skip tensor, which the next ADD reads beside it: the model input where an ADD reads that (start_run), then every fork tensor as it is written
     size_t batch;
     int last_op, last_real;
     hipStream_t stream;
@@ -321,12 +335,18 @@ struct Run {
 static int run_step(ModelImpl *m, Run &r, int i) {
     OpImpl *o = m->g.ops[(size_t)i];
     const bool f32in = r.src_f32 && i == m->g.first_real;
+    const bool add = m->pm.ops[(size_t)i].kind == MF_OP_ADD; // a launch of its own: the running tensor and the live skip tensor
     int8_t *dst = m->act[r.which];
     if (dst == r.cur) {
         r.which ^= 1;
         dst = m->act[r.which];
     }
-    const Launch l = f32in ? r.entry : launch_at(m, i, r.last_op, r.cur, r.batch);
+    const Launch l = f32in ? r.entry : add ? Launch{nullptr, i} : launch_at(m, i, r.last_op, r.cur, r.batch);
+    // A launch whose result a later ADD reads beside the running value writes it where the ping-pong never writes: the fork buffer
+    // that does not hold the live skip (an ADD may read one and write the other).  No group holds such a tensor inside
+    // (model_groups.cpp: splits), so it is always a launch's result
+    const bool forks = m->forks[(size_t)l.last] != 0;
+    if (forks) dst = (m->fork[0] == r.skip || m->fork[0] == r.cur) ? m->fork[1] : m->fork[0];
     const bool ends = l.last >= r.last_real;
     const bool f32out = r.final_f32 && ends && (l.f ? fused_emits_f32(l.f) : op_emits_f32(o));
     if (r.final_dst && ends) dst = r.final_dst;
@@ -338,9 +358,13 @@ static int run_step(ModelImpl *m, Run &r, int i) {
         r.left_f32 = f32out;
     } else if (l.f) { // several groups, or the whole group, in one launch
         fused_run(l.f, r.cur, r.batch, dst, r.stream);
+    } else if (add) { // (the operand order is the file's: it matters for the f32 sum)
+        const bool run_first = m->pm.ops[(size_t)i].run_input == 0;
+        op_run2(o, run_first ? r.cur : r.skip, run_first ? r.skip : r.cur, r.batch, dst, r.stream, false);
     } else {
         op_run(o, r.cur, r.batch, dst, r.stream);
     }
+    if (forks) r.skip = dst;
     r.cur = dst;
     r.which ^= 1;
     return l.last;
@@ -352,7 +376,7 @@ static int run_step(ModelImpl *m, Run &r, int i) {
 // dequantised floats there if it has such an instance.  The return value says where the int8 result is; nullptr: it left as floats.
 static const int8_t *run_ops(ModelImpl *m, const int8_t *src, size_t batch, int last_op, hipStream_t stream,
                              const float *src_f32 = nullptr, int8_t *final_dst = nullptr, float *final_f32 = nullptr) {
-    Run r{src, batch, last_op, last_real_upto(m, last_op), stream, src_f32};
+    Run r{src, m->pm.input_skip ? src : nullptr, batch, last_op, last_real_upto(m, last_op), stream, src_f32};
     if (src_f32) r.entry = f32_entry(m, last_op);
     if (src_f32 && r.entry.last < 0) fail(MF_ERR_UNSUPPORTED, "no launch takes the f32 input");
     r.final_dst = final_dst, r.final_f32 = final_f32;
@@ -383,6 +407,7 @@ static Boundary boundary_plan(const ModelImpl *m, const float *in_f32, const flo
                               int last_op) {
     Boundary b;
     if (!m->fusion || m->generic || last_op != (int)m->pm.ops.size() - 1) return b;
+    // (a model whose ADD reads the quantised input has no f32 entry -- nothing would materialise it: rule (7) -- so f32_entry says no)
     b.in = in_f32 && ((uintptr_t)in_f32 & 15) == 0 && f32_entry(m, last_op).last >= 0;
     b.out = out_f32 && ((uintptr_t)out_f32 & 3) == 0 && !ranges_overlap(out_f32, out_count * sizeof(float), in_any, in_bytes);
     return b;
@@ -716,7 +741,7 @@ void model_time_device(ModelImpl *m, const int8_t *d_in, size_t batch, int8_t *d
     const hipEvent_t *ev = evs.v.data() + 2;
     std::vector<std::vector<float>> samples((size_t)nops); // per operator: one duration per iteration
     for (int it = 0; it < iters; ++it) {
-        Run r{d_in, batch, nops - 1, m->g.last_real, s};
+        Run r{d_in, m->pm.input_skip ? d_in : nullptr, batch, nops - 1, m->g.last_real, s};
         MF_HIP(hipEventRecord(ev[0], s));
         for (int i = 0; i < nops; ++i) {
             if (m->g.ops[(size_t)i]) { // a stage or a group is timed as one unit (index i), its other ops 0

@@ -44,6 +44,19 @@ struct GroupBuilder {
     bool free_op(size_t i) const { return g.ops[i] && !g.fused[i] && !covered(i) && !owned(i); }
     bool free_fc(size_t i) const { return i < n && kind(i) == MF_OP_FULLY_CONNECTED && free_op(i); }
     bool free_sm(size_t i) const { return i < n && kind(i) == MF_OP_SOFTMAX && free_op(i); }
+    // A fork tensor -- an operator's output that a later ADD reads beside the running value -- has to exist in memory, so no group
+    // may hold one strictly inside: true when operators first .. last as ONE launch would swallow such a tensor (the operator that
+    // launches it at or behind `first` and in front of `last`; a group may end at one or start behind one), or would hold an ADD,
+    // which is a launch of its own.  A candidate this refuses falls back exactly as an unmatched one does
+    bool splits(size_t first, size_t last) const {
+        for (size_t k = 0; k < n; ++k) {
+            if (kind(k) != MF_OP_ADD) continue;
+            if (k >= first && k <= last) return true;
+            const int s = pm.skip_real(k);
+            if (s >= (int)first && s < (int)last) return true;
+        }
+        return false;
+    }
     size_t skip_reshapes(size_t j) const {
         while (j < n && kind(j) == MF_OP_RESHAPE) ++j;
         return j;
@@ -72,6 +85,10 @@ static OpSpec op_spec(const ParsedModel &pm, const ParsedOp &po, float cur_scale
     s.c2 = po.c2.empty() ? nullptr : po.c2.data();
     s.c3 = po.c3;
     if (po.kind == MF_OP_AVERAGE_POOL_2D || po.kind == MF_OP_MAX_POOL_2D) s.pool_c0 = po.c0[0], s.pool_c1 = po.c1[0];
+    if (po.kind == MF_OP_ADD) { // (the operands' quantisation is the file's, by input position: izp / in_scale are not used)
+        s.add_elems = po.in_elems, s.add_za = po.a_zp, s.add_zb = po.b_zp;
+        s.add_ca = po.c0[0], s.add_cb = po.c1[0];
+    }
     return s;
 }
 
@@ -94,8 +111,9 @@ static void create_operators(GroupBuilder &b) {
     while (b.g.first_real < (int)b.n && !ops[(size_t)b.g.first_real]) ++b.g.first_real;
     b.g.last_real = (int)b.n - 1;
     while (b.g.last_real >= 0 && !ops[(size_t)b.g.last_real]) --b.g.last_real;
-    // peephole (0): the boundary quantize of M::predict folds into operator 0 when that is the stem
-    if (!ops.empty() && ops[0]) (void)op_set_input_quant(ops[0], b.pm.in_scale, b.pm.in_zp, b.pm.u8);
+    // peephole (0): the boundary quantize of M::predict folds into operator 0 when that is the stem -- unless an ADD reads the
+    // quantised model input later: nothing would materialise it (the runtime never copies a skip tensor)
+    if (!ops.empty() && ops[0] && !b.pm.input_skip) (void)op_set_input_quant(ops[0], b.pm.in_scale, b.pm.in_zp, b.pm.u8);
 }
 
 // peepholes.  (1) DepthwiseConv2D 3x3 directly followed by a 1x1 Conv2D -> one fused kernel.
@@ -107,13 +125,13 @@ static void rule_1_2_3_first_level(GroupBuilder &b) {
     std::vector<int> &fused_last = b.g.fused_last;
     for (size_t i = 0; i + 1 < b.n; ++i) {
         if (b.kind(i) == MF_OP_DEPTHWISE_CONV_2D && b.kind(i + 1) == MF_OP_CONV_2D) {
-            if ((fused[i] = fused_create(ops[i], ops[i + 1]))) fused_last[i] = (int)i + 1;
+            if (!b.splits(i, i + 1) && (fused[i] = fused_create(ops[i], ops[i + 1]))) fused_last[i] = (int)i + 1;
         } else if (b.kind(i) == MF_OP_AVERAGE_POOL_2D && b.kind(i + 1) == MF_OP_CONV_2D) {
             const size_t j = b.skip_reshapes(i + 2);
-            if (j < b.n && b.kind(j) == MF_OP_SOFTMAX && (fused[i] = fused_tail_create(ops[i], ops[i + 1], ops[j]))) fused_last[i] = (int)j;
+            if (j < b.n && b.kind(j) == MF_OP_SOFTMAX && !b.splits(i, j) && (fused[i] = fused_tail_create(ops[i], ops[i + 1], ops[j]))) fused_last[i] = (int)j;
         } else if (b.kind(i) == MF_OP_FULLY_CONNECTED) { // (3) FC -> [Reshape] -> Softmax
             const size_t j = b.skip_reshapes(i + 1);
-            if (j < b.n && b.kind(j) == MF_OP_SOFTMAX && (fused[i] = fused_fc_softmax_create(ops[i], ops[j]))) fused_last[i] = (int)j;
+            if (j < b.n && b.kind(j) == MF_OP_SOFTMAX && !b.splits(i, j) && (fused[i] = fused_fc_softmax_create(ops[i], ops[j]))) fused_last[i] = (int)j;
         }
         if (fused[i]) i = (size_t)fused_last[i]; // groups do not overlap
     }
@@ -127,7 +145,7 @@ static void rule_4_stage_runs(GroupBuilder &b) {
         std::vector<FusedImpl *> run;
         size_t a = i;
         while (a + 1 < b.n && b.is_pair_group(a) && b.po(a).H == b.po(i).H && b.po(a).W == b.po(i).W && b.po(a).C == b.po(i).C &&
-               b.po(a + 1).N == b.po(i).C && b.po(a).sh == 1) {
+               b.po(a + 1).N == b.po(i).C && b.po(a).sh == 1 && !(a > i && b.splits(a - 1, a))) { // (a fork tensor ends the run)
             run.push_back(b.g.fused[a]);
             a += 2;
         }
@@ -150,6 +168,7 @@ static void rule_4b_quads(GroupBuilder &b) {
     for (size_t i = 0; i + 3 < b.n; ++i) {
         if (!b.is_pair_group(i) || b.covered(i) || b.covered(i + 2)) continue;
         if (!b.is_pair_group(i + 2)) continue;
+        if (b.splits(i, i + 3)) continue;
         if (FusedImpl *f = fused_quad_create(b.g.fused[i], b.g.fused[i + 2])) {
             b.add_stage(f, i, i + 3);
             // ... and with the stem in front of it: ops i - 1 .. i + 3 in one launch.  Both stay: a run that does not
@@ -157,7 +176,7 @@ static void rule_4b_quads(GroupBuilder &b) {
             // (The stem test does not ask owned(i - 1), and need not: fused_quad_stem_create takes a one-channel depthwise stem only,
             // and a depthwise operator is never a later member of a first-level group -- (1) starts at one, (2) and (3) hold none.  The
             // operator that CAN sit there owned, the 1x1 of a pair group at i - 2, is refused by its kind)
-            if (i >= 1 && b.g.ops[i - 1] && !b.g.fused[i - 1] && !b.covered(i - 1))
+            if (i >= 1 && b.g.ops[i - 1] && !b.g.fused[i - 1] && !b.covered(i - 1) && !b.splits(i - 1, i + 3))
                 if (FusedImpl *g = fused_quad_stem_create(b.g.ops[i - 1], f)) b.add_stage(g, i - 1, i + 3);
             i += 3;
         }
@@ -171,12 +190,12 @@ static void rule_4b1_pair_tail(GroupBuilder &b) {
     for (size_t i = 0; i + 2 < b.n; ++i) {
         if (!b.is_pair_group(i) || b.covered(i)) continue;
         const size_t j = i + 2;
-        if (fused[j] && !b.covered(j))
+        if (fused[j] && !b.covered(j) && !b.splits(i, (size_t)b.g.fused_last[j]))
             if (FusedImpl *f = fused_pair_tail_create(fused[i], fused[j])) {
                 b.add_stage(f, i, (size_t)b.g.fused_last[j]);
                 // ... and with the pair group in front of it: ops i - 2 .. the tail's end in one launch.  Both stay (a run that
                 // ends before the tail uses the pair groups, mf_model_run_until pieces that start at i the pair + tail stage)
-                if (i >= 2 && b.is_pair_group(i - 2) && !b.covered(i - 2))
+                if (i >= 2 && b.is_pair_group(i - 2) && !b.covered(i - 2) && !b.splits(i - 2, (size_t)b.g.fused_last[j]))
                     if (FusedImpl *g = fused_front_pair_tail_create(fused[i - 2], f)) b.add_stage(g, i - 2, (size_t)b.g.fused_last[j]);
             }
     }
@@ -194,7 +213,7 @@ static void rule_4c_chains(GroupBuilder &b) {
         chain_runs = true;
         std::vector<FusedImpl *> run;
         size_t a = i;
-        for (; a + 1 < b.n && chain_pair(a); a += 2) run.push_back(fused[a]);
+        for (; a + 1 < b.n && chain_pair(a) && !(a > i && b.splits(a - 1, a)); a += 2) run.push_back(fused[a]); // (a fork tensor ends the run)
         const int rn = (int)run.size();
         std::vector<int> seg((size_t)rn, 0);
         std::unique_ptr<bool[]> unf(new bool[(size_t)rn]);
@@ -223,7 +242,7 @@ static void rule_4d_expand_blocks(GroupBuilder &b) {
     const std::vector<OpImpl *> &ops = b.g.ops;
     for (size_t i = 0; i + 2 < b.n; ++i) {
         if (b.kind(i) != MF_OP_CONV_2D || !b.free_op(i)) continue;
-        if (!ops[i + 1] || !ops[i + 2] || b.covered(i + 1) || b.covered(i + 2)) continue;
+        if (!ops[i + 1] || !ops[i + 2] || b.covered(i + 1) || b.covered(i + 2) || b.splits(i, i + 2)) continue;
         if (FusedImpl *f = fused_block_create(ops[i], ops[i + 1], ops[i + 2], b.g.fused[i + 1] != nullptr)) {
             b.add_stage(f, i, i + 2);
             i += 2;
@@ -239,7 +258,7 @@ static void rule_5_dwfc(GroupBuilder &b) {
     for (size_t i = 0; i + 1 < b.n; ++i) {
         if (!b.g.ops[i] || b.g.fused[i] || b.covered(i) || b.kind(i) != MF_OP_DEPTHWISE_CONV_2D) continue;
         const size_t j = b.skip_reshapes(i + 1);
-        if (j < b.n && b.g.fused[j] && !b.covered(j))
+        if (j < b.n && b.g.fused[j] && !b.covered(j) && !b.splits(i, (size_t)b.g.fused_last[j]))
             if (FusedImpl *f = fused_dwfc_create(b.g.ops[i], b.g.fused[j])) b.add_stage(f, i, (size_t)b.g.fused_last[j]);
     }
 }
@@ -254,14 +273,15 @@ static void rule_5a_conv1_fc(GroupBuilder &b) {
         if (!b.free_op(i) || (b.kind(i) != MF_OP_DEPTHWISE_CONV_2D && b.kind(i) != MF_OP_CONV_2D) || b.po(i).C != 1) continue;
         const size_t j0 = b.skip_reshapes(i + 1);
         if (j0 >= b.n || !ops[j0] || b.kind(j0) != MF_OP_FULLY_CONNECTED || b.po(j0).M != 1 || b.covered(j0) || b.owned(j0)) continue;
+        if (b.splits(i, j0)) continue;
         if (b.g.fused[j0]) {
             const int last = b.g.fused_last[j0];
-            if (last > (int)j0 && b.kind((size_t)last) == MF_OP_SOFTMAX)
+            if (last > (int)j0 && b.kind((size_t)last) == MF_OP_SOFTMAX && !b.splits(i, (size_t)last))
                 if (FusedImpl *f = fused_conv1_fc_create(ops[i], ops[j0], ops[(size_t)last])) b.add_stage(f, i, (size_t)last);
             continue;
         }
         const size_t smi = b.skip_reshapes(j0 + 1);
-        OpImpl *sm = b.free_sm(smi) ? ops[smi] : nullptr;
+        OpImpl *sm = b.free_sm(smi) && !b.splits(i, smi) ? ops[smi] : nullptr;
         if (sm && !fused_conv1_fc_fits(ops[i], ops[j0], sm)) sm = nullptr; // (the two operators without the Softmax)
         if (FusedImpl *f = fused_conv1_fc_create(ops[i], ops[j0], sm)) b.add_stage(f, i, sm ? smi : j0);
     }
@@ -281,21 +301,22 @@ static void rule_5b_pool_fc(GroupBuilder &b) {
             b.kind((size_t)b.g.fused_last[j0]) == MF_OP_SOFTMAX) {
             OpImpl *fc = ops[j0];
             const size_t last = (size_t)b.g.fused_last[j0];
+            if (b.splits(i, last)) continue;
             if (FusedImpl *f = fused_pool_fc_create(ops[i], &fc, 1, ops[last])) b.add_stage(f, i, last);
             continue;
         }
-        if (!b.free_fc(j0) || b.po(j0).M != 1) continue;
+        if (!b.free_fc(j0) || b.po(j0).M != 1 || b.splits(i, j0)) continue;
         std::vector<size_t> idx{j0};
         for (;;) {
             const size_t j = b.skip_reshapes(idx.back() + 1);
-            if (!b.free_fc(j) || b.po(j).M != 1 || b.po(j).K != b.po(idx.back()).N) break;
+            if (!b.free_fc(j) || b.po(j).M != 1 || b.po(j).K != b.po(idx.back()).N || b.splits(i, j)) break;
             idx.push_back(j);
         }
         std::vector<OpImpl *> run;
         for (size_t j : idx) run.push_back(ops[j]);
         for (size_t len = run.size(); len >= 1; --len) {
             const size_t smi = b.skip_reshapes(idx[len - 1] + 1);
-            OpImpl *sm = b.free_sm(smi) ? ops[smi] : nullptr;
+            OpImpl *sm = b.free_sm(smi) && !b.splits(i, smi) ? ops[smi] : nullptr;
             if (sm && !fused_pool_fc_fits(ops[i], run.data(), (int)len, sm)) sm = nullptr; // (the layers without their Softmax)
             if (FusedImpl *f = fused_pool_fc_create(ops[i], run.data(), (int)len, sm)) {
                 b.add_stage(f, i, sm ? smi : idx[len - 1]);
@@ -340,11 +361,11 @@ static void rule_6_fc_chains(GroupBuilder &b) {
         std::vector<size_t> idx{i};
         for (;;) {
             const size_t j = b.skip_reshapes(idx.back() + 1);
-            if (!b.free_fc(j) || b.po(j).M != b.po(idx.back()).M || b.po(j).K != b.po(idx.back()).N) break;
+            if (!b.free_fc(j) || b.po(j).M != b.po(idx.back()).M || b.po(j).K != b.po(idx.back()).N || b.splits(i, j)) break;
             idx.push_back(j);
         }
         const size_t smi = b.skip_reshapes(idx.back() + 1);
-        OpImpl *sm = b.free_sm(smi) ? b.g.ops[smi] : nullptr;
+        OpImpl *sm = b.free_sm(smi) && !b.splits(i, smi) ? b.g.ops[smi] : nullptr;
         std::vector<OpImpl *> run;
         for (size_t j : idx) run.push_back(b.g.ops[j]);
         cut_fc_run(b, idx, run, sm, smi);
@@ -361,7 +382,7 @@ static void rule_6a_conv_pool(GroupBuilder &b) {
     for (size_t i = 0; i + 1 < b.n; ++i) {
         const int pk = b.kind(i + 1); // (an AveragePool2D: conv_pool_rt; a MaxPool2D: conv_maxpool_rt)
         if (b.kind(i) != MF_OP_CONV_2D || (pk != MF_OP_AVERAGE_POOL_2D && pk != MF_OP_MAX_POOL_2D) || !b.free_op(i) || !b.free_op(i + 1)) continue;
-        if (b.po(i + 1).OH * b.po(i + 1).OW < 2) continue;
+        if (b.po(i + 1).OH * b.po(i + 1).OW < 2 || b.splits(i, i + 1)) continue;
         if ((int)i == b.g.first_real && op_accepts_f32(b.g.ops[i])) continue;
         if (FusedImpl *f = fused_conv_pool_create(b.g.ops[i], b.g.ops[i + 1])) {
             b.add_stage(f, i, i + 1);
@@ -377,13 +398,14 @@ static void rule_7_boundaries(GroupBuilder &b) {
     const ParsedModel &pm = b.pm;
     const ModelGroups &g = b.g;
     const size_t first_real = (size_t)g.first_real;
-    if (first_real < b.n && g.fused[first_real]) (void)fused_set_input_quant(g.fused[first_real], pm.in_scale, pm.in_zp, pm.u8);
-    if (first_real > 0 && first_real < b.n) (void)op_set_input_quant(g.ops[first_real], pm.in_scale, pm.in_zp, pm.u8);
+    const bool entry = !pm.input_skip; // (an ADD that reads the quantised model input needs it in memory: no f32 entry)
+    if (entry && first_real < b.n && g.fused[first_real]) (void)fused_set_input_quant(g.fused[first_real], pm.in_scale, pm.in_zp, pm.u8);
+    if (entry && first_real > 0 && first_real < b.n) (void)op_set_input_quant(g.ops[first_real], pm.in_scale, pm.in_zp, pm.u8);
     if (g.last_real >= 0) (void)op_set_output_dequant(g.ops[(size_t)g.last_real], pm.out_scale, pm.out_zp, pm.u8);
     for (size_t i = 0; i < b.n; ++i)
         if (g.fused[i] && g.fused_last[i] == g.last_real) (void)fused_set_output_dequant(g.fused[i], pm.out_scale, pm.out_zp, pm.u8);
     for (const ModelGroups::Stage &st : g.stages) {
-        if (st.first == g.first_real) (void)fused_set_input_quant(st.f, pm.in_scale, pm.in_zp, pm.u8);
+        if (entry && st.first == g.first_real) (void)fused_set_input_quant(st.f, pm.in_scale, pm.in_zp, pm.u8);
         if (st.last == g.last_real) (void)fused_set_output_dequant(st.f, pm.out_scale, pm.out_zp, pm.u8);
     }
 }

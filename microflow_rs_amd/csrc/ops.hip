@@ -772,6 +772,25 @@ void create_softmax(OpImpl &op, const OpSpec &s, int xr) {
     op.generic_name = "softmax_table";
 }
 
+// ADD: no weights; the constants of both domains the operator is run in (kernels.hpp: AddArgs)
+void create_add(OpImpl &op, const OpSpec &s, int lo, int hi) {
+    if (!s.add_elems) fail(MF_ERR_INVALID_ARG, "add: bad arguments");
+    op.in_elems = op.out_elems = s.add_elems;
+    k::AddArgs &a = op.add;
+    const int off = s.u8 ? 0 : 128;
+    a.ca = s.add_ca, a.cb = s.add_cb, a.ka = (float)(off + s.add_za), a.kb = (float)(off + s.add_zb);
+    a.zo_f = (float)s.ozp, a.lo_f = (float)lo, a.hi_f = (float)hi; // (act_bounds: [lo, hi] lies inside T's range)
+    op.add_fma = h_add_fma_form(a.ca, a.cb, off + s.add_za, off + s.add_zb, s.ozp, lo, hi, &a.k1);
+    a.xin4 = 0x80808080u, a.xout4 = s.u8 ? 0x80808080u : 0u;
+    op.add_ext = a;
+    if (s.u8) op.add_ext.xin4 = op.add_ext.xout4 = 0u; // real u8 bytes
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, op.device) != hipSuccess) (void)hipGetLastError(), cus = 0;
+    op.cus = cus;
+    op.generic_name = "add_generic";
+    op.fast = OpImpl::ADD_C16, op.fast_name = op.add_fma ? "add_c16<fma>" : "add_c16"; // taken where all three pointers are 16-byte aligned
+}
+
 } // namespace
 
 OpImpl *op_create(int device, const OpSpec &spec) {
@@ -791,6 +810,7 @@ OpImpl *op_create(int device, const OpSpec &spec) {
     case MF_OP_MAX_POOL_2D: create_pool(*op, s, lo, hi, xr); break;
     case MF_OP_FULLY_CONNECTED: create_fc(*op, s, dom, lo, hi, xr); break;
     case MF_OP_SOFTMAX: create_softmax(*op, s, xr); break;
+    case MF_OP_ADD: create_add(*op, s, lo, hi); break;
     default: fail(MF_ERR_UNSUPPORTED, "unsupported operator kind " + std::to_string(s.kind));
     }
     op->s = s;
@@ -836,6 +856,7 @@ int op_fma_patches(const OpImpl *op) { return op->fma_ok ? op->fma_patch.n : -1;
 void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream) {
     if (!batch) return;
     if (!d_in || !d_out) fail(MF_ERR_INVALID_ARG, "op_run: null device pointer");
+    if (op->s.kind == MF_OP_ADD) fail(MF_ERR_INVALID_ARG, "op_run: an ADD has two inputs (mf_op_run2)");
     hipStream_t s = (hipStream_t)stream;
     const OpSpec &sp = op->s;
     // the fast kernels move 4- and 16-byte words (vector loads, LDS-DMA, packed stores): buffers that are not 16-byte
@@ -986,8 +1007,30 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
     MF_HIP(hipGetLastError());
 }
 
+// ADD.  The output may be exactly one of the inputs; add_c16 where all three pointers are 16-byte aligned, else the byte-wise kernel
+void op_run2(OpImpl *op, const int8_t *d_a, const int8_t *d_b, size_t batch, int8_t *d_out, void *stream, bool external) {
+    if (op->s.kind != MF_OP_ADD) fail(MF_ERR_INVALID_ARG, "op_run2: the operator has one input (mf_op_run)");
+    if (!batch) return;
+    if (!d_a || !d_b || !d_out) fail(MF_ERR_INVALID_ARG, "op_run2: null device pointer");
+    if (batch > (~(size_t)0 >> 1) / op->in_elems) fail(MF_ERR_INVALID_ARG, "batch too large");
+    const size_t n = batch * op->in_elems;
+    const uintptr_t o = (uintptr_t)d_out;
+    for (const int8_t *in : {d_a, d_b}) {
+        const uintptr_t i = (uintptr_t)in;
+        if (i != o && i < o + n && o < i + n) fail(MF_ERR_INVALID_ARG, "op_run2: the output partly overlaps an input");
+    }
+    if (external) MF_HIP(hipSetDevice(op->device));
+    hipStream_t s = (hipStream_t)stream;
+    const k::AddArgs &a = external ? op->add_ext : op->add;
+    const bool aligned = (((uintptr_t)d_a | (uintptr_t)d_b | o) & 15) == 0;
+    if (aligned && !op->force_generic) k::launch_add_c16(d_a, d_b, d_out, a, n, op->cus, op->add_fma, s);
+    else k::launch_add_generic(d_a, d_b, d_out, a, n, s);
+    MF_HIP(hipGetLastError());
+}
+
 // The C ABI's mf_op_run: a u8 operator takes and returns real u8 bytes.
 void op_run_external(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream) {
+    if (op->s.kind == MF_OP_ADD) fail(MF_ERR_INVALID_ARG, "op_run: an ADD has two inputs (mf_op_run2)");
     MF_HIP(hipSetDevice(op->device)); // the operator's buffers and kernels live on its device
     if (!op->s.u8) return op_run(op, d_in, batch, d_out, stream);
     if (!batch) return;

@@ -5,6 +5,7 @@
 // flatbuffers bindings (23k lines upstream) are replaced by a bounds-checked
 // cursor over the handful of tables the path reads.  Field ids are from
 // microflow-macros/flatbuffers/tflite.fbs.
+#include <cmath>
 #include <cstring>
 
 #include "mf_internal.hpp"
@@ -233,6 +234,10 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
     // same shape, from the graph input through every operator to the graph output.
     int32_t prev_index = g_in.get<int32_t>(0);
     std::vector<int> prev_shape(pm.in_shape, pm.in_shape + pm.in_rank);
+    // ... with skip edges (ADD, below): the output tensor index of every operator so far, and the last ADD -- the point up to which
+    // an earlier skip tensor was alive
+    std::vector<int32_t> out_index;
+    int last_add = -1;
     auto same_tensor = [](std::vector<int> a, std::vector<int> b) {
         if (a.size() == 1) a.insert(a.begin(), 1);
         if (b.size() == 1) b.insert(b.begin(), 1);
@@ -251,7 +256,8 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
         if (!ins.size() || !outs.size()) fail(MF_ERR_INVALID_MODEL, "invalid model: operator without tensors");
         TensorInfo in = read_tensor(tensors, buffers, ins.get<int32_t>(0));
         TensorInfo out = read_tensor(tensors, buffers, outs.get<int32_t>(0));
-        if (ins.get<int32_t>(0) != prev_index && !same_tensor(in.shape, prev_shape))
+        const int32_t running_index = prev_index;
+        if (code != MF_OP_ADD && ins.get<int32_t>(0) != prev_index && !same_tensor(in.shape, prev_shape)) // (an ADD checks its own inputs)
             fail(MF_ERR_UNSUPPORTED, "operator " + std::to_string(oi) + " does not consume the previous operator's "
                                      "output (or the model input): only linear operator chains are supported");
         prev_index = outs.get<int32_t>(0);
@@ -385,9 +391,56 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             if (in.elems() != out.elems()) fail(MF_ERR_INVALID_MODEL, "invalid model: reshape changes size");
             break;
         }
+        case MF_OP_ADD: { // not in the reference (lib.rs:148 answers "unsupported operator: 0"): the contract is include/microflow_amd.h's
+            // The graphs that load are chains with skip edges: the ADD reads the running value (in either position) and ONE earlier
+            // tensor of the chain, matched by tensor index; at most one such tensor is alive at a time.  Everything else keeps the
+            // reference's answer, with the reason behind it
+            auto refuse = [](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: 0 (ADD: " + why + ")"); };
+            if (ins.size() < 2) refuse("it needs two inputs");
+            const int32_t ia = ins.get<int32_t>(0), ib = ins.get<int32_t>(1);
+            TensorInfo tb = read_tensor(tensors, buffers, ib);
+            if (in.data_len || tb.data_len) refuse("a constant operand");
+            if (ins.size() != 2) refuse("it needs two inputs");
+            for (const TensorInfo *t : {&in, &tb, &out}) {
+                if ((t->type != TT_INT8 && t->type != TT_UINT8) || (t->type == TT_UINT8) != pm.u8) refuse("mixed element types");
+                need_quant(*t, "ADD");
+                if (t->scale.size() != 1 || t->zp.size() != 1) refuse("per-channel quantisation on an operand");
+                if (!(t->scale[0] > 0.0f) || !std::isfinite(t->scale[0]))
+                    fail(MF_ERR_INVALID_MODEL, "invalid model: ADD scales must be finite and positive");
+            }
+            if (ia == ib) refuse("both inputs are the same tensor");
+            if (ia != running_index && ib != running_index) refuse("neither input is the running value");
+            po.run_input = ia == running_index ? 0 : 1;
+            const int32_t is = po.run_input == 0 ? ib : ia;
+            int src = -2;
+            if (is == g_in.get<int32_t>(0)) src = -1;
+            for (size_t j = 0; j < out_index.size(); ++j)
+                if (out_index[j] == is) src = (int)j;
+            if (src == -2) refuse("the other input is no earlier tensor of the chain");
+            for (const ParsedOp &e : pm.ops)
+                if (e.kind == MF_OP_ADD && e.skip_src == src) refuse("a fork tensor is used twice");
+            if (src < last_add) refuse("two skip tensors alive at once (overlapping or nested skips)");
+            if (in.shape != tb.shape || in.shape != out.shape) refuse("differing shapes (no broadcasting)");
+            if (in.shape.size() != 2 && in.shape.size() != 4) refuse("tensor rank must be 2 or 4");
+            if (in.shape.size() == 4 && in.shape[0] != 1) refuse("tensor batch must be 1");
+            set_shapes(po, po.run_input == 0 ? in : tb, out, pm.u8); // (in_scale / in_zp: the running operand's)
+            po.skip_src = src;
+            po.act = check_act(opt.scalar<int8_t>(0, 0)); // AddOptions { act:0 pot_scale_int16:1 (ignored) }
+            po.a_scale = in.scale[0], po.b_scale = tb.scale[0];
+            po.a_zp = zp_of(in.zp[0], pm.u8), po.b_zp = zp_of(tb.zp[0], pm.u8);
+            po.c0.resize(1), po.c1.resize(1);
+            h_preprocess_add(po.a_scale, po.b_scale, out.scale[0], po.c0.data(), po.c1.data());
+            int real = src; // (Reshapes are aliases: the operator that launches the tensor, or the model input)
+            while (real >= 0 && pm.ops[(size_t)real].kind == MF_OP_RESHAPE) --real;
+            if (real < 0) pm.input_skip = true;
+            else if (po.in_elems > pm.max_fork_elems) pm.max_fork_elems = po.in_elems;
+            last_add = (int)oi;
+            break;
+        }
         default:
             fail(MF_ERR_UNSUPPORTED, "unsupported operator: " + std::to_string(code)); // lib.rs:148
         }
+        out_index.push_back(outs.get<int32_t>(0));
         if (po.out_elems > pm.max_elems) pm.max_elems = po.out_elems;
         if (po.in_elems > pm.max_elems) pm.max_elems = po.in_elems;
         pm.ops.push_back(std::move(po));

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 
-OP_NAMES = {1: "average_pool_2d", 3: "conv_2d", 4: "depthwise_conv_2d", 9: "fully_connected", 17: "max_pool_2d",
+OP_NAMES = {0: "add", 1: "average_pool_2d", 3: "conv_2d", 4: "depthwise_conv_2d", 9: "fully_connected", 17: "max_pool_2d",
             22: "reshape", 25: "softmax"}
 
 
@@ -62,6 +62,13 @@ class Model:
         mode = C.c_int(-1)
         _lib.check(_lib.lib().mf_model_get_op_epilogue_mode(self._h, int(i), C.byref(mode)))
         return mode.value
+
+    def op_skip(self, i):
+        """(source, running_input) of ADD i: the operator whose output it reads beside the running value (-1: the model input) and
+        which of its two inputs (0 or 1) the running value is.  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
+        src, pos = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().mf_model_get_op_skip(self._h, int(i), C.byref(src), C.byref(pos)))
+        return src.value, pos.value
 
     @property
     def ops(self):

@@ -6,6 +6,7 @@ names, argument order and meaning, executed by the HIP kernels behind the C ABI.
     depthwise_conv_2d(input, weights, output_scale, output_zero_point, options, constants, output_shape)
     average_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)
     max_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)   (not in the reference)
+    add(a, b, output_scale, output_zero_point, options, constants)                                        (not in the reference)
     softmax(input, output_scale, output_zero_point)
     reshape(input, output_shape)
 
@@ -87,8 +88,9 @@ def _fn(name, dtype):
 class PreparedOp:
     """A prepared operator (mf_op): weights + folded constants resident in HBM."""
 
-    def __init__(self, handle, in_tail, out_tail, dtype=np.int8):
+    def __init__(self, handle, in_tail, out_tail, dtype=np.int8, binary=False):
         self._h = handle
+        self.binary = binary   # an ADD: two inputs (mf_op_run2)
         self.in_tail, self.out_tail = tuple(in_tail), tuple(out_tail)
         self.dtype = dtype
 
@@ -100,9 +102,7 @@ class PreparedOp:
         _lib.check(_lib.lib().mf_op_set_generic(self._h, int(generic)))
         return self
 
-    def __call__(self, x):
-        """x: numpy (host) or torch cuda tensor of the operator's element type (int8 / uint8),
-        shape [..batch] + in_tail."""
+    def _stage(self, x):
         torch = _torch()
         is_np = not isinstance(x, torch.Tensor)
         tdt = torch.uint8 if self.dtype == np.uint8 else torch.int8
@@ -112,6 +112,19 @@ class PreparedOp:
         xt = torch.as_tensor(np.ascontiguousarray(x, dtype=self.dtype)).cuda() if is_np else x.contiguous()
         if xt.dtype != tdt:
             raise TypeError("%s tensor expected" % np.dtype(self.dtype).name)
+        return xt, is_np, tdt
+
+    def __call__(self, x, y=None):
+        """x: numpy (host) or torch cuda tensor of the operator's element type (int8 / uint8),
+        shape [..batch] + in_tail.  An ADD takes two of them, of one shape: x is operand a, y operand b."""
+        torch = _torch()
+        if self.binary != (y is not None):
+            raise TypeError("the operator takes %s" % ("two inputs" if self.binary else "one input"))
+        xt, is_np, tdt = self._stage(x)
+        if self.binary:
+            yt = self._stage(y)[0]
+            if tuple(yt.shape) != tuple(xt.shape) or yt.device != xt.device:
+                raise ValueError("the two inputs of an ADD must have one shape and one device")
         in_elems = int(np.prod(self.in_tail))
         if xt.numel() % in_elems:
             raise ValueError("input size %d is not a multiple of %d" % (xt.numel(), in_elems))
@@ -123,7 +136,10 @@ class PreparedOp:
             lead = (batch,)
         out = torch.empty(lead + self.out_tail, dtype=tdt, device=xt.device)
         stream = torch.cuda.current_stream(xt.device).cuda_stream
-        _lib.check(_lib.lib().mf_op_run(self._h, xt.data_ptr(), batch, out.data_ptr(), stream))
+        if self.binary:
+            _lib.check(_lib.lib().mf_op_run2(self._h, xt.data_ptr(), yt.data_ptr(), batch, out.data_ptr(), stream))
+        else:
+            _lib.check(_lib.lib().mf_op_run(self._h, xt.data_ptr(), batch, out.data_ptr(), stream))
         if is_np:
             return out.cpu().numpy()
         return out
@@ -269,6 +285,41 @@ def max_pool_2d(input: Tensor4D, filter_shape, output_scale, output_zero_point,
     op = prepare_max_pool_2d(shp[-3:], filter_shape, output_scale[0], output_zero_point[0],
                              options, constants, output_shape, dtype=_elem(input.buffer))
     return Tensor4D(op(input.buffer), list(output_scale), list(output_zero_point))
+
+
+@dataclass
+class AddOptions:                         # (not in the reference) tflite.fbs AddOptions
+    fused_activation: FusedActivation = FusedActivation.NONE
+
+
+def preprocess_add(a_scale, b_scale, output_scale):
+    """(ca, cb) = (a_scale / output_scale, b_scale / output_scale) in f32, as the library's host computes them."""
+    ca, cb = C.c_float(0), C.c_float(0)
+    _lib.check(_lib.lib().mf_preprocess_add(float(a_scale), float(b_scale), float(output_scale), C.byref(ca), C.byref(cb)))
+    return np.float32(ca.value), np.float32(cb.value)
+
+
+def prepare_add(elems_or_shape, a_q, b_q, out_q, options, constants=None, dtype=np.int8):
+    """a_q, b_q, out_q: (scale, zero_point) of the two operands and the output; constants: (ca, cb), computed when None."""
+    tail = (int(elems_or_shape),) if np.isscalar(elems_or_shape) else tuple(int(d) for d in elems_or_shape)
+    if constants is None:
+        constants = preprocess_add(a_q[0], b_q[0], out_q[0])
+    h = C.c_void_p()
+    _lib.check(_fn("mf_add_create", dtype)(
+        _device(), int(np.prod(tail)), float(a_q[0]), int(a_q[1]), float(b_q[0]), int(b_q[1]), float(out_q[0]), int(out_q[1]),
+        int(options.fused_activation), float(constants[0]), float(constants[1]), C.byref(h)))
+    return PreparedOp(h, tail, tail, dtype, binary=True)
+
+
+def add(a, b, output_scale, output_zero_point, options: AddOptions, constants=None):
+    """ADD (TFLite builtin 0; the reference has none) of two tensors of one shape and element type, per-tensor quantisation:
+    y = T::from(roundf((f32(zo) + ca * f32(a - za)) + cb * f32(b - zb))), every step rounded to f32, then the fused activation
+    (include/microflow_amd.h).  The operand order is kept."""
+    shp = tuple(a.buffer.shape)
+    tail = shp[-3:] if len(shp) >= 3 else shp[-2:]
+    op = prepare_add(tail, (a.scale[0], a.zero_point[0]), (b.scale[0], b.zero_point[0]),
+                     (output_scale[0], output_zero_point[0]), options, constants, dtype=_elem(a.buffer))
+    return type(a)(op(a.buffer, b.buffer), list(output_scale), list(output_zero_point))
 
 
 def prepare_softmax(rows, cols, input_scale, output_scale, output_zero_point, dtype=np.int8):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes small .tflite models made of the six operators MicroFlow supports
-(microflow-macros/src/lib.rs:138-148) and MaxPool2D, for randomized model-level tests: parser + constant
+(microflow-macros/src/lib.rs:138-148), MaxPool2D and ADD, for randomized model-level tests: parser + constant
 preparation + kernel routing + run, product vs oracle.  Only the fields the MicroFlow front
 end reads are written (tflite.fbs field ids as used by microflow-macros/src/ops/*.rs).
 
@@ -15,6 +15,9 @@ Each layer dict (all quantization parameters are given, nothing is derived):
     average_pool_2d   filter (h,w), padding, strides, act, out_shape, out_q
     max_pool_2d       the same fields
     fully_connected   weights int8 [N,K], wscale, wzp, bias int32 [N], bscale, bzp, act, out_shape (M,N), out_q
+    add               skip (the layer whose output is the second operand; -1: the model input), swap (False: inputs [running, skip];
+                      True: [skip, running]), act, out_shape, out_q.  Negative tests place the inputs by hand: inputs = a list of
+                      "cur", a layer index (-1: the model input) or dict(shape, q, type=, data=) for a fresh tensor
     reshape           out_shape
     softmax           out_shape, out_q
 """
@@ -25,10 +28,10 @@ import numpy as np
 from make_fc_model import FB, Table, TableVec, Vec, emit, prune_2_4
 
 INT32, UINT8, INT8 = 2, 3, 9
-OPCODES = {"average_pool_2d": 1, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "max_pool_2d": 17, "reshape": 22,
+OPCODES = {"add": 0, "average_pool_2d": 1, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "max_pool_2d": 17, "reshape": 22,
            "softmax": 25}
 # BuiltinOptions union type ids (tflite.fbs)
-OPT_TYPE = {"conv_2d": 1, "depthwise_conv_2d": 2, "average_pool_2d": 5, "max_pool_2d": 5, "fully_connected": 8, "softmax": 9,
+OPT_TYPE = {"add": 11, "conv_2d": 1, "depthwise_conv_2d": 2, "average_pool_2d": 5, "max_pool_2d": 5, "fully_connected": 8, "softmax": 9,
             "reshape": 17}
 ACT = {None: 0, "none": 0, "relu": 1, "relu6": 3, 0: 0, 1: 1, 3: 3}
 PAD = {"same": 0, "valid": 1, 0: 0, 1: 1}
@@ -61,6 +64,7 @@ def build_model(input_shape, input_q, layers, elem=INT8):
 
     cur = add_tensor(input_shape, elem, 0, input_q[0], input_q[1])
     first = cur
+    outs = []  # every layer's output tensor index (an ADD names its second operand by layer)
     wdt = np.uint8 if elem == UINT8 else np.int8
     for L in layers:
         op = L["op"]
@@ -105,12 +109,25 @@ def build_model(input_shape, input_q, layers, elem=INT8):
             out = add_tensor(L["out_shape"], elem, 0, *L["out_q"])
             opts = Table({0: ("f32", 1.0)})
             ins = [cur]
+        elif op == "add":
+            def place(item):
+                if isinstance(item, dict):
+                    data = item.get("data")
+                    return add_tensor(item["shape"], item.get("type", elem), 0 if data is None else add_buffer(data), *item["q"])
+                return cur if item == "cur" else first if item < 0 else outs[item]
+            if "inputs" in L:
+                ins = [place(i) for i in L["inputs"]]
+            else:
+                ins = [place(L["skip"]), cur] if L.get("swap") else [cur, place(L["skip"])]
+            out = add_tensor(L["out_shape"], L.get("out_type", elem), 0, *L["out_q"])
+            opts = Table({0: ("i8", ACT[L.get("act")])})  # AddOptions { fused_activation_function:0 }
         else:
             raise ValueError(op)
         # Operator { opcode_index:0 inputs:1 outputs:2 builtin_options_type:3 builtin_options:4 }
         operators.append(Table({0: ("u32", oc), 1: ("ref", Vec("<i", ins)), 2: ("ref", Vec("<i", [out])),
                                 3: ("u8", OPT_TYPE[op]), 4: ("ref", opts)}))
         cur = out
+        outs.append(out)
     subgraph = Table({0: ("ref", TableVec(tensors)), 1: ("ref", Vec("<i", [first])), 2: ("ref", Vec("<i", [cur])),
                       3: ("ref", TableVec(operators))})
     # OperatorCode { deprecated_builtin_code:0 builtin_code:3 }
@@ -516,11 +533,26 @@ def ds_cnn(rng, shape=(49, 10), filters=64, blocks=4, classes=12, stem=(10, 4, (
     return build_model((1, int(shape[0]), int(shape[1]), 1), in_q, layers, elem)
 
 
-def inverted_residual_net(rng, input_shape, blocks, elem=INT8, wzp_nonzero=False, head=10):
+def _add_layer(rng, skip, shape, q_run, q_skip, act="none", elem=INT8, swap=False):
+    """one ADD layer dict: the running tensor (q_run) + the output of layer `skip` (q_skip; -1: the model input), an output scale that
+    keeps the sum spread over the range"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    osc = float(np.float32((q_run[0] + q_skip[0]) * rng.uniform(0.55, 0.75)))
+    ozp = lo if act in ("relu", "relu6") else int(rng.integers(lo + 40, hi - 40))
+    return dict(op="add", skip=int(skip), swap=bool(swap), act=act, out_shape=tuple(shape), out_q=(osc, ozp))
+
+
+def inverted_residual_net(rng, input_shape, blocks, elem=INT8, wzp_nonzero=False, head=10, residual=False):
+    return build_model(*inverted_residual_layers(rng, input_shape, blocks, elem, wzp_nonzero, head, residual), elem)
+
+
+def inverted_residual_layers(rng, input_shape, blocks, elem=INT8, wzp_nonzero=False, head=10, residual=False):
     """MobileNetV2/V3-style inverted-residual blocks: input_shape = (H, W, C); blocks = [(expand, K, stride, out), ...], each a
     1x1 Conv2D to `expand` channels (relu6) -> KxK depthwise SAME at `stride` (relu6) -> 1x1 Conv2D to `out` channels (no
     activation); then AveragePool over the whole image, FullyConnected(head) and Softmax.  Per-channel filter quantization; with
-    wzp_nonzero every filter zero point (the depthwise ones included) sits off the middle, as in classic asymmetric-u8 models."""
+    wzp_nonzero every filter zero point (the depthwise ones included) sits off the middle, as in classic asymmetric-u8 models.
+    residual: an ADD (no activation) of the block's input behind every block with stride 1 and out == its input channels, as
+    MobileNet-v2 has them; without it the bytes are the ones written before ADD existed.  -> build_model's arguments"""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     H, W, C = input_shape
@@ -544,9 +576,13 @@ def inverted_residual_net(rng, input_shape, blocks, elem=INT8, wzp_nonzero=False
         q, H, W, C = d["out_q"], oh, ow, n
 
     for expand, k, s, out in blocks:
+        skip, q_skip, c_in = len(layers) - 1, q, C  # the block's input: the layer in front of it (-1: the model input)
         conv(False, expand, 1, 1, "relu6")
         conv(True, expand, k, s, "relu6")
         conv(False, out, 1, 1, "none")
+        if residual and s == 1 and out == c_in:
+            layers.append(_add_layer(rng, skip, (1, H, W, C), q, q_skip, "none", elem))
+            q = layers[-1]["out_q"]
     layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none", out_shape=(1, 1, 1, C), out_q=q))
     layers.append(dict(op="reshape", out_shape=(1, C), out_q=q))
     wsc = np.float32(rng.uniform(0.002, 0.02))
@@ -555,7 +591,34 @@ def inverted_residual_net(rng, input_shape, blocks, elem=INT8, wzp_nonzero=False
                        bias=rng.integers(-2000, 2000, head), bscale=[np.float32(q[0]) * wsc], bzp=[0], act="none",
                        out_shape=(1, head), out_q=(osc, int(rng.integers(lo + 20, hi - 20)))))
     layers.append(dict(op="softmax", out_shape=(1, head), out_q=(1.0 / 256.0, lo)))
-    return build_model((1,) + tuple(input_shape), in_q, layers, elem)
+    return (1,) + tuple(input_shape), in_q, layers
+
+
+def resnet_like_layers(rng, input_shape, blocks, elem=INT8, k=3, swap=(), head=10):
+    """ResNet-style basic blocks without projection shortcuts: input_shape = (H, W, C); `blocks` of them, each Conv2D kxk SAME (relu) ->
+    Conv2D kxk SAME (no activation) -> ADD with relu onto the block's input; block b's ADD is written [skip, running] when b is in
+    `swap`.  Then AveragePool over the whole image, FullyConnected(head) and Softmax (head = 0: none of the three).  -> build_model's
+    arguments"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    H, W, C = (int(v) for v in input_shape)
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers = in_q, []
+    for b in range(int(blocks)):
+        skip, q_skip = len(layers) - 1, q
+        layers.append(_conv_layer(rng, (H, W, C), q, False, C, k, 1, "same", "relu", elem))
+        layers.append(_conv_layer(rng, (H, W, C), layers[-1]["out_q"], False, C, k, 1, "same", "none", elem))
+        layers.append(_add_layer(rng, skip, (1, H, W, C), layers[-1]["out_q"], q_skip, "relu", elem, swap=b in swap))
+        q = layers[-1]["out_q"]
+    if head:
+        layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none", out_shape=(1, 1, 1, C), out_q=q))
+        layers.append(dict(op="reshape", out_shape=(1, C), out_q=q))
+        layers.append(_fc_layer(rng, C, head, q, "none", elem))
+        layers.append(dict(op="softmax", out_shape=(1, head), out_q=(1.0 / 256.0, lo)))
+    return (1, H, W, C), in_q, layers
+
+
+def resnet_like(rng, input_shape, blocks, elem=INT8, **kw):
+    return build_model(*resnet_like_layers(rng, input_shape, blocks, elem, **kw), elem)
 
 
 # person_detect_like(quant=...): the head's effective multiplier in_scale * fscale / out_scale (256 products of a byte
