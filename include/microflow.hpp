@@ -276,6 +276,12 @@ class Model {
     Model(const Model &) = delete;
     Model &operator=(const Model &) = delete;
     const mf_model_info &info() const { return info_; }
+    // the operator whose output side operator i reads (-1: the model input); throws MF_ERR_INVALID_ARG for any other operator
+    int op_source(int i) const {
+        int src = 0;
+        check(mf_model_get_op_source(m_, i, &src));
+        return src;
+    }
     // predict: f32 in -> f32 out; `input` holds batch x input_elems values
     std::vector<float> predict(const std::vector<float> &input) {
         const size_t batch = input.size() / info_.input_elems;

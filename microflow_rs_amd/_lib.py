@@ -109,6 +109,7 @@ SIGNATURES = {
     "mf_model_get_op_constants": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mf_model_get_op_epilogue_mode": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     "mf_model_get_op_skip": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mf_model_get_op_source": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     "mf_model_prepare": (C.c_int, [_vp, C.c_int, C.c_size_t]),
     "mf_model_set_stream": (C.c_int, [_vp, _vp]),
     "mf_model_sync": (C.c_int, [_vp]),

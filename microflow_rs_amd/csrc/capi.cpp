@@ -508,6 +508,17 @@ int mf_model_get_op_skip(const mf_model *model, int index, int *source, int *run
     })
 }
 
+int mf_model_get_op_source(const mf_model *model, int index, int *source) {
+    MF_TRY({
+        MF_NEED(model && model->impl);
+        const mf::ParsedModel &pm = mf::model_parsed(model->impl);
+        MF_NEED(index >= 0 && index < (int)pm.ops.size());
+        const mf::ParsedOp &o = pm.ops[(size_t)index];
+        if (!o.side()) mf::fail(MF_ERR_INVALID_ARG, "mf_model_get_op_source: the operator is no side operator");
+        if (source) *source = o.side_src;
+    })
+}
+
 int mf_model_prepare(mf_model *model, int device, size_t max_batch) {
     MF_TRY({
         MF_NEED(model && model->impl);

@@ -98,6 +98,7 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
     case FusedImpl::FCSM:
         if (!k::launch_fc_rowwave_softmax(d_in, d_out, f->a->fc, f->b->sm, batch, st)) fail(MF_ERR_UNSUPPORTED, "fused kernel missing");
         break;
+    case FusedImpl::SHORTCUT: fail(MF_ERR_INVALID_ARG, "shortcut_add_rt takes two inputs: fused_run2"); break;
     case FusedImpl::DWPW: {
         const OpSpec &d = f->a->s;
         if (!k::launch_dwpw(d.H, d.W, d.C, d.sh, f->b->s.N, d_in, d_out, f->dwpw, (int)batch, st)) fail(MF_ERR_UNSUPPORTED, "fused kernel missing");
@@ -108,6 +109,17 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
 }
 void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream) {
     if (batch) launch(f, d_in, batch, d_out, 0, (hipStream_t)stream);
+}
+void fused_run2(FusedImpl *f, const int8_t *d_t, const int8_t *d_run, size_t batch, int8_t *d_out, void *stream) {
+    if (f->kind != FusedImpl::SHORTCUT) fail(MF_ERR_INVALID_ARG, "fused_run2: not a two-input group");
+    if (!batch) return;
+    const size_t tb = batch * f->a->in_elems, ob = batch * f->b->s.add_elems;
+    const uintptr_t t0 = (uintptr_t)d_t, o0 = (uintptr_t)d_out, r0 = (uintptr_t)d_run;
+    if ((t0 < o0 + ob && o0 < t0 + tb) || (d_out != d_run && r0 < o0 + ob && o0 < r0 + ob)) // (pixels of T are read while others are written)
+        fail(MF_ERR_INVALID_ARG, "shortcut_add_rt: the output overlaps an input");
+    if ((t0 | o0 | r0) & 15) fail(MF_ERR_INVALID_ARG, "shortcut_add_rt: a pointer is not 16-byte aligned"); // (16-byte loads and stores; the runtime's buffers are)
+    k::launch_shortcut_add(d_t, d_run, d_out, f->shortcut, (long long)batch, (hipStream_t)stream);
+    MF_HIP(hipGetLastError());
 }
 void fused_run_f32(FusedImpl *f, const void *d_in, bool in_f32, size_t batch, void *d_out, bool out_f32, void *stream) {
     if (!batch) return;

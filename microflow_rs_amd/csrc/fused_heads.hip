@@ -313,4 +313,41 @@ FusedImpl *fused_dwfc_create(OpImpl *dw, FusedImpl *fcsm) {
     return f.release();
 }
 
+// A 1x1 Conv2D on a skip edge and the ADD that reads its result beside the running tensor, as one shortcut_add_rt launch
+// (k_shortcut_add.hip).  The class: KH = KW = 1, strides (1,1) or (2,2), C and N in whole sixteens inside
+// k::shortcut_add_supported, filter zero points all zero in the i8 domain, finite constants on both, neither forced generic.
+// Everything else keeps its two launches.  Operand A is the group's own, built from the convolution's host copy -- alone a stride-2
+// 1x1 runs conv_mm_rt, which keeps another image; the constants, the clamp and the epilogue mode are the convolution's own, as pw_rt
+// takes them (ops.hip: epi_fields); the ADD's block is the operator's internal-domain one.
+bool shortcut_add_class(const OpSpec &d, bool zero_wzp, bool finite) {
+    return d.kind == MF_OP_CONV_2D && d.KH == 1 && d.KW == 1 && d.sh == d.sw && (d.sh == 1 || d.sh == 2) && zero_wzp && finite &&
+           d.OH == (d.H + d.sh - 1) / d.sh && d.OW == (d.W + d.sw - 1) / d.sw && k::shortcut_add_supported(d.C, d.N);
+}
+FusedImpl *fused_shortcut_add_create(OpImpl *conv, OpImpl *add, bool conv_first) {
+    if (switches().no_shortcut_add || !conv || !add || conv->force_generic || add->force_generic) return nullptr;
+    const OpSpec &d = conv->s, &q = add->s;
+    if (q.kind != MF_OP_ADD || conv->device != add->device || d.u8 != q.u8) return nullptr;
+    const bool zero_wzp = std::all_of(conv->h_wzp.begin(), conv->h_wzp.end(), [](int32_t z) { return z == 0; });
+    if (!shortcut_add_class(d, zero_wzp, conv->finite_consts)) return nullptr;
+    if (q.add_elems != (size_t)d.OH * d.OW * d.N || conv->h_w.size() != (size_t)d.N * d.C) return nullptr; // on exactly the convolution's output
+    const k::AddArgs &aa = add->add;
+    if (!std::isfinite(aa.ca) || !std::isfinite(aa.cb)) return nullptr;
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::SHORTCUT, conv, add, nullptr, "");
+    k::ShortcutAddArgs &a = f->shortcut;
+    const int NT = d.N / 16, TB = NT < 4 ? NT : 4, NBLK = (NT + TB - 1) / TB, NSPLIT = NBLK <= 1 ? 1 : (NBLK == 2 ? 2 : 4);
+    const std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(conv->h_w.data(), d.C, d.N, 1, TB, NSPLIT); // [N][1][1][C], i8 domain
+    a.pw.wprep = keep(*f, prep.data(), prep.size());
+    a.pw.A = conv->conv.A, a.pw.S = conv->conv.S, a.pw.Kc = conv->conv.Kc, a.pw.wzp = conv->conv.wzp;
+    a.pw.lo_f = conv->conv.lo_f, a.pw.hi_f = conv->conv.hi_f;
+    a.pw.K = d.C, a.pw.N = d.N, a.pw.KS = (d.C + 63) / 64, a.pw.NT = NT, a.pw.patch_pitch = d.N;
+    a.pw.TB = TB, a.pw.NSPLIT = NSPLIT;
+    a.pw.magic = std::min(conv->magic_mode, 2), a.pw.xr = conv->conv.xr;
+    a.add = aa;
+    a.H = d.H, a.W = d.W, a.OH = d.OH, a.OW = d.OW, a.sh = d.sh, a.sw = d.sw;
+    a.conv_first = conv_first ? 1 : 0;
+    f->epi_mode = a.pw.magic;
+    f->name = "shortcut_add_rt<" + std::to_string(d.C) + "," + std::to_string(d.N) + (d.sh == 2 ? ",s2>" : ">");
+    return f.release();
+}
+
 } // namespace mf

@@ -17,7 +17,7 @@ namespace mf {
 // One argument block (or a named sub-struct: block + what the launch path needs beside it) per kind; a group uses its own kind's.
 // Plain members, no variant: the chain planner swaps whole groups (std::swap(*groups[i], *trial)).
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK, CONVPOOL } kind = DWPW;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK, CONVPOOL, SHORTCUT } kind = DWPW;
     OpImpl *a = nullptr, *b = nullptr, *c = nullptr;
     std::string name;
     std::vector<std::unique_ptr<DevBuf>> owned; // the group's own operand arrays and tables (keep)
@@ -75,6 +75,9 @@ struct FusedImpl {
         bool wz = false; // the convolution has non-zero filter zero points (internal domain)
         bool mx = false; // the pool is a MaxPool2D: conv_maxpool_rt
     } convpool;
+    // SHORTCUT: a 1x1 shortcut convolution + the ADD on its result and the running tensor (k_shortcut_add.hip); a = the convolution, b = the
+    // ADD.  The one kind with TWO inputs: fused_run2, never the launch path of the others
+    k::ShortcutAddArgs shortcut{};
     // the model's f32 boundary inside this group's launch (fused_set_input_quant / fused_set_output_dequant; KindFacts f32_in / f32_out)
     k::F32Edge edge{};
     bool edge_in = false, edge_out = false;
@@ -105,6 +108,7 @@ inline KindFacts kind_facts(FusedImpl::Kind kind) {
     case FusedImpl::CONV1FC: return {"conv1_fc_rt", false, false, false};
     case FusedImpl::BLOCK: return {"block_band_rt", true, false, false};
     case FusedImpl::CONVPOOL: return {"conv_pool_rt", true, false, false};
+    case FusedImpl::SHORTCUT: return {nullptr, false, false, false}; // (16-byte words at all three pointers, the caller's output buffer among them: fused_run2 checks the alignment itself)
     }
     return {nullptr, false, false, false};
 }

@@ -247,6 +247,17 @@ struct PwRtArgs {
     int TB, NSPLIT;     // pw_rt (weights in registers): tiles per wave block (1..4; 0 = use pw_rt_lds) and waves per chunk (1, 2, 4)
     int magic, xr;
 };
+// A 1x1 shortcut convolution (strides (1,1) or (2,2)) + the ADD that reads its result beside the running tensor, in one launch
+// (k_shortcut_add.hip)
+struct ShortcutAddArgs {
+    PwRtArgs pw;         // the convolution as pw_rt takes it: operand A (build_pw_rt_reg_weights, group 1) in wprep, the operator's own
+                         // constants, clamp and epilogue mode, K = C, N, KS, TB, NSPLIT
+    AddArgs add;         // the ADD in the internal domain
+    int H, W, OH, OW, sh, sw;
+    int conv_first;      // 1: the ADD's input a is the convolution's result and b the running tensor; 0: the other way round
+};
+bool shortcut_add_supported(int C, int N);
+void launch_shortcut_add(const int8_t *t_in, const int8_t *run, int8_t *out, const ShortcutAddArgs &a, long long batch, hipStream_t s);
 // Conv2D with few input channels / DepthwiseConv2D with one input channel, any filter (k_rt.hip: conv_rows_lds)
 struct ConvRowsArgs {
     int H, W, C, N, KH, KW, sh, sw, OH, OW;

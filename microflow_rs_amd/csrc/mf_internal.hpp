@@ -108,6 +108,11 @@ struct ParsedOp {
     int skip_src = -2, run_input = 0;
     float a_scale = 0, b_scale = 0;
     int a_zp = 0, b_zp = 0;
+    // A side operator only (one Conv2D on a skip edge: it reads an earlier tensor T of the chain, not the running value, and one later
+    // ADD reads its output beside the running value): the operator whose output T is (-1: the model input); -2: no side operator.
+    // That ADD's skip_src is this operator's index.  in_scale / in_zp are T's
+    int side_src = -2;
+    bool side() const { return side_src != -2; }
 };
 struct ParsedModel {
     bool u8 = false; // element type T of every quantized tensor: INT8 (false) or UINT8 (true)
@@ -119,12 +124,25 @@ struct ParsedModel {
     size_t max_fork_elems = 0; // the largest tensor an operator produces for a later ADD to read beside the running one (0: none)
     bool input_skip = false;   // some ADD reads the model input beside the running tensor
     std::vector<ParsedOp> ops;
-    // the operator that launches the tensor ADD i reads beside the running one: skip_src with the Reshapes (aliases) in front of it
-    // skipped; -1: the model input
+    // the operator that launches tensor s of the chain (-1: the model input): the Reshapes (aliases) in front of it skipped, and the
+    // side operators that stand between them in file order passed over
+    int launcher(int s) const {
+        while (s >= 0 && ops[(size_t)s].kind == MF_OP_RESHAPE)
+            do --s;
+            while (s >= 0 && ops[(size_t)s].side());
+        return s;
+    }
+    // the operator that launches the tensor that has to stay in memory for ADD i: the one it reads beside the running one or, where
+    // that is a side operator's output, the tensor T the side operator reads; -1: the model input
     int skip_real(size_t i) const {
         int s = ops[i].skip_src;
-        while (s >= 0 && ops[(size_t)s].kind == MF_OP_RESHAPE) --s;
-        return s;
+        if (s >= 0 && ops[(size_t)s].side()) s = ops[(size_t)s].side_src;
+        return launcher(s);
+    }
+    // ADD i reads a side operator's output: that operator's index, else -1
+    int side_of_add(size_t i) const {
+        const int s = ops[i].kind == MF_OP_ADD ? ops[i].skip_src : -2;
+        return s >= 0 && ops[(size_t)s].side() ? s : -1;
     }
 };
 ParsedModel parse_tflite(const uint8_t *buf, size_t len);
@@ -191,6 +209,11 @@ unsigned long long &dev_launch_counter();
 struct FusedImpl;
 FusedImpl *fused_create(OpImpl *dw, OpImpl *pw);
 FusedImpl *fused_block_create(OpImpl *expand, OpImpl *dw, OpImpl *pw, bool pair_grouped = false); // a 1x1 expand + depthwise 3x3 + 1x1 project block in one launch (k_block_band.hip), or nullptr; pair_grouped: the last two have a launch of their own
+// a 1x1 Conv2D on a skip edge + the ADD that reads its result beside the running tensor as one shortcut_add_rt launch
+// (k_shortcut_add.hip), or nullptr: outside the class, the two run their own launches.  conv_first: the ADD's input a is the
+// convolution's result.  fused_run2 runs it: d_t the convolution's input, d_run the running tensor; d_out may be exactly d_run
+FusedImpl *fused_shortcut_add_create(OpImpl *conv, OpImpl *add, bool conv_first);
+void fused_run2(FusedImpl *f, const int8_t *d_t, const int8_t *d_run, size_t batch, int8_t *d_out, void *stream);
 FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool); // a Conv2D + the AveragePool2D (k_conv_pool.hip) or MaxPool2D (k_conv_maxpool.hip) with more than one output pixel on its output in one launch, or nullptr
 // fused tail: AveragePool2D (1x1 output) -> Conv2D 1x1 (N <= 8) -> Softmax (one row of N)
 FusedImpl *fused_tail_create(OpImpl *pool, OpImpl *conv, OpImpl *softmax);

@@ -1,5 +1,6 @@
 // model_groups.cpp -- the grouping rules of the model runtime: which operators of a parsed model run as one launch.  One function
 // per rule over a builder; build_groups at the end of the file lists them in the order they depend on.
+#include <cmath>
 #include <memory>
 
 #include "model_groups.hpp"
@@ -8,9 +9,34 @@ namespace mf {
 
 void ModelGroups::clear() {
     for (const Stage &st : stages) fused_destroy(st.f); // they borrow the groups' buffers: first
+    for (FusedImpl *f : shortcut) fused_destroy(f);
     for (FusedImpl *f : fused) fused_destroy(f);
     for (OpImpl *o : ops) op_destroy(o);
-    stages.clear(), fused.clear(), fused_last.clear(), ops.clear();
+    stages.clear(), shortcut.clear(), fused.clear(), fused_last.clear(), ops.clear();
+}
+
+bool group_splits(const ParsedModel &pm, size_t first, size_t last) {
+    for (size_t k = 0; k < pm.ops.size(); ++k) {
+        if (pm.ops[k].side() && k >= first && k <= last) return true;
+        if (pm.ops[k].kind != MF_OP_ADD) continue;
+        if (k >= first && k <= last) return true;
+        const int s = pm.skip_real(k);
+        if (s >= (int)first && s < (int)last) return true;
+    }
+    return false;
+}
+
+int shortcut_candidate(const ParsedModel &pm, size_t add) {
+    const int s = pm.side_of_add(add);
+    if (s < 0) return -1;
+    const ParsedOp &po = pm.ops[(size_t)s];
+    bool zero_wzp = true, finite = std::isfinite(pm.ops[add].c0[0]) && std::isfinite(pm.ops[add].c1[0]);
+    for (int z : po.wzp) zero_wzp = zero_wzp && z - (pm.u8 ? 128 : 0) == 0;
+    for (float c : po.c0) finite = finite && std::isfinite(c);
+    for (float c : po.c1) finite = finite && std::isfinite(c);
+    OpSpec d;
+    d.kind = po.kind, d.KH = po.KH, d.KW = po.KW, d.sh = po.sh, d.sw = po.sw, d.H = po.H, d.W = po.W, d.C = po.C, d.N = po.N, d.OH = po.OH, d.OW = po.OW;
+    return shortcut_add_class(d, zero_wzp, finite) ? s : -1;
 }
 
 namespace {
@@ -48,15 +74,8 @@ struct GroupBuilder {
     // may hold one strictly inside: true when operators first .. last as ONE launch would swallow such a tensor (the operator that
     // launches it at or behind `first` and in front of `last`; a group may end at one or start behind one), or would hold an ADD,
     // which is a launch of its own.  A candidate this refuses falls back exactly as an unmatched one does
-    bool splits(size_t first, size_t last) const {
-        for (size_t k = 0; k < n; ++k) {
-            if (kind(k) != MF_OP_ADD) continue;
-            if (k >= first && k <= last) return true;
-            const int s = pm.skip_real(k);
-            if (s >= (int)first && s < (int)last) return true;
-        }
-        return false;
-    }
+    // A side operator (ParsedOp::side) runs at its ADD, not at its own index: no group of consecutive operators may hold one either
+    bool splits(size_t first, size_t last) const { return group_splits(pm, first, last); }
     size_t skip_reshapes(size_t j) const {
         while (j < n && kind(j) == MF_OP_RESHAPE) ++j;
         return j;
@@ -101,6 +120,11 @@ static void create_operators(GroupBuilder &b) {
     for (const ParsedOp &po : b.pm.ops) {
         ops.push_back(nullptr); // reserve the slot first: a throwing push_back must not leak the operator
         if (po.kind == MF_OP_RESHAPE) continue;
+        if (po.side()) { // a side operator reads T, not the running tensor: what T's launcher stamped on it; it stamps nothing itself
+            const int t = b.pm.launcher(po.side_src);
+            ops.back() = op_create(b.device, op_spec(b.pm, po, t < 0 ? b.pm.in_scale : b.pm.ops[(size_t)t].out_scale, t < 0 ? b.pm.in_zp : b.pm.ops[(size_t)t].out_zp));
+            continue;
+        }
         ops.back() = op_create(b.device, op_spec(b.pm, po, cur_scale, cur_zp));
         cur_scale = po.out_scale;
         cur_zp = po.out_zp;
@@ -108,6 +132,7 @@ static void create_operators(GroupBuilder &b) {
     b.n = ops.size();
     b.g.fused.assign(b.n, nullptr);
     b.g.fused_last.assign(b.n, -1);
+    b.g.shortcut.assign(b.n, nullptr);
     while (b.g.first_real < (int)b.n && !ops[(size_t)b.g.first_real]) ++b.g.first_real;
     b.g.last_real = (int)b.n - 1;
     while (b.g.last_real >= 0 && !ops[(size_t)b.g.last_real]) --b.g.last_real;
@@ -391,6 +416,16 @@ static void rule_6a_conv_pool(GroupBuilder &b) {
     }
 }
 
+// (6b) a side operator -- one Conv2D on a skip edge -- and the ADD that reads its output -> one shortcut_add_rt launch at the ADD
+// (fused_heads.hip: fused_shortcut_add_create), wherever the two stand in file order.  No other rule matches a side operator
+// (splits), so the pair is free; outside the kernel's class the side operator runs its own launch at the ADD, then the ADD
+static void rule_6b_shortcut_add(GroupBuilder &b) {
+    for (size_t i = 0; i < b.n; ++i) {
+        const int s = shortcut_candidate(b.pm, i); // (what the file says; the builder asks the prepared operators again)
+        if (s >= 0) b.g.shortcut[i] = fused_shortcut_add_create(b.g.ops[(size_t)s], b.g.ops[i], b.po(i).run_input == 1); // (run_input 1: input a is the side operator's)
+    }
+}
+
 // (7) the boundary conversions of M::predict inside the launches at the two ends of the whole model: every launch that can
 // start a run at operator 0 learns the input's scale and zero point, every one that can end at the last operator the ones
 // that operator stamped (the stem was told above; a kernel without such an instance says no and keeps the separate pass)
@@ -422,6 +457,7 @@ ModelGroups build_groups(const ParsedModel &pm, int device, bool autotune) {
     //   - (5) before (5a): speech.tflite's own geometry keeps (5); (5a), (5b) before (6): a FullyConnected run behind a one-channel
     //     convolution or a global pool is offered there first, (6) takes what they left
     //   - (6a) behind every rule above: a global pool stays with the tail and pool_fc_chain groups, a pair's Conv2D with its pair
+    //   - (6b) anywhere behind the operators: it looks at side operators and their ADDs, which no other rule touches
     //   - (7) last: it tells every launch that exists by then, at either end of the model, the boundary's quantisation
     create_operators(b);
     rule_1_2_3_first_level(b);
@@ -435,6 +471,7 @@ ModelGroups build_groups(const ParsedModel &pm, int device, bool autotune) {
     rule_5b_pool_fc(b);
     rule_6_fc_chains(b);
     rule_6a_conv_pool(b);
+    rule_6b_shortcut_add(b);
     rule_7_boundaries(b);
     return std::move(b.g);
 }

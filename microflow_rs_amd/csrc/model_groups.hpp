@@ -23,6 +23,9 @@ struct ModelGroups {
         int first, last;
     };
     std::vector<Stage> stages;
+    // shortcut[i] != nullptr: ADD i and the side operator whose output it reads (ParsedModel::side_of_add) run as ONE launch at the
+    // ADD's index (k_shortcut_add.hip).  The one group whose members need not be neighbours in file order, and the one with two inputs
+    std::vector<FusedImpl *> shortcut;
     // the first / last operator that launches anything (leading Reshapes alias the input -- speech.tflite starts with one --
     // trailing ones the output): ops.size() / -1 where there is none
     int first_real = 0, last_real = -1;
@@ -38,10 +41,18 @@ struct ModelGroups {
     ~ModelGroups() { clear(); }
     void clear(); // stages borrow the groups' buffers, groups the operators': in that order
     void swap(ModelGroups &o) noexcept {
-        ops.swap(o.ops), fused.swap(o.fused), fused_last.swap(o.fused_last), stages.swap(o.stages);
+        ops.swap(o.ops), fused.swap(o.fused), fused_last.swap(o.fused_last), stages.swap(o.stages), shortcut.swap(o.shortcut);
         std::swap(first_real, o.first_real), std::swap(last_real, o.last_real);
     }
 };
+
+// What the rules ask of the parsed model alone (host only; tests/cpp/shortcut_route.cpp prints them):
+// would operators first .. last as ONE launch swallow a tensor that has to exist in memory, an ADD, or a side operator?
+bool group_splits(const ParsedModel &pm, size_t first, size_t last);
+// rule (6b) by everything the file says: the side operator that forms one shortcut_add_rt launch with ADD `add` (geometry, filter zero
+// points in the i8 domain, finite constants: shortcut_add_class), or -1 -- no side operator there, or one outside the class
+int shortcut_candidate(const ParsedModel &pm, size_t add);
+bool shortcut_add_class(const OpSpec &conv, bool zero_wzp, bool finite); // (fused_heads.hip)
 
 // Operators and every group the grouping rules find, built in a local: a failure half way (a HIP error, OOM, a geometry an
 // operator rejects) destroys what exists and throws.  autotune: time the run-time-geometry chain candidates on the device

@@ -238,6 +238,25 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
     // an earlier skip tensor was alive
     std::vector<int32_t> out_index;
     int last_add = -1;
+    // ... and with a side operator (one Conv2D on a skip edge, below): the one whose ADD has not come yet, or -1
+    int pending_side = -1;
+    // who reads tensor t behind operator `from`: ADDs (either input) and other operators (input 0)
+    auto readers_behind = [&](int32_t t, uint32_t from, int &adds, int &others) {
+        adds = others = 0;
+        for (uint32_t k = from + 1; k < operators.size(); ++k) {
+            const Table o = operators.table(k);
+            const uint32_t c = o.scalar<uint32_t>(0, 0);
+            const Vec in_k = vec(o, 1);
+            if (c >= opcodes.size() || !in_k.size()) continue; // (refused when the walk reaches it)
+            if (opcodes.table(c).scalar<int8_t>(0, 0) == MF_OP_ADD) adds += in_k.get<int32_t>(0) == t || (in_k.size() > 1 && in_k.get<int32_t>(1) == t);
+            else others += in_k.get<int32_t>(0) == t;
+        }
+    };
+    // the non-linear graphs that stay refused keep the chain check's answer, with the reason behind it
+    auto refuse_side = [](uint32_t oi, const std::string &why) {
+        fail(MF_ERR_UNSUPPORTED, "operator " + std::to_string(oi) + " does not consume the previous operator's output (or the model "
+                                 "input): only linear operator chains are supported (side operator: " + why + ")");
+    };
     auto same_tensor = [](std::vector<int> a, std::vector<int> b) {
         if (a.size() == 1) a.insert(a.begin(), 1);
         if (b.size() == 1) b.insert(b.begin(), 1);
@@ -257,13 +276,47 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
         TensorInfo in = read_tensor(tensors, buffers, ins.get<int32_t>(0));
         TensorInfo out = read_tensor(tensors, buffers, outs.get<int32_t>(0));
         const int32_t running_index = prev_index;
-        if (code != MF_OP_ADD && ins.get<int32_t>(0) != prev_index && !same_tensor(in.shape, prev_shape)) // (an ADD checks its own inputs)
-            fail(MF_ERR_UNSUPPORTED, "operator " + std::to_string(oi) + " does not consume the previous operator's "
-                                     "output (or the model input): only linear operator chains are supported");
-        prev_index = outs.get<int32_t>(0);
-        prev_shape = out.shape;
         ParsedOp po;
         po.kind = code;
+        if (code != MF_OP_ADD) { // (an ADD checks its own inputs)
+            // A side operator: ONE Conv2D on a skip edge.  Its input 0 is a tensor T of the chain, by index -- the model input or an
+            // earlier operator's output -- that the main chain also continues from: either T is not the running value any more (the
+            // side operator stands between the main operators or in front of its ADD), or it still is and a later operator reads
+            // it as well (the side operator stands directly behind the fork).  Its output is read by exactly one later ADD and by
+            // nothing else.  It does not become the running value: the chain bookkeeping passes over it
+            const int32_t in0 = ins.get<int32_t>(0);
+            if (pending_side >= 0 && in0 == out_index[(size_t)pending_side]) refuse_side(oi, "two or more operators on the skip edge");
+            int t = in0 == g_in.get<int32_t>(0) ? -1 : -2;
+            for (size_t j = 0; j < out_index.size(); ++j)
+                if (out_index[j] == in0 && !pm.ops[j].side()) t = (int)j;
+            int adds = 0, others = 0;
+            bool side = false;
+            if (t != -2 && in0 != prev_index) side = true;
+            else if (t != -2) { // (of two operators that read the running value, the one no further operator reads is off the chain)
+                readers_behind(in0, oi, adds, others);
+                const bool read_again = others > 0;
+                readers_behind(outs.get<int32_t>(0), oi, adds, others);
+                side = read_again && others == 0;
+            }
+            if (side) {
+                if (code != MF_OP_CONV_2D) refuse_side(oi, "a side operator that is not a Conv2D");
+                readers_behind(outs.get<int32_t>(0), oi, adds, others);
+                if (!adds && others == 1) refuse_side(oi, "two or more operators on the skip edge");
+                if (!adds && !others) refuse_side(oi, "its output is never read");
+                if (adds != 1 || others) refuse_side(oi, "its output is read by something other than one ADD");
+                if (pending_side >= 0 || t < last_add) refuse_side(oi, "a side operator while another skip is alive");
+                for (const TensorInfo *ti : {&in, &out})
+                    if ((ti->type == TT_INT8 || ti->type == TT_UINT8) && (ti->type == TT_UINT8) != pm.u8) refuse_side(oi, "mixed element types");
+                po.side_src = t;
+                pending_side = (int)oi;
+            } else if (in0 != prev_index && !same_tensor(in.shape, prev_shape)) {
+                refuse_side(oi, "its input is no tensor of the chain");
+            }
+        }
+        if (!po.side()) {
+            prev_index = outs.get<int32_t>(0);
+            prev_shape = out.shape;
+        }
 
         switch (code) {
         case MF_OP_FULLY_CONNECTED: { // microflow-macros/src/ops/fully_connected.rs:66-98
@@ -419,7 +472,10 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             if (src == -2) refuse("the other input is no earlier tensor of the chain");
             for (const ParsedOp &e : pm.ops)
                 if (e.kind == MF_OP_ADD && e.skip_src == src) refuse("a fork tensor is used twice");
-            if (src < last_add) refuse("two skip tensors alive at once (overlapping or nested skips)");
+            // (a side operator's output: T and S count as one skip, alive from T's producer -- checked at the side operator -- to here)
+            const bool via_side = src >= 0 && pm.ops[(size_t)src].side();
+            if (pending_side >= 0 && src != pending_side) refuse("a side operator while another skip is alive");
+            if (!via_side && src < last_add) refuse("two skip tensors alive at once (overlapping or nested skips)");
             if (in.shape != tb.shape || in.shape != out.shape) refuse("differing shapes (no broadcasting)");
             if (in.shape.size() != 2 && in.shape.size() != 4) refuse("tensor rank must be 2 or 4");
             if (in.shape.size() == 4 && in.shape[0] != 1) refuse("tensor batch must be 1");
@@ -430,10 +486,14 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             po.a_zp = zp_of(in.zp[0], pm.u8), po.b_zp = zp_of(tb.zp[0], pm.u8);
             po.c0.resize(1), po.c1.resize(1);
             h_preprocess_add(po.a_scale, po.b_scale, out.scale[0], po.c0.data(), po.c1.data());
-            int real = src; // (Reshapes are aliases: the operator that launches the tensor, or the model input)
-            while (real >= 0 && pm.ops[(size_t)real].kind == MF_OP_RESHAPE) --real;
+            // what has to stay in memory up to here: the skip tensor itself or, through a side operator, its input T (Reshapes are
+            // aliases: the operator that launches the tensor, or the model input); the side operator's output lives in a fork buffer too
+            const int real = pm.launcher(via_side ? pm.ops[(size_t)src].side_src : src);
+            const size_t kept = via_side ? pm.ops[(size_t)src].in_elems : po.in_elems;
             if (real < 0) pm.input_skip = true;
-            else if (po.in_elems > pm.max_fork_elems) pm.max_fork_elems = po.in_elems;
+            else if (kept > pm.max_fork_elems) pm.max_fork_elems = kept;
+            if (via_side && po.in_elems > pm.max_fork_elems) pm.max_fork_elems = po.in_elems;
+            pending_side = -1;
             last_add = (int)oi;
             break;
         }

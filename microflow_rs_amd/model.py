@@ -70,6 +70,13 @@ class Model:
         _lib.check(_lib.lib().mf_model_get_op_skip(self._h, int(i), C.byref(src), C.byref(pos)))
         return src.value, pos.value
 
+    def op_source(self, i):
+        """the operator whose output side operator i (the Conv2D on a skip edge) reads instead of the running value; -1: the model
+        input.  The ADD behind it names i as its skip (op_skip).  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
+        src = C.c_int(0)
+        _lib.check(_lib.lib().mf_model_get_op_source(self._h, int(i), C.byref(src)))
+        return src.value
+
     @property
     def ops(self):
         return [self.op(i) for i in range(self.num_ops)]

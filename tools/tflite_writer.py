@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes small .tflite models made of the six operators MicroFlow supports
-(microflow-macros/src/lib.rs:138-148), MaxPool2D and ADD, for randomized model-level tests: parser + constant
+(microflow-macros/src/lib.rs:138-148), MaxPool2D and ADD (identity and projection shortcuts), for randomized model-level tests: parser + constant
 preparation + kernel routing + run, product vs oracle.  Only the fields the MicroFlow front
 end reads are written (tflite.fbs field ids as used by microflow-macros/src/ops/*.rs).
 
@@ -10,7 +10,9 @@ end reads are written (tflite.fbs field ids as used by microflow-macros/src/ops/
 Each layer dict (all quantization parameters are given, nothing is derived):
     conv_2d           filters int8 [N,KH,KW,C], fscale [N or 1], fzp [N or 1], bias int32 [N],
                       bscale [N or 1], bzp [N or 1], padding "same"|"valid", strides (h,w), act,
-                      out_shape (1,OH,OW,N), out_q (scale, zp)
+                      out_shape (1,OH,OW,N), out_q (scale, zp).  side_of = a layer index (-1: the model input): the convolution reads
+                      that layer's output instead of the running tensor and does not become the running tensor (a projection
+                      shortcut: a later add names this layer as its skip)
     depthwise_conv_2d weights int8 [1,KH,KW,C] + the same fields
     average_pool_2d   filter (h,w), padding, strides, act, out_shape, out_q
     max_pool_2d       the same fields
@@ -78,7 +80,7 @@ def build_model(input_shape, input_q, layers, elem=INT8):
             tw = add_tensor(w.shape, elem, add_buffer(w), L["fscale"], L["fzp"])
             tb = add_tensor((w.shape[0] if op == "conv_2d" else w.shape[3],), INT32,
                             add_buffer(np.asarray(L["bias"], np.int32)), L["bscale"], L["bzp"])
-            out = add_tensor(L["out_shape"], elem, 0, *L["out_q"])
+            out = add_tensor(L["out_shape"], L.get("out_type", elem), 0, *L["out_q"])  # (out_type: negative tests)
             if op == "conv_2d":  # Conv2DOptions { padding:0 stride_w:1 stride_h:2 act:3 }
                 opts = Table({0: ("i8", PAD[L["padding"]]), 1: ("i32", L["strides"][1]), 2: ("i32", L["strides"][0]),
                               3: ("i8", ACT[L.get("act")])})
@@ -86,6 +88,8 @@ def build_model(input_shape, input_q, layers, elem=INT8):
                 opts = Table({0: ("i8", PAD[L["padding"]]), 1: ("i32", L["strides"][1]), 2: ("i32", L["strides"][0]),
                               3: ("i32", L.get("depth_multiplier", 1)), 4: ("i8", ACT[L.get("act")])})
             ins = [cur, tw, tb]
+            if "side_of" in L:
+                ins[0] = first if L["side_of"] < 0 else outs[L["side_of"]]
         elif op in ("average_pool_2d", "max_pool_2d"):
             out = add_tensor(L["out_shape"], elem, 0, *L["out_q"])
             # Pool2DOptions { padding:0 stride_w:1 stride_h:2 filter_width:3 filter_height:4 act:5 }
@@ -126,7 +130,8 @@ def build_model(input_shape, input_q, layers, elem=INT8):
         # Operator { opcode_index:0 inputs:1 outputs:2 builtin_options_type:3 builtin_options:4 }
         operators.append(Table({0: ("u32", oc), 1: ("ref", Vec("<i", ins)), 2: ("ref", Vec("<i", [out])),
                                 3: ("u8", OPT_TYPE[op]), 4: ("ref", opts)}))
-        cur = out
+        if "side_of" not in L:
+            cur = out
         outs.append(out)
     subgraph = Table({0: ("ref", TableVec(tensors)), 1: ("ref", Vec("<i", [first])), 2: ("ref", Vec("<i", [cur])),
                       3: ("ref", TableVec(operators))})
@@ -594,31 +599,75 @@ def inverted_residual_layers(rng, input_shape, blocks, elem=INT8, wzp_nonzero=Fa
     return (1,) + tuple(input_shape), in_q, layers
 
 
-def resnet_like_layers(rng, input_shape, blocks, elem=INT8, k=3, swap=(), head=10):
-    """ResNet-style basic blocks without projection shortcuts: input_shape = (H, W, C); `blocks` of them, each Conv2D kxk SAME (relu) ->
+def resnet_like_layers(rng, input_shape, blocks, elem=INT8, k=3, swap=(), head=10, side="first", side_wzp="none", side_act="none",
+                       add_act="relu", in_q=None, act_scale=None):
+    """ResNet-style basic blocks: input_shape = (H, W, C); `blocks` of them (a count: identity blocks), each Conv2D kxk SAME (relu) ->
     Conv2D kxk SAME (no activation) -> ADD with relu onto the block's input; block b's ADD is written [skip, running] when b is in
-    `swap`.  Then AveragePool over the whole image, FullyConnected(head) and Softmax (head = 0: none of the three).  -> build_model's
-    arguments"""
+    `swap`.  `blocks` may also be a list of (stride, width): the block's first convolution has that stride and both have that many
+    outputs; a block with stride 2 or a changed width is a projection block, whose ADD reads a 1x1 Conv2D (that stride, no activation
+    unless side_act, filter zero points by side_wzp as _conv_layer's wzp) of the block's input instead of the input itself.  `side`
+    places that convolution in file order: "first" (directly behind the fork) or "last" (directly in front of the ADD); the operators
+    are the same either way.  act_scale: every convolution's output scale (_conv_layer's act_scale: a deep stack keeps its scales),
+    else each layer's own spread-keeping one; in_q: the input's quantisation, where a caller puts a stem in front.  Then AveragePool
+    over the whole image, FullyConnected(head) and Softmax (head = 0: none of the three).  -> build_model's arguments"""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     H, W, C = (int(v) for v in input_shape)
-    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    in_q = in_q or (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))  # (given: the tensor in front)
     q, layers = in_q, []
-    for b in range(int(blocks)):
+    plan = [(1, C)] * blocks if isinstance(blocks, int) else [(int(s), int(n)) for s, n in blocks]
+    assert side in ("first", "last")
+    for b, (s, n) in enumerate(plan):
         skip, q_skip = len(layers) - 1, q
-        layers.append(_conv_layer(rng, (H, W, C), q, False, C, k, 1, "same", "relu", elem))
-        layers.append(_conv_layer(rng, (H, W, C), layers[-1]["out_q"], False, C, k, 1, "same", "none", elem))
-        layers.append(_add_layer(rng, skip, (1, H, W, C), layers[-1]["out_q"], q_skip, "relu", elem, swap=b in swap))
+        proj = s != 1 or n != C
+        sc = None
+        if proj:  # (drawn here wherever it stands: both placements write the same operators)
+            sc = dict(_conv_layer(rng, (H, W, C), q, False, n, 1, s, "same", side_act, elem, wzp=side_wzp, act_scale=act_scale), side_of=skip)
+        if proj and side == "first":
+            layers.append(sc)
+        layers.append(_conv_layer(rng, (H, W, C), q, False, n, k, s, "same", "relu", elem, act_scale=act_scale))
+        oh, ow = layers[-1]["out_shape"][1:3]
+        layers.append(_conv_layer(rng, (oh, ow, n), layers[-1]["out_q"], False, n, k, 1, "same", "none", elem, act_scale=act_scale))
+        q_run = layers[-1]["out_q"]
+        if proj and side == "last":
+            layers.append(sc)
+        if proj:
+            skip = len(layers) - 1 if side == "last" else skip + 1
+            q_skip = sc["out_q"]
+        H, W, C = oh, ow, n
+        layers.append(_add_layer(rng, skip, (1, H, W, C), q_run, q_skip, add_act, elem, swap=b in swap))
         q = layers[-1]["out_q"]
     if head:
         layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none", out_shape=(1, 1, 1, C), out_q=q))
         layers.append(dict(op="reshape", out_shape=(1, C), out_q=q))
         layers.append(_fc_layer(rng, C, head, q, "none", elem))
         layers.append(dict(op="softmax", out_shape=(1, head), out_q=(1.0 / 256.0, lo)))
-    return (1, H, W, C), in_q, layers
+    return (1,) + tuple(int(v) for v in input_shape), in_q, layers
 
 
 def resnet_like(rng, input_shape, blocks, elem=INT8, **kw):
     return build_model(*resnet_like_layers(rng, input_shape, blocks, elem, **kw), elem)
+
+
+def resnet8_layers(rng, elem=INT8, side="first", input_shape=(32, 32, 3), widths=(16, 32, 64), head=10):
+    """MLPerf-Tiny's image classifier: 32x32x3 -> Conv2D 3x3 to 16 (relu) -> an identity block at 16 -> projection blocks to 32 and to 64
+    at stride 2 (1x1 stride-2 convolutions on their shortcuts) -> AveragePool over the 8x8 image -> FullyConnected(10) -> Softmax.
+    input_shape / widths: a cut-down twin of the same graph.  -> build_model's arguments"""
+    lo = 0 if elem == UINT8 else -128
+    H, W, C = (int(v) for v in input_shape)
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, lo + 236)))
+    stem = _conv_layer(rng, (H, W, C), in_q, False, widths[0], 3, 1, "same", "relu", elem, act_scale=in_q[0])
+    blocks = [(1, widths[0])] + [(2, int(n)) for n in widths[1:]]
+    _, _, body = resnet_like_layers(rng, (H, W, widths[0]), blocks, elem, head=head, side=side, in_q=stem["out_q"], act_scale=in_q[0])
+    for L in body:  # (the body's layer indices are one behind the model's: the stem is layer 0; its "model input" is the stem)
+        if "side_of" in L:
+            L["side_of"] += 1
+        if L["op"] == "add":
+            L["skip"] += 1
+    return (1, H, W, C), in_q, [stem] + body
+
+
+def resnet8(rng, elem=INT8, **kw):
+    return build_model(*resnet8_layers(rng, elem, **kw), elem)
 
 
 # person_detect_like(quant=...): the head's effective multiplier in_scale * fscale / out_scale (256 products of a byte
