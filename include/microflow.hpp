@@ -7,7 +7,7 @@
 //
 //   microflow::Tensor2D / Tensor4D                      src/tensor.rs:27-47
 //   microflow::FusedActivation, TensorViewPadding       src/activation.rs:6-13, src/tensor.rs:9-15
-//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / average_pool_2d / max_pool_2d (ours) / add (ours) /
+//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / average_pool_2d / max_pool_2d (ours) / add (ours) / pad (ours) /
 //                   softmax / reshape                    src/ops/*.rs
 //   microflow::Model  (what #[model("x.tflite")] generates: predict, predict_quantized)
 //                                                        microflow-macros/src/lib.rs:185-203
@@ -228,6 +228,18 @@ inline Tensor4D add(const Tensor4D &a, const Tensor4D &b, std::array<float, 1> o
     out.buffer = detail::run2(op, a.buffer, b.buffer, (size_t)a.batches);
     out.batches = a.batches, out.rows = a.rows, out.cols = a.cols, out.chans = a.chans;
     out.scale = {output_scale[0]}, out.zero_point = {output_zero_point[0]};
+    return out;
+}
+
+// PAD: no counterpart in the reference (microflow_amd.h states the contract).  pads = {top, bottom, left, right} new rows / columns of the
+// tensor's own zero point; scale and zero point stay.  (MEAN over H and W is average_pool_2d with the whole image as filter.)
+inline Tensor4D pad(const Tensor4D &input, std::array<int, 4> pads, int device = 0) {
+    mf_op *op = nullptr;
+    check(mf_pad_create(device, input.rows, input.cols, input.chans, pads[0], pads[1], pads[2], pads[3], input.zero_point[0], &op));
+    Tensor4D out;
+    out.buffer = detail::run(op, input.buffer, (size_t)input.batches);
+    out.batches = input.batches, out.rows = input.rows + pads[0] + pads[1], out.cols = input.cols + pads[2] + pads[3], out.chans = input.chans;
+    out.scale = input.scale, out.zero_point = input.zero_point;
     return out;
 }
 

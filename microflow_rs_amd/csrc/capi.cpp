@@ -363,6 +363,25 @@ int mf_add_create_u8(int device, size_t elems, float a_scale, uint8_t a_zero_poi
     })
 }
 
+// PAD (include/microflow_amd.h: the library's own contract).  Bad pads are a bad argument whether or not there is a device
+static void create_pad(int device, bool u8, int H, int W, int C, int top, int bottom, int left, int right, int zp, mf_op **op) {
+    MF_NEED(op);
+    if (H <= 0 || W <= 0 || C <= 0 || top < 0 || bottom < 0 || left < 0 || right < 0 || (long long)H + top + bottom > (1 << 24) ||
+        (long long)W + left + right > (1 << 24))
+        mf::fail(MF_ERR_INVALID_ARG, "pad: bad arguments");
+    mf::OpSpec s;
+    s.kind = MF_OP_PAD, s.u8 = u8;
+    s.H = H, s.W = W, s.C = C, s.N = C, s.OH = H + top + bottom, s.OW = W + left + right, s.izp = s.ozp = zp;
+    s.pads[0] = top, s.pads[1] = bottom, s.pads[2] = left, s.pads[3] = right;
+    wrap_op(mf::op_create(device, s), op);
+}
+int mf_pad_create(int device, int H, int W, int C, int top, int bottom, int left, int right, int8_t zero_point, mf_op **op) {
+    MF_TRY({ create_pad(device, false, H, W, C, top, bottom, left, right, zero_point, op); })
+}
+int mf_pad_create_u8(int device, int H, int W, int C, int top, int bottom, int left, int right, uint8_t zero_point, mf_op **op) {
+    MF_TRY({ create_pad(device, true, H, W, C, top, bottom, left, right, zero_point, op); })
+}
+
 int mf_op_run2(mf_op *op, const int8_t *d_a, const int8_t *d_b, size_t batch, int8_t *d_output, void *stream) {
     MF_TRY({
         MF_NEED(op && op->impl);
@@ -463,7 +482,7 @@ int mf_model_get_op(const mf_model *model, int index, mf_op_desc *d) {
         MF_NEED(index >= 0 && index < (int)pm.ops.size());
         const mf::ParsedOp &o = pm.ops[(size_t)index];
         std::memset(d, 0, sizeof(*d));
-        d->kind = o.kind, d->in_rank = o.in_rank, d->out_rank = o.out_rank;
+        d->kind = o.file_kind >= 0 ? o.file_kind : o.kind, d->in_rank = o.in_rank, d->out_rank = o.out_rank;
         for (int i = 0; i < 4; ++i) d->in_shape[i] = o.in_shape[i], d->out_shape[i] = o.out_shape[i];
         d->KH = o.KH, d->KW = o.KW, d->stride_h = o.sh, d->stride_w = o.sw;
         d->padding = o.pad, d->activation = o.act;
@@ -516,6 +535,17 @@ int mf_model_get_op_source(const mf_model *model, int index, int *source) {
         const mf::ParsedOp &o = pm.ops[(size_t)index];
         if (!o.side()) mf::fail(MF_ERR_INVALID_ARG, "mf_model_get_op_source: the operator is no side operator");
         if (source) *source = o.side_src;
+    })
+}
+
+int mf_model_get_op_pads(const mf_model *model, int index, int *pads) {
+    MF_TRY({
+        MF_NEED(model && model->impl && pads);
+        const mf::ParsedModel &pm = mf::model_parsed(model->impl);
+        MF_NEED(index >= 0 && index < (int)pm.ops.size());
+        const mf::ParsedOp &o = pm.ops[(size_t)index];
+        if (o.kind != MF_OP_PAD) mf::fail(MF_ERR_INVALID_ARG, "mf_model_get_op_pads: the operator is no PAD");
+        for (int k = 0; k < 4; ++k) pads[k] = o.pads[k];
     })
 }
 

@@ -98,6 +98,10 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
     case FusedImpl::FCSM:
         if (!k::launch_fc_rowwave_softmax(d_in, d_out, f->a->fc, f->b->sm, batch, st)) fail(MF_ERR_UNSUPPORTED, "fused kernel missing");
         break;
+    case FusedImpl::PADCONV: // (the inner operator's generic kernel knows no explicit pads: never an unaligned pointer)
+        if ((uintptr_t)d_out & 15) fail(MF_ERR_INVALID_ARG, "pad+conv: the output pointer is not 16-byte aligned");
+        op_run(f->padconv.get(), d_in, batch, d_out, st);
+        break;
     case FusedImpl::SHORTCUT: fail(MF_ERR_INVALID_ARG, "shortcut_add_rt takes two inputs: fused_run2"); break;
     case FusedImpl::DWPW: {
         const OpSpec &d = f->a->s;

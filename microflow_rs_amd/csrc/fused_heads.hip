@@ -255,6 +255,30 @@ FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool) {
     return f.release();
 }
 
+// A PAD directly followed by a VALID Conv2D / DepthwiseConv2D on exactly its output, as ONE launch of the kernel the convolution gets from
+// the run-time-geometry planners when it is taken as an operator on the unpadded image with the PAD's top / left rows and columns as its
+// window placement (ops.hip op_create_padded_conv).  Those kernels fill every tile byte outside the image with the input zero
+// point, which is the PAD's fill: the same bytes as PAD, then the VALID convolution.  Same device and element type, finite constants,
+// neither forced generic, a filter larger than 1 x 1 (a 1x1 convolution has no window to place).  nullptr: the two launches stay
+FusedImpl *fused_pad_conv_create(OpImpl *pad, OpImpl *conv) {
+    if (switches().no_pad_conv || !pad || !conv || pad->force_generic || conv->force_generic) return nullptr;
+    const OpSpec &p = pad->s, &d = conv->s;
+    const bool dw = d.kind == MF_OP_DEPTHWISE_CONV_2D;
+    if (p.kind != MF_OP_PAD || (d.kind != MF_OP_CONV_2D && !dw) || d.pad != MF_PAD_VALID || pad->device != conv->device || p.u8 != d.u8) return nullptr;
+    if (d.H != p.OH || d.W != p.OW || d.C != p.C) return nullptr; // on exactly the PAD's output
+    if (d.KH == 1 && d.KW == 1) return nullptr;
+    if (!conv->finite_consts) return nullptr;
+    // the PAD's fill is the byte the kernels put outside the image: the convolution's input zero point (it is, where the model's
+    // quantisation is consistent; where not, the two launches compute what the file says)
+    if ((pad->padargs.fill4 & 0xffu) != (uint32_t)(uint8_t)(int8_t)conv->conv.izp) return nullptr;
+    std::shared_ptr<OpImpl> inner(op_create_padded_conv(conv, p.H, p.W, p.pads[0], p.pads[2]), op_destroy);
+    if (!inner) return nullptr;
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::PADCONV, pad, conv, nullptr, "pad+" + inner->fast_name);
+    f->padconv = inner;
+    f->epi_mode = conv->magic_mode;
+    return f.release();
+}
+
 // DepthwiseConv2D with one input channel (the dw_c1_lds operator) -> [Reshape] -> FullyConnected + Softmax group, as
 // one kernel (k_dwfc.hip; speech.tflite ops 1..3).  Second level like the stage: the operator and the group inside
 // stay available for mf_model_run_until.  nullptr when the shapes are not the compiled instance.

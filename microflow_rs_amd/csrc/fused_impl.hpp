@@ -17,7 +17,7 @@ namespace mf {
 // One argument block (or a named sub-struct: block + what the launch path needs beside it) per kind; a group uses its own kind's.
 // Plain members, no variant: the chain planner swaps whole groups (std::swap(*groups[i], *trial)).
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK, CONVPOOL, SHORTCUT } kind = DWPW;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK, CONVPOOL, SHORTCUT, PADCONV } kind = DWPW;
     OpImpl *a = nullptr, *b = nullptr, *c = nullptr;
     std::string name;
     std::vector<std::unique_ptr<DevBuf>> owned; // the group's own operand arrays and tables (keep)
@@ -78,6 +78,11 @@ struct FusedImpl {
     // SHORTCUT: a 1x1 shortcut convolution + the ADD on its result and the running tensor (k_shortcut_add.hip); a = the convolution, b = the
     // ADD.  The one kind with TWO inputs: fused_run2, never the launch path of the others
     k::ShortcutAddArgs shortcut{};
+    // PADCONV: a PAD + the VALID Conv2D / DepthwiseConv2D on its output as one launch of the convolution's own run-time-geometry kernel;
+    // a = the PAD, b = the convolution.  padconv = that convolution taken as an operator on the UNPADDED image with the PAD's top / left
+    // rows and columns as its window placement (ops.hip op_create_padded_conv): it borrows b's weights and constants, owns the images
+    // and tables of its plan, and has no generic kernel -- the group runs it on 16-byte aligned pointers only
+    std::shared_ptr<OpImpl> padconv;
     // the model's f32 boundary inside this group's launch (fused_set_input_quant / fused_set_output_dequant; KindFacts f32_in / f32_out)
     k::F32Edge edge{};
     bool edge_in = false, edge_out = false;
@@ -108,6 +113,7 @@ inline KindFacts kind_facts(FusedImpl::Kind kind) {
     case FusedImpl::CONV1FC: return {"conv1_fc_rt", false, false, false};
     case FusedImpl::BLOCK: return {"block_band_rt", true, false, false};
     case FusedImpl::CONVPOOL: return {"conv_pool_rt", true, false, false};
+    case FusedImpl::PADCONV: return {"pad+conv", true, false, false};
     case FusedImpl::SHORTCUT: return {nullptr, false, false, false}; // (16-byte words at all three pointers, the caller's output buffer among them: fused_run2 checks the alignment itself)
     }
     return {nullptr, false, false, false};

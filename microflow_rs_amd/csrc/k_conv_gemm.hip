@@ -162,11 +162,16 @@ __global__ __launch_bounds__(256) void conv_gemm_rt(const int8_t *__restrict__ i
 // at all; the image step as conv_mm_rt's: G whole images (<= 48 KiB of tiles) or one band of output rows.
 bool conv_gemm_plan(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uint32_t> &mask, int H, int W, int C, int N, int KH, int KW, int sh,
                     int sw, int OH, int OW, bool pad_same, bool wz) {
+    return conv_gemm_plan_pads(a, tap, mask, H, W, C, N, KH, KW, sh, sw, OH, OW, pad_same ? (KH - 1) / 2 : 0, pad_same ? (KW - 1) / 2 : 0, wz);
+}
+// ... with the window placement given (k_rt.hip conv_rows_plan_pads): the tile is sized from padt, padl, OH and OW
+bool conv_gemm_plan_pads(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uint32_t> &mask, int H, int W, int C, int N, int KH, int KW,
+                         int sh, int sw, int OH, int OW, int padt, int padl, bool wz) {
+    if (padt < 0 || padl < 0) return false;
     if (H < 1 || W < 1 || C < 1 || N < 1 || KH < 1 || KW < 1 || sh < 1 || sw < 1 || OH < 1 || OW < 1) return false;
     if ((W * C) % 4 != 0) return false;                  // whole-dword image rows
     const int KWC = KW * C, KWCP = (KWC + 15) & ~15, KS = (KH * KWCP + 63) / 64, NT = (N + 15) / 16;
     if (KS > CONV_GEMM_KS_MAX) return false;
-    const int padl = pad_same ? (KW - 1) / 2 : 0, padt = pad_same ? (KH - 1) / 2 : 0;
     const int LP = (padl * C + 15) & ~15;
     // bytes read right of the image row: the last window's padded filter row (+ the 4 bytes of the aligned reads)
     const int over = std::max(0, ((OW - 1) * sw - padl) * C + KWCP + 4 - W * C);

@@ -169,9 +169,13 @@ __global__ __launch_bounds__(256) void dw_gemm_rt(const int8_t *__restrict__ in,
 // ---- host side ----------------------------------------------------------------------------------------------------
 // The image step as conv_gemm_rt's: G whole images (<= 48 KiB of tiles) or one band of output rows.
 bool dw_gemm_plan(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same) {
+    return dw_gemm_plan_pads(a, H, W, C, KH, KW, sh, sw, OH, OW, pad_same ? (KH - 1) / 2 : 0, pad_same ? (KW - 1) / 2 : 0);
+}
+// ... with the window placement given (k_rt.hip conv_rows_plan_pads): the tile is sized from padt, padl, OH and OW
+bool dw_gemm_plan_pads(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl) {
+    if (padt < 0 || padl < 0) return false;
     if (H < 1 || W < 1 || C < 2 || KH < 1 || KW < 1 || sh < 1 || sw < 1 || OH < 1 || OW < 1) return false;
     if (KH > 7 || KW > 7 || (W * C) % 4 != 0) return false;
-    const int padl = pad_same ? (KW - 1) / 2 : 0, padt = pad_same ? (KH - 1) / 2 : 0;
     const int LP = (padl * C + 15) & ~15;
     // bytes read right of the image row: the last window's last tap, the last group's 16 bytes from its start (<= C - 1 past the
     // tap's first channel) and the 4 bytes of the aligned reads

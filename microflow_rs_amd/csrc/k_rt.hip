@@ -998,14 +998,23 @@ int conv_rows_lds_bytes(const ConvRowsArgs &a) {
 }
 // fills the geometry of a; false: the shape is not for this kernel
 bool conv_rows_plan(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same) {
+    return conv_rows_plan_pads(a, H, W, C, N, KH, KW, sh, sw, OH, OW, pad_same ? (KH - 1) / 2 : 0, pad_same ? (KW - 1) / 2 : 0, false);
+}
+// ... with the window placement given: output (oy, ox) reads rows oy sh - padt .. + KH - 1 and columns ox sw - padl .. + KW - 1 of the
+// H x W image, whatever lies outside it filled with the input zero point -- above and left as far as the pads say, below and right as
+// far as OH, OW reach (the tile is sized from them: TH, TWP)
+// bytes_any_c: rows that are not whole dwords with ANY channel count (conv_rows_bytes' staging is written in row bytes and has no
+// C = 1 assumption; an operator alone is routed there for one channel only, the PAD + convolution group for any: an
+// RGB image of even width behind Keras' ZeroPadding2D has such rows)
+bool conv_rows_plan_pads(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl, bool bytes_any_c) {
     const int RWB = KW * C;
     // rows that are not whole dwords: conv_rows_bytes, routed for one input channel only (the kernel is written in row bytes; C >= 2
     // with such rows stays on the generic kernels)
     const bool bytes = (W * C) % 4 != 0;
-    if (RWB > 64 || KH > 16 || N < 1 || N > 64 || (bytes && (C != 1 || switches().no_conv_rows_bytes)) || C >= 16) return false; // (16 and more channels: conv_mm_rt)
+    if (RWB > 64 || KH > 16 || N < 1 || N > 64 || (bytes && ((C != 1 && !bytes_any_c) || switches().no_conv_rows_bytes)) || C >= 16) return false; // (16 and more channels: conv_mm_rt)
     a.H = H, a.W = W, a.C = C, a.N = N, a.KH = KH, a.KW = KW, a.sh = sh, a.sw = sw, a.OH = OH, a.OW = OW;
     a.ROWB = W * C, a.KG = (RWB + 3) / 4, a.NP = (N + 7) & ~7;
-    const int padl = pad_same ? (KW - 1) / 2 : 0, padt = pad_same ? (KH - 1) / 2 : 0;
+    if (padt < 0 || padl < 0) return false;
     a.shy = padt;
     a.XO = (padl * C + 3) & ~3;                       // image column 0 at a dword boundary
     a.X0 = a.XO - padl * C;                           // window of output column 0 starts here
@@ -1125,6 +1134,13 @@ int conv_mm_lds_bytes(const ConvMmArgs &a, bool wz) {
 // fills the geometry and the tap-offset table (host copy in `tap`); false: not for this kernel
 bool conv_mm_plan(ConvMmArgs &a, std::vector<int> &tap, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW,
                   bool pad_same, bool wz, bool dwise) {
+    return conv_mm_plan_pads(a, tap, H, W, C, N, KH, KW, sh, sw, OH, OW, pad_same ? (KH - 1) / 2 : 0, pad_same ? (KW - 1) / 2 : 0, wz, dwise);
+}
+// ... with the window placement given (conv_rows_plan_pads): rows above the image by padt, columns left of it by LP; below and right the
+// tile is sized from OH, OW (RB, RP), and every tile byte the staging does not write holds the input zero point
+bool conv_mm_plan_pads(ConvMmArgs &a, std::vector<int> &tap, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW,
+                       int padt, int padl, bool wz, bool dwise) {
+    if (padt < 0 || padl < 0) return false;
     if (C % 16 != 0 || N % 4 != 0 || KH > 7 || KW > 7 || (W * C) % 16 != 0) return false;
     if (dwise && (N != C || wz)) return false;           // one output per input channel; filter zero points take the generic kernel
     const int Ktot = dwise ? KH * KW * 16 : KH * KW * C; // depthwise: 16 k-bytes per tap and block
@@ -1135,7 +1151,6 @@ bool conv_mm_plan(ConvMmArgs &a, std::vector<int> &tap, int H, int W, int C, int
     a.dwise = dwise ? 1 : 0;
     const int wbytes = NBLK * TB * KS * 1024 + (wz ? KS * 1024 : 0);
     if (wbytes > 96 * 1024) return false;
-    const int padl = pad_same ? (KW - 1) / 2 : 0, padt = pad_same ? (KH - 1) / 2 : 0;
     const int LP = (padl * C + 15) & ~15;
     int over = ((OW - 1) * sw - padl + KW - W) * C;      // bytes read right of the image row
     if (over < 0) over = 0;

@@ -73,6 +73,14 @@ struct AddArgs {
     float k1;             // the gated form (add_c16<fma>): y = fma(cb, f32(ub), fma(ca, f32(ua), k1)), k1 = zo - ca ka - cb kb folded on the host
     uint32_t xin4, xout4; // per dword: input bytes ^ xin4 are offset values; result bytes (value & 0xff) ^ xout4 are stored
 };
+// PAD (k_pad.hip).  Rows are counted in bytes: an output row is lp fill bytes, the image row (in_row), rp fill bytes.
+struct PadArgs {
+    int H, OH;            // image rows, output rows (top + H + bottom)
+    int top;              // fill rows above the image
+    int in_row, out_row;  // W * C, OW * C
+    int lp;               // left * C
+    uint32_t fill4;       // the input zero point as a stored byte (u8: internal domain, zp ^ 0x80), splatted over a dword
+};
 struct FcArgs {
     int K, N;
     int wzp;
@@ -303,6 +311,7 @@ void launch_dw_stem_rt(const int8_t *in, int8_t *out, const DwStemRtArgs &a, int
 int conv_rows_lds_bytes(const ConvRowsArgs &a);
 // (a.BYTES() after a plan that succeeded: launch_conv_rows launches conv_rows_bytes, which has no f32 entry -- eg must be null)
 bool conv_rows_plan(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same);
+bool conv_rows_plan_pads(ConvRowsArgs &a, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl, bool bytes_any_c = false); // explicit top / left pads (PAD + convolution); bytes_any_c: k_rt.hip
 void launch_conv_rows(const int8_t *in, int8_t *out, const ConvRowsArgs &a, bool wz, int batch, hipStream_t s, const F32Edge *eg = nullptr);
 // Conv2D with any filter, C % 16 == 0, as an MFMA product over K = KH KW C (k_rt.hip: conv_mm_rt)
 struct ConvMmArgs {
@@ -326,6 +335,8 @@ struct ConvMmArgs {
 };
 bool conv_mm_plan(ConvMmArgs &a, std::vector<int> &tap, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW,
                   bool pad_same, bool wz, bool dwise = false);
+bool conv_mm_plan_pads(ConvMmArgs &a, std::vector<int> &tap, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW,
+                       int padt, int padl, bool wz, bool dwise = false); // explicit top / left pads (PAD + convolution)
 void launch_conv_mm(const int8_t *in, int8_t *out, const ConvMmArgs &a, bool wz, int batch, hipStream_t s);
 void launch_dw_mm(const int8_t *in, int8_t *out, const ConvMmArgs &a, int batch, hipStream_t s); // a.dwise: dw_mm_rt (k_rt.hip)
 bool dw_rt_plan(DwRtArgs &a, int H, int W, int C, int S, int OH, int OW); // fills the geometry; false: not supported
@@ -723,6 +734,10 @@ void launch_maxpool_c4(const int8_t *in, int8_t *out, const PoolArgs &a, size_t 
 // fma: the gated form, only where the host checked it identical over all 65 536 byte pairs (hostmath.cpp: h_add_fma_form)
 void launch_add_c16(const int8_t *a, const int8_t *b, int8_t *out, const AddArgs &p, size_t n, int cus, bool fma, hipStream_t s);
 void launch_add_generic(const int8_t *a, const int8_t *b, int8_t *out, const AddArgs &p, size_t n, hipStream_t s);
+// PAD: out = in with fill bytes around every image.  pad_generic: any shape and pointers; pad_c4 (units = 4: in_row, out_row, lp
+// multiples of 4, pointers 4-byte aligned; units = 16: all of them multiples of 16): every output word written once, no LDS
+void launch_pad_generic(const int8_t *in, int8_t *out, const PadArgs &a, size_t batch, hipStream_t s);
+void launch_pad_c4(const int8_t *in, int8_t *out, const PadArgs &a, size_t batch, int unit, hipStream_t s);
 void launch_fc_generic(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s);
 bool launch_fc_rowwave(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s);
 bool launch_fc_rowwave_softmax(const int8_t *in, int8_t *out, const FcArgs &a, const SoftmaxArgs &sm, size_t rows,
@@ -788,6 +803,8 @@ constexpr int CONV_GEMM_LDS_MAX = 160 * 1024 - 1024;
 constexpr int CONV_GEMM_KS_MAX = 128; // K' <= 8192: one resident 16-column tile is at most 128 KiB
 bool conv_gemm_plan(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uint32_t> &mask, int H, int W, int C, int N, int KH, int KW, int sh,
                     int sw, int OH, int OW, bool pad_same, bool wz); // false: beyond the limits
+bool conv_gemm_plan_pads(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uint32_t> &mask, int H, int W, int C, int N, int KH, int KW,
+                         int sh, int sw, int OH, int OW, int padt, int padl, bool wz); // explicit top / left pads (PAD + convolution)
 std::vector<int8_t> conv_gemm_weight_image(const int8_t *w /*[N][KH][KW][C]*/, const ConvGemmArgs &a);
 void launch_conv_gemm(const int8_t *in, int8_t *out, const ConvGemmArgs &a, bool wz, int batch, hipStream_t s);
 // A Conv2D + the AveragePool2D (more than one output pixel) on exactly its output in one launch (k_conv_pool.hip: conv_pool_rt).  The
@@ -852,6 +869,7 @@ struct DwGemmArgs {
 };
 constexpr int DW_GEMM_LDS_MAX = 160 * 1024 - 1024;
 bool dw_gemm_plan(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same); // false: beyond the limits
+bool dw_gemm_plan_pads(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl); // explicit top / left pads (PAD + convolution)
 void launch_dw_gemm(const int8_t *in, int8_t *out, const DwGemmArgs &a, bool wz, int batch, hipStream_t s);
 // Consecutive FullyConnected layers (+ a Softmax over one row) in one launch (k_fc_rt.hip: fc_chain).  Every layer's weight image
 // (its fc_rt image, all tiles) stays resident in LDS; the int8 tensors between the layers never leave LDS.

@@ -113,6 +113,11 @@ struct ParsedOp {
     // That ADD's skip_src is this operator's index.  in_scale / in_zp are T's
     int side_src = -2;
     bool side() const { return side_src != -2; }
+    // PAD only: new rows / columns (top, bottom, left, right); H, W, C the input, OH, OW the output
+    int pads[4] = {0, 0, 0, 0};
+    // what mf_model_get_op reports as the kind: the file's.  A MEAN over {1, 2} is parsed into a global AveragePool2D (kind), so that
+    // every rule that matches one sees it, and reports MF_OP_MEAN; -1: kind
+    int file_kind = -1;
 };
 struct ParsedModel {
     bool u8 = false; // element type T of every quantized tensor: INT8 (false) or UINT8 (true)
@@ -175,6 +180,9 @@ struct OpSpec {
     size_t add_elems = 0;
     int add_za = 0, add_zb = 0;
     float add_ca = 0, add_cb = 0;
+    // PAD only: new rows / columns (top, bottom, left, right) around the H x W x C image, each element izp; OH, OW the padded size.
+    // (A convolution's spec carries SAME / VALID and nothing else: explicit pads exist only inside the PAD + convolution group)
+    int pads[4] = {0, 0, 0, 0};
 };
 OpImpl *op_create(int device, const OpSpec &spec);
 void op_destroy(OpImpl *op);
@@ -214,6 +222,14 @@ FusedImpl *fused_block_create(OpImpl *expand, OpImpl *dw, OpImpl *pw, bool pair_
 // convolution's result.  fused_run2 runs it: d_t the convolution's input, d_run the running tensor; d_out may be exactly d_run
 FusedImpl *fused_shortcut_add_create(OpImpl *conv, OpImpl *add, bool conv_first);
 void fused_run2(FusedImpl *f, const int8_t *d_t, const int8_t *d_run, size_t batch, int8_t *d_out, void *stream);
+// a PAD + the VALID Conv2D / DepthwiseConv2D on its output as ONE launch of the kernel the convolution, taken as an operator on the
+// unpadded image with the PAD's top / left pads, gets from the run-time-geometry planners (conv_rows, conv_mm / dw_mm, dw_gemm, conv_gemm);
+// nullptr: no planner accepts (or the class is excluded) and the two launches stay
+FusedImpl *fused_pad_conv_create(OpImpl *pad, OpImpl *conv);
+// the convolution `conv` (VALID, on the padded H x W) as an operator on the unpadded Hin x Win image whose windows start padt rows above
+// and padl columns left of it, everything outside the image reading the input zero point; OH, OW stay.  It borrows conv's weights and
+// constants (destroy it first), has a matrix-pipe / row kernel or does not exist (nullptr), and must only be run on 16-byte aligned pointers
+OpImpl *op_create_padded_conv(const OpImpl *conv, int Hin, int Win, int padt, int padl);
 FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool); // a Conv2D + the AveragePool2D (k_conv_pool.hip) or MaxPool2D (k_conv_maxpool.hip) with more than one output pixel on its output in one launch, or nullptr
 // fused tail: AveragePool2D (1x1 output) -> Conv2D 1x1 (N <= 8) -> Softmax (one row of N)
 FusedImpl *fused_tail_create(OpImpl *pool, OpImpl *conv, OpImpl *softmax);

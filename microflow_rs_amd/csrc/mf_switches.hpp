@@ -40,6 +40,7 @@ struct Switches {
     bool no_pool_fc = false;      // MF_NO_POOL_FC      global AveragePool2D + FullyConnected (+ Softmax) heads one launch per operator, not one pool_fc_chain launch (k_pool_fc.hip)
     bool no_pair_band = false;     // MF_NO_PAIR_BAND     pairs too large for chain_rt one launch per operator, not one pair_band_rt / pair_band_deep_rt launch (k_pair_band.hip, k_pair_band_deep.hip)
     bool no_expand_block = false;  // MF_NO_EXPAND_BLOCK  1x1 expand + depthwise 3x3 + 1x1 project blocks as the launches they had before (the expand's own, then the pair's group or operators), not one block_band_rt launch (k_block_band.hip)
+    bool no_pad_conv = false;      // MF_NO_PAD_CONV      a PAD + the VALID Conv2D / DepthwiseConv2D behind it one launch per operator, not one launch of the convolution's kernel with explicit pads (fused_heads.hip fused_pad_conv_create)
     bool no_conv_pool = false;     // MF_NO_CONV_POOL     Conv2D + AveragePool2D (more than one output pixel) stages one launch per operator, not one conv_pool_rt launch (k_conv_pool.hip)
     bool conv_pool_all = false;    // MF_CONV_POOL_ALL    measurements and tests: also the Conv2D + AveragePool2D classes the route excludes by measurement run as one conv_pool_rt launch -- every pair the plan accepts
     bool no_shortcut_add = false;  // MF_NO_SHORTCUT_ADD  a 1x1 shortcut convolution and its ADD as two launches (the convolution's own into a fork buffer, then add_c16), not one shortcut_add_rt launch (k_shortcut_add.hip)

@@ -65,7 +65,8 @@ struct GroupBuilder {
         return false;
     }
     // a first-level pair group: operators i and i + 1
-    bool is_pair_group(size_t i) const { return g.fused[i] && g.fused_last[i] == (int)i + 1; }
+    // (a depthwise + 1x1 pair of rule (1): the PAD + convolution group has two operators too and is none)
+    bool is_pair_group(size_t i) const { return g.fused[i] && g.fused_last[i] == (int)i + 1 && kind(i) != MF_OP_PAD; }
     // an operator with a launch of its own that no group starts at, covers or owns
     bool free_op(size_t i) const { return g.ops[i] && !g.fused[i] && !covered(i) && !owned(i); }
     bool free_fc(size_t i) const { return i < n && kind(i) == MF_OP_FULLY_CONNECTED && free_op(i); }
@@ -108,6 +109,8 @@ static OpSpec op_spec(const ParsedModel &pm, const ParsedOp &po, float cur_scale
         s.add_elems = po.in_elems, s.add_za = po.a_zp, s.add_zb = po.b_zp;
         s.add_ca = po.c0[0], s.add_cb = po.c1[0];
     }
+    if (po.kind == MF_OP_PAD)
+        for (int k = 0; k < 4; ++k) s.pads[k] = po.pads[k];
     return s;
 }
 
@@ -144,12 +147,18 @@ static void create_operators(GroupBuilder &b) {
 // peepholes.  (1) DepthwiseConv2D 3x3 directly followed by a 1x1 Conv2D -> one fused kernel.
 // (2) AveragePool2D (1x1 output) -> Conv2D 1x1 -> [Reshape] -> Softmax -> one tail kernel.
 // (3) FullyConnected (few outputs, one row) -> [Reshape] -> Softmax -> one kernel.
+// (0p) a PAD directly followed by a VALID Conv2D / DepthwiseConv2D -> one launch of the convolution's kernel with explicit pads.
+// In the same loop as (1)-(3) and in front of them: the group at i owns the convolution at i + 1 (the loop continues behind it), so a
+// depthwise there is never also offered to (1) with the 1x1 behind it -- that pair would be formed over the padded tensor, which this
+// launch never writes.  The PAD's output has one reader (the parser's chain: the convolution) unless an ADD reads it too: splits
 static void rule_1_2_3_first_level(GroupBuilder &b) {
     const std::vector<OpImpl *> &ops = b.g.ops;
     std::vector<FusedImpl *> &fused = b.g.fused;
     std::vector<int> &fused_last = b.g.fused_last;
     for (size_t i = 0; i + 1 < b.n; ++i) {
-        if (b.kind(i) == MF_OP_DEPTHWISE_CONV_2D && b.kind(i + 1) == MF_OP_CONV_2D) {
+        if (b.kind(i) == MF_OP_PAD && (b.kind(i + 1) == MF_OP_CONV_2D || b.kind(i + 1) == MF_OP_DEPTHWISE_CONV_2D)) {
+            if (!b.splits(i, i + 1) && (fused[i] = fused_pad_conv_create(ops[i], ops[i + 1]))) fused_last[i] = (int)i + 1;
+        } else if (b.kind(i) == MF_OP_DEPTHWISE_CONV_2D && b.kind(i + 1) == MF_OP_CONV_2D) {
             if (!b.splits(i, i + 1) && (fused[i] = fused_create(ops[i], ops[i + 1]))) fused_last[i] = (int)i + 1;
         } else if (b.kind(i) == MF_OP_AVERAGE_POOL_2D && b.kind(i + 1) == MF_OP_CONV_2D) {
             const size_t j = b.skip_reshapes(i + 2);
@@ -198,10 +207,10 @@ static void rule_4b_quads(GroupBuilder &b) {
             b.add_stage(f, i, i + 3);
             // ... and with the stem in front of it: ops i - 1 .. i + 3 in one launch.  Both stay: a run that does not
             // start at the stem (mf_model_run_until pieces, the f32 entry whose stem kernel quantises) uses the quad.
-            // (The stem test does not ask owned(i - 1), and need not: fused_quad_stem_create takes a one-channel depthwise stem only,
-            // and a depthwise operator is never a later member of a first-level group -- (1) starts at one, (2) and (3) hold none.  The
-            // operator that CAN sit there owned, the 1x1 of a pair group at i - 2, is refused by its kind)
-            if (i >= 1 && b.g.ops[i - 1] && !b.g.fused[i - 1] && !b.covered(i - 1) && !b.splits(i - 1, i + 3))
+            // (The stem test asks owned(i - 1): fused_quad_stem_create takes a one-channel depthwise stem only, and a depthwise operator
+            // is a later member of a first-level group in one place -- the convolution of a PAD + convolution group (0p); (1) starts at
+            // one, (2) and (3) hold none.  The other operator that can sit there owned, the 1x1 of a pair group at i - 2, is refused by its kind)
+            if (i >= 1 && b.g.ops[i - 1] && !b.g.fused[i - 1] && !b.covered(i - 1) && !b.owned(i - 1) && !b.splits(i - 1, i + 3))
                 if (FusedImpl *g = fused_quad_stem_create(b.g.ops[i - 1], f)) b.add_stage(g, i - 1, i + 3);
             i += 3;
         }
@@ -276,12 +285,12 @@ static void rule_4d_expand_blocks(GroupBuilder &b) {
 }
 
 // (5) DepthwiseConv2D with one input channel -> [Reshape] -> the FullyConnected + Softmax group -> one kernel.
-// (The test on operator i does not ask owned(i), and need not: no operator sequence makes a depthwise operator a later member of a
-// first-level group -- (1) starts at the depthwise, (2) is pool + Conv2D + Softmax, (3) FullyConnected + Softmax -- so owned(i) is
-// false for every i that passes the kind test.  The group at j is a group's FIRST operator, which owned() does not concern)
+// (The test on operator i asks owned(i): a depthwise operator is a later member of a first-level group in one place, the convolution
+// of a PAD + convolution group (0p) -- (1) starts at the depthwise, (2) is pool + Conv2D + Softmax, (3) FullyConnected + Softmax.
+// The group at j is a group's FIRST operator, which owned() does not concern)
 static void rule_5_dwfc(GroupBuilder &b) {
     for (size_t i = 0; i + 1 < b.n; ++i) {
-        if (!b.g.ops[i] || b.g.fused[i] || b.covered(i) || b.kind(i) != MF_OP_DEPTHWISE_CONV_2D) continue;
+        if (!b.g.ops[i] || b.g.fused[i] || b.covered(i) || b.kind(i) != MF_OP_DEPTHWISE_CONV_2D || b.owned(i)) continue; // (owned: by a PAD + convolution group)
         const size_t j = b.skip_reshapes(i + 1);
         if (j < b.n && b.g.fused[j] && !b.covered(j) && !b.splits(i, (size_t)b.g.fused_last[j]))
             if (FusedImpl *f = fused_dwfc_create(b.g.ops[i], b.g.fused[j])) b.add_stage(f, i, (size_t)b.g.fused_last[j]);
@@ -450,6 +459,9 @@ ModelGroups build_groups(const ParsedModel &pm, int device, bool autotune) {
     // The order is part of what the rules mean; each later rule sees what the earlier ones took (covered / owned / fused[]):
     //   - operators first: every group borrows their device buffers; (0) tells the stem the input's quantisation before any group
     //     is built over it (fused_stages.hip: the quad + stem's f32 entry reads it)
+    //   - (0p), the PAD + convolution group, with (1)-(3) and ahead of them at every index: where it is formed, the convolution is its
+    //     member and no pair (1) is formed from a depthwise there and the 1x1 behind it; where it is not (no planner accepts,
+    //     MF_NO_PAD_CONV), the convolution is a VALID operator on the padded tensor like any other and (1) may take it
     //   - (1)-(3) before every second-level rule: stages are built from first-level groups
     //   - (4) before (4b), (4b), (4b') before (4c): a pair a stage, a quad or the pair + tail took is no chain candidate; (4c) may
     //     also take a pair's group away

@@ -75,6 +75,9 @@ struct ConvCtx {
     bool zero_wzp = true; // (for u8 these are the shifted zero points: the fast kernels need wzp_u8 == 128)
                           // ... and finite constants (their epilogue has no NaN test)
     bool same3x3 = false;
+    int padt = 0, padl = 0; // where the window of output (0, 0) starts above / left of the image: SAME's (K - 1) / 2, VALID's 0 -- or the
+                            // rows / columns of a PAD in front of the operator (op_create_padded_conv), which only the planners see
+    bool rows_bytes_any_c = false; // conv_rows_plan_pads' bytes_any_c: the PAD + convolution group's inner operator only
     bool whole_range() const { return lo == (s.u8 ? 0 : -128) && hi == (s.u8 ? 255 : 127); } // the clamp is the element type's range
 };
 
@@ -206,6 +209,7 @@ ConvCtx prepare_conv(OpImpl &op, const OpSpec &s, bool dw, int lo, int hi, int x
     c.zero_wzp = !c.wz && c.finite;
     c.same3x3 = s.KH == 3 && s.KW == 3 && s.pad == MF_PAD_SAME && s.sh == s.sw &&
                 s.OH == (s.H + s.sh - 1) / s.sh && s.OW == (s.W + s.sw - 1) / s.sw;
+    c.padt = s.pad == MF_PAD_SAME ? (s.KH - 1) / 2 : 0, c.padl = s.pad == MF_PAD_SAME ? (s.KW - 1) / 2 : 0;
     c.magic = !no_magic && c.acc_bound < (1 << 22) ? 1 : 0;
     // mode 2 (k_common.hpp): the clamp is the element type's whole range (so a saturating pack can do it) and
     // |x| = |A + S * acc| stays below 2^15 for every input (so x + 128 fits the i16 the pack saturates from)
@@ -469,7 +473,7 @@ bool route_conv_rows(OpImpl &op, const ConvCtx &c) {
     const bool rows_for_c1 = !c1_lds && !k::dwfc_supported(s.H, s.W, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.N, 4);
     if (!((op.fast == OpImpl::NONE || (op.fast == OpImpl::DW_C1 && rows_for_c1)) && !no_rt && c.finite &&
           (!c.dw || s.C == 1) && !(s.KH == 1 && s.KW == 1 && !c.dw && k::conv1x1_rowwave_supported(op.conv)) &&
-          k::conv_rows_plan(op.crows, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.pad == MF_PAD_SAME)))
+          k::conv_rows_plan_pads(op.crows, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, c.padt, c.padl, c.rows_bytes_any_c)))
         return false;
     k::ConvRowsArgs &f = op.crows;
     const std::vector<uint32_t> wp = wimage::build_conv_rows_pack(s.weights, c.dw, s.KH, s.KW, s.C, s.N, f.KG, f.NP);
@@ -504,7 +508,7 @@ bool route_dw_mm(OpImpl &op, const ConvCtx &c) {
     const OpSpec &s = c.s;
     if (!(rt_candidate(op, c) && c.dw && s.C == s.N && s.C % 16 == 0 && !c.wz)) return false;
     std::vector<int> tap;
-    if (!k::conv_mm_plan(op.cmm, tap, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.pad == MF_PAD_SAME, false, true)) return false;
+    if (!k::conv_mm_plan_pads(op.cmm, tap, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, c.padt, c.padl, false, true)) return false;
     conv_mm_fields(op, c, wimage::build_dw_mm_rt_weights(s.weights, s.KH, s.KW, s.C, op.cmm.KS), tap);
     op.rt_wz = false;
     op.fast_name = "dw_mm_rt<" + std::to_string(s.KH) + "x" + std::to_string(s.KW) + ">";
@@ -520,7 +524,7 @@ bool route_dw_gemm(OpImpl &op, const ConvCtx &c) {
     const OpSpec &s = c.s;
     k::DwGemmArgs &f = op.dwg;
     if (!(dw_gemm_candidate(op, c) && s.C == s.N && s.C >= 2)) return false;
-    if (!k::dw_gemm_plan(f, s.H, s.W, s.C, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.pad == MF_PAD_SAME)) return false;
+    if (!k::dw_gemm_plan_pads(f, s.H, s.W, s.C, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, c.padt, c.padl)) return false;
     const bool wz = c.wz;
     const std::vector<int8_t> prep = wimage::build_dw_mm_rt_weights(s.weights, s.KH, s.KW, s.C, f.KS, f.P);
     op.d_wprep.upload(prep.data(), prep.size());
@@ -545,7 +549,7 @@ bool route_conv_mm(OpImpl &op, const ConvCtx &c) {
     if (!(rt_candidate(op, c) && !c.dw && !(s.KH == 1 && s.KW == 1 && k::conv1x1_rowwave_supported(op.conv)))) return false;
     const bool wz = c.wz;
     std::vector<int> tap;
-    if (!k::conv_mm_plan(op.cmm, tap, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.pad == MF_PAD_SAME, wz)) return false;
+    if (!k::conv_mm_plan_pads(op.cmm, tap, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, c.padt, c.padl, wz)) return false;
     const int Ktot = s.KH * s.KW * s.C;
     std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(s.weights, Ktot, s.N, 1, op.cmm.TB, op.cmm.NBLK); // [N][KH][KW][C] IS [N][K]
     if (wz) { // + a tile of ones over the real k-bytes
@@ -585,7 +589,7 @@ bool route_conv_gemm(OpImpl &op, const ConvCtx &c) {
             for (int t = 0; t < T; ++t) wt[(size_t)n * T + t] = s.weights[(size_t)t * s.N + n];
     }
     k::ConvGemmArgs &f = op.cgm;
-    if (!k::conv_gemm_plan(f, tap, mask, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.pad == MF_PAD_SAME, wz)) return false;
+    if (!k::conv_gemm_plan_pads(f, tap, mask, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, c.padt, c.padl, wz)) return false;
     const std::vector<int8_t> img = k::conv_gemm_weight_image(dw_c1 ? wt.data() : s.weights, f);
     op.d_fcw.upload(img.data(), img.size());
     op.d_tap.upload(tap.data(), tap.size() * sizeof(int));
@@ -791,7 +795,57 @@ void create_add(OpImpl &op, const OpSpec &s, int lo, int hi) {
     op.fast = OpImpl::ADD_C16, op.fast_name = op.add_fma ? "add_c16<fma>" : "add_c16"; // taken where all three pointers are 16-byte aligned
 }
 
+// PAD: no weights, no constants; the fill byte is the input zero point as the kernels see stored bytes (u8: the internal domain)
+void create_pad(OpImpl &op, const OpSpec &s) {
+    const int t = s.pads[0], b = s.pads[1], l = s.pads[2], r = s.pads[3];
+    if (s.H <= 0 || s.W <= 0 || s.C <= 0 || t < 0 || b < 0 || l < 0 || r < 0) fail(MF_ERR_INVALID_ARG, "pad: bad arguments");
+    const long long OH = (long long)s.H + t + b, OW = (long long)s.W + l + r;
+    if (OH != s.OH || OW != s.OW || OW * s.C > 0x7fffffffll || OH > 0x7fffffffll) fail(MF_ERR_INVALID_ARG, "pad: the output shape is not input + pads");
+    if (s.izp < (s.u8 ? 0 : -128) || s.izp > (s.u8 ? 255 : 127)) fail(MF_ERR_INVALID_ARG, "pad: the zero point is no value of T");
+    op.in_elems = (size_t)s.H * s.W * s.C;
+    op.out_elems = (size_t)OH * (size_t)OW * s.C;
+    k::PadArgs &a = op.padargs;
+    a.H = s.H, a.OH = (int)OH, a.top = t, a.in_row = s.W * s.C, a.out_row = (int)OW * s.C, a.lp = l * s.C;
+    a.fill4 = 0x01010101u * (uint32_t)(uint8_t)(s.u8 ? s.izp ^ 0x80 : s.izp);
+    op.generic_name = "pad_generic";
+    // whole words in every row segment: dwords with C % 4 == 0; 16 bytes where the image row and both fills are multiples of 16
+    if (s.C % 4 == 0) {
+        op.pad_unit = (a.in_row % 16 == 0 && a.lp % 16 == 0 && a.out_row % 16 == 0) ? 16 : 4;
+        op.fast = OpImpl::PAD_C4, op.fast_name = op.pad_unit == 16 ? "pad_c4<v16>" : "pad_c4";
+    }
+}
+
 } // namespace
+
+OpImpl *op_create_padded_conv(const OpImpl *conv, int Hin, int Win, int padt, int padl) {
+    const OpSpec &q = conv->s;
+    const bool dw = q.kind == MF_OP_DEPTHWISE_CONV_2D;
+    if ((q.kind != MF_OP_CONV_2D && !dw) || q.pad != MF_PAD_VALID || Hin <= 0 || Win <= 0 || padt < 0 || padl < 0 || Hin + padt > q.H ||
+        Win + padl > q.W || conv->h_w.empty())
+        return nullptr;
+    MF_HIP(hipSetDevice(conv->device));
+    std::unique_ptr<OpImpl> op(new OpImpl);
+    op->device = conv->device;
+    op->s = q;
+    op->s.H = Hin, op->s.W = Win;
+    op->s.weights = conv->h_w.data(); // (i8 domain, as uploaded: what the image builders read; cleared again below)
+    op->in_elems = (size_t)Hin * Win * q.C, op->out_elems = conv->out_elems;
+    op->h_A = conv->h_A, op->h_S = conv->h_S, op->h_Kc = conv->h_Kc, op->h_wzp = conv->h_wzp;
+    op->finite_consts = conv->finite_consts, op->magic_mode = conv->magic_mode;
+    op->conv = conv->conv; // the borrowed device arrays (w, wzp, A, S, Kc), the clamp, the input zero point
+    op->conv.H = Hin, op->conv.W = Win;
+    op->generic_name = "(none)";
+    ConvCtx c{op->s, dw, op->h_A, op->h_S, op->h_Kc, op->h_wzp};
+    c.lo = (int)conv->conv.lo_f, c.hi = (int)conv->conv.hi_f, c.xr = conv->conv.xr;
+    c.magic = conv->magic_mode, c.finite = conv->finite_consts;
+    c.wz = !all_zero(c.wzp), c.zero_wzp = !c.wz && c.finite;
+    c.padt = padt, c.padl = padl, c.rows_bytes_any_c = true;
+    // the run-time-geometry routes that take a window placement, in create_conv's order; the two-rounding epilogue (no single-fma form)
+    for (Route r : {route_conv_rows, route_dw_mm, route_dw_gemm, route_conv_mm, route_conv_gemm}) r(*op, c);
+    op->s.weights = nullptr, op->s.wzp = nullptr, op->s.c0 = op->s.c1 = nullptr, op->s.c2 = nullptr;
+    if (op->fast == OpImpl::NONE) return nullptr;
+    return op.release();
+}
 
 OpImpl *op_create(int device, const OpSpec &spec) {
     dev_require(device);
@@ -811,6 +865,7 @@ OpImpl *op_create(int device, const OpSpec &spec) {
     case MF_OP_FULLY_CONNECTED: create_fc(*op, s, dom, lo, hi, xr); break;
     case MF_OP_SOFTMAX: create_softmax(*op, s, xr); break;
     case MF_OP_ADD: create_add(*op, s, lo, hi); break;
+    case MF_OP_PAD: create_pad(*op, s); break;
     default: fail(MF_ERR_UNSUPPORTED, "unsupported operator kind " + std::to_string(s.kind));
     }
     op->s = s;
@@ -894,6 +949,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             break;
         case OpImpl::MAXPOOL_C4:
             k::launch_maxpool_c4(d_in, d_out, op->pool, batch, s);
+            done = true;
+            break;
+        case OpImpl::PAD_C4:
+            k::launch_pad_c4(d_in, d_out, op->padargs, batch, op->pad_unit, s);
             done = true;
             break;
         case OpImpl::DW_C1:
@@ -1001,6 +1060,7 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
         case MF_OP_MAX_POOL_2D: k::launch_maxpool_generic(d_in, d_out, op->pool, batch, s); break;
         case MF_OP_FULLY_CONNECTED: k::launch_fc_generic(d_in, d_out, op->fc, batch * sp.M, s); break;
         case MF_OP_SOFTMAX: k::launch_softmax(d_in, d_out, op->sm, batch, s); break;
+        case MF_OP_PAD: k::launch_pad_generic(d_in, d_out, op->padargs, batch, s); break;
         default: fail(MF_ERR_UNSUPPORTED, "op_run: bad kind");
         }
     }

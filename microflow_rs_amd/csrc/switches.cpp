@@ -73,6 +73,7 @@ Switches switches_parse() {
     s.no_pair_band = env_set("MF_NO_PAIR_BAND");
     s.no_expand_block = env_set("MF_NO_EXPAND_BLOCK");
     s.no_conv_pool = env_set("MF_NO_CONV_POOL");
+    s.no_pad_conv = env_set("MF_NO_PAD_CONV");
     s.conv_pool_all = env_set("MF_CONV_POOL_ALL");
     s.no_pair_wz = env_set("MF_NO_PAIR_WZ");
     s.no_shortcut_add = env_set("MF_NO_SHORTCUT_ADD");

@@ -76,7 +76,8 @@ Vec vec(const Table &t, int id) {
     return {t.b, f + t.b->at<uint32_t>(f)};
 }
 
-enum { TT_INT32 = 2, TT_UINT8 = 3, TT_INT8 = 9 };
+enum { TT_INT32 = 2, TT_UINT8 = 3, TT_INT64 = 4, TT_INT8 = 9 };
+enum { BUILTIN_PADV2 = 60, BUILTIN_MIRROR_PAD = 100 }; // the neighbours of PAD, refused by name
 
 struct TensorInfo {
     std::vector<int> shape;
@@ -497,6 +498,87 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             last_add = (int)oi;
             break;
         }
+        case MF_OP_PAD: { // not in the reference (lib.rs:148 answers "unsupported operator: 34"): the contract is include/microflow_amd.h's
+            auto refuse = [](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: 34 (PAD: " + why + ")"); };
+            if (ins.size() != 2) refuse("it needs an input and a paddings operand");
+            for (const TensorInfo *t : {&in, &out}) {
+                if ((t->type != TT_INT8 && t->type != TT_UINT8) || (t->type == TT_UINT8) != pm.u8) refuse("mixed element types");
+                need_quant(*t, "PAD");
+                if (t->scale.size() != 1 || t->zp.size() != 1) refuse("per-channel quantisation on an operand");
+            }
+            if (in.data_len) refuse("a constant operand");
+            if (in.shape.size() != 4 || out.shape.size() != 4) refuse("tensor rank must be 4");
+            if (in.shape[0] != 1) refuse("tensor batch must be 1");
+            const TensorInfo pd = read_tensor(tensors, buffers, ins.get<int32_t>(1));
+            if (!pd.data_len) refuse("the paddings operand is not constant");
+            if (pd.type != TT_INT32 && pd.type != TT_INT64) refuse("the paddings operand must be INT32 or INT64");
+            if (pd.shape != std::vector<int>{4, 2}) refuse("the paddings operand must have shape [4, 2]");
+            const size_t esz = pd.type == TT_INT64 ? 8 : 4;
+            if (pd.data_len < 8 * esz) fail(MF_ERR_INVALID_MODEL, "invalid model: short PAD paddings buffer");
+            int64_t pv[8];
+            for (int k = 0; k < 8; ++k) {
+                if (esz == 8) {
+                    std::memcpy(&pv[k], pd.data + 8 * k, 8);
+                } else {
+                    int32_t v;
+                    std::memcpy(&v, pd.data + 4 * k, 4);
+                    pv[k] = v;
+                }
+                if (pv[k] < 0) fail(MF_ERR_INVALID_MODEL, "invalid model: PAD with a negative pad");
+                if (pv[k] > (1 << 24)) fail(MF_ERR_INVALID_MODEL, "invalid model: bad tensor dimension");
+            }
+            if (pv[0] || pv[1] || pv[6] || pv[7]) refuse("a batch or channel pad");
+            if (std::memcmp(&in.scale[0], &out.scale[0], sizeof(float)) != 0 || zp_of(in.zp[0], pm.u8) != zp_of(out.zp[0], pm.u8))
+                refuse("input and output quantisation differ");
+            for (int d = 0; d < 4; ++d)
+                if ((int64_t)out.shape[(size_t)d] != (int64_t)in.shape[(size_t)d] + pv[2 * d] + pv[2 * d + 1])
+                    fail(MF_ERR_INVALID_MODEL, "invalid model: PAD output shape is not input + pads");
+            set_shapes(po, in, out, pm.u8);
+            po.H = in.shape[1], po.W = in.shape[2], po.C = in.shape[3], po.N = po.C;
+            po.OH = out.shape[1], po.OW = out.shape[2];
+            for (int k = 0; k < 4; ++k) po.pads[k] = (int)pv[2 + k]; // top, bottom, left, right
+            break;
+        }
+        case MF_OP_MEAN: { // not in the reference: over axes {1, 2} it is the reference's average_pool_2d over the whole image
+            // (include/microflow_amd.h), and is parsed into that operator: every rule that matches a global AveragePool2D sees one
+            auto refuse = [](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: 40 (MEAN: " + why + ")"); };
+            if (ins.size() != 2) refuse("it needs an input and an axes operand");
+            require_elem(in, "MEAN", pm.u8), require_elem(out, "MEAN", pm.u8);
+            need_quant(in, "MEAN"), need_quant(out, "MEAN");
+            if (in.shape.size() != 4) refuse("tensor rank must be 4");
+            if (in.shape[0] != 1) refuse("tensor batch must be 1");
+            const TensorInfo ax = read_tensor(tensors, buffers, ins.get<int32_t>(1));
+            if (!ax.data_len) refuse("the axes operand is not constant");
+            if (ax.type != TT_INT32) refuse("the axes operand must be INT32");
+            const size_t na = ax.elems();
+            if (!na || ax.data_len < na * 4) fail(MF_ERR_INVALID_MODEL, "invalid model: short MEAN axes buffer");
+            unsigned named = 0;
+            for (size_t k = 0; k < na; ++k) {
+                int32_t a;
+                std::memcpy(&a, ax.data + 4 * k, 4);
+                if (a < 0) a += 4;
+                if (a != 1 && a != 2) refuse("axes other than {1, 2}");
+                named |= 1u << a;
+            }
+            if (named != 6u) refuse("axes other than {1, 2}");
+            const bool keep = opt.scalar<uint8_t>(0, 0) != 0; // ReducerOptions { keep_dims:0 }
+            const int C = in.shape[3];
+            if (out.shape != (keep ? std::vector<int>{1, 1, 1, C} : std::vector<int>{1, C}))
+                fail(MF_ERR_INVALID_MODEL, "invalid model: MEAN output shape does not follow from the axes and keep_dims");
+            set_shapes(po, in, out, pm.u8);
+            po.kind = MF_OP_AVERAGE_POOL_2D, po.file_kind = MF_OP_MEAN;
+            po.H = in.shape[1], po.W = in.shape[2], po.C = C, po.N = C;
+            po.KH = po.H, po.KW = po.W, po.sh = po.sw = 1, po.pad = MF_PAD_VALID, po.act = MF_ACT_NONE;
+            po.OH = po.OW = 1;
+            po.c0.resize(1), po.c1.resize(1);
+            h_preprocess_pool(in.scale[0], zp_of(in.zp[0], pm.u8), out.scale[0], zp_of(out.zp[0], pm.u8), po.c0.data(),
+                              po.c1.data());
+            break;
+        }
+        case BUILTIN_PADV2:
+            fail(MF_ERR_UNSUPPORTED, "unsupported operator: 60 (PADV2: only PAD, whose fill is the tensor's zero point, is supported)");
+        case BUILTIN_MIRROR_PAD:
+            fail(MF_ERR_UNSUPPORTED, "unsupported operator: 100 (MIRROR_PAD: reflect / symmetric padding is not supported)");
         default:
             fail(MF_ERR_UNSUPPORTED, "unsupported operator: " + std::to_string(code)); // lib.rs:148
         }

@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 
 OP_NAMES = {0: "add", 1: "average_pool_2d", 3: "conv_2d", 4: "depthwise_conv_2d", 9: "fully_connected", 17: "max_pool_2d",
-            22: "reshape", 25: "softmax"}
+            22: "reshape", 25: "softmax", 34: "pad", 40: "mean"}
 
 
 class Model:
@@ -69,6 +69,12 @@ class Model:
         src, pos = C.c_int(0), C.c_int(0)
         _lib.check(_lib.lib().mf_model_get_op_skip(self._h, int(i), C.byref(src), C.byref(pos)))
         return src.value, pos.value
+
+    def op_pads(self, i):
+        """((top, bottom), (left, right)) of PAD i: the new rows and columns.  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
+        p = (C.c_int * 4)()
+        _lib.check(_lib.lib().mf_model_get_op_pads(self._h, int(i), p))
+        return (p[0], p[1]), (p[2], p[3])
 
     def op_source(self, i):
         """the operator whose output side operator i (the Conv2D on a skip edge) reads instead of the running value; -1: the model

@@ -7,6 +7,7 @@ names, argument order and meaning, executed by the HIP kernels behind the C ABI.
     average_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)
     max_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)   (not in the reference)
     add(a, b, output_scale, output_zero_point, options, constants)                                        (not in the reference)
+    pad(input, pads)                                                                                      (not in the reference)
     softmax(input, output_scale, output_zero_point)
     reshape(input, output_shape)
 
@@ -320,6 +321,24 @@ def add(a, b, output_scale, output_zero_point, options: AddOptions, constants=No
     op = prepare_add(tail, (a.scale[0], a.zero_point[0]), (b.scale[0], b.zero_point[0]),
                      (output_scale[0], output_zero_point[0]), options, constants, dtype=_elem(a.buffer))
     return type(a)(op(a.buffer, b.buffer), list(output_scale), list(output_zero_point))
+
+
+def prepare_pad(in_hwc, pads, zero_point, dtype=np.int8):
+    """pads: ((top, bottom), (left, right)) new rows / columns around the H x W x C image, each new element zero_point."""
+    H, W, Cc = (int(d) for d in in_hwc)
+    (t, b), (l, r) = ((int(v) for v in p) for p in pads)
+    h = C.c_void_p()
+    _lib.check(_fn("mf_pad_create", dtype)(_device(), H, W, Cc, t, b, l, r, int(zero_point), C.byref(h)))
+    return PreparedOp(h, (H, W, Cc), (H + t + b, W + l + r, Cc), dtype)
+
+
+def pad(input: Tensor4D, pads) -> Tensor4D:
+    """PAD (TFLite builtin 34; the reference has none) in H and W: the tensor with new rows and columns of its own zero point around
+    every image; scale and zero point stay (include/microflow_amd.h).  MEAN over H and W needs no function of its own: it is
+    average_pool_2d with the whole image as filter."""
+    shp = tuple(input.buffer.shape)
+    op = prepare_pad(shp[-3:], pads, input.zero_point[0], dtype=_elem(input.buffer))
+    return Tensor4D(op(input.buffer), list(input.scale), list(input.zero_point))
 
 
 def prepare_softmax(rows, cols, input_scale, output_scale, output_zero_point, dtype=np.int8):

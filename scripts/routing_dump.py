@@ -47,9 +47,18 @@ def corpus():
     return c
 
 
+def corpus_all():
+    """corpus() -- whose names and bytes tests/golden/writer_blobs.json pins -- and behind it the models of operators added since: new
+    entries at the end only, so that an older tree's dump is a prefix of this one's"""
+    import tflite_writer as tw
+    rng = np.random.default_rng
+    return corpus() + [("keras_mobilenet_v2-96-w0.25", lambda: tw.keras_mobilenet_v2(rng(40), 96, 0.25)),   # PAD, MEAN (DESIGN 4.22)
+                       ("keras_resnet_stem-64", lambda: tw.keras_resnet_stem(rng(41), 64))]
+
+
 def one(idx):
     import microflow_rs_amd as mf
-    name, make = corpus()[idx]
+    name, make = corpus_all()[idx]
     m = mf.Model(make(), autotune=False)
     m.prepare(64)
     print("# " + name)
@@ -65,7 +74,7 @@ def main():
     if a.only >= 0:
         return one(a.only)
     lines = []
-    for idx in range(len(corpus())):
+    for idx in range(len(corpus_all())):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--only", str(idx)], timeout=STEP_TIMEOUT, stdout=subprocess.PIPE, text=True)
         except subprocess.TimeoutExpired:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Writes small .tflite models made of the six operators MicroFlow supports
-(microflow-macros/src/lib.rs:138-148), MaxPool2D and ADD (identity and projection shortcuts), for randomized model-level tests: parser + constant
+(microflow-macros/src/lib.rs:138-148), MaxPool2D, ADD (identity and projection shortcuts), PAD and MEAN, for randomized model-level tests: parser + constant
 preparation + kernel routing + run, product vs oracle.  Only the fields the MicroFlow front
 end reads are written (tflite.fbs field ids as used by microflow-macros/src/ops/*.rs).
 
@@ -22,6 +22,10 @@ Each layer dict (all quantization parameters are given, nothing is derived):
                       "cur", a layer index (-1: the model input) or dict(shape, q, type=, data=) for a fresh tensor
     reshape           out_shape
     softmax           out_shape, out_q
+    pad               pads ((top, bottom), (left, right)), out_shape, out_q (the input's, for a model that loads).  Negative tests:
+                      paddings (the whole [4, 2] operand, any shape), pad_type (INT32 | INT64), pad_const=False (the operand has no
+                      buffer), code ("padv2" | "mirror_pad": the same operator under another builtin code)
+    mean              keep_dims (out_shape (1,1,1,C) or (1,C)), out_shape, out_q; axes (default (1, 2)), axes_const=False, axes_type
 """
 import struct
 
@@ -29,12 +33,12 @@ import numpy as np
 
 from make_fc_model import FB, Table, TableVec, Vec, emit, prune_2_4
 
-INT32, UINT8, INT8 = 2, 3, 9
+INT32, UINT8, INT64, INT8 = 2, 3, 4, 9
 OPCODES = {"add": 0, "average_pool_2d": 1, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "max_pool_2d": 17, "reshape": 22,
-           "softmax": 25}
+           "softmax": 25, "pad": 34, "mean": 40, "padv2": 60, "mirror_pad": 100}
 # BuiltinOptions union type ids (tflite.fbs)
 OPT_TYPE = {"add": 11, "conv_2d": 1, "depthwise_conv_2d": 2, "average_pool_2d": 5, "max_pool_2d": 5, "fully_connected": 8, "softmax": 9,
-            "reshape": 17}
+            "reshape": 17, "pad": 22, "mean": 27, "padv2": 43, "mirror_pad": 77}
 ACT = {None: 0, "none": 0, "relu": 1, "relu6": 3, 0: 0, 1: 1, 3: 3}
 PAD = {"same": 0, "valid": 1, 0: 0, 1: 1}
 
@@ -70,11 +74,12 @@ def build_model(input_shape, input_q, layers, elem=INT8):
     wdt = np.uint8 if elem == UINT8 else np.int8
     for L in layers:
         op = L["op"]
+        code = L.get("code", op)  # (negative tests: the layer written under another builtin code)
         if "detach_input" in L:  # negative tests: this operator reads a fresh tensor instead of the running one
             cur = add_tensor(L["detach_input"], elem, 0, input_q[0], input_q[1])
-        if op not in used_ops:
-            used_ops.append(op)
-        oc = used_ops.index(op)
+        if code not in used_ops:
+            used_ops.append(code)
+        oc = used_ops.index(code)
         if op in ("conv_2d", "depthwise_conv_2d"):
             w = np.asarray(L["filters" if op == "conv_2d" else "weights"], wdt)
             tw = add_tensor(w.shape, elem, add_buffer(w), L["fscale"], L["fzp"])
@@ -125,11 +130,25 @@ def build_model(input_shape, input_q, layers, elem=INT8):
                 ins = [place(L["skip"]), cur] if L.get("swap") else [cur, place(L["skip"])]
             out = add_tensor(L["out_shape"], L.get("out_type", elem), 0, *L["out_q"])
             opts = Table({0: ("i8", ACT[L.get("act")])})  # AddOptions { fused_activation_function:0 }
+        elif op == "pad":
+            pv = np.asarray(L["paddings"] if "paddings" in L else ((0, 0),) + tuple(tuple(p) for p in L["pads"]) + ((0, 0),))
+            ptype = L.get("pad_type", INT32)
+            pbuf = add_buffer(pv.astype(np.int64 if ptype == INT64 else np.int32)) if L.get("pad_const", True) else 0
+            tp = add_tensor(pv.shape, ptype, pbuf, 1.0, 0)
+            out = add_tensor(L["out_shape"], L.get("out_type", elem), 0, *L["out_q"])
+            opts = Table({})  # PadOptions {}
+            ins = [cur, tp]
+        elif op == "mean":
+            ax = np.asarray(L.get("axes", (1, 2)), np.int32)
+            ta = add_tensor(ax.shape, L.get("axes_type", INT32), add_buffer(ax) if L.get("axes_const", True) else 0, 1.0, 0)
+            out = add_tensor(L["out_shape"], elem, 0, *L["out_q"])
+            opts = Table({0: ("u8", int(bool(L.get("keep_dims", False))))})  # ReducerOptions { keep_dims:0 }
+            ins = [cur, ta]
         else:
             raise ValueError(op)
         # Operator { opcode_index:0 inputs:1 outputs:2 builtin_options_type:3 builtin_options:4 }
         operators.append(Table({0: ("u32", oc), 1: ("ref", Vec("<i", ins)), 2: ("ref", Vec("<i", [out])),
-                                3: ("u8", OPT_TYPE[op]), 4: ("ref", opts)}))
+                                3: ("u8", OPT_TYPE[code]), 4: ("ref", opts)}))
         if "side_of" not in L:
             cur = out
         outs.append(out)
@@ -898,4 +917,98 @@ def stack_layers(rng, input_shape, segments, elem=INT8, wzp="none", act_scale=No
 def stack(rng, input_shape, segments, elem=INT8, wzp="none", act_scale=None):
     """stack_layers' model as a flatbuffer"""
     in_shape, in_q, layers = stack_layers(rng, input_shape, segments, elem, wzp, act_scale)
+    return build_model(in_shape, in_q, layers, elem)
+
+
+def _pad_layer(shape, q, pads):
+    """one PAD layer dict on a tensor shape = (H, W, C) of quantisation q (which its output keeps); pads ((top, bottom), (left, right))"""
+    H, W, C = (int(v) for v in shape)
+    (t, b), (l, r) = pads
+    return dict(op="pad", pads=((int(t), int(b)), (int(l), int(r))), out_shape=(1, H + t + b, W + l + r, C), out_q=q)
+
+
+def keras_pad_for(size, k, stride):
+    """the ZeroPadding2D Keras' MobileNets write in front of a stride-2 k x k VALID convolution (correct_pad): (k // 2 - 1, k // 2) on
+    an even side, (k // 2, k // 2) on an odd one"""
+    return (k // 2 - (1 - size % 2), k // 2)
+
+
+def keras_mobilenet_v2_layers(rng, side=32, width=0.25, elem=INT8, classes=10, blocks=None, keep_dims=False, wzp="none", last=None):
+    """MobileNet-v2 as the TFLite converter writes it from Keras: the 3x3 stride-2 stem and every stride-2 depthwise as
+    ZeroPadding2D (PAD) + a VALID convolution, stride-1 depthwise SAME, an ADD behind every stride-1 block that keeps its channel
+    count, a 1x1 Conv2D, GlobalAveragePooling2D as MEAN over {1, 2}, FullyConnected and Softmax.  blocks = [(t, c, n, s), ...] as in
+    the paper (expansion, channels at width 1, repeats, first stride); the default is the paper's, cut where the image reaches one
+    pixel.  Channels are c * width rounded to a multiple of 8 (at least 8); last: the channels of the 1x1 in front of the pool (the
+    paper's 1280, which widths below 1 keep).  -> build_model's arguments"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    mid = (lo + hi) // 2
+    if blocks is None:
+        blocks = [(1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)]
+
+    def ch(c):
+        return max(8, int(c * width + 4) // 8 * 8)
+
+    H = W = int(side)
+    C = 3
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers = in_q, []
+
+    def conv(dw, n, k, s, act):
+        nonlocal q, H, W, C
+        if s == 2:  # Keras: ZeroPadding2D + VALID
+            pt, pl = keras_pad_for(H, k, s), keras_pad_for(W, k, s)
+            layers.append(_pad_layer((H, W, C), q, (pt, pl)))
+            H, W = H + sum(pt), W + sum(pl)
+        d = _conv_layer(rng, (H, W, C), q, dw, n, k, s, "valid" if s == 2 else "same", act, elem, wzp)
+        layers.append(d)
+        q, (_, H, W, C) = d["out_q"], d["out_shape"]
+
+    conv(False, ch(32), 3, 2, "relu6")
+    for t, c, n, s in blocks:
+        for r in range(n):
+            stride = s if r == 0 else 1
+            if stride == 2 and min(H, W) < 2:
+                stride = 1
+            skip, q_skip, c_in = len(layers) - 1, q, C
+            if t != 1:
+                conv(False, c_in * t, 1, 1, "relu6")
+            conv(True, C, 3, stride, "relu6")
+            conv(False, ch(c), 1, 1, "none")
+            if stride == 1 and C == c_in:
+                layers.append(_add_layer(rng, skip, (1, H, W, C), q, q_skip, "none", elem))
+                q = layers[-1]["out_q"]
+    conv(False, int(last) if last else (ch(1280) if width > 1.0 else 1280), 1, 1, "relu6")
+    layers.append(dict(op="mean", keep_dims=bool(keep_dims), out_shape=(1, 1, 1, C) if keep_dims else (1, C), out_q=q))
+    if keep_dims:
+        layers.append(dict(op="reshape", out_shape=(1, C), out_q=q))
+    layers.append(_fc_layer(rng, C, int(classes), q, "none", elem))
+    layers.append(dict(op="softmax", out_shape=(1, int(classes)), out_q=(1.0 / 256.0, lo)))
+    return (1, int(side), int(side), 3), in_q, layers
+
+
+def keras_mobilenet_v2(rng, side=32, width=0.25, elem=INT8, **kw):
+    """keras_mobilenet_v2_layers' model as a flatbuffer"""
+    in_shape, in_q, layers = keras_mobilenet_v2_layers(rng, side, width, elem, **kw)
+    return build_model(in_shape, in_q, layers, elem)
+
+
+def keras_resnet_stem_layers(rng, side=32, elem=INT8, filters=64):
+    """The stem of Keras' ResNets: ZeroPadding2D(3) + Conv2D 7x7 stride 2 VALID (relu) + ZeroPadding2D(1) + MaxPool2D 3x3 stride 2
+    VALID, on a side x side x 3 image.  -> build_model's arguments"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    H = W = int(side)
+    layers = [_pad_layer((H, W, 3), in_q, ((3, 3), (3, 3)))]
+    d = _conv_layer(rng, (H + 6, W + 6, 3), in_q, False, int(filters), 7, 2, "valid", "relu", elem)
+    layers.append(d)
+    q, (_, H, W, C) = d["out_q"], d["out_shape"]
+    layers.append(_pad_layer((H, W, C), q, ((1, 1), (1, 1))))
+    oh, ow = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+    layers.append(dict(op="max_pool_2d", filter=(3, 3), padding="valid", strides=(2, 2), act="none", out_shape=(1, oh, ow, C), out_q=q))
+    return (1, int(side), int(side), 3), in_q, layers
+
+
+def keras_resnet_stem(rng, side=32, elem=INT8, **kw):
+    """keras_resnet_stem_layers' model as a flatbuffer"""
+    in_shape, in_q, layers = keras_resnet_stem_layers(rng, side, elem, **kw)
     return build_model(in_shape, in_q, layers, elem)
