@@ -6,8 +6,12 @@
 //       stages a whole batch, step by step, through rows_bytes_elem / rows_bytes_src / rows_bytes_keep / rows_bytes_merge into a host
 //       copy of the tiles, exactly as k_conv_rows_body.inc does (512 threads x 16 elements, the element registers kept from step to
 //       step, aligned dword loads only), and compares the tiles byte for byte with what they must hold
-//       ->  "ok G steps shifts"   (shifts: bit s set = byte shift s occurred on a dword that exists)
+//       ->  "ok G steps shifts bases"   (shifts: bit s set = byte shift s occurred on a dword that exists; bases: bit s set = a step
+//       started at a byte with (address & 3) == s)
 //       exit 1 and a line on stderr at the first difference, at a sentinel byte in a tile, or at a load wholly outside the batch
+//   conv_rows_bytes_plan stage_pads H W C N KH KW sh sw padt padl OH OW batch
+//       the same with any channel count and an explicit window placement: the plan of k::conv_rows_plan_pads(..., bytes_any_c = true),
+//       what the PAD + convolution group asks for (rows W C bytes long, the image at tile row shy, tile byte XO)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,7 +28,20 @@ static bool make_plan(ConvRowsArgs &r, int H, int W, int C, int N, int KH, int K
 
 static uint32_t alignbyte(uint32_t hi, uint32_t lo, uint32_t sh) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * sh)); } // v_alignbyte_b32
 
+static int stage(ConvRowsArgs p, int batch);
+
 int main(int argc, char **argv) {
+    if (argc == 15 && !strcmp(argv[1], "stage_pads")) {
+        int a[13];
+        for (int i = 0; i < 13; ++i) a[i] = atoi(argv[2 + i]);
+        ConvRowsArgs p{};
+        if (a[6] < 1 || a[7] < 1 || a[12] < 1 || !conv_rows_plan_pads(p, a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[10], a[11], a[8], a[9], true) ||
+            !p.BYTES()) {
+            fprintf(stderr, "no BYTES plan\n");
+            return 1;
+        }
+        return stage(p, a[12]);
+    }
     if (argc == 11 && !strcmp(argv[1], "plan")) {
         int a[9];
         for (int i = 0; i < 9; ++i) a[i] = atoi(argv[2 + i]);
@@ -46,10 +63,15 @@ int main(int argc, char **argv) {
         fprintf(stderr, "no BYTES plan\n");
         return 1;
     }
+    return stage(p, batch);
+}
+
+static int stage(ConvRowsArgs p, int batch) {
+    const int H = p.H, W = p.W, ROWB = p.ROWB;
     constexpr int NTHR = 512, MAXE = 16, GUARD = 16;
     constexpr uint8_t SENT = 0x5a, IZP = 0xc3;           // neither is an image byte below
     p.izp4 = 0x01010101u * IZP;
-    const long total = (long)batch * H * W;
+    const long total = (long)batch * H * ROWB;
     // [GUARD sentinel bytes][the batch, 16-byte aligned][GUARD sentinel bytes]
     std::vector<uint8_t> store((size_t)total + 2 * GUARD + 16, SENT);
     uint8_t *in = store.data();
@@ -72,12 +94,13 @@ int main(int argc, char **argv) {
     std::vector<uint8_t> tile((size_t)G * p.TILE, IZP), want;
     std::vector<uint32_t> el((size_t)NTHR * MAXE), lo(el.size()), hi(el.size());
     for (size_t i = 0; i < el.size(); ++i) el[i] = rows_bytes_elem(p, (int)i);   // slot tid + NTHR * e
-    unsigned shifts = 0;
+    unsigned shifts = 0, bases = 0;
     for (int st = 0; st < nsteps; ++st) {
         // fetch(st)
         const size_t sb = (size_t)st * G * IMGB;
         const long src = (long)(sb >> 2);
         const uint32_t low2 = (uint32_t)sb & 3u;
+        bases |= 1u << low2;
         const int lim = (G < batch - st * G ? G : batch - st * G) * IMGB;
         for (size_t i = 0; i < el.size(); ++i) {
             const RowsBytesSrc m = rows_bytes_src(el[i], low2, p.ROWB);
@@ -103,7 +126,7 @@ int main(int argc, char **argv) {
         want.assign(tile.size(), IZP);
         for (int g = 0; g < G && st * G + g < batch; ++g)
             for (int y = 0; y < H; ++y)
-                memcpy(want.data() + (size_t)g * p.TILE + (size_t)(y + p.shy) * p.TWP + p.XO, in + ((size_t)(st * G + g) * H + y) * W, (size_t)W);
+                memcpy(want.data() + (size_t)g * p.TILE + (size_t)(y + p.shy) * p.TWP + p.XO, in + ((size_t)(st * G + g) * H + y) * ROWB, (size_t)ROWB);
         for (size_t i = 0; i < tile.size(); ++i) {
             if (tile[i] == SENT) {
                 fprintf(stderr, "step %d: sentinel at tile byte %zu\n", st, i);
@@ -119,6 +142,6 @@ int main(int argc, char **argv) {
         fprintf(stderr, "%ld loads of a dword wholly outside the batch\n", outside);
         return 1;
     }
-    printf("ok %d %d %u\n", G, nsteps, shifts);
+    printf("ok %d %d %u %u\n", G, nsteps, shifts, bases);
     return 0;
 }

@@ -72,7 +72,7 @@ int main(int argc, char **argv) {
         ConvMmArgs a = zeroed<ConvMmArgs>();
         std::vector<int> t;
         if (conv_mm_plan_pads(a, t, H, W, C, N, KH, KW, S, S, OH, OW, pt, pl, wz, dw))
-            printf("conv_mm padt=%d padl=%d LP=%d ROW=%d RB=%d TILE=%d G=%d BH=%d NBANDS=%d\n", a.padt, a.padl, a.LP, a.ROW, a.RB, a.TILE, a.G, a.BH, a.NBANDS);
+            printf("conv_mm padt=%d padl=%d LP=%d ROW=%d RB=%d TILE=%d G=%d BH=%d NBANDS=%d NTHR=%d\n", a.padt, a.padl, a.LP, a.ROW, a.RB, a.TILE, a.G, a.BH, a.NBANDS, a.NTHR);
         else printf("conv_mm none\n");
     }
     {

@@ -136,6 +136,44 @@ def test_staging_map_under_address_and_ub_sanitizers(exe_sanitized, name):
     _stage(exe_sanitized, name)
 
 
+# ---- three channels behind a PAD: conv_rows_plan_pads(..., bytes_any_c = true), what the PAD + convolution group routes here ----------
+# (tests/pad_cases.py; the batch staged: whole steps and a ragged last one).  RGB rows that are not whole dwords put image bases -- 75
+# and 243 bytes -- and with G = 7 images of 4185 bytes step bases too at every byte shift: the map's low2, its two-dword fetch and the
+# alignbyte at shifts 1, 2, 3, which one-channel images of the same sizes reach only through W.
+PADDED_C3 = {"conv3s2_5x5x3": 21, "conv3s2_45x31x3": 23, "conv3s1_9x9x3_p4": 13}
+
+
+def _stage_pads(exe, name):
+    from tests import pad_cases as P
+    dw, H, W, C, K, S, (t, b, l, r), N, wz = P.SMALL[name]
+    OH, OW = P.out_hw(P.SMALL[name])
+    batch = PADDED_C3[name]
+    assert not dw and C == 3 and (W * C) % 4 != 0 and (H * W * C) % 4 != 0
+    res = subprocess.run([exe, "stage_pads"] + [str(int(v)) for v in (H, W, C, N, K, K, S, S, t, l, OH, OW, batch)], capture_output=True, text=True,
+                         timeout=120, env=_env())
+    assert res.returncode == 0, (name, res.stdout[-500:], res.stderr[-3000:])
+    f = res.stdout.split()
+    assert f[0] == "ok", res.stdout
+    G, steps, shifts, bases = (int(v) for v in f[1:5])
+    assert G == P.PINNED[name][1]["G"] and steps == -(-batch // G) and steps >= 2 and batch % G != 0
+    assert shifts == 15, (name, shifts)                                        # all four byte shifts occurred
+    if name == "conv3s2_45x31x3":
+        assert bases == 15, bases                                              # ... and a step started at each of them
+    return G
+
+
+@pytest.mark.parametrize("name", sorted(PADDED_C3))
+def test_staging_map_with_three_channels_and_explicit_pads(exe, name):
+    """the claim conv_rows_plan_pads makes for bytes_any_c -- the staging is written in row bytes and has no C = 1 assumption -- byte
+    for byte, with the image at the tile row and column the PAD's top and left put it"""
+    _stage_pads(exe, name)
+
+
+@pytest.mark.parametrize("name", sorted(PADDED_C3))
+def test_three_channel_staging_under_address_and_ub_sanitizers(exe_sanitized, name):
+    _stage_pads(exe_sanitized, name)
+
+
 # ---- the listing ---------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def listing():

@@ -35,7 +35,7 @@ def run(exe, *args):
     return r.stdout
 
 
-ALL = dict(P.CASES, **P.REFUSED)
+ALL = dict(P.EVERY, **P.REFUSED)   # (the banded, small and many-step geometries of tests/test_gpu_pad_conv_steps.py included)
 
 
 @pytest.mark.parametrize("name", list(ALL))
@@ -88,3 +88,64 @@ def test_the_tile_covers_every_window_of_the_padded_geometry(exe, name):
                 assert p["BH"] == OH and p["RB"] >= last_row
             else:
                 assert p["BH"] * p["NBANDS"] >= OH and p["RB"] >= (p["BH"] - 1) * S + K and p["G"] == 1
+
+
+def _plans(exe, case):
+    dw, H, W, C, K, S, (t, b, l, r), N, wz = case
+    OH, OW = P.out_hw(case)
+    return dict(_fields(line) for line in run(exe, "pads", dw, H, W, C, N, K, K, S, wz, t, l, OH, OW).splitlines())
+
+
+def _routed(plans, dw):
+    """the planner op_create_padded_conv's route order ends at: conv_rows, dw_mm (conv_mm_plan_pads in its depthwise mode: the conv_mm
+    line of a depthwise), dw_gemm, conv_mm, conv_gemm"""
+    for planner in ("conv_rows", "conv_mm", "dw_gemm", "conv_gemm"):
+        if plans[planner] is not None:
+            return ("dw_mm" if dw and planner == "conv_mm" else planner), plans[planner]
+    return None, None
+
+
+def test_every_pinned_case_is_a_case():
+    assert set(P.PINNED) == set(P.BANDED) | set(P.SMALL) | set(P.MANY_STEPS)
+    assert set(P.MANY_STEPS) <= set(P.EVERY) and set(P.SMALL_BATCH) <= set(P.SMALL) and set(P.BYTE_FORM) <= set(P.SMALL)
+
+
+@pytest.mark.parametrize("name", list(P.PINNED))
+def test_the_plans_the_gpu_tests_rest_on(exe, name):
+    """what tests/test_gpu_pad_conv_steps.py takes for granted about the planner the group routes to: the bands and their height, a
+    ragged last band, the images per step, conv_mm_rt's 1024-thread form, image and step bases off the dword boundary"""
+    case = P.EVERY[name]
+    dw, H, W, C, K, S, pads, N, wz = case
+    OH, OW = P.out_hw(case)
+    planner, want, ragged = P.PINNED[name]
+    got_planner, p = _routed(_plans(exe, case), dw)
+    assert got_planner == planner, (name, got_planner)
+    assert {k: p[k] for k in want} == want, (name, p)
+    if name in P.BANDED:
+        assert p["NBANDS"] >= 2 and p["G"] == 1, p
+        assert (OH % p["BH"] != 0) == ragged and (p["NBANDS"] - 1) * p["BH"] < OH <= p["NBANDS"] * p["BH"], (OH, p)
+    else:
+        assert planner == "conv_rows" or p["NBANDS"] == 1, p
+    G = p["G"]
+    batch = P.SMALL_BATCH.get(name, 4 if name in P.BANDED else 5)
+    if name in P.SMALL_BATCH:
+        assert batch // G >= 3 and 0 < batch % G < G, (batch, G)              # several steps and a ragged last one
+    if name in P.BYTE_FORM:
+        assert planner == "conv_rows" and C == 3 and (W * C) % 4 != 0 and (H * W * C) % 4 != 0
+    if name.startswith("conv3s2_45x31x3"):
+        assert (G * H * W * C) % 2 == 1 and G * H * W * C < 32768           # consecutive steps start at byte shifts 0, 3, 2, 1
+    if name in P.MANY_STEPS:
+        g, nthr, batch = P.MANY_STEPS[name]
+        assert g == G and nthr == p.get("NTHR", 512 if planner == "conv_rows" else 256), (name, p)
+        steps, r = divmod(batch, G)
+        assert 0 < r < G and steps >= 2 * 256 * (2048 // nthr) + 1
+        assert batch * (H * W * C + OH * OW * (C if dw else N)) < 256 << 20
+
+
+def test_pads_beyond_the_filter_put_whole_windows_in_fill():
+    for name in ("conv3s1_10x8x16_p3", "dw3s1_10x8x16_p3", "conv3s1_9x9x3_p4"):
+        dw, H, W, C, K, S, (t, b, l, r), N, wz = P.SMALL[name]
+        assert min(t, b, l, r) >= K
+    for name in ("conv3s1_71x48x16_tl", "dw3s1_71x48x16_tl"):
+        dw, H, W, C, K, S, (t, b, l, r), N, wz = P.BANDED[name]
+        assert b == 0 and r == 0 and t > (K - 1) // 2 and l > (K - 1) // 2
