@@ -7,7 +7,7 @@
 //
 //   microflow::Tensor2D / Tensor4D                      src/tensor.rs:27-47
 //   microflow::FusedActivation, TensorViewPadding       src/activation.rs:6-13, src/tensor.rs:9-15
-//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / average_pool_2d / max_pool_2d (ours) / add (ours) / pad (ours) /
+//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / average_pool_2d / max_pool_2d (ours) / add (ours) / concatenation (ours) / pad (ours) /
 //                   softmax / reshape                    src/ops/*.rs
 //   microflow::Model  (what #[model("x.tflite")] generates: predict, predict_quantized)
 //                                                        microflow-macros/src/lib.rs:185-203
@@ -87,16 +87,16 @@ inline std::vector<int8_t> run(mf_op *op, const std::vector<int8_t> &in, size_t 
     if (hipMemcpy(out.data(), dout.p, out_n, 2 /*D2H*/) != 0) throw Error(MF_ERR_HIP, "hipMemcpy D2H failed");
     return out;
 }
-// ... an operator with two inputs (ADD)
+// ... an operator with two inputs (ADD, CONCATENATION)
 inline std::vector<int8_t> run2(mf_op *op, const std::vector<int8_t> &a, const std::vector<int8_t> &b, size_t batch) {
     struct Guard {
         mf_op *o;
         ~Guard() { mf_op_destroy(o); }
     } g{op};
-    const size_t n = mf_op_input_elems(op) * batch;
-    if (a.size() != n || b.size() != n) throw Error(MF_ERR_INVALID_ARG, "input size does not match the operator");
-    DeviceBuffer da(n), db(n), dout(n);
-    if (hipMemcpy(da.p, a.data(), n, 1 /*H2D*/) != 0 || hipMemcpy(db.p, b.data(), n, 1) != 0) throw Error(MF_ERR_HIP, "hipMemcpy H2D failed");
+    const size_t na = mf_op_input_elems(op) * batch, nb = mf_op_input2_elems(op) * batch, n = mf_op_output_elems(op) * batch;
+    if (a.size() != na || b.size() != nb) throw Error(MF_ERR_INVALID_ARG, "input size does not match the operator");
+    DeviceBuffer da(na), db(nb), dout(n);
+    if (hipMemcpy(da.p, a.data(), na, 1 /*H2D*/) != 0 || hipMemcpy(db.p, b.data(), nb, 1) != 0) throw Error(MF_ERR_HIP, "hipMemcpy H2D failed");
     check(mf_op_run2(op, (const int8_t *)da.p, (const int8_t *)db.p, batch, (int8_t *)dout.p, nullptr));
     std::vector<int8_t> out(n);
     if (hipMemcpy(out.data(), dout.p, n, 2 /*D2H*/) != 0) throw Error(MF_ERR_HIP, "hipMemcpy D2H failed");
@@ -240,6 +240,21 @@ inline Tensor4D pad(const Tensor4D &input, std::array<int, 4> pads, int device =
     out.buffer = detail::run(op, input.buffer, (size_t)input.batches);
     out.batches = input.batches, out.rows = input.rows + pads[0] + pads[1], out.cols = input.cols + pads[2] + pads[3], out.chans = input.chans;
     out.scale = input.scale, out.zero_point = input.zero_point;
+    return out;
+}
+
+// CONCATENATION along the channels: no counterpart in the reference (microflow_amd.h states the contract).  Two tensors of equal
+// batches, rows and cols, per-tensor quantisation; constants = {ca, cb} of mf_preprocess_concatenation.  The operand order is kept.
+inline Tensor4D concatenation(const Tensor4D &a, const Tensor4D &b, std::array<float, 1> output_scale, std::array<int8_t, 1> output_zero_point,
+                              std::array<float, 2> constants, int device = 0) {
+    if (a.batches != b.batches || a.rows != b.rows || a.cols != b.cols) throw Error(MF_ERR_INVALID_ARG, "concatenation: the inputs differ in another dimension than the channels");
+    mf_op *op = nullptr;
+    check(mf_concatenation_create(device, (size_t)a.rows * a.cols, a.chans, b.chans, a.scale[0], a.zero_point[0], b.scale[0], b.zero_point[0],
+                                  output_scale[0], output_zero_point[0], constants[0], constants[1], &op));
+    Tensor4D out;
+    out.buffer = detail::run2(op, a.buffer, b.buffer, (size_t)a.batches);
+    out.batches = a.batches, out.rows = a.rows, out.cols = a.cols, out.chans = a.chans + b.chans;
+    out.scale = {output_scale[0]}, out.zero_point = {output_zero_point[0]};
     return out;
 }
 

@@ -15,6 +15,7 @@ MF_MEM_HOST, MF_MEM_DEVICE = 0, 1
 MF_ELEM_I8, MF_ELEM_U8 = 0, 1
 MF_OP_AVERAGE_POOL_2D, MF_OP_MAX_POOL_2D = 1, 17   # mf_op_kind of the two pools (TFLite builtin codes)
 MF_OP_ADD = 0
+MF_OP_CONCATENATION = 2
 MF_OP_PAD, MF_OP_MEAN = 34, 40   # (not in the reference: include/microflow_amd.h mf_pad_create)
 STATUS_NAMES = {0: "MF_OK", 1: "MF_ERR_INVALID_MODEL", 2: "MF_ERR_UNSUPPORTED",
                 3: "MF_ERR_INVALID_ARG", 4: "MF_ERR_NO_DEVICE", 5: "MF_ERR_HIP", 6: "MF_ERR_OOM"}
@@ -95,6 +96,10 @@ SIGNATURES = {
     "mf_add_create": (C.c_int, [C.c_int, C.c_size_t, C.c_float, C.c_int8, C.c_float, C.c_int8, C.c_float, C.c_int8, C.c_int,
                                 C.c_float, C.c_float, C.POINTER(_vp)]),
     "mf_pad_create": (C.c_int, [C.c_int] * 8 + [C.c_int8, C.POINTER(_vp)]),
+    "mf_preprocess_concatenation": (C.c_int, [C.c_float, C.c_float, C.c_float, _vp, _vp]),
+    "mf_concatenation_create": (C.c_int, [C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int8, C.c_float, C.c_int8, C.c_float,
+                                          C.c_int8, C.c_float, C.c_float, C.POINTER(_vp)]),
+    "mf_op_input2_elems": (C.c_size_t, [_vp]),
     "mf_op_run": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp]),
     "mf_op_run2": (C.c_int, [_vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "mf_op_input_elems": (C.c_size_t, [_vp]),
@@ -158,7 +163,7 @@ SIGNATURES = {
 # T = u8 instantiations: the i8 signature with every int8_t value parameter as uint8_t
 for _n in ("mf_preprocess_fully_connected", "mf_preprocess_average_pool_2d",
            "mf_fully_connected_create", "mf_conv_2d_create", "mf_depthwise_conv_2d_create",
-           "mf_average_pool_2d_create", "mf_max_pool_2d_create", "mf_add_create", "mf_pad_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
+           "mf_average_pool_2d_create", "mf_max_pool_2d_create", "mf_add_create", "mf_concatenation_create", "mf_pad_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
            "mf_window_gather_quantize"):
     _r, _a = SIGNATURES[_n]
     SIGNATURES[_n + "_u8"] = (_r, [C.c_uint8 if t is C.c_int8 else t for t in _a])

@@ -120,6 +120,13 @@ int mf_preprocess_add(float a_scale, float b_scale, float output_scale, float *c
     })
 }
 
+int mf_preprocess_concatenation(float a_scale, float b_scale, float output_scale, float *ca, float *cb) {
+    MF_TRY({
+        MF_NEED(ca && cb);
+        mf::h_preprocess_concatenation(a_scale, b_scale, output_scale, ca, cb);
+    })
+}
+
 int mf_add_fma_form(float ca, float cb, int a_zero_point, int b_zero_point, float output_scale, int output_zero_point,
                     int fused_activation, int is_u8, float *k1, int *admitted) {
     MF_TRY({
@@ -382,6 +389,35 @@ int mf_pad_create_u8(int device, int H, int W, int C, int top, int bottom, int l
     MF_TRY({ create_pad(device, true, H, W, C, top, bottom, left, right, zero_point, op); })
 }
 
+// CONCATENATION (include/microflow_amd.h: the library's own contract).  Bad scales are a bad argument whether or not there is a device
+static void create_concatenation(int device, bool u8, size_t rows, int Ca, int Cb, float sa, int za, float sb, int zb, float so, int zo,
+                                 float ca, float cb, mf_op **op) {
+    MF_NEED(op && rows > 0 && Ca > 0 && Cb > 0);
+    for (float v : {sa, sb, so})
+        if (!(v > 0.0f) || !std::isfinite(v)) mf::fail(MF_ERR_INVALID_ARG, "concatenation: scales must be finite and positive");
+    mf::OpSpec s;
+    s.kind = MF_OP_CONCATENATION, s.u8 = u8;
+    s.cat_rows = rows, s.cat_ca = Ca, s.cat_cb = Cb;
+    s.add_za = za, s.add_zb = zb, s.add_ca = ca, s.add_cb = cb;
+    s.cat_copy_a = mf::h_concat_identity(sa, za, so, zo, ca), s.cat_copy_b = mf::h_concat_identity(sb, zb, so, zo, cb);
+    s.oscale = so, s.ozp = zo, s.act = MF_ACT_NONE;
+    wrap_op(mf::op_create(device, s), op);
+}
+int mf_concatenation_create(int device, size_t rows, int Ca, int Cb, float a_scale, int8_t a_zero_point, float b_scale,
+                            int8_t b_zero_point, float output_scale, int8_t output_zero_point, float ca, float cb, mf_op **op) {
+    MF_TRY({
+        create_concatenation(device, false, rows, Ca, Cb, a_scale, a_zero_point, b_scale, b_zero_point, output_scale, output_zero_point, ca,
+                             cb, op);
+    })
+}
+int mf_concatenation_create_u8(int device, size_t rows, int Ca, int Cb, float a_scale, uint8_t a_zero_point, float b_scale,
+                               uint8_t b_zero_point, float output_scale, uint8_t output_zero_point, float ca, float cb, mf_op **op) {
+    MF_TRY({
+        create_concatenation(device, true, rows, Ca, Cb, a_scale, a_zero_point, b_scale, b_zero_point, output_scale, output_zero_point, ca,
+                             cb, op);
+    })
+}
+
 int mf_op_run2(mf_op *op, const int8_t *d_a, const int8_t *d_b, size_t batch, int8_t *d_output, void *stream) {
     MF_TRY({
         MF_NEED(op && op->impl);
@@ -395,6 +431,7 @@ int mf_op_run(mf_op *op, const int8_t *d_input, size_t batch, int8_t *d_output, 
     })
 }
 size_t mf_op_input_elems(const mf_op *op) { return op && op->impl ? mf::op_in_elems(op->impl) : 0; }
+size_t mf_op_input2_elems(const mf_op *op) { return op && op->impl ? mf::op_in2_elems(op->impl) : 0; }
 size_t mf_op_output_elems(const mf_op *op) { return op && op->impl ? mf::op_out_elems(op->impl) : 0; }
 const char *mf_op_kernel_name(const mf_op *op) { return op && op->impl ? mf::op_kernel_name(op->impl) : ""; }
 int mf_op_set_generic(mf_op *op, int generic) {
@@ -521,7 +558,7 @@ int mf_model_get_op_skip(const mf_model *model, int index, int *source, int *run
         const mf::ParsedModel &pm = mf::model_parsed(model->impl);
         MF_NEED(index >= 0 && index < (int)pm.ops.size());
         const mf::ParsedOp &o = pm.ops[(size_t)index];
-        if (o.kind != MF_OP_ADD) mf::fail(MF_ERR_INVALID_ARG, "mf_model_get_op_skip: the operator is no ADD");
+        if (!o.join()) mf::fail(MF_ERR_INVALID_ARG, "mf_model_get_op_skip: the operator is no ADD");
         if (source) *source = o.skip_src;
         if (running_input) *running_input = o.run_input;
     })

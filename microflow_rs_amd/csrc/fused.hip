@@ -103,6 +103,7 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
         op_run(f->padconv.get(), d_in, batch, d_out, st);
         break;
     case FusedImpl::SHORTCUT: fail(MF_ERR_INVALID_ARG, "shortcut_add_rt takes two inputs: fused_run2"); break;
+    case FusedImpl::SIDECONCAT: fail(MF_ERR_INVALID_ARG, "side_concat_rt takes two inputs: fused_run2"); break;
     case FusedImpl::DWPW: {
         const OpSpec &d = f->a->s;
         if (!k::launch_dwpw(d.H, d.W, d.C, d.sh, f->b->s.N, d_in, d_out, f->dwpw, (int)batch, st)) fail(MF_ERR_UNSUPPORTED, "fused kernel missing");
@@ -114,7 +115,22 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
 void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream) {
     if (batch) launch(f, d_in, batch, d_out, 0, (hipStream_t)stream);
 }
+// side_concat_rt: the output overlaps neither T nor the running tensor (the pitches differ); 16-byte words at all three pointers
+static void run_side_concat(FusedImpl *f, const int8_t *d_t, const int8_t *d_run, size_t batch, int8_t *d_out, void *stream) {
+    const k::SideConcatArgs &a = f->sideconcat;
+    const size_t tb = batch * f->a->in_elems, ob = batch * f->b->out_elems, rb = batch * (size_t)a.OH * a.OW * (size_t)a.CR;
+    const uintptr_t t0 = (uintptr_t)d_t, o0 = (uintptr_t)d_out, r0 = (uintptr_t)d_run;
+    if (!d_t || !d_run || !d_out) fail(MF_ERR_INVALID_ARG, "side_concat_rt: null device pointer");
+    if ((t0 < o0 + ob && o0 < t0 + tb) || (r0 < o0 + ob && o0 < r0 + rb)) fail(MF_ERR_INVALID_ARG, "side_concat_rt: the output overlaps an input");
+    if ((t0 | o0 | r0) & 15) fail(MF_ERR_INVALID_ARG, "side_concat_rt: a pointer is not 16-byte aligned");
+    k::launch_side_concat(d_t, d_run, d_out, a, (long long)batch, (hipStream_t)stream);
+    MF_HIP(hipGetLastError());
+}
 void fused_run2(FusedImpl *f, const int8_t *d_t, const int8_t *d_run, size_t batch, int8_t *d_out, void *stream) {
+    if (f->kind == FusedImpl::SIDECONCAT) {
+        if (batch) run_side_concat(f, d_t, d_run, batch, d_out, stream);
+        return;
+    }
     if (f->kind != FusedImpl::SHORTCUT) fail(MF_ERR_INVALID_ARG, "fused_run2: not a two-input group");
     if (!batch) return;
     const size_t tb = batch * f->a->in_elems, ob = batch * f->b->s.add_elems;

@@ -374,4 +374,41 @@ FusedImpl *fused_shortcut_add_create(OpImpl *conv, OpImpl *add, bool conv_first)
     return f.release();
 }
 
+// A 1x1 Conv2D on a skip edge and the CONCATENATION that reads its result beside the running tensor -- a fire module's 1x1 expand and
+// its join -- as one side_concat_rt launch (k_side_concat.hip).  The class is shortcut_add_rt's for the convolution
+// (shortcut_add_class) with the running slice in whole sixteens too; everything else keeps its two launches.  Operand A, the
+// constants, the clamp and the epilogue mode (0 to 2) are set up as for shortcut_add_rt; the join's block is the operator's
+// internal-domain one.
+bool side_concat_class(const OpSpec &d, int run_channels, bool zero_wzp, bool finite) {
+    return shortcut_add_class(d, zero_wzp, finite) && k::side_concat_supported(d.C, d.N, run_channels);
+}
+FusedImpl *fused_side_concat_create(OpImpl *conv, OpImpl *cat, bool conv_first) {
+    if (switches().no_side_concat || !conv || !cat || conv->force_generic || cat->force_generic) return nullptr;
+    const OpSpec &d = conv->s, &q = cat->s;
+    if (q.kind != MF_OP_CONCATENATION || conv->device != cat->device || d.u8 != q.u8) return nullptr;
+    const bool zero_wzp = std::all_of(conv->h_wzp.begin(), conv->h_wzp.end(), [](int32_t z) { return z == 0; });
+    const int CR = conv_first ? q.cat_cb : q.cat_ca;
+    if (!side_concat_class(d, CR, zero_wzp, conv->finite_consts)) return nullptr;
+    // on exactly the convolution's output: its pixels are the join's rows, its channels the join's slice for that input
+    if (q.cat_rows != (size_t)d.OH * d.OW || (conv_first ? q.cat_ca : q.cat_cb) != d.N || conv->h_w.size() != (size_t)d.N * d.C) return nullptr;
+    const k::ConcatArgs &ca = cat->cat;
+    if (!std::isfinite(ca.ca) || !std::isfinite(ca.cb)) return nullptr;
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::SIDECONCAT, conv, cat, nullptr, "");
+    k::SideConcatArgs &a = f->sideconcat;
+    const int NT = d.N / 16, TB = NT < 4 ? NT : 4, NBLK = (NT + TB - 1) / TB, NSPLIT = NBLK <= 1 ? 1 : (NBLK == 2 ? 2 : 4);
+    const std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(conv->h_w.data(), d.C, d.N, 1, TB, NSPLIT); // [N][1][1][C], i8 domain
+    a.pw.wprep = keep(*f, prep.data(), prep.size());
+    a.pw.A = conv->conv.A, a.pw.S = conv->conv.S, a.pw.Kc = conv->conv.Kc, a.pw.wzp = conv->conv.wzp;
+    a.pw.lo_f = conv->conv.lo_f, a.pw.hi_f = conv->conv.hi_f;
+    a.pw.K = d.C, a.pw.N = d.N, a.pw.KS = (d.C + 63) / 64, a.pw.NT = NT, a.pw.patch_pitch = d.N;
+    a.pw.TB = TB, a.pw.NSPLIT = NSPLIT;
+    a.pw.magic = std::min(conv->magic_mode, 2), a.pw.xr = conv->conv.xr;
+    a.cat = ca;
+    a.H = d.H, a.W = d.W, a.OH = d.OH, a.OW = d.OW, a.sh = d.sh, a.sw = d.sw;
+    a.CR = CR, a.conv_first = conv_first ? 1 : 0;
+    f->epi_mode = a.pw.magic;
+    f->name = "side_concat_rt<" + std::to_string(d.C) + "," + std::to_string(d.N) + "," + std::to_string(CR) + (d.sh == 2 ? ",s2>" : ">");
+    return f.release();
+}
+
 } // namespace mf

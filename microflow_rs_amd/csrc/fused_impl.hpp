@@ -17,7 +17,7 @@ namespace mf {
 // One argument block (or a named sub-struct: block + what the launch path needs beside it) per kind; a group uses its own kind's.
 // Plain members, no variant: the chain planner swaps whole groups (std::swap(*groups[i], *trial)).
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK, CONVPOOL, SHORTCUT, PADCONV } kind = DWPW;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK, CONVPOOL, SHORTCUT, PADCONV, SIDECONCAT } kind = DWPW;
     OpImpl *a = nullptr, *b = nullptr, *c = nullptr;
     std::string name;
     std::vector<std::unique_ptr<DevBuf>> owned; // the group's own operand arrays and tables (keep)
@@ -78,6 +78,9 @@ struct FusedImpl {
     // SHORTCUT: a 1x1 shortcut convolution + the ADD on its result and the running tensor (k_shortcut_add.hip); a = the convolution, b = the
     // ADD.  The one kind with TWO inputs: fused_run2, never the launch path of the others
     k::ShortcutAddArgs shortcut{};
+    // SIDECONCAT: a 1x1 Conv2D on a skip edge + the CONCATENATION of its result and the running tensor (k_side_concat.hip); a = the
+    // convolution, b = the CONCATENATION.  Two inputs, as SHORTCUT: fused_run2
+    k::SideConcatArgs sideconcat{};
     // PADCONV: a PAD + the VALID Conv2D / DepthwiseConv2D on its output as one launch of the convolution's own run-time-geometry kernel;
     // a = the PAD, b = the convolution.  padconv = that convolution taken as an operator on the UNPADDED image with the PAD's top / left
     // rows and columns as its window placement (ops.hip op_create_padded_conv): it borrows b's weights and constants, owns the images
@@ -114,6 +117,7 @@ inline KindFacts kind_facts(FusedImpl::Kind kind) {
     case FusedImpl::BLOCK: return {"block_band_rt", true, false, false};
     case FusedImpl::CONVPOOL: return {"conv_pool_rt", true, false, false};
     case FusedImpl::PADCONV: return {"pad+conv", true, false, false};
+    case FusedImpl::SIDECONCAT: return {nullptr, false, false, false}; // (as SHORTCUT)
     case FusedImpl::SHORTCUT: return {nullptr, false, false, false}; // (16-byte words at all three pointers, the caller's output buffer among them: fused_run2 checks the alignment itself)
     }
     return {nullptr, false, false, false};

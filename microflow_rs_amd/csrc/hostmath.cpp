@@ -181,6 +181,14 @@ void h_preprocess_add(float sa, float sb, float so, float *ca, float *cb) {
     *cb = sb / so;
 }
 
+void h_preprocess_concatenation(float sa, float sb, float so, float *ca, float *cb) {
+    *ca = sa / so;
+    *cb = sb / so;
+}
+bool h_concat_identity(float s_i, int z_i, float so, int zo, float c) {
+    return std::memcmp(&s_i, &so, sizeof(float)) == 0 && z_i == zo && c == 1.0f;
+}
+
 // One element's tail on the host, the device's instructions one by one (k_add.hip add_one): roundf as y + copysign(0.49999997, y)
 // truncated, NaN -> 0, the clamp
 static int add_tail(float y, int lo, int hi) {

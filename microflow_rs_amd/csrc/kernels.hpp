@@ -73,6 +73,17 @@ struct AddArgs {
     float k1;             // the gated form (add_c16<fma>): y = fma(cb, f32(ub), fma(ca, f32(ua), k1)), k1 = zo - ca ka - cb kb folded on the host
     uint32_t xin4, xout4; // per dword: input bytes ^ xin4 are offset values; result bytes (value & 0xff) ^ xout4 are stored
 };
+// CONCATENATION along the last axis (k_concat.hip): output row r is row r of a (Ca bytes) followed by row r of b (Cb bytes).  Stored
+// bytes as AddArgs': input i's value is (u ^ xin) - off, k_i = f32(off + z_i).  copy_i: the slice's requantisation is the identity
+// (scale bit-equal to the output's, equal zero points, c_i == 1.0f) and its bytes are moved as they are.
+struct ConcatArgs {
+    float ca, cb, ka, kb;
+    float zo_f;
+    float lo_f, hi_f;     // `as T` saturation, values of T (no fused activation)
+    uint32_t xin4, xout4; // per dword, as AddArgs'
+    int Ca, Cb;
+    int copy_a, copy_b;
+};
 // PAD (k_pad.hip).  Rows are counted in bytes: an output row is lp fill bytes, the image row (in_row), rp fill bytes.
 struct PadArgs {
     int H, OH;            // image rows, output rows (top + H + bottom)
@@ -265,6 +276,17 @@ struct ShortcutAddArgs {
     int conv_first;      // 1: the ADD's input a is the convolution's result and b the running tensor; 0: the other way round
 };
 bool shortcut_add_supported(int C, int N);
+// A 1x1 Conv2D on a skip edge (strides (1,1) or (2,2)) + the CONCATENATION that reads its result beside the running tensor, in one
+// launch (k_side_concat.hip)
+struct SideConcatArgs {
+    PwRtArgs pw;         // the convolution, as ShortcutAddArgs::pw
+    ConcatArgs cat;      // the CONCATENATION in the internal domain (Ca, Cb by input position)
+    int H, W, OH, OW, sh, sw;
+    int CR;              // the running tensor's channels (a whole number of sixteens)
+    int conv_first;      // 1: the join's input a is the convolution's result and b the running tensor; 0: the other way round
+};
+bool side_concat_supported(int C, int N, int CR);
+void launch_side_concat(const int8_t *t_in, const int8_t *run, int8_t *out, const SideConcatArgs &a, long long batch, hipStream_t s);
 void launch_shortcut_add(const int8_t *t_in, const int8_t *run, int8_t *out, const ShortcutAddArgs &a, long long batch, hipStream_t s);
 // Conv2D with few input channels / DepthwiseConv2D with one input channel, any filter (k_rt.hip: conv_rows_lds)
 struct ConvRowsArgs {
@@ -736,6 +758,10 @@ void launch_add_c16(const int8_t *a, const int8_t *b, int8_t *out, const AddArgs
 void launch_add_generic(const int8_t *a, const int8_t *b, int8_t *out, const AddArgs &p, size_t n, hipStream_t s);
 // PAD: out = in with fill bytes around every image.  pad_generic: any shape and pointers; pad_c4 (units = 4: in_row, out_row, lp
 // multiples of 4, pointers 4-byte aligned; units = 16: all of them multiples of 16): every output word written once, no LDS
+// CONCATENATION over `rows` rows (k_concat.hip).  The output overlaps neither input.  c4: Ca % unit == 0, Cb % unit == 0 and all three
+// pointers aligned to `unit` (16, 8 or 4) bytes; cus: the device's CU count
+void launch_concat_c4(const int8_t *a, const int8_t *b, int8_t *out, const ConcatArgs &p, size_t rows, int unit, int cus, hipStream_t s);
+void launch_concat_generic(const int8_t *a, const int8_t *b, int8_t *out, const ConcatArgs &p, size_t rows, hipStream_t s);
 void launch_pad_generic(const int8_t *in, int8_t *out, const PadArgs &a, size_t batch, hipStream_t s);
 void launch_pad_c4(const int8_t *in, int8_t *out, const PadArgs &a, size_t batch, int unit, hipStream_t s);
 void launch_fc_generic(const int8_t *in, int8_t *out, const FcArgs &a, size_t rows, hipStream_t s);

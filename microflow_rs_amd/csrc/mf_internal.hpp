@@ -53,6 +53,10 @@ void h_preprocess_pool(float iscale, int izp, float oscale, int ozp, float *c0, 
 bool h_pool_window_empty(int H, int W, int KH, int KW, int sh, int sw, bool same, int OH, int OW);
 // ADD (not in the reference; include/microflow_amd.h states the contract): ca = sa / so, cb = sb / so, two f32 divisions
 void h_preprocess_add(float sa, float sb, float so, float *ca, float *cb);
+// CONCATENATION (not in the reference; include/microflow_amd.h states the contract): the same two divisions
+void h_preprocess_concatenation(float sa, float sb, float so, float *ca, float *cb);
+// ... and whether input i's slice is the identity of that contract: its scale bit-equal to the output's, equal zero points, c == 1.0f
+bool h_concat_identity(float s_i, int z_i, float so, int zo, float c);
 // ADD's gated form y = fma(cb, f32(ub), fma(ca, f32(ua), k1)) with k1 = zo - ca ka - cb kb (ua, ub: bytes 0 .. 255 whose values are
 // ua - ka, ub - kb).  true, with *k1: the constants are finite and the form gives the text's byte -- through the same rounding and
 // the clamp [lo, hi] -- for ALL 65 536 (ua, ub) pairs.  Host only, exhaustive
@@ -108,6 +112,14 @@ struct ParsedOp {
     int skip_src = -2, run_input = 0;
     float a_scale = 0, b_scale = 0;
     int a_zp = 0, b_zp = 0;
+    // A join: an ADD or a CONCATENATION -- the two operators that read the running tensor AND one other (skip_src, run_input, a_*, b_*
+    // as above, for either).  CONCATENATION only: rows (the product of all axes but the last), the two inputs' last axes by input
+    // position, and whether each slice's requantisation is the identity (h_concat_identity); in_elems is the running operand's
+    bool join() const { return kind == MF_OP_ADD || kind == MF_OP_CONCATENATION; }
+    size_t cat_rows = 0;
+    int cat_ca = 0, cat_cb = 0;
+    bool cat_copy_a = false, cat_copy_b = false;
+    size_t skip_elems() const { return kind == MF_OP_CONCATENATION ? cat_rows * (size_t)(run_input == 0 ? cat_cb : cat_ca) : in_elems; } // the other operand's
     // A side operator only (one Conv2D on a skip edge: it reads an earlier tensor T of the chain, not the running value, and one later
     // ADD reads its output beside the running value): the operator whose output T is (-1: the model input); -2: no side operator.
     // That ADD's skip_src is this operator's index.  in_scale / in_zp are T's
@@ -126,8 +138,8 @@ struct ParsedModel {
     float in_scale = 0, out_scale = 0;
     int in_zp = 0, out_zp = 0;
     size_t in_elems = 0, out_elems = 0, max_elems = 0;
-    size_t max_fork_elems = 0; // the largest tensor an operator produces for a later ADD to read beside the running one (0: none)
-    bool input_skip = false;   // some ADD reads the model input beside the running tensor
+    size_t max_fork_elems = 0; // the largest tensor an operator produces for a later join (ADD, CONCATENATION) to read beside the running one (0: none)
+    bool input_skip = false;   // some join reads the model input beside the running tensor
     std::vector<ParsedOp> ops;
     // the operator that launches tensor s of the chain (-1: the model input): the Reshapes (aliases) in front of it skipped, and the
     // side operators that stand between them in file order passed over
@@ -137,16 +149,16 @@ struct ParsedModel {
             while (s >= 0 && ops[(size_t)s].side());
         return s;
     }
-    // the operator that launches the tensor that has to stay in memory for ADD i: the one it reads beside the running one or, where
+    // the operator that launches the tensor that has to stay in memory for join i (an ADD or a CONCATENATION): the one it reads beside the running one or, where
     // that is a side operator's output, the tensor T the side operator reads; -1: the model input
     int skip_real(size_t i) const {
         int s = ops[i].skip_src;
         if (s >= 0 && ops[(size_t)s].side()) s = ops[(size_t)s].side_src;
         return launcher(s);
     }
-    // ADD i reads a side operator's output: that operator's index, else -1
+    // join i (an ADD or a CONCATENATION) reads a side operator's output: that operator's index, else -1
     int side_of_add(size_t i) const {
-        const int s = ops[i].kind == MF_OP_ADD ? ops[i].skip_src : -2;
+        const int s = ops[i].join() ? ops[i].skip_src : -2;
         return s >= 0 && ops[(size_t)s].side() ? s : -1;
     }
 };
@@ -180,6 +192,11 @@ struct OpSpec {
     size_t add_elems = 0;
     int add_za = 0, add_zb = 0;
     float add_ca = 0, add_cb = 0;
+    // CONCATENATION: rows per inference, the inputs' last axes, whether a slice is copied (h_concat_identity); the zero points and the
+    // constants in add_za, add_zb, add_ca, add_cb
+    size_t cat_rows = 0;
+    int cat_ca = 0, cat_cb = 0;
+    bool cat_copy_a = false, cat_copy_b = false;
     // PAD only: new rows / columns (top, bottom, left, right) around the H x W x C image, each element izp; OH, OW the padded size.
     // (A convolution's spec carries SAME / VALID and nothing else: explicit pads exist only inside the PAD + convolution group)
     int pads[4] = {0, 0, 0, 0};
@@ -188,11 +205,13 @@ OpImpl *op_create(int device, const OpSpec &spec);
 void op_destroy(OpImpl *op);
 void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream);
 // an ADD: out = a + b over batch x elems bytes.  d_out may be exactly d_a or exactly d_b (in place); any other overlap is refused.
+// a CONCATENATION: batch x rows rows of Ca + Cb bytes; the output overlaps neither input.
 // external: a u8 operator exchanges real u8 bytes (the ABI's view, in the same launch), else the internal domain
 void op_run2(OpImpl *op, const int8_t *d_a, const int8_t *d_b, size_t batch, int8_t *d_out, void *stream, bool external);
 // the ABI's view: a u8 operator exchanges real u8 bytes (two extra byte passes)
 void op_run_external(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream);
 size_t op_in_elems(const OpImpl *op);
+size_t op_in2_elems(const OpImpl *op); // the second input of an ADD or a CONCATENATION; 0 otherwise
 size_t op_out_elems(const OpImpl *op);
 const char *op_kernel_name(const OpImpl *op);
 int op_epilogue_mode(const OpImpl *op); // k_common.hpp epilogue mode (0 .. 3) of the operator's own launch; -1: no requantising epilogue of that kind
@@ -221,6 +240,9 @@ FusedImpl *fused_block_create(OpImpl *expand, OpImpl *dw, OpImpl *pw, bool pair_
 // (k_shortcut_add.hip), or nullptr: outside the class, the two run their own launches.  conv_first: the ADD's input a is the
 // convolution's result.  fused_run2 runs it: d_t the convolution's input, d_run the running tensor; d_out may be exactly d_run
 FusedImpl *fused_shortcut_add_create(OpImpl *conv, OpImpl *add, bool conv_first);
+// ... and its sibling for a CONCATENATION join: a 1x1 Conv2D on a skip edge + the CONCATENATION of its result and the running tensor as
+// one side_concat_rt launch (k_side_concat.hip), or nullptr.  fused_run2 runs it; d_out overlaps neither input
+FusedImpl *fused_side_concat_create(OpImpl *conv, OpImpl *cat, bool conv_first);
 void fused_run2(FusedImpl *f, const int8_t *d_t, const int8_t *d_run, size_t batch, int8_t *d_out, void *stream);
 // a PAD + the VALID Conv2D / DepthwiseConv2D on its output as ONE launch of the kernel the convolution, taken as an operator on the
 // unpadded image with the PAD's top / left pads, gets from the run-time-geometry planners (conv_rows, conv_mm / dw_mm, dw_gemm, conv_gemm);

@@ -6,7 +6,7 @@
 //   weights + folded constants : resident per op (person_detect: ~0.3 MB)
 //   act[0], act[1]             : ping-pong activation buffers, batch x max tensor bytes
 //   in_q / io_f32              : staging for host-fed batches
-//   fork[0], fork[1]           : models with an ADD only -- where a tensor that a later ADD reads beside the running one is
+//   fork[0], fork[1]           : models with a join (ADD, CONCATENATION) only -- where a tensor that a later join reads beside the running one is
 //                                written, batch x largest such tensor; the ping-pong never writes there, so no skip is ever copied.
 //                                A side operator's result (a Conv2D on a skip edge, run at its ADD) goes to the one that holds
 //                                neither its input nor the running tensor -- where the two are not one launch, which writes neither
@@ -46,8 +46,8 @@ struct ModelImpl {
     bool autotune = false; // model_set_autotune: time the run-time-geometry chain candidates at creation
     size_t cap_batch = 0;
     int8_t *act[2] = {nullptr, nullptr};
-    int8_t *fork[2] = {nullptr, nullptr}; // skip tensors (pm.max_fork_elems != 0): two, for an ADD whose sum is the next skip
-    std::vector<char> forks;  // per operator: its tensor (through the Reshapes behind it) is read by a later ADD beside the running one
+    int8_t *fork[2] = {nullptr, nullptr}; // skip tensors (pm.max_fork_elems != 0): two, for a join whose result is the next skip
+    std::vector<char> forks;  // per operator: its tensor (through the Reshapes behind it) is read by a later join (ADD, CONCATENATION) beside the running one
     int8_t *in_q = nullptr;   // quantized input staging (host-fed or f32 path)
     float *io_f32 = nullptr;  // f32 input / output staging
     size_t io_f32_elems = 0;
@@ -127,7 +127,7 @@ ModelImpl *model_create(const uint8_t *buf, size_t len) {
     m->pm = parse_tflite(buf, len);
     m->forks.assign(m->pm.ops.size(), 0);
     for (size_t i = 0; i < m->pm.ops.size(); ++i)
-        if (m->pm.ops[i].kind == MF_OP_ADD && m->pm.skip_real(i) >= 0) m->forks[(size_t)m->pm.skip_real(i)] = 1;
+        if (m->pm.ops[i].join() && m->pm.skip_real(i) >= 0) m->forks[(size_t)m->pm.skip_real(i)] = 1;
     return m.release();
 }
 void model_destroy(ModelImpl *m) { delete m; }
@@ -177,11 +177,12 @@ static int fused_owner(const ModelImpl *m, int i) {
         if (fused_at(m, j) && m->g.fused_last[(size_t)j] >= i) return j;
     return -1;
 }
-// the side operator + ADD launch at ADD i, if the model has one there and nothing switched it off
+// the side operator + join launch (shortcut_add_rt at an ADD, side_concat_rt at a CONCATENATION) at join i, if the model has one there
+// and nothing switched it off
 static FusedImpl *shortcut_at(const ModelImpl *m, int i) {
     return m->fusion && !m->generic && i >= 0 && i < (int)m->g.shortcut.size() ? m->g.shortcut[(size_t)i] : nullptr;
 }
-// ... and seen from the side operator: the ADD that reads its output
+// ... and seen from the side operator: the join that reads its output
 static int add_of_side(const ModelImpl *m, int i) {
     for (size_t k = (size_t)i + 1; k < m->pm.ops.size(); ++k)
         if (m->pm.side_of_add(k) == i) return (int)k;
@@ -190,7 +191,8 @@ static int add_of_side(const ModelImpl *m, int i) {
 const char *model_op_kernel(const ModelImpl *m, int i) {
     if (!m->prepared || i < 0 || i >= (int)m->g.ops.size() || !m->g.ops[i]) return "";
     // (the launch is named where it runs and where time_device(per_op) books its time: at the ADD)
-    if (m->pm.ops[(size_t)i].side() && shortcut_at(m, add_of_side(m, i))) return "(fused into its ADD)";
+    if (m->pm.ops[(size_t)i].side() && shortcut_at(m, add_of_side(m, i)))
+        return m->pm.ops[(size_t)add_of_side(m, i)].kind == MF_OP_CONCATENATION ? "(fused into its CONCATENATION)" : "(fused into its ADD)";
     if (shortcut_at(m, i)) return fused_kernel_name(shortcut_at(m, i));
     if (const Stage *best = covering_stage(m, i)) return best->first == i ? fused_kernel_name(best->f) : "(fused into the previous operator)";
     if (fused_at(m, i)) return fused_kernel_name(m->g.fused[(size_t)i]);
@@ -337,7 +339,7 @@ static int last_real_upto(const ModelImpl *m, int last_op) {
 // A run of ops [0 .. last_op] in flight: where the running tensor is, and what the two ends of the run ask for (run_ops)
 struct Run {
     const int8_t *cur; // the running tensor
-    const int8_t *skip; // the live skip tensor, which the next ADD reads beside it: the model input where an ADD reads that (start_run), then every fork tensor as it is written
+    const int8_t *skip; // the live skip tensor, which the next join (ADD, CONCATENATION) reads beside it: the model input where a join reads that (start_run), then every fork tensor as it is written
     size_t batch;
     int last_op, last_real;
     hipStream_t stream;
@@ -353,7 +355,7 @@ struct Run {
 static int run_step(ModelImpl *m, Run &r, int i) {
     OpImpl *o = m->g.ops[(size_t)i];
     const bool f32in = r.src_f32 && i == m->g.first_real;
-    const bool add = m->pm.ops[(size_t)i].kind == MF_OP_ADD; // a launch of its own: the running tensor and the live skip tensor
+    const bool add = m->pm.ops[(size_t)i].join(); // an ADD or a CONCATENATION: a launch of its own: the running tensor and the live skip tensor
     int8_t *dst = m->act[r.which];
     if (dst == r.cur) {
         r.which ^= 1;
@@ -384,6 +386,9 @@ static int run_step(ModelImpl *m, Run &r, int i) {
         const int8_t *other = r.skip;
         if (side >= 0) { // T stays where it is; S goes to the fork buffer that holds neither T nor the running tensor
             int8_t *s_buf = (m->fork[0] == r.skip || m->fork[0] == r.cur) ? m->fork[1] : m->fork[0];
+            // (a CONCATENATION writes beside both inputs: where its own result goes to that fork buffer, S takes the activation
+            // buffer that holds neither the running tensor nor that result)
+            if (m->pm.ops[(size_t)i].kind == MF_OP_CONCATENATION && s_buf == dst) s_buf = m->act[0] == r.cur ? m->act[1] : m->act[0];
             op_run(m->g.ops[(size_t)side], r.skip, r.batch, s_buf, r.stream);
             other = s_buf;
         }

@@ -18,7 +18,7 @@ void ModelGroups::clear() {
 bool group_splits(const ParsedModel &pm, size_t first, size_t last) {
     for (size_t k = 0; k < pm.ops.size(); ++k) {
         if (pm.ops[k].side() && k >= first && k <= last) return true;
-        if (pm.ops[k].kind != MF_OP_ADD) continue;
+        if (!pm.ops[k].join()) continue;
         if (k >= first && k <= last) return true;
         const int s = pm.skip_real(k);
         if (s >= (int)first && s < (int)last) return true;
@@ -27,7 +27,7 @@ bool group_splits(const ParsedModel &pm, size_t first, size_t last) {
 }
 
 int shortcut_candidate(const ParsedModel &pm, size_t add) {
-    const int s = pm.side_of_add(add);
+    const int s = pm.ops[add].kind == MF_OP_ADD ? pm.side_of_add(add) : -1;
     if (s < 0) return -1;
     const ParsedOp &po = pm.ops[(size_t)s];
     bool zero_wzp = true, finite = std::isfinite(pm.ops[add].c0[0]) && std::isfinite(pm.ops[add].c1[0]);
@@ -37,6 +37,19 @@ int shortcut_candidate(const ParsedModel &pm, size_t add) {
     OpSpec d;
     d.kind = po.kind, d.KH = po.KH, d.KW = po.KW, d.sh = po.sh, d.sw = po.sw, d.H = po.H, d.W = po.W, d.C = po.C, d.N = po.N, d.OH = po.OH, d.OW = po.OW;
     return shortcut_add_class(d, zero_wzp, finite) ? s : -1;
+}
+
+int side_concat_candidate(const ParsedModel &pm, size_t join) {
+    const int s = pm.ops[join].kind == MF_OP_CONCATENATION ? pm.side_of_add(join) : -1;
+    if (s < 0) return -1;
+    const ParsedOp &po = pm.ops[(size_t)s], &pj = pm.ops[join];
+    bool zero_wzp = true, finite = std::isfinite(pj.c0[0]) && std::isfinite(pj.c1[0]);
+    for (int z : po.wzp) zero_wzp = zero_wzp && z - (pm.u8 ? 128 : 0) == 0;
+    for (float c : po.c0) finite = finite && std::isfinite(c);
+    for (float c : po.c1) finite = finite && std::isfinite(c);
+    OpSpec d;
+    d.kind = po.kind, d.KH = po.KH, d.KW = po.KW, d.sh = po.sh, d.sw = po.sw, d.H = po.H, d.W = po.W, d.C = po.C, d.N = po.N, d.OH = po.OH, d.OW = po.OW;
+    return side_concat_class(d, pj.run_input == 0 ? pj.cat_ca : pj.cat_cb, zero_wzp, finite) ? s : -1; // (the running operand's channels)
 }
 
 namespace {
@@ -108,6 +121,11 @@ static OpSpec op_spec(const ParsedModel &pm, const ParsedOp &po, float cur_scale
     if (po.kind == MF_OP_ADD) { // (the operands' quantisation is the file's, by input position: izp / in_scale are not used)
         s.add_elems = po.in_elems, s.add_za = po.a_zp, s.add_zb = po.b_zp;
         s.add_ca = po.c0[0], s.add_cb = po.c1[0];
+    }
+    if (po.kind == MF_OP_CONCATENATION) {
+        s.cat_rows = po.cat_rows, s.cat_ca = po.cat_ca, s.cat_cb = po.cat_cb, s.cat_copy_a = po.cat_copy_a, s.cat_copy_b = po.cat_copy_b;
+        s.add_za = po.a_zp, s.add_zb = po.b_zp, s.add_ca = po.c0[0], s.add_cb = po.c1[0];
+        s.act = MF_ACT_NONE;
     }
     if (po.kind == MF_OP_PAD)
         for (int k = 0; k < 4; ++k) s.pads[k] = po.pads[k];
@@ -435,6 +453,15 @@ static void rule_6b_shortcut_add(GroupBuilder &b) {
     }
 }
 
+// (6c) the same for a CONCATENATION join: a side operator and the CONCATENATION that reads its output -> one side_concat_rt launch at
+// the join (fused_heads.hip: fused_side_concat_create) -- a fire module's 1x1 expand and its join
+static void rule_6c_side_concat(GroupBuilder &b) {
+    for (size_t i = 0; i < b.n; ++i) {
+        const int s = side_concat_candidate(b.pm, i);
+        if (s >= 0) b.g.shortcut[i] = fused_side_concat_create(b.g.ops[(size_t)s], b.g.ops[i], b.po(i).run_input == 1);
+    }
+}
+
 // (7) the boundary conversions of M::predict inside the launches at the two ends of the whole model: every launch that can
 // start a run at operator 0 learns the input's scale and zero point, every one that can end at the last operator the ones
 // that operator stamped (the stem was told above; a kernel without such an instance says no and keeps the separate pass)
@@ -470,6 +497,7 @@ ModelGroups build_groups(const ParsedModel &pm, int device, bool autotune) {
     //     convolution or a global pool is offered there first, (6) takes what they left
     //   - (6a) behind every rule above: a global pool stays with the tail and pool_fc_chain groups, a pair's Conv2D with its pair
     //   - (6b) anywhere behind the operators: it looks at side operators and their ADDs, which no other rule touches
+    //   - (6c) likewise: side operators and their CONCATENATIONs
     //   - (7) last: it tells every launch that exists by then, at either end of the model, the boundary's quantisation
     create_operators(b);
     rule_1_2_3_first_level(b);
@@ -484,6 +512,7 @@ ModelGroups build_groups(const ParsedModel &pm, int device, bool autotune) {
     rule_6_fc_chains(b);
     rule_6a_conv_pool(b);
     rule_6b_shortcut_add(b);
+    rule_6c_side_concat(b);
     rule_7_boundaries(b);
     return std::move(b.g);
 }

@@ -24,7 +24,8 @@ struct ModelGroups {
     };
     std::vector<Stage> stages;
     // shortcut[i] != nullptr: ADD i and the side operator whose output it reads (ParsedModel::side_of_add) run as ONE launch at the
-    // ADD's index (k_shortcut_add.hip).  The one group whose members need not be neighbours in file order, and the one with two inputs
+    // ADD's index (k_shortcut_add.hip) -- or CONCATENATION i and its side operator (k_side_concat.hip).  The one group whose members
+    // need not be neighbours in file order, and the one with two inputs
     std::vector<FusedImpl *> shortcut;
     // the first / last operator that launches anything (leading Reshapes alias the input -- speech.tflite starts with one --
     // trailing ones the output): ops.size() / -1 where there is none
@@ -47,12 +48,15 @@ struct ModelGroups {
 };
 
 // What the rules ask of the parsed model alone (host only; tests/cpp/shortcut_route.cpp prints them):
-// would operators first .. last as ONE launch swallow a tensor that has to exist in memory, an ADD, or a side operator?
+// would operators first .. last as ONE launch swallow a tensor that has to exist in memory, a join (ADD, CONCATENATION), or a side operator?
 bool group_splits(const ParsedModel &pm, size_t first, size_t last);
 // rule (6b) by everything the file says: the side operator that forms one shortcut_add_rt launch with ADD `add` (geometry, filter zero
 // points in the i8 domain, finite constants: shortcut_add_class), or -1 -- no side operator there, or one outside the class
 int shortcut_candidate(const ParsedModel &pm, size_t add);
 bool shortcut_add_class(const OpSpec &conv, bool zero_wzp, bool finite); // (fused_heads.hip)
+// rule (6c), the same for a CONCATENATION join: the side operator that forms one side_concat_rt launch with it, or -1
+int side_concat_candidate(const ParsedModel &pm, size_t join);
+bool side_concat_class(const OpSpec &conv, int run_channels, bool zero_wzp, bool finite); // (fused_heads.hip)
 
 // Operators and every group the grouping rules find, built in a local: a failure half way (a HIP error, OOM, a geometry an
 // operator rejects) destroys what exists and throws.  autotune: time the run-time-geometry chain candidates on the device

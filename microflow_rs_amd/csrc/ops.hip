@@ -779,7 +779,7 @@ void create_softmax(OpImpl &op, const OpSpec &s, int xr) {
 // ADD: no weights; the constants of both domains the operator is run in (kernels.hpp: AddArgs)
 void create_add(OpImpl &op, const OpSpec &s, int lo, int hi) {
     if (!s.add_elems) fail(MF_ERR_INVALID_ARG, "add: bad arguments");
-    op.in_elems = op.out_elems = s.add_elems;
+    op.in_elems = op.in2_elems = op.out_elems = s.add_elems;
     k::AddArgs &a = op.add;
     const int off = s.u8 ? 0 : 128;
     a.ca = s.add_ca, a.cb = s.add_cb, a.ka = (float)(off + s.add_za), a.kb = (float)(off + s.add_zb);
@@ -793,6 +793,31 @@ void create_add(OpImpl &op, const OpSpec &s, int lo, int hi) {
     op.cus = cus;
     op.generic_name = "add_generic";
     op.fast = OpImpl::ADD_C16, op.fast_name = op.add_fma ? "add_c16<fma>" : "add_c16"; // taken where all three pointers are 16-byte aligned
+}
+
+// CONCATENATION: no weights; the constants of both domains the operator is run in (kernels.hpp: ConcatArgs).  No activation: the
+// clamp is T's range
+void create_concat(OpImpl &op, const OpSpec &s) {
+    if (!s.cat_rows || s.cat_ca <= 0 || s.cat_cb <= 0 || (long long)s.cat_ca + s.cat_cb > 0x7fffffffll) fail(MF_ERR_INVALID_ARG, "concatenation: bad arguments");
+    if (s.cat_rows > (~(size_t)0 >> 2) / ((size_t)s.cat_ca + (size_t)s.cat_cb)) fail(MF_ERR_INVALID_ARG, "concatenation: bad arguments");
+    op.in_elems = s.cat_rows * (size_t)s.cat_ca, op.in2_elems = s.cat_rows * (size_t)s.cat_cb;
+    op.out_elems = op.in_elems + op.in2_elems;
+    k::ConcatArgs &a = op.cat;
+    const int off = s.u8 ? 0 : 128;
+    a.ca = s.add_ca, a.cb = s.add_cb, a.ka = (float)(off + s.add_za), a.kb = (float)(off + s.add_zb);
+    a.zo_f = (float)s.ozp, a.lo_f = s.u8 ? 0.0f : -128.0f, a.hi_f = s.u8 ? 255.0f : 127.0f;
+    a.xin4 = 0x80808080u, a.xout4 = s.u8 ? 0x80808080u : 0u;
+    a.Ca = s.cat_ca, a.Cb = s.cat_cb, a.copy_a = s.cat_copy_a, a.copy_b = s.cat_copy_b;
+    op.cat_ext = a;
+    if (s.u8) op.cat_ext.xin4 = op.cat_ext.xout4 = 0u; // real u8 bytes
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, op.device) != hipSuccess) (void)hipGetLastError(), cus = 0;
+    op.cus = cus;
+    op.generic_name = "concat_generic";
+    // the widest word that divides both slices; the pointers may narrow it at run time (op_run2)
+    const int both = s.cat_ca | s.cat_cb;
+    op.cat_unit = both % 16 == 0 ? 16 : both % 8 == 0 ? 8 : both % 4 == 0 ? 4 : 0;
+    if (op.cat_unit) op.fast = OpImpl::CONCAT_C4, op.fast_name = op.cat_unit == 16 ? "concat_c4<v16>" : op.cat_unit == 8 ? "concat_c4<v8>" : "concat_c4";
 }
 
 // PAD: no weights, no constants; the fill byte is the input zero point as the kernels see stored bytes (u8: the internal domain)
@@ -865,6 +890,7 @@ OpImpl *op_create(int device, const OpSpec &spec) {
     case MF_OP_FULLY_CONNECTED: create_fc(*op, s, dom, lo, hi, xr); break;
     case MF_OP_SOFTMAX: create_softmax(*op, s, xr); break;
     case MF_OP_ADD: create_add(*op, s, lo, hi); break;
+    case MF_OP_CONCATENATION: create_concat(*op, s); break;
     case MF_OP_PAD: create_pad(*op, s); break;
     default: fail(MF_ERR_UNSUPPORTED, "unsupported operator kind " + std::to_string(s.kind));
     }
@@ -887,6 +913,7 @@ void op_destroy(OpImpl *op) {
 }
 
 size_t op_in_elems(const OpImpl *op) { return op->in_elems; }
+size_t op_in2_elems(const OpImpl *op) { return op->in2_elems; }
 size_t op_out_elems(const OpImpl *op) { return op->out_elems; }
 const char *op_kernel_name(const OpImpl *op) {
     return (op->fast != OpImpl::NONE && !op->force_generic) ? op->fast_name.c_str()
@@ -912,6 +939,7 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
     if (!batch) return;
     if (!d_in || !d_out) fail(MF_ERR_INVALID_ARG, "op_run: null device pointer");
     if (op->s.kind == MF_OP_ADD) fail(MF_ERR_INVALID_ARG, "op_run: an ADD has two inputs (mf_op_run2)");
+    if (op->s.kind == MF_OP_CONCATENATION) fail(MF_ERR_INVALID_ARG, "op_run: a CONCATENATION has two inputs (mf_op_run2)");
     hipStream_t s = (hipStream_t)stream;
     const OpSpec &sp = op->s;
     // the fast kernels move 4- and 16-byte words (vector loads, LDS-DMA, packed stores): buffers that are not 16-byte
@@ -1068,7 +1096,29 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
 }
 
 // ADD.  The output may be exactly one of the inputs; add_c16 where all three pointers are 16-byte aligned, else the byte-wise kernel
+// CONCATENATION.  The output overlaps neither input; concat_c4 on the widest word (16, 8, 4 bytes) that divides Ca, Cb and all three
+// pointers, else the byte-wise kernel
+static void run_concat(OpImpl *op, const int8_t *d_a, const int8_t *d_b, size_t batch, int8_t *d_out, void *stream, bool external) {
+    if (!batch) return;
+    if (!d_a || !d_b || !d_out) fail(MF_ERR_INVALID_ARG, "op_run2: null device pointer");
+    if (batch > (~(size_t)0 >> 1) / op->out_elems) fail(MF_ERR_INVALID_ARG, "batch too large");
+    const uintptr_t o = (uintptr_t)d_out, a = (uintptr_t)d_a, b = (uintptr_t)d_b;
+    const size_t na = batch * op->in_elems, nb = batch * op->in2_elems, no = batch * op->out_elems;
+    if ((a < o + no && o < a + na) || (b < o + no && o < b + nb)) fail(MF_ERR_INVALID_ARG, "op_run2: the output overlaps an input");
+    if (external) MF_HIP(hipSetDevice(op->device));
+    hipStream_t s = (hipStream_t)stream;
+    const k::ConcatArgs &p = external ? op->cat_ext : op->cat;
+    const size_t rows = batch * op->s.cat_rows;
+    const uintptr_t bits = a | b | o;
+    int unit = op->force_generic ? 0 : op->cat_unit;
+    while (unit && (bits & (uintptr_t)(unit - 1))) unit = unit > 4 ? unit / 2 : 0;
+    if (unit) k::launch_concat_c4(d_a, d_b, d_out, p, rows, unit, op->cus, s);
+    else k::launch_concat_generic(d_a, d_b, d_out, p, rows, s);
+    MF_HIP(hipGetLastError());
+}
+
 void op_run2(OpImpl *op, const int8_t *d_a, const int8_t *d_b, size_t batch, int8_t *d_out, void *stream, bool external) {
+    if (op->s.kind == MF_OP_CONCATENATION) return run_concat(op, d_a, d_b, batch, d_out, stream, external);
     if (op->s.kind != MF_OP_ADD) fail(MF_ERR_INVALID_ARG, "op_run2: the operator has one input (mf_op_run)");
     if (!batch) return;
     if (!d_a || !d_b || !d_out) fail(MF_ERR_INVALID_ARG, "op_run2: null device pointer");
@@ -1091,6 +1141,7 @@ void op_run2(OpImpl *op, const int8_t *d_a, const int8_t *d_b, size_t batch, int
 // The C ABI's mf_op_run: a u8 operator takes and returns real u8 bytes.
 void op_run_external(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream) {
     if (op->s.kind == MF_OP_ADD) fail(MF_ERR_INVALID_ARG, "op_run: an ADD has two inputs (mf_op_run2)");
+    if (op->s.kind == MF_OP_CONCATENATION) fail(MF_ERR_INVALID_ARG, "op_run: a CONCATENATION has two inputs (mf_op_run2)");
     MF_HIP(hipSetDevice(op->device)); // the operator's buffers and kernels live on its device
     if (!op->s.u8) return op_run(op, d_in, batch, d_out, stream);
     if (!batch) return;

@@ -66,7 +66,7 @@ struct OpImpl {
     bool finite_consts = true; // A / S all finite (the shape-specialised and fused epilogues assume it)
     std::string generic_name, fast_name;
     enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM, FC_RT,
-                CONV_GEMM, DW_GEMM, FC_SPARSE24, MAXPOOL_C4, ADD_C16, PAD_C4 } fast = NONE;
+                CONV_GEMM, DW_GEMM, FC_SPARSE24, MAXPOOL_C4, ADD_C16, PAD_C4, CONCAT_C4 } fast = NONE;
     int *d_rowsum = nullptr; // FC_MFMA / FC_SPARSE24 with wzp != 0: per-row input sums
     size_t rowsum_cap = 0, rowsum_rows = 0; // (ints allocated; the row count the counter pairs currently sit behind)
     int8_t *d_ext = nullptr; // op_run_external on a u8 operator: input moved to the i8 domain
@@ -118,6 +118,9 @@ struct OpImpl {
     k::AddArgs add{}, add_ext{}; // ADD in the internal domain (the model runtime) and on real bytes of T (mf_op_run2); the same for i8
     int cus = 0;                 // ... the device's CU count (add_c16's grid)
     bool add_fma = false;        // ... the gated form was admitted for these constants (hostmath.cpp: h_add_fma_form)
+    k::ConcatArgs cat{}, cat_ext{}; // CONCATENATION in the internal domain and on real bytes of T (mf_op_run2); the same for i8
+    size_t in2_elems = 0;        // ADD, CONCATENATION: the second input's elements per inference
+    int cat_unit = 0;            // ... bytes per word of concat_c4 on 16-byte aligned pointers: 16, 8 or 4 (0: Ca or Cb is no multiple of 4)
     k::PadArgs padargs{};        // PAD (k_pad.hip)
     int pad_unit = 0;            // ... bytes per word of pad_c4: 4 or 16 (0: the shape has no word kernel)
     k::FcArgs fc{};

@@ -77,6 +77,7 @@ Switches switches_parse() {
     s.conv_pool_all = env_set("MF_CONV_POOL_ALL");
     s.no_pair_wz = env_set("MF_NO_PAIR_WZ");
     s.no_shortcut_add = env_set("MF_NO_SHORTCUT_ADD");
+    s.no_side_concat = env_set("MF_NO_SIDE_CONCAT");
     s.pair_wz_gmul = (int)env_ll("MF_PAIR_WZ_GMUL", 2);
     s.no_conv_gemm = env_set("MF_NO_CONV_GEMM");
     s.no_dw_gemm = env_set("MF_NO_DW_GEMM");

@@ -241,7 +241,7 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
     int last_add = -1;
     // ... and with a side operator (one Conv2D on a skip edge, below): the one whose ADD has not come yet, or -1
     int pending_side = -1;
-    // who reads tensor t behind operator `from`: ADDs (either input) and other operators (input 0)
+    // who reads tensor t behind operator `from`: joins -- ADDs and CONCATENATIONs -- (any input) and other operators (input 0)
     auto readers_behind = [&](int32_t t, uint32_t from, int &adds, int &others) {
         adds = others = 0;
         for (uint32_t k = from + 1; k < operators.size(); ++k) {
@@ -249,8 +249,13 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             const uint32_t c = o.scalar<uint32_t>(0, 0);
             const Vec in_k = vec(o, 1);
             if (c >= opcodes.size() || !in_k.size()) continue; // (refused when the walk reaches it)
-            if (opcodes.table(c).scalar<int8_t>(0, 0) == MF_OP_ADD) adds += in_k.get<int32_t>(0) == t || (in_k.size() > 1 && in_k.get<int32_t>(1) == t);
-            else others += in_k.get<int32_t>(0) == t;
+            const int code_k = opcodes.table(c).scalar<int8_t>(0, 0);
+            if (code_k == MF_OP_ADD) adds += in_k.get<int32_t>(0) == t || (in_k.size() > 1 && in_k.get<int32_t>(1) == t);
+            else if (code_k == MF_OP_CONCATENATION) {
+                bool reads = false;
+                for (uint32_t j = 0; j < in_k.size(); ++j) reads = reads || in_k.get<int32_t>(j) == t;
+                adds += reads;
+            } else others += in_k.get<int32_t>(0) == t;
         }
     };
     // the non-linear graphs that stay refused keep the chain check's answer, with the reason behind it
@@ -279,7 +284,7 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
         const int32_t running_index = prev_index;
         ParsedOp po;
         po.kind = code;
-        if (code != MF_OP_ADD) { // (an ADD checks its own inputs)
+        if (code != MF_OP_ADD && code != MF_OP_CONCATENATION) { // (a join checks its own inputs)
             // A side operator: ONE Conv2D on a skip edge.  Its input 0 is a tensor T of the chain, by index -- the model input or an
             // earlier operator's output -- that the main chain also continues from: either T is not the running value any more (the
             // side operator stands between the main operators or in front of its ADD), or it still is and a later operator reads
@@ -472,7 +477,7 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
                 if (out_index[j] == is) src = (int)j;
             if (src == -2) refuse("the other input is no earlier tensor of the chain");
             for (const ParsedOp &e : pm.ops)
-                if (e.kind == MF_OP_ADD && e.skip_src == src) refuse("a fork tensor is used twice");
+                if (e.join() && e.skip_src == src) refuse("a fork tensor is used twice");
             // (a side operator's output: T and S count as one skip, alive from T's producer -- checked at the side operator -- to here)
             const bool via_side = src >= 0 && pm.ops[(size_t)src].side();
             if (pending_side >= 0 && src != pending_side) refuse("a side operator while another skip is alive");
@@ -494,6 +499,74 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             if (real < 0) pm.input_skip = true;
             else if (kept > pm.max_fork_elems) pm.max_fork_elems = kept;
             if (via_side && po.in_elems > pm.max_fork_elems) pm.max_fork_elems = po.in_elems;
+            pending_side = -1;
+            last_add = (int)oi;
+            break;
+        }
+        case MF_OP_CONCATENATION: { // not in the reference (lib.rs:148 answers "unsupported operator: 2"): the contract is include/microflow_amd.h's
+            // A second kind of join beside ADD, in the same graph form: it reads the running value (in either position) and ONE other
+            // tensor -- an earlier tensor of the chain or the side operator's output -- along the last axis
+            auto refuse = [](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: 2 (CONCATENATION: " + why + ")"); };
+            if (ins.size() != 2) refuse("it needs exactly two inputs");
+            const int32_t ia = ins.get<int32_t>(0), ib = ins.get<int32_t>(1);
+            TensorInfo tb = read_tensor(tensors, buffers, ib);
+            if (in.data_len || tb.data_len) refuse("a constant operand");
+            for (const TensorInfo *t : {&in, &tb, &out}) {
+                if ((t->type != TT_INT8 && t->type != TT_UINT8) || (t->type == TT_UINT8) != pm.u8) refuse("mixed element types");
+                need_quant(*t, "CONCATENATION");
+                if (t->scale.size() != 1 || t->zp.size() != 1) refuse("per-channel quantisation on an operand");
+                if (!(t->scale[0] > 0.0f) || !std::isfinite(t->scale[0]))
+                    fail(MF_ERR_INVALID_MODEL, "invalid model: CONCATENATION scales must be finite and positive");
+            }
+            // ConcatenationOptions { axis:0 fused_activation_function:1 }
+            if (opt.scalar<int8_t>(1, 0) != MF_ACT_NONE) refuse("a fused activation");
+            if (ia == ib) refuse("both inputs are the same tensor");
+            if (ia != running_index && ib != running_index) refuse("neither input is the running value");
+            po.run_input = ia == running_index ? 0 : 1;
+            const int32_t is = po.run_input == 0 ? ib : ia;
+            int src = -2;
+            if (is == g_in.get<int32_t>(0)) src = -1;
+            for (size_t j = 0; j < out_index.size(); ++j)
+                if (out_index[j] == is) src = (int)j;
+            if (src == -2) refuse("the other input is no earlier tensor of the chain");
+            for (const ParsedOp &e : pm.ops)
+                if (e.join() && e.skip_src == src) refuse("a fork tensor is used twice");
+            const bool via_side = src >= 0 && pm.ops[(size_t)src].side();
+            if (pending_side >= 0 && src != pending_side) refuse("a side operator while another skip is alive");
+            if (!via_side && src < last_add) refuse("two skip tensors alive at once (overlapping or nested skips)");
+            const size_t rank = in.shape.size();
+            if (rank < 2 || rank > 4 || tb.shape.size() != rank || out.shape.size() != rank) refuse("tensor rank must be 2 to 4, the same for all");
+            int axis = opt.scalar<int32_t>(0, 0);
+            if (axis < 0) axis += (int)rank;
+            if (axis != (int)rank - 1) refuse("an axis other than the last");
+            size_t rows = 1;
+            for (size_t d = 0; d + 1 < rank; ++d) {
+                if (in.shape[d] != tb.shape[d]) refuse("the inputs differ in another dimension than the axis");
+                rows *= (size_t)in.shape[d];
+            }
+            if (rank > 2 && in.shape[0] != 1) refuse("tensor batch must be 1");
+            const int Ca = in.shape[rank - 1], Cb = tb.shape[rank - 1];
+            if (Ca <= 0 || Cb <= 0 || !rows) fail(MF_ERR_INVALID_MODEL, "invalid model: bad tensor dimension");
+            for (size_t d = 0; d < rank; ++d)
+                if ((int64_t)out.shape[d] != (d + 1 < rank ? (int64_t)in.shape[d] : (int64_t)Ca + Cb))
+                    fail(MF_ERR_INVALID_MODEL, "invalid model: CONCATENATION output shape is not the two inputs joined");
+            set_shapes(po, po.run_input == 0 ? in : tb, out, pm.u8); // (in_scale / in_zp / in_elems: the running operand's)
+            po.skip_src = src;
+            po.act = MF_ACT_NONE;
+            po.a_scale = in.scale[0], po.b_scale = tb.scale[0];
+            po.a_zp = zp_of(in.zp[0], pm.u8), po.b_zp = zp_of(tb.zp[0], pm.u8);
+            po.cat_rows = rows, po.cat_ca = Ca, po.cat_cb = Cb, po.N = Ca + Cb;
+            po.c0.resize(1), po.c1.resize(1);
+            h_preprocess_concatenation(po.a_scale, po.b_scale, out.scale[0], po.c0.data(), po.c1.data());
+            po.cat_copy_a = h_concat_identity(po.a_scale, po.a_zp, out.scale[0], po.out_zp, po.c0[0]);
+            po.cat_copy_b = h_concat_identity(po.b_scale, po.b_zp, out.scale[0], po.out_zp, po.c1[0]);
+            // what has to stay in memory up to here, as for an ADD: the skip tensor itself or, through a side operator, its input T;
+            // the side operator's output lives in a fork buffer too
+            const int real = pm.launcher(via_side ? pm.ops[(size_t)src].side_src : src);
+            const size_t kept = via_side ? pm.ops[(size_t)src].in_elems : po.skip_elems();
+            if (real < 0) pm.input_skip = true;
+            else if (kept > pm.max_fork_elems) pm.max_fork_elems = kept;
+            if (via_side && po.skip_elems() > pm.max_fork_elems) pm.max_fork_elems = po.skip_elems();
             pending_side = -1;
             last_add = (int)oi;
             break;

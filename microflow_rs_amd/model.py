@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 
-OP_NAMES = {0: "add", 1: "average_pool_2d", 3: "conv_2d", 4: "depthwise_conv_2d", 9: "fully_connected", 17: "max_pool_2d",
+OP_NAMES = {0: "add", 1: "average_pool_2d", 2: "concatenation", 3: "conv_2d", 4: "depthwise_conv_2d", 9: "fully_connected", 17: "max_pool_2d",
             22: "reshape", 25: "softmax", 34: "pad", 40: "mean"}
 
 
@@ -64,7 +64,7 @@ class Model:
         return mode.value
 
     def op_skip(self, i):
-        """(source, running_input) of ADD i: the operator whose output it reads beside the running value (-1: the model input) and
+        """(source, running_input) of join i (an ADD or a CONCATENATION): the operator whose output it reads beside the running value (-1: the model input) and
         which of its two inputs (0 or 1) the running value is.  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
         src, pos = C.c_int(0), C.c_int(0)
         _lib.check(_lib.lib().mf_model_get_op_skip(self._h, int(i), C.byref(src), C.byref(pos)))
@@ -78,7 +78,7 @@ class Model:
 
     def op_source(self, i):
         """the operator whose output side operator i (the Conv2D on a skip edge) reads instead of the running value; -1: the model
-        input.  The ADD behind it names i as its skip (op_skip).  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
+        input.  The ADD or CONCATENATION behind it names i as its skip (op_skip).  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
         src = C.c_int(0)
         _lib.check(_lib.lib().mf_model_get_op_source(self._h, int(i), C.byref(src)))
         return src.value

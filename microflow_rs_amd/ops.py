@@ -7,6 +7,7 @@ names, argument order and meaning, executed by the HIP kernels behind the C ABI.
     average_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)
     max_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)   (not in the reference)
     add(a, b, output_scale, output_zero_point, options, constants)                                        (not in the reference)
+    concatenation(a, b, output_scale, output_zero_point, options, constants)                              (not in the reference)
     pad(input, pads)                                                                                      (not in the reference)
     softmax(input, output_scale, output_zero_point)
     reshape(input, output_shape)
@@ -89,9 +90,10 @@ def _fn(name, dtype):
 class PreparedOp:
     """A prepared operator (mf_op): weights + folded constants resident in HBM."""
 
-    def __init__(self, handle, in_tail, out_tail, dtype=np.int8, binary=False):
+    def __init__(self, handle, in_tail, out_tail, dtype=np.int8, binary=False, in2_tail=None):
         self._h = handle
-        self.binary = binary   # an ADD: two inputs (mf_op_run2)
+        self.binary = binary   # an ADD or a CONCATENATION: two inputs (mf_op_run2)
+        self.in2_tail = None if in2_tail is None else tuple(in2_tail)   # the second input's shape where it differs (CONCATENATION)
         self.in_tail, self.out_tail = tuple(in_tail), tuple(out_tail)
         self.dtype = dtype
 
@@ -117,16 +119,20 @@ class PreparedOp:
 
     def __call__(self, x, y=None):
         """x: numpy (host) or torch cuda tensor of the operator's element type (int8 / uint8),
-        shape [..batch] + in_tail.  An ADD takes two of them, of one shape: x is operand a, y operand b."""
+        shape [..batch] + in_tail.  An ADD takes two of them, of one shape: x is operand a, y operand b; a CONCATENATION's y
+        has shape [..batch] + in2_tail."""
         torch = _torch()
         if self.binary != (y is not None):
             raise TypeError("the operator takes %s" % ("two inputs" if self.binary else "one input"))
         xt, is_np, tdt = self._stage(x)
         if self.binary:
             yt = self._stage(y)[0]
-            if tuple(yt.shape) != tuple(xt.shape) or yt.device != xt.device:
+            if self.in2_tail is None and (tuple(yt.shape) != tuple(xt.shape) or yt.device != xt.device):
                 raise ValueError("the two inputs of an ADD must have one shape and one device")
         in_elems = int(np.prod(self.in_tail))
+        if self.binary and self.in2_tail is not None and (
+                yt.device != xt.device or yt.numel() * in_elems != xt.numel() * int(np.prod(self.in2_tail))):
+            raise ValueError("the two inputs of a CONCATENATION must hold the same rows on one device")
         if xt.numel() % in_elems:
             raise ValueError("input size %d is not a multiple of %d" % (xt.numel(), in_elems))
         batch = xt.numel() // in_elems
@@ -320,6 +326,47 @@ def add(a, b, output_scale, output_zero_point, options: AddOptions, constants=No
     tail = shp[-3:] if len(shp) >= 3 else shp[-2:]
     op = prepare_add(tail, (a.scale[0], a.zero_point[0]), (b.scale[0], b.zero_point[0]),
                      (output_scale[0], output_zero_point[0]), options, constants, dtype=_elem(a.buffer))
+    return type(a)(op(a.buffer, b.buffer), list(output_scale), list(output_zero_point))
+
+
+@dataclass
+class ConcatenationOptions:               # (not in the reference) tflite.fbs ConcatenationOptions; no fused activation
+    axis: int = -1
+
+
+def preprocess_concatenation(a_scale, b_scale, output_scale):
+    """(ca, cb) = (a_scale / output_scale, b_scale / output_scale) in f32, as the library's host computes them."""
+    ca, cb = C.c_float(0), C.c_float(0)
+    _lib.check(_lib.lib().mf_preprocess_concatenation(float(a_scale), float(b_scale), float(output_scale), C.byref(ca), C.byref(cb)))
+    return np.float32(ca.value), np.float32(cb.value)
+
+
+def prepare_concatenation(rows_or_shape, Ca, Cb, a_q, b_q, out_q, constants=None, dtype=np.int8):
+    """rows_or_shape: the axes in front of the last one (their product is `rows`); a_q, b_q, out_q: (scale, zero_point) of the two
+    inputs and the output; constants: (ca, cb), computed when None."""
+    lead = (int(rows_or_shape),) if np.isscalar(rows_or_shape) else tuple(int(d) for d in rows_or_shape)
+    if constants is None:
+        constants = preprocess_concatenation(a_q[0], b_q[0], out_q[0])
+    h = C.c_void_p()
+    _lib.check(_fn("mf_concatenation_create", dtype)(
+        _device(), int(np.prod(lead)), int(Ca), int(Cb), float(a_q[0]), int(a_q[1]), float(b_q[0]), int(b_q[1]), float(out_q[0]),
+        int(out_q[1]), float(constants[0]), float(constants[1]), C.byref(h)))
+    return PreparedOp(h, lead + (int(Ca),), lead + (int(Ca) + int(Cb),), dtype, binary=True, in2_tail=lead + (int(Cb),))
+
+
+def concatenation(a, b, output_scale, output_zero_point, options: ConcatenationOptions = None, constants=None):
+    """CONCATENATION (TFLite builtin 2; the reference has none) of two tensors along the last axis, per-tensor quantisation: every
+    element of input i becomes T::from(roundf(f32(zo) + c_i * f32(x - z_i))), every step rounded to f32 (include/microflow_amd.h);
+    a slice whose quantisation is the output's is copied.  The operand order is kept."""
+    shp_a, shp_b = tuple(a.buffer.shape), tuple(b.buffer.shape)
+    nd = 3 if isinstance(a, Tensor4D) else 2   # axes of one inference in the buffer: H, W, C or rows, cols
+    axis = -1 if options is None else int(options.axis)
+    if axis not in (-1, 3 if isinstance(a, Tensor4D) else 1):   # (counted in the tensor's own rank: [1][H][W][C] or [rows][cols])
+        raise ValueError("concatenation: only the last axis is supported")
+    if shp_a[:-1] != shp_b[:-1]:
+        raise ValueError("concatenation: the inputs differ in another dimension than the axis")
+    op = prepare_concatenation(shp_a[-nd:-1], shp_a[-1], shp_b[-1], (a.scale[0], a.zero_point[0]), (b.scale[0], b.zero_point[0]),
+                               (output_scale[0], output_zero_point[0]), constants, dtype=_elem(a.buffer))
     return type(a)(op(a.buffer, b.buffer), list(output_scale), list(output_zero_point))
 
 

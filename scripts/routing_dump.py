@@ -53,7 +53,10 @@ def corpus_all():
     import tflite_writer as tw
     rng = np.random.default_rng
     return corpus() + [("keras_mobilenet_v2-96-w0.25", lambda: tw.keras_mobilenet_v2(rng(40), 96, 0.25)),   # PAD, MEAN
-                       ("keras_resnet_stem-64", lambda: tw.keras_resnet_stem(rng(41), 64))]
+                       ("keras_resnet_stem-64", lambda: tw.keras_resnet_stem(rng(41), 64)),
+                       ("squeezenet-64", lambda: tw.squeezenet(rng(42), 64)),                                   # CONCATENATION
+                       ("fire_net-8x8x64-s2", lambda: tw.fire_net(rng(43), (8, 8, 64), [(16, 64, 64), (32, 128, 128, 2, "31")], head=10)),
+                       ("dense_net-8x8x16", lambda: tw.dense_net(rng(44), (8, 8, 16), (16, 32), head=10))]
 
 
 def one(idx):

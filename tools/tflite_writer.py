@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Writes small .tflite models made of the six operators MicroFlow supports
-(microflow-macros/src/lib.rs:138-148), MaxPool2D, ADD (identity and projection shortcuts), PAD and MEAN, for randomized model-level tests: parser + constant
+(microflow-macros/src/lib.rs:138-148), MaxPool2D, ADD (identity and projection shortcuts), CONCATENATION (fire modules and
+identity skips), PAD and MEAN, for randomized model-level tests: parser + constant
 preparation + kernel routing + run, product vs oracle.  Only the fields the MicroFlow front
 end reads are written (tflite.fbs field ids as used by microflow-macros/src/ops/*.rs).
 
@@ -20,6 +21,8 @@ Each layer dict (all quantization parameters are given, nothing is derived):
     add               skip (the layer whose output is the second operand; -1: the model input), swap (False: inputs [running, skip];
                       True: [skip, running]), act, out_shape, out_q.  Negative tests place the inputs by hand: inputs = a list of
                       "cur", a layer index (-1: the model input) or dict(shape, q, type=, data=) for a fresh tensor
+    concatenation     skip, swap and inputs as add's (the join is along `axis`, default -1: the last), out_shape, out_q; act (a file that
+                      loads carries none)
     reshape           out_shape
     softmax           out_shape, out_q
     pad               pads ((top, bottom), (left, right)), out_shape, out_q (the input's, for a model that loads).  Negative tests:
@@ -34,10 +37,10 @@ import numpy as np
 from make_fc_model import FB, Table, TableVec, Vec, emit, prune_2_4
 
 INT32, UINT8, INT64, INT8 = 2, 3, 4, 9
-OPCODES = {"add": 0, "average_pool_2d": 1, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "max_pool_2d": 17, "reshape": 22,
+OPCODES = {"add": 0, "average_pool_2d": 1, "concatenation": 2, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "max_pool_2d": 17, "reshape": 22,
            "softmax": 25, "pad": 34, "mean": 40, "padv2": 60, "mirror_pad": 100}
 # BuiltinOptions union type ids (tflite.fbs)
-OPT_TYPE = {"add": 11, "conv_2d": 1, "depthwise_conv_2d": 2, "average_pool_2d": 5, "max_pool_2d": 5, "fully_connected": 8, "softmax": 9,
+OPT_TYPE = {"add": 11, "concatenation": 10, "conv_2d": 1, "depthwise_conv_2d": 2, "average_pool_2d": 5, "max_pool_2d": 5, "fully_connected": 8, "softmax": 9,
             "reshape": 17, "pad": 22, "mean": 27, "padv2": 43, "mirror_pad": 77}
 ACT = {None: 0, "none": 0, "relu": 1, "relu6": 3, 0: 0, 1: 1, 3: 3}
 PAD = {"same": 0, "valid": 1, 0: 0, 1: 1}
@@ -118,7 +121,7 @@ def build_model(input_shape, input_q, layers, elem=INT8):
             out = add_tensor(L["out_shape"], elem, 0, *L["out_q"])
             opts = Table({0: ("f32", 1.0)})
             ins = [cur]
-        elif op == "add":
+        elif op in ("add", "concatenation"):
             def place(item):
                 if isinstance(item, dict):
                     data = item.get("data")
@@ -129,7 +132,10 @@ def build_model(input_shape, input_q, layers, elem=INT8):
             else:
                 ins = [place(L["skip"]), cur] if L.get("swap") else [cur, place(L["skip"])]
             out = add_tensor(L["out_shape"], L.get("out_type", elem), 0, *L["out_q"])
-            opts = Table({0: ("i8", ACT[L.get("act")])})  # AddOptions { fused_activation_function:0 }
+            if op == "add":
+                opts = Table({0: ("i8", ACT[L.get("act")])})  # AddOptions { fused_activation_function:0 }
+            else:            # ConcatenationOptions { axis:0 fused_activation_function:1 }
+                opts = Table({0: ("i32", int(L.get("axis", -1))), 1: ("i8", ACT[L.get("act")])})
         elif op == "pad":
             pv = np.asarray(L["paddings"] if "paddings" in L else ((0, 0),) + tuple(tuple(p) for p in L["pads"]) + ((0, 0),))
             ptype = L.get("pad_type", INT32)
@@ -687,6 +693,122 @@ def resnet8_layers(rng, elem=INT8, side="first", input_shape=(32, 32, 3), widths
 
 def resnet8(rng, elem=INT8, **kw):
     return build_model(*resnet8_layers(rng, elem, **kw), elem)
+
+
+def _concat_layer(skip, shape, q, swap=False, axis=-1):
+    """one CONCATENATION layer dict: the running tensor and the output of layer `skip` (-1: the model input) joined along `axis`
+    into `shape` with quantisation q; swap: the skip tensor is input a"""
+    return dict(op="concatenation", skip=int(skip), swap=bool(swap), axis=int(axis), out_shape=tuple(int(v) for v in shape),
+                out_q=(float(q[0]), int(q[1])))
+
+
+def fire_layers(rng, shape, q, fire, base=0, elem=INT8, act="relu", e1_first=True, identity=(True, True), side_wzp="none", act_scale=None):
+    """One SqueezeNet fire module on a tensor shape = (H, W, C) of quantisation q, whose producer is layer base - 1 of the model:
+    fire = (S, E1, E3[, stride[, order]]) -- a squeeze 1x1 Conv2D to S channels, then two expands that both read it, 1x1 to E1 and
+    3x3 SAME to E3 channels (both at `stride`, 1 or 2), then the CONCATENATION of the two along the channels.  order: "13" writes the
+    1x1 expand first, which makes it the side operator and the 3x3 the main chain; "31" the other way round.  e1_first: the join
+    reads [e1, e3], else [e3, e1].  identity = (e1, e3): a slice that carries the join's output quantisation, as the converter
+    writes both; a slice that does not gets a scale 0.5 .. 1.4 times the output's.  -> (layers, (H, W, C), q) of the output"""
+    S, E1, E3 = (int(v) for v in fire[:3])
+    stride = int(fire[3]) if len(fire) > 3 else 1
+    order = fire[4] if len(fire) > 4 else "13"
+    assert order in ("13", "31")
+    H, W, C = (int(v) for v in shape)
+    sq = _conv_layer(rng, (H, W, C), q, False, S, 1, 1, "same", act, elem, act_scale=act_scale)
+    qs = sq["out_q"]
+    e1 = _conv_layer(rng, (H, W, S), qs, False, E1, 1, stride, "same", act, elem, wzp=side_wzp if order == "13" else "none", act_scale=act_scale)
+    e3 = _conv_layer(rng, (H, W, S), qs, False, E3, 3, stride, "same", act, elem, wzp=side_wzp if order == "31" else "none", act_scale=act_scale)
+    oh, ow = e1["out_shape"][1:3]
+    q0 = e1["out_q"]
+    for e, same in ((e1, identity[0]), (e3, identity[1])):
+        e["out_q"] = q0 if same else (float(np.float32(q0[0] * rng.uniform(0.5, 1.4))), e["out_q"][1])
+    qo = q0 if (identity[0] or identity[1]) else (float(np.float32(q0[0] * rng.uniform(0.8, 1.2))), q0[1])
+    first, second = (e1, e3) if order == "13" else (e3, e1)
+    first["side_of"] = base  # (the squeeze is layer `base`; the first expand in the file is the side operator)
+    swap = (order == "13") == bool(e1_first)  # the skip tensor -- the side operator's -- is input a
+    cat = _concat_layer(base + 1, (1, oh, ow, E1 + E3), qo, swap=swap)
+    return [sq, first, second, cat], (oh, ow, E1 + E3), qo
+
+
+def fire_net(rng, input_shape, fires, elem=INT8, head=0, in_q=None, **kw):
+    """Fire modules one behind the other on input_shape = (H, W, C) (fire_layers' arguments), then, with head, AveragePool over the
+    whole image, FullyConnected(head) and Softmax."""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    H, W, C = (int(v) for v in input_shape)
+    in_q = in_q or (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers, shape = in_q, [], (H, W, C)
+    for fire in fires:
+        ls, shape, q = fire_layers(rng, shape, q, fire, base=len(layers), elem=elem, **kw)
+        layers += ls
+    if head:
+        H2, W2, C2 = shape
+        layers.append(dict(op="average_pool_2d", filter=(H2, W2), padding="valid", strides=(H2, W2), act="none", out_shape=(1, 1, 1, C2), out_q=q))
+        layers.append(dict(op="reshape", out_shape=(1, C2), out_q=q))
+        layers.append(_fc_layer(rng, C2, head, q, "none", elem))
+        layers.append(dict(op="softmax", out_shape=(1, head), out_q=(1.0 / 256.0, lo)))
+    return build_model((1, H, W, C), in_q, layers, elem)
+
+
+def dense_net_layers(rng, input_shape, growths, elem=INT8, k=3, swap=(), head=0):
+    """DenseNet-style single-level blocks on input_shape = (H, W, C): block b is a Conv2D k x k SAME (relu) to growths[b] channels on
+    the block's input x and the CONCATENATION concat(x, conv(x)) -- an identity skip; written [conv(x), x] when b is in `swap`.  The
+    join carries x's quantisation, so x's slice is copied and the convolution's is requantised wherever their zero points differ.
+    -> build_model's arguments"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    H, W, C = (int(v) for v in input_shape)
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers = in_q, []
+    for b, g in enumerate(growths):
+        skip = len(layers) - 1
+        layers.append(_conv_layer(rng, (H, W, C), q, False, int(g), k, 1, "same", "relu", elem, act_scale=q[0]))
+        C += int(g)
+        layers.append(_concat_layer(skip, (1, H, W, C), q, swap=b not in swap))  # (swap: the skip tensor x is input a)
+    if head:
+        layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none", out_shape=(1, 1, 1, C), out_q=q))
+        layers.append(dict(op="reshape", out_shape=(1, C), out_q=q))
+        layers.append(_fc_layer(rng, C, head, q, "none", elem))
+        layers.append(dict(op="softmax", out_shape=(1, head), out_q=(1.0 / 256.0, lo)))
+    return (1,) + tuple(int(v) for v in input_shape), in_q, layers
+
+
+def dense_net(rng, input_shape, growths, elem=INT8, **kw):
+    return build_model(*dense_net_layers(rng, input_shape, growths, elem, **kw), elem)
+
+
+def squeezenet_layers(rng, side=64, classes=10, elem=INT8, order="13", fires=None):
+    """SqueezeNet 1.1's layer list at a reduced input side x side x 3: Conv2D 3x3 stride 2 to 64 (relu) -> MaxPool 3x3 stride 2 ->
+    fires (16,64,64) x 2 -> MaxPool -> (32,128,128) x 2 -> MaxPool -> (48,192,192) x 2, (64,256,256) x 2 -> Conv2D 1x1 to `classes`
+    (relu) -> AveragePool over the whole image -> Softmax.  Every convolution carries one output scale (a deep stack keeps its
+    scales), so both slices of every join are copies, as in converter-written files.  fires: another list of stages, each a list of
+    (S, E1, E3), with a MaxPool behind every stage but the last two.  -> build_model's arguments"""
+    lo = 0 if elem == UINT8 else -128
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, lo + 236)))
+    stages = fires or [[(16, 64, 64)] * 2, [(32, 128, 128)] * 2, [(48, 192, 192)] * 2, [(64, 256, 256)] * 2]
+    layers = [_conv_layer(rng, (side, side, 3), in_q, False, 64, 3, 2, "same", "relu", elem, act_scale=in_q[0])]
+    q, (H, W, C) = layers[0]["out_q"], layers[0]["out_shape"][1:]
+
+    def pool():
+        nonlocal H, W
+        H, W = _same_or_valid(H, 3, 2, "valid"), _same_or_valid(W, 3, 2, "valid")
+        layers.append(dict(op="max_pool_2d", filter=(3, 3), padding="valid", strides=(2, 2), act="none", out_shape=(1, H, W, C), out_q=q))
+
+    pool()
+    for si, stage in enumerate(stages):
+        for fire in stage:
+            ls, (H, W, C), q = fire_layers(rng, (H, W, C), q, tuple(fire) + (1, order), base=len(layers), elem=elem, act_scale=in_q[0])
+            layers += ls
+        if si + 2 < len(stages):
+            pool()
+    layers.append(_conv_layer(rng, (H, W, C), q, False, classes, 1, 1, "same", "relu", elem, act_scale=in_q[0]))
+    q = layers[-1]["out_q"]
+    layers.append(dict(op="average_pool_2d", filter=(H, W), padding="valid", strides=(H, W), act="none", out_shape=(1, 1, 1, classes), out_q=q))
+    layers.append(dict(op="reshape", out_shape=(1, classes), out_q=q))
+    layers.append(dict(op="softmax", out_shape=(1, classes), out_q=(1.0 / 256.0, lo)))
+    return (1, side, side, 3), in_q, layers
+
+
+def squeezenet(rng, side=64, classes=10, elem=INT8, **kw):
+    return build_model(*squeezenet_layers(rng, side, classes, elem, **kw), elem)
 
 
 # person_detect_like(quant=...): the head's effective multiplier in_scale * fscale / out_scale (256 products of a byte
