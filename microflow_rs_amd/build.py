@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmicroflow_amd.so")
 SOURCES = ["capi.cpp", "hostmath.cpp", "epi_fma.cpp", "switches.cpp", "tflite.cpp", "model.cpp", "model_groups.cpp", "wimage.cpp", "ops.hip", "fused.hip", "fused_pairs.hip", "fused_heads.hip", "fused_stages.hip", "chain_partition.hip", "k_generic.hip", "k_depthwise.hip",
            "k_pointwise.hip", "k_fused_mm.hip", "k_stage.hip", "k_dwfc.hip", "k_tail3.hip", "k_gemm.hip", "k_rt.hip", "k_quad.hip", "k_quad_mm.hip", "k_chain.hip", "k_pair_band.hip", "k_pair_band_deep.hip", "k_block_band.hip", "k_pair_wz.hip", "k_fc_rt.hip", "k_pool_fc.hip", "k_conv1_fc.hip", "k_fc_f32.hip",
-           "k_conv_gemm.hip", "k_conv_pool.hip", "k_conv_maxpool.hip", "k_add.hip", "k_concat.hip", "k_pad.hip", "k_shortcut_add.hip", "k_side_concat.hip", "k_dw_gemm.hip", "k_fc_sparse.hip", "k_windows.hip", "windows_spec.cpp"]
+           "k_conv_gemm.hip", "k_conv_pool.hip", "k_conv_maxpool.hip", "k_add.hip", "k_concat.hip", "k_pad.hip", "k_side_join.hip", "k_dw_gemm.hip", "k_fc_sparse.hip", "k_windows.hip", "windows_spec.cpp"]
 HEADERS = ["mf_internal.hpp", "model_groups.hpp", "windows_spec.hpp", "mf_switches.hpp", "ops_impl.hpp", "fused_impl.hpp", "wimage.hpp", "kernels.hpp", "k_common.hpp", "k_add.hpp", "k_concat.hpp", "k_fc_layer.hpp", "k_fc_rt_body.hpp", "k_pool_fc_body.hpp", "k_dwtask.hpp", "k_tail.hpp", "k_pair_band_body.hpp", "k_pair_band_body.inc", "k_conv_rows_body.inc", "k_conv_pool_body.inc", "conv_rows_bytes_map.hpp", os.path.join("..", "..", "include", "microflow_amd.h")]
 # -amdgpu-mfma-vgpr-form: MFMA results land in VGPRs (gfx950's register file is unified), which
 # removes one v_accvgpr_read per accumulator element from every fused epilogue.

@@ -351,7 +351,7 @@ static void create_add(int device, bool u8, size_t elems, float sa, int za, floa
         if (!(v > 0.0f) || !std::isfinite(v)) mf::fail(MF_ERR_INVALID_ARG, "add: scales must be finite and positive");
     mf::OpSpec s;
     s.kind = MF_OP_ADD, s.u8 = u8;
-    s.add_elems = elems, s.add_za = za, s.add_zb = zb, s.add_ca = ca, s.add_cb = cb;
+    s.add_elems = elems, s.join_za = za, s.join_zb = zb, s.join_ca = ca, s.join_cb = cb;
     s.oscale = so, s.ozp = zo, s.act = check_act_arg(act);
     wrap_op(mf::op_create(device, s), op);
 }
@@ -398,7 +398,7 @@ static void create_concatenation(int device, bool u8, size_t rows, int Ca, int C
     mf::OpSpec s;
     s.kind = MF_OP_CONCATENATION, s.u8 = u8;
     s.cat_rows = rows, s.cat_ca = Ca, s.cat_cb = Cb;
-    s.add_za = za, s.add_zb = zb, s.add_ca = ca, s.add_cb = cb;
+    s.join_za = za, s.join_zb = zb, s.join_ca = ca, s.join_cb = cb;
     s.cat_copy_a = mf::h_concat_identity(sa, za, so, zo, ca), s.cat_copy_b = mf::h_concat_identity(sb, zb, so, zo, cb);
     s.oscale = so, s.ozp = zo, s.act = MF_ACT_NONE;
     wrap_op(mf::op_create(device, s), op);

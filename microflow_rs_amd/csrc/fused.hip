@@ -115,30 +115,23 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
 void fused_run(FusedImpl *f, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream) {
     if (batch) launch(f, d_in, batch, d_out, 0, (hipStream_t)stream);
 }
-// side_concat_rt: the output overlaps neither T nor the running tensor (the pitches differ); 16-byte words at all three pointers
-static void run_side_concat(FusedImpl *f, const int8_t *d_t, const int8_t *d_run, size_t batch, int8_t *d_out, void *stream) {
-    const k::SideConcatArgs &a = f->sideconcat;
-    const size_t tb = batch * f->a->in_elems, ob = batch * f->b->out_elems, rb = batch * (size_t)a.OH * a.OW * (size_t)a.CR;
-    const uintptr_t t0 = (uintptr_t)d_t, o0 = (uintptr_t)d_out, r0 = (uintptr_t)d_run;
-    if (!d_t || !d_run || !d_out) fail(MF_ERR_INVALID_ARG, "side_concat_rt: null device pointer");
-    if ((t0 < o0 + ob && o0 < t0 + tb) || (r0 < o0 + ob && o0 < r0 + rb)) fail(MF_ERR_INVALID_ARG, "side_concat_rt: the output overlaps an input");
-    if ((t0 | o0 | r0) & 15) fail(MF_ERR_INVALID_ARG, "side_concat_rt: a pointer is not 16-byte aligned");
-    k::launch_side_concat(d_t, d_run, d_out, a, (long long)batch, (hipStream_t)stream);
-    MF_HIP(hipGetLastError());
-}
+// The two-input groups.  Pixels of T are read while others are written, so the output never overlaps T.  shortcut_add_rt: the output
+// may be exactly the running tensor (a lane reads its bytes before it writes them), any other overlap is refused; side_concat_rt: the
+// output overlaps neither input (the pitches differ).  16-byte loads and stores at all three pointers (the runtime's buffers are aligned)
 void fused_run2(FusedImpl *f, const int8_t *d_t, const int8_t *d_run, size_t batch, int8_t *d_out, void *stream) {
-    if (f->kind == FusedImpl::SIDECONCAT) {
-        if (batch) run_side_concat(f, d_t, d_run, batch, d_out, stream);
-        return;
-    }
-    if (f->kind != FusedImpl::SHORTCUT) fail(MF_ERR_INVALID_ARG, "fused_run2: not a two-input group");
+    const bool cat = f->kind == FusedImpl::SIDECONCAT;
+    if (!cat && f->kind != FusedImpl::SHORTCUT) fail(MF_ERR_INVALID_ARG, "fused_run2: not a two-input group");
     if (!batch) return;
-    const size_t tb = batch * f->a->in_elems, ob = batch * f->b->s.add_elems;
+    const std::string name = cat ? "side_concat_rt" : "shortcut_add_rt";
+    const k::SideConvArgs &c = cat ? f->sideconcat.conv : f->shortcut.conv;
+    const size_t tb = batch * f->a->in_elems, ob = batch * (cat ? f->b->out_elems : f->b->s.add_elems);
+    const size_t rb = cat ? batch * (size_t)c.OH * c.OW * (size_t)f->sideconcat.CR : ob;
     const uintptr_t t0 = (uintptr_t)d_t, o0 = (uintptr_t)d_out, r0 = (uintptr_t)d_run;
-    if ((t0 < o0 + ob && o0 < t0 + tb) || (d_out != d_run && r0 < o0 + ob && o0 < r0 + ob)) // (pixels of T are read while others are written)
-        fail(MF_ERR_INVALID_ARG, "shortcut_add_rt: the output overlaps an input");
-    if ((t0 | o0 | r0) & 15) fail(MF_ERR_INVALID_ARG, "shortcut_add_rt: a pointer is not 16-byte aligned"); // (16-byte loads and stores; the runtime's buffers are)
-    k::launch_shortcut_add(d_t, d_run, d_out, f->shortcut, (long long)batch, (hipStream_t)stream);
+    if (!d_t || !d_run || !d_out) fail(MF_ERR_INVALID_ARG, name + ": null device pointer");
+    if ((t0 < o0 + ob && o0 < t0 + tb) || ((cat || d_out != d_run) && r0 < o0 + ob && o0 < r0 + rb)) fail(MF_ERR_INVALID_ARG, name + ": the output overlaps an input");
+    if ((t0 | o0 | r0) & 15) fail(MF_ERR_INVALID_ARG, name + ": a pointer is not 16-byte aligned");
+    if (cat) k::launch_side_concat(d_t, d_run, d_out, f->sideconcat, (long long)batch, (hipStream_t)stream);
+    else k::launch_shortcut_add(d_t, d_run, d_out, f->shortcut, (long long)batch, (hipStream_t)stream);
     MF_HIP(hipGetLastError());
 }
 void fused_run_f32(FusedImpl *f, const void *d_in, bool in_f32, size_t batch, void *d_out, bool out_f32, void *stream) {

@@ -337,64 +337,32 @@ FusedImpl *fused_dwfc_create(OpImpl *dw, FusedImpl *fcsm) {
     return f.release();
 }
 
-// A 1x1 Conv2D on a skip edge and the ADD that reads its result beside the running tensor, as one shortcut_add_rt launch
-// (k_shortcut_add.hip).  The class: KH = KW = 1, strides (1,1) or (2,2), C and N in whole sixteens inside
-// k::shortcut_add_supported, filter zero points all zero in the i8 domain, finite constants on both, neither forced generic.
+// A 1x1 Conv2D on a skip edge and the join -- an ADD or a CONCATENATION -- that reads its result beside
+// the running tensor, as one side_join_rt launch (k_side_join.hip) under the name shortcut_add_rt or side_concat_rt.  The class:
+// KH = KW = 1, strides (1,1) or (2,2), C and N in whole sixteens inside k::shortcut_add_supported -- for a CONCATENATION the running
+// slice in whole sixteens too -- filter zero points all zero in the i8 domain, finite constants on both, neither forced generic.
 // Everything else keeps its two launches.  Operand A is the group's own, built from the convolution's host copy -- alone a stride-2
-// 1x1 runs conv_mm_rt, which keeps another image; the constants, the clamp and the epilogue mode are the convolution's own, as pw_rt
-// takes them (ops.hip: epi_fields); the ADD's block is the operator's internal-domain one.
+// 1x1 runs conv_mm_rt, which keeps another image; the constants, the clamp and the epilogue mode (0 to 2) are the convolution's own, as
+// pw_rt takes them (ops.hip: epi_fields); the join's block is the operator's internal-domain one.
 bool shortcut_add_class(const OpSpec &d, bool zero_wzp, bool finite) {
     return d.kind == MF_OP_CONV_2D && d.KH == 1 && d.KW == 1 && d.sh == d.sw && (d.sh == 1 || d.sh == 2) && zero_wzp && finite &&
            d.OH == (d.H + d.sh - 1) / d.sh && d.OW == (d.W + d.sw - 1) / d.sw && k::shortcut_add_supported(d.C, d.N);
 }
-FusedImpl *fused_shortcut_add_create(OpImpl *conv, OpImpl *add, bool conv_first) {
-    if (switches().no_shortcut_add || !conv || !add || conv->force_generic || add->force_generic) return nullptr;
-    const OpSpec &d = conv->s, &q = add->s;
-    if (q.kind != MF_OP_ADD || conv->device != add->device || d.u8 != q.u8) return nullptr;
-    const bool zero_wzp = std::all_of(conv->h_wzp.begin(), conv->h_wzp.end(), [](int32_t z) { return z == 0; });
-    if (!shortcut_add_class(d, zero_wzp, conv->finite_consts)) return nullptr;
-    if (q.add_elems != (size_t)d.OH * d.OW * d.N || conv->h_w.size() != (size_t)d.N * d.C) return nullptr; // on exactly the convolution's output
-    const k::AddArgs &aa = add->add;
-    if (!std::isfinite(aa.ca) || !std::isfinite(aa.cb)) return nullptr;
-    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::SHORTCUT, conv, add, nullptr, "");
-    k::ShortcutAddArgs &a = f->shortcut;
-    const int NT = d.N / 16, TB = NT < 4 ? NT : 4, NBLK = (NT + TB - 1) / TB, NSPLIT = NBLK <= 1 ? 1 : (NBLK == 2 ? 2 : 4);
-    const std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(conv->h_w.data(), d.C, d.N, 1, TB, NSPLIT); // [N][1][1][C], i8 domain
-    a.pw.wprep = keep(*f, prep.data(), prep.size());
-    a.pw.A = conv->conv.A, a.pw.S = conv->conv.S, a.pw.Kc = conv->conv.Kc, a.pw.wzp = conv->conv.wzp;
-    a.pw.lo_f = conv->conv.lo_f, a.pw.hi_f = conv->conv.hi_f;
-    a.pw.K = d.C, a.pw.N = d.N, a.pw.KS = (d.C + 63) / 64, a.pw.NT = NT, a.pw.patch_pitch = d.N;
-    a.pw.TB = TB, a.pw.NSPLIT = NSPLIT;
-    a.pw.magic = std::min(conv->magic_mode, 2), a.pw.xr = conv->conv.xr;
-    a.add = aa;
-    a.H = d.H, a.W = d.W, a.OH = d.OH, a.OW = d.OW, a.sh = d.sh, a.sw = d.sw;
-    a.conv_first = conv_first ? 1 : 0;
-    f->epi_mode = a.pw.magic;
-    f->name = "shortcut_add_rt<" + std::to_string(d.C) + "," + std::to_string(d.N) + (d.sh == 2 ? ",s2>" : ">");
-    return f.release();
-}
-
-// A 1x1 Conv2D on a skip edge and the CONCATENATION that reads its result beside the running tensor -- a fire module's 1x1 expand and
-// its join -- as one side_concat_rt launch (k_side_concat.hip).  The class is shortcut_add_rt's for the convolution
-// (shortcut_add_class) with the running slice in whole sixteens too; everything else keeps its two launches.  Operand A, the
-// constants, the clamp and the epilogue mode (0 to 2) are set up as for shortcut_add_rt; the join's block is the operator's
-// internal-domain one.
 bool side_concat_class(const OpSpec &d, int run_channels, bool zero_wzp, bool finite) {
     return shortcut_add_class(d, zero_wzp, finite) && k::side_concat_supported(d.C, d.N, run_channels);
 }
-FusedImpl *fused_side_concat_create(OpImpl *conv, OpImpl *cat, bool conv_first) {
-    if (switches().no_side_concat || !conv || !cat || conv->force_generic || cat->force_generic) return nullptr;
-    const OpSpec &d = conv->s, &q = cat->s;
-    if (q.kind != MF_OP_CONCATENATION || conv->device != cat->device || d.u8 != q.u8) return nullptr;
+// What the two creators share: every check that does not depend on the join's own geometry, the group, and the convolution's part of
+// its argument block.  CR: the running tensor's channels at a CONCATENATION (an ADD's class does not ask).  nullptr: outside the class
+static std::unique_ptr<FusedImpl> side_join_group(FusedImpl::Kind kind, OpImpl *conv, OpImpl *join, bool conv_first, int CR) {
+    const bool add = kind == FusedImpl::SHORTCUT;
+    if ((add ? switches().no_shortcut_add : switches().no_side_concat) || !conv || !join || conv->force_generic || join->force_generic) return nullptr;
+    const OpSpec &d = conv->s, &q = join->s;
+    if (q.kind != (add ? MF_OP_ADD : MF_OP_CONCATENATION) || conv->device != join->device || d.u8 != q.u8) return nullptr;
     const bool zero_wzp = std::all_of(conv->h_wzp.begin(), conv->h_wzp.end(), [](int32_t z) { return z == 0; });
-    const int CR = conv_first ? q.cat_cb : q.cat_ca;
-    if (!side_concat_class(d, CR, zero_wzp, conv->finite_consts)) return nullptr;
-    // on exactly the convolution's output: its pixels are the join's rows, its channels the join's slice for that input
-    if (q.cat_rows != (size_t)d.OH * d.OW || (conv_first ? q.cat_ca : q.cat_cb) != d.N || conv->h_w.size() != (size_t)d.N * d.C) return nullptr;
-    const k::ConcatArgs &ca = cat->cat;
-    if (!std::isfinite(ca.ca) || !std::isfinite(ca.cb)) return nullptr;
-    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::SIDECONCAT, conv, cat, nullptr, "");
-    k::SideConcatArgs &a = f->sideconcat;
+    if (!(add ? shortcut_add_class(d, zero_wzp, conv->finite_consts) : side_concat_class(d, CR, zero_wzp, conv->finite_consts))) return nullptr;
+    if (conv->h_w.size() != (size_t)d.N * d.C || !std::isfinite(q.join_ca) || !std::isfinite(q.join_cb)) return nullptr;
+    std::unique_ptr<FusedImpl> f = make_group(kind, conv, join, nullptr, "");
+    k::SideConvArgs &a = add ? f->shortcut.conv : f->sideconcat.conv;
     const int NT = d.N / 16, TB = NT < 4 ? NT : 4, NBLK = (NT + TB - 1) / TB, NSPLIT = NBLK <= 1 ? 1 : (NBLK == 2 ? 2 : 4);
     const std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(conv->h_w.data(), d.C, d.N, 1, TB, NSPLIT); // [N][1][1][C], i8 domain
     a.pw.wprep = keep(*f, prep.data(), prep.size());
@@ -403,11 +371,27 @@ FusedImpl *fused_side_concat_create(OpImpl *conv, OpImpl *cat, bool conv_first) 
     a.pw.K = d.C, a.pw.N = d.N, a.pw.KS = (d.C + 63) / 64, a.pw.NT = NT, a.pw.patch_pitch = d.N;
     a.pw.TB = TB, a.pw.NSPLIT = NSPLIT;
     a.pw.magic = std::min(conv->magic_mode, 2), a.pw.xr = conv->conv.xr;
-    a.cat = ca;
     a.H = d.H, a.W = d.W, a.OH = d.OH, a.OW = d.OW, a.sh = d.sh, a.sw = d.sw;
-    a.CR = CR, a.conv_first = conv_first ? 1 : 0;
+    a.conv_first = conv_first ? 1 : 0;
     f->epi_mode = a.pw.magic;
-    f->name = "side_concat_rt<" + std::to_string(d.C) + "," + std::to_string(d.N) + "," + std::to_string(CR) + (d.sh == 2 ? ",s2>" : ">");
+    f->name = std::string(add ? "shortcut_add_rt<" : "side_concat_rt<") + std::to_string(d.C) + "," + std::to_string(d.N) + (add ? "" : "," + std::to_string(CR)) +
+              (d.sh == 2 ? ",s2>" : ">");
+    return f;
+}
+FusedImpl *fused_shortcut_add_create(OpImpl *conv, OpImpl *add, bool conv_first) {
+    std::unique_ptr<FusedImpl> f = side_join_group(FusedImpl::SHORTCUT, conv, add, conv_first, 0);
+    if (!f || add->s.add_elems != (size_t)conv->s.OH * conv->s.OW * conv->s.N) return nullptr; // on exactly the convolution's output
+    f->shortcut.add = add->add;
+    return f.release();
+}
+FusedImpl *fused_side_concat_create(OpImpl *conv, OpImpl *cat, bool conv_first) {
+    const int CR = !cat ? 0 : conv_first ? cat->s.cat_cb : cat->s.cat_ca;
+    std::unique_ptr<FusedImpl> f = side_join_group(FusedImpl::SIDECONCAT, conv, cat, conv_first, CR);
+    if (!f) return nullptr;
+    // on exactly the convolution's output: its pixels are the join's rows, its channels the join's slice for that input
+    const OpSpec &d = conv->s, &q = cat->s;
+    if (q.cat_rows != (size_t)d.OH * d.OW || (conv_first ? q.cat_ca : q.cat_cb) != d.N) return nullptr;
+    f->sideconcat.cat = cat->cat, f->sideconcat.CR = CR;
     return f.release();
 }
 

@@ -75,10 +75,10 @@ struct FusedImpl {
         bool wz = false; // the convolution has non-zero filter zero points (internal domain)
         bool mx = false; // the pool is a MaxPool2D: conv_maxpool_rt
     } convpool;
-    // SHORTCUT: a 1x1 shortcut convolution + the ADD on its result and the running tensor (k_shortcut_add.hip); a = the convolution, b = the
-    // ADD.  The one kind with TWO inputs: fused_run2, never the launch path of the others
+    // SHORTCUT: a 1x1 shortcut convolution + the ADD on its result and the running tensor (k_side_join.hip); a = the convolution, b = the
+    // ADD.  With SIDECONCAT the kinds with TWO inputs: fused_run2, never the launch path of the others
     k::ShortcutAddArgs shortcut{};
-    // SIDECONCAT: a 1x1 Conv2D on a skip edge + the CONCATENATION of its result and the running tensor (k_side_concat.hip); a = the
+    // SIDECONCAT: a 1x1 Conv2D on a skip edge + the CONCATENATION of its result and the running tensor (k_side_join.hip); a = the
     // convolution, b = the CONCATENATION.  Two inputs, as SHORTCUT: fused_run2
     k::SideConcatArgs sideconcat{};
     // PADCONV: a PAD + the VALID Conv2D / DepthwiseConv2D on its output as one launch of the convolution's own run-time-geometry kernel;

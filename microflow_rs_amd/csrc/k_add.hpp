@@ -1,5 +1,5 @@
 // k_add.hpp -- ADD's arithmetic as device functions: one element, one dword, one 16-byte group.  The contract is DESIGN section 2's
-// (k_add.hip states it); shared by the ADD kernels (k_add.hip) and the shortcut convolution + ADD launch (k_shortcut_add.hip), so that
+// (k_add.hip states it); shared by the ADD kernels (k_add.hip) and the shortcut convolution + ADD launch (k_side_join.hip), so that
 // there is ONE text of it.
 #pragma once
 #include "k_common.hpp"

@@ -1,6 +1,6 @@
 // k_concat.hpp -- CONCATENATION's per-element arithmetic as device functions: one byte, one dword.  The contract is DESIGN section 2's
 // (k_concat.hip states it); shared by the CONCATENATION kernels (k_concat.hip) and the side convolution + CONCATENATION launch
-// (k_side_concat.hip), so that there is ONE text of it.
+// (k_side_join.hip), so that there is ONE text of it.
 #pragma once
 #include "k_common.hpp"
 

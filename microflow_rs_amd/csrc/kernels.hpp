@@ -266,24 +266,25 @@ struct PwRtArgs {
     int TB, NSPLIT;     // pw_rt (weights in registers): tiles per wave block (1..4; 0 = use pw_rt_lds) and waves per chunk (1, 2, 4)
     int magic, xr;
 };
-// A 1x1 shortcut convolution (strides (1,1) or (2,2)) + the ADD that reads its result beside the running tensor, in one launch
-// (k_shortcut_add.hip)
-struct ShortcutAddArgs {
+// A 1x1 Conv2D on a skip edge (strides (1,1) or (2,2)) + the join that reads its result beside the running tensor, in one launch
+// (k_side_join.hip).  The convolution's part, whatever the join:
+struct SideConvArgs {
     PwRtArgs pw;         // the convolution as pw_rt takes it: operand A (build_pw_rt_reg_weights, group 1) in wprep, the operator's own
                          // constants, clamp and epilogue mode, K = C, N, KS, TB, NSPLIT
-    AddArgs add;         // the ADD in the internal domain
     int H, W, OH, OW, sh, sw;
-    int conv_first;      // 1: the ADD's input a is the convolution's result and b the running tensor; 0: the other way round
+    int conv_first;      // 1: the join's input a is the convolution's result and b the running tensor; 0: the other way round
+};
+// ... + an ADD (a ResNet projection shortcut): shortcut_add_rt
+struct ShortcutAddArgs {
+    SideConvArgs conv;
+    AddArgs add;         // the ADD in the internal domain
 };
 bool shortcut_add_supported(int C, int N);
-// A 1x1 Conv2D on a skip edge (strides (1,1) or (2,2)) + the CONCATENATION that reads its result beside the running tensor, in one
-// launch (k_side_concat.hip)
+// ... + a CONCATENATION (a fire module's 1x1 expand): side_concat_rt
 struct SideConcatArgs {
-    PwRtArgs pw;         // the convolution, as ShortcutAddArgs::pw
+    SideConvArgs conv;
     ConcatArgs cat;      // the CONCATENATION in the internal domain (Ca, Cb by input position)
-    int H, W, OH, OW, sh, sw;
     int CR;              // the running tensor's channels (a whole number of sixteens)
-    int conv_first;      // 1: the join's input a is the convolution's result and b the running tensor; 0: the other way round
 };
 bool side_concat_supported(int C, int N, int CR);
 void launch_side_concat(const int8_t *t_in, const int8_t *run, int8_t *out, const SideConcatArgs &a, long long batch, hipStream_t s);

@@ -106,8 +106,8 @@ struct ParsedOp {
     std::vector<float> c0, c1;
     std::vector<int32_t> c2;
     int32_t c3 = 0;
-    // ADD only: the tensor beside the running one.  skip_src: the operator whose output it is (-1: the model input; -2: no ADD);
-    // run_input: which of the ADD's two inputs (0 = a, 1 = b) the running tensor is; (a_*, b_*): the operands' quantisation by
+    // A join only: the tensor beside the running one.  skip_src: the operator whose output it is (-1: the model input; -2: no join);
+    // run_input: which of the join's two inputs (0 = a, 1 = b) the running tensor is; (a_*, b_*): the operands' quantisation by
     // input position, zero points as values of T.  c0[0] = ca, c1[0] = cb
     int skip_src = -2, run_input = 0;
     float a_scale = 0, b_scale = 0;
@@ -121,8 +121,8 @@ struct ParsedOp {
     bool cat_copy_a = false, cat_copy_b = false;
     size_t skip_elems() const { return kind == MF_OP_CONCATENATION ? cat_rows * (size_t)(run_input == 0 ? cat_cb : cat_ca) : in_elems; } // the other operand's
     // A side operator only (one Conv2D on a skip edge: it reads an earlier tensor T of the chain, not the running value, and one later
-    // ADD reads its output beside the running value): the operator whose output T is (-1: the model input); -2: no side operator.
-    // That ADD's skip_src is this operator's index.  in_scale / in_zp are T's
+    // join reads its output beside the running value): the operator whose output T is (-1: the model input); -2: no side operator.
+    // That join's skip_src is this operator's index.  in_scale / in_zp are T's
     int side_src = -2;
     bool side() const { return side_src != -2; }
     // PAD only: new rows / columns (top, bottom, left, right); H, W, C the input, OH, OW the output
@@ -157,7 +157,7 @@ struct ParsedModel {
         return launcher(s);
     }
     // join i (an ADD or a CONCATENATION) reads a side operator's output: that operator's index, else -1
-    int side_of_add(size_t i) const {
+    int side_of_join(size_t i) const {
         const int s = ops[i].join() ? ops[i].skip_src : -2;
         return s >= 0 && ops[(size_t)s].side() ? s : -1;
     }
@@ -188,12 +188,12 @@ struct OpSpec {
     const int32_t *c2 = nullptr;
     int32_t c3 = 0;
     float pool_c0 = 0, pool_c1 = 0;
-    // ADD: elements per inference, the operands' zero points (values of T) and the two constants
+    // a join (ADD, CONCATENATION): the operands' zero points (values of T) and the two constants, by input position
+    int join_za = 0, join_zb = 0;
+    float join_ca = 0, join_cb = 0;
+    // ADD: elements per inference
     size_t add_elems = 0;
-    int add_za = 0, add_zb = 0;
-    float add_ca = 0, add_cb = 0;
-    // CONCATENATION: rows per inference, the inputs' last axes, whether a slice is copied (h_concat_identity); the zero points and the
-    // constants in add_za, add_zb, add_ca, add_cb
+    // CONCATENATION: rows per inference, the inputs' last axes, whether a slice is copied (h_concat_identity)
     size_t cat_rows = 0;
     int cat_ca = 0, cat_cb = 0;
     bool cat_copy_a = false, cat_copy_b = false;
@@ -237,11 +237,11 @@ struct FusedImpl;
 FusedImpl *fused_create(OpImpl *dw, OpImpl *pw);
 FusedImpl *fused_block_create(OpImpl *expand, OpImpl *dw, OpImpl *pw, bool pair_grouped = false); // a 1x1 expand + depthwise 3x3 + 1x1 project block in one launch (k_block_band.hip), or nullptr; pair_grouped: the last two have a launch of their own
 // a 1x1 Conv2D on a skip edge + the ADD that reads its result beside the running tensor as one shortcut_add_rt launch
-// (k_shortcut_add.hip), or nullptr: outside the class, the two run their own launches.  conv_first: the ADD's input a is the
+// (k_side_join.hip), or nullptr: outside the class, the two run their own launches.  conv_first: the ADD's input a is the
 // convolution's result.  fused_run2 runs it: d_t the convolution's input, d_run the running tensor; d_out may be exactly d_run
 FusedImpl *fused_shortcut_add_create(OpImpl *conv, OpImpl *add, bool conv_first);
 // ... and its sibling for a CONCATENATION join: a 1x1 Conv2D on a skip edge + the CONCATENATION of its result and the running tensor as
-// one side_concat_rt launch (k_side_concat.hip), or nullptr.  fused_run2 runs it; d_out overlaps neither input
+// one side_concat_rt launch (k_side_join.hip), or nullptr.  fused_run2 runs it; d_out overlaps neither input
 FusedImpl *fused_side_concat_create(OpImpl *conv, OpImpl *cat, bool conv_first);
 void fused_run2(FusedImpl *f, const int8_t *d_t, const int8_t *d_run, size_t batch, int8_t *d_out, void *stream);
 // a PAD + the VALID Conv2D / DepthwiseConv2D on its output as ONE launch of the kernel the convolution, taken as an operator on the

@@ -43,8 +43,8 @@ struct Switches {
     bool no_pad_conv = false;      // MF_NO_PAD_CONV      a PAD + the VALID Conv2D / DepthwiseConv2D behind it one launch per operator, not one launch of the convolution's kernel with explicit pads (fused_heads.hip fused_pad_conv_create)
     bool no_conv_pool = false;     // MF_NO_CONV_POOL     Conv2D + AveragePool2D (more than one output pixel) stages one launch per operator, not one conv_pool_rt launch (k_conv_pool.hip)
     bool conv_pool_all = false;    // MF_CONV_POOL_ALL    measurements and tests: also the Conv2D + AveragePool2D classes the route excludes by measurement run as one conv_pool_rt launch -- every pair the plan accepts
-    bool no_shortcut_add = false;  // MF_NO_SHORTCUT_ADD  a 1x1 shortcut convolution and its ADD as two launches (the convolution's own into a fork buffer, then add_c16), not one shortcut_add_rt launch (k_shortcut_add.hip)
-    bool no_side_concat = false;   // MF_NO_SIDE_CONCAT   a 1x1 side convolution and its CONCATENATION as two launches (the convolution's own into a fork buffer, then concat_c4), not one side_concat_rt launch (k_side_concat.hip)
+    bool no_shortcut_add = false;  // MF_NO_SHORTCUT_ADD  a 1x1 shortcut convolution and its ADD as two launches (the convolution's own into a fork buffer, then add_c16), not one shortcut_add_rt launch (k_side_join.hip)
+    bool no_side_concat = false;   // MF_NO_SIDE_CONCAT   a 1x1 side convolution and its CONCATENATION as two launches (the convolution's own into a fork buffer, then concat_c4), not one side_concat_rt launch (k_side_join.hip)
     bool no_pair_wz = false;       // MF_NO_PAIR_WZ       pairs with filter zero points one launch per operator (dw3x3_rt<S,wzp>, pw_rt<K,N,wzp>), not one pair_wz_rt launch (k_pair_wz.hip)
     bool no_conv_gemm = false;     // MF_NO_CONV_GEMM     Conv2D shapes outside the other Conv2D kernels take conv2d_generic, not conv_gemm_rt (k_conv_gemm.hip)
     bool no_dw_gemm = false;       // MF_NO_DW_GEMM       DepthwiseConv2D shapes outside the other depthwise kernels take dwconv_generic, not dw_gemm_rt / conv_gemm_rt<dw> (k_dw_gemm.hip)

@@ -8,7 +8,7 @@
 //   in_q / io_f32              : staging for host-fed batches
 //   fork[0], fork[1]           : models with a join (ADD, CONCATENATION) only -- where a tensor that a later join reads beside the running one is
 //                                written, batch x largest such tensor; the ping-pong never writes there, so no skip is ever copied.
-//                                A side operator's result (a Conv2D on a skip edge, run at its ADD) goes to the one that holds
+//                                A side operator's result (a Conv2D on a skip edge, run at its join) goes to the one that holds
 //                                neither its input nor the running tensor -- where the two are not one launch, which writes neither
 // Every op reads one buffer and writes the other; Reshape is an alias (the 2D<->4D
 // maps of src/tensor.rs:103-141 are the identity in NHWC memory).
@@ -179,21 +179,21 @@ static int fused_owner(const ModelImpl *m, int i) {
 }
 // the side operator + join launch (shortcut_add_rt at an ADD, side_concat_rt at a CONCATENATION) at join i, if the model has one there
 // and nothing switched it off
-static FusedImpl *shortcut_at(const ModelImpl *m, int i) {
-    return m->fusion && !m->generic && i >= 0 && i < (int)m->g.shortcut.size() ? m->g.shortcut[(size_t)i] : nullptr;
+static FusedImpl *side_join_at(const ModelImpl *m, int i) {
+    return m->fusion && !m->generic && i >= 0 && i < (int)m->g.side_join.size() ? m->g.side_join[(size_t)i] : nullptr;
 }
 // ... and seen from the side operator: the join that reads its output
-static int add_of_side(const ModelImpl *m, int i) {
+static int join_of_side(const ModelImpl *m, int i) {
     for (size_t k = (size_t)i + 1; k < m->pm.ops.size(); ++k)
-        if (m->pm.side_of_add(k) == i) return (int)k;
+        if (m->pm.side_of_join(k) == i) return (int)k;
     return -1;
 }
 const char *model_op_kernel(const ModelImpl *m, int i) {
     if (!m->prepared || i < 0 || i >= (int)m->g.ops.size() || !m->g.ops[i]) return "";
-    // (the launch is named where it runs and where time_device(per_op) books its time: at the ADD)
-    if (m->pm.ops[(size_t)i].side() && shortcut_at(m, add_of_side(m, i)))
-        return m->pm.ops[(size_t)add_of_side(m, i)].kind == MF_OP_CONCATENATION ? "(fused into its CONCATENATION)" : "(fused into its ADD)";
-    if (shortcut_at(m, i)) return fused_kernel_name(shortcut_at(m, i));
+    // (the launch is named where it runs and where time_device(per_op) books its time: at the join)
+    if (m->pm.ops[(size_t)i].side() && side_join_at(m, join_of_side(m, i)))
+        return m->pm.ops[(size_t)join_of_side(m, i)].kind == MF_OP_CONCATENATION ? "(fused into its CONCATENATION)" : "(fused into its ADD)";
+    if (side_join_at(m, i)) return fused_kernel_name(side_join_at(m, i));
     if (const Stage *best = covering_stage(m, i)) return best->first == i ? fused_kernel_name(best->f) : "(fused into the previous operator)";
     if (fused_at(m, i)) return fused_kernel_name(m->g.fused[(size_t)i]);
     if (fused_owner(m, i) >= 0) return "(fused into the previous operator)";
@@ -202,7 +202,7 @@ const char *model_op_kernel(const ModelImpl *m, int i) {
 
 int model_op_epilogue_mode(const ModelImpl *m, int i) { // (a swallowed operator answers with its own launch's mode)
     if (!m->prepared || i < 0 || i >= (int)m->g.ops.size() || !m->g.ops[i]) return -1;
-    if (shortcut_at(m, i)) return fused_epilogue_mode(shortcut_at(m, i));
+    if (side_join_at(m, i)) return fused_epilogue_mode(side_join_at(m, i));
     const Stage *best = covering_stage(m, i);
     if (best && best->first == i) return fused_epilogue_mode(best->f);
     if (!best && fused_at(m, i)) return fused_epilogue_mode(m->g.fused[(size_t)i]);
@@ -355,17 +355,17 @@ struct Run {
 static int run_step(ModelImpl *m, Run &r, int i) {
     OpImpl *o = m->g.ops[(size_t)i];
     const bool f32in = r.src_f32 && i == m->g.first_real;
-    const bool add = m->pm.ops[(size_t)i].join(); // an ADD or a CONCATENATION: a launch of its own: the running tensor and the live skip tensor
+    const bool join = m->pm.ops[(size_t)i].join(); // an ADD or a CONCATENATION: a launch of its own: the running tensor and the live skip tensor
     int8_t *dst = m->act[r.which];
     if (dst == r.cur) {
         r.which ^= 1;
         dst = m->act[r.which];
     }
-    const int side = add ? m->pm.side_of_add((size_t)i) : -1; // the ADD reads a side operator's output: that operator runs here, from the live skip
+    const int side = join ? m->pm.side_of_join((size_t)i) : -1; // the join reads a side operator's output: that operator runs here, from the live skip
     const bool side_alone = m->pm.ops[(size_t)i].side();      // a run that ends at a side operator (run_until): its result from the live skip
-    const Launch l = f32in ? r.entry : (add || side_alone) ? Launch{nullptr, i} : launch_at(m, i, r.last_op, r.cur, r.batch);
-    // A launch whose result a later ADD reads beside the running value writes it where the ping-pong never writes: the fork buffer
-    // that does not hold the live skip (an ADD may read one and write the other).  No group holds such a tensor inside
+    const Launch l = f32in ? r.entry : (join || side_alone) ? Launch{nullptr, i} : launch_at(m, i, r.last_op, r.cur, r.batch);
+    // A launch whose result a later join reads beside the running value writes it where the ping-pong never writes: the fork buffer
+    // that does not hold the live skip (a join may read one and write the other).  No group holds such a tensor inside
     // (model_groups.cpp: splits), so it is always a launch's result
     const bool forks = m->forks[(size_t)l.last] != 0;
     if (forks) dst = (m->fork[0] == r.skip || m->fork[0] == r.cur) ? m->fork[1] : m->fork[0];
@@ -380,9 +380,9 @@ static int run_step(ModelImpl *m, Run &r, int i) {
         r.left_f32 = f32out;
     } else if (l.f) { // several groups, or the whole group, in one launch
         fused_run(l.f, r.cur, r.batch, dst, r.stream);
-    } else if (side >= 0 && shortcut_at(m, i)) { // the side operator and the ADD in one launch: its result is never written
-        fused_run2(shortcut_at(m, i), r.skip, r.cur, r.batch, dst, r.stream);
-    } else if (add) { // (the operand order is the file's: it matters for the f32 sum)
+    } else if (side >= 0 && side_join_at(m, i)) { // the side operator and the join in one launch: its result is never written
+        fused_run2(side_join_at(m, i), r.skip, r.cur, r.batch, dst, r.stream);
+    } else if (join) { // (the operand order is the file's: it matters for an ADD's f32 sum)
         const int8_t *other = r.skip;
         if (side >= 0) { // T stays where it is; S goes to the fork buffer that holds neither T nor the running tensor
             int8_t *s_buf = (m->fork[0] == r.skip || m->fork[0] == r.cur) ? m->fork[1] : m->fork[0];
@@ -415,7 +415,7 @@ static const int8_t *run_ops(ModelImpl *m, const int8_t *src, size_t batch, int 
     if (src_f32) r.entry = f32_entry(m, last_op);
     if (src_f32 && r.entry.last < 0) fail(MF_ERR_UNSUPPORTED, "no launch takes the f32 input");
     r.final_dst = final_dst, r.final_f32 = final_f32;
-    for (int i = 0; i <= last_op && !r.left_f32; ++i) // (a Reshape is an alias; a side operator runs at its ADD, or where the run ends at it)
+    for (int i = 0; i <= last_op && !r.left_f32; ++i) // (a Reshape is an alias; a side operator runs at its join, or where the run ends at it)
         if (m->g.ops[(size_t)i] && !(m->pm.ops[(size_t)i].side() && i != last_op)) i = run_step(m, r, i);
     return r.left_f32 ? nullptr : r.cur;
 }
@@ -442,7 +442,7 @@ static Boundary boundary_plan(const ModelImpl *m, const float *in_f32, const flo
                               int last_op) {
     Boundary b;
     if (!m->fusion || m->generic || last_op != (int)m->pm.ops.size() - 1) return b;
-    // (a model whose ADD reads the quantised input has no f32 entry -- nothing would materialise it: rule (7) -- so f32_entry says no)
+    // (a model whose join reads the quantised input has no f32 entry -- nothing would materialise it: rule (7) -- so f32_entry says no)
     b.in = in_f32 && ((uintptr_t)in_f32 & 15) == 0 && f32_entry(m, last_op).last >= 0;
     b.out = out_f32 && ((uintptr_t)out_f32 & 3) == 0 && !ranges_overlap(out_f32, out_count * sizeof(float), in_any, in_bytes);
     return b;
@@ -779,7 +779,7 @@ void model_time_device(ModelImpl *m, const int8_t *d_in, size_t batch, int8_t *d
         Run r{d_in, m->pm.input_skip ? d_in : nullptr, batch, nops - 1, m->g.last_real, s};
         MF_HIP(hipEventRecord(ev[0], s));
         for (int i = 0; i < nops; ++i) {
-            if (m->g.ops[(size_t)i] && !m->pm.ops[(size_t)i].side()) { // a stage or a group is timed as one unit (index i), its other ops 0; a side operator at its ADD
+            if (m->g.ops[(size_t)i] && !m->pm.ops[(size_t)i].side()) { // a stage or a group is timed as one unit (index i), its other ops 0; a side operator at its join
                 const int end = run_step(m, r, i);
                 for (; i < end; ++i) MF_HIP(hipEventRecord(ev[(size_t)i + 1], s));
             }

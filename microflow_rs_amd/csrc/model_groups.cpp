@@ -9,10 +9,10 @@ namespace mf {
 
 void ModelGroups::clear() {
     for (const Stage &st : stages) fused_destroy(st.f); // they borrow the groups' buffers: first
-    for (FusedImpl *f : shortcut) fused_destroy(f);
+    for (FusedImpl *f : side_join) fused_destroy(f);
     for (FusedImpl *f : fused) fused_destroy(f);
     for (OpImpl *o : ops) op_destroy(o);
-    stages.clear(), shortcut.clear(), fused.clear(), fused_last.clear(), ops.clear();
+    stages.clear(), side_join.clear(), fused.clear(), fused_last.clear(), ops.clear();
 }
 
 bool group_splits(const ParsedModel &pm, size_t first, size_t last) {
@@ -26,21 +26,8 @@ bool group_splits(const ParsedModel &pm, size_t first, size_t last) {
     return false;
 }
 
-int shortcut_candidate(const ParsedModel &pm, size_t add) {
-    const int s = pm.ops[add].kind == MF_OP_ADD ? pm.side_of_add(add) : -1;
-    if (s < 0) return -1;
-    const ParsedOp &po = pm.ops[(size_t)s];
-    bool zero_wzp = true, finite = std::isfinite(pm.ops[add].c0[0]) && std::isfinite(pm.ops[add].c1[0]);
-    for (int z : po.wzp) zero_wzp = zero_wzp && z - (pm.u8 ? 128 : 0) == 0;
-    for (float c : po.c0) finite = finite && std::isfinite(c);
-    for (float c : po.c1) finite = finite && std::isfinite(c);
-    OpSpec d;
-    d.kind = po.kind, d.KH = po.KH, d.KW = po.KW, d.sh = po.sh, d.sw = po.sw, d.H = po.H, d.W = po.W, d.C = po.C, d.N = po.N, d.OH = po.OH, d.OW = po.OW;
-    return shortcut_add_class(d, zero_wzp, finite) ? s : -1;
-}
-
-int side_concat_candidate(const ParsedModel &pm, size_t join) {
-    const int s = pm.ops[join].kind == MF_OP_CONCATENATION ? pm.side_of_add(join) : -1;
+int side_join_candidate(const ParsedModel &pm, size_t join) {
+    const int s = pm.side_of_join(join);
     if (s < 0) return -1;
     const ParsedOp &po = pm.ops[(size_t)s], &pj = pm.ops[join];
     bool zero_wzp = true, finite = std::isfinite(pj.c0[0]) && std::isfinite(pj.c1[0]);
@@ -49,6 +36,7 @@ int side_concat_candidate(const ParsedModel &pm, size_t join) {
     for (float c : po.c1) finite = finite && std::isfinite(c);
     OpSpec d;
     d.kind = po.kind, d.KH = po.KH, d.KW = po.KW, d.sh = po.sh, d.sw = po.sw, d.H = po.H, d.W = po.W, d.C = po.C, d.N = po.N, d.OH = po.OH, d.OW = po.OW;
+    if (pj.kind == MF_OP_ADD) return shortcut_add_class(d, zero_wzp, finite) ? s : -1;
     return side_concat_class(d, pj.run_input == 0 ? pj.cat_ca : pj.cat_cb, zero_wzp, finite) ? s : -1; // (the running operand's channels)
 }
 
@@ -84,11 +72,11 @@ struct GroupBuilder {
     bool free_op(size_t i) const { return g.ops[i] && !g.fused[i] && !covered(i) && !owned(i); }
     bool free_fc(size_t i) const { return i < n && kind(i) == MF_OP_FULLY_CONNECTED && free_op(i); }
     bool free_sm(size_t i) const { return i < n && kind(i) == MF_OP_SOFTMAX && free_op(i); }
-    // A fork tensor -- an operator's output that a later ADD reads beside the running value -- has to exist in memory, so no group
+    // A fork tensor -- an operator's output that a later join (ADD, CONCATENATION) reads beside the running value -- has to exist in memory, so no group
     // may hold one strictly inside: true when operators first .. last as ONE launch would swallow such a tensor (the operator that
-    // launches it at or behind `first` and in front of `last`; a group may end at one or start behind one), or would hold an ADD,
+    // launches it at or behind `first` and in front of `last`; a group may end at one or start behind one), or would hold a join,
     // which is a launch of its own.  A candidate this refuses falls back exactly as an unmatched one does
-    // A side operator (ParsedOp::side) runs at its ADD, not at its own index: no group of consecutive operators may hold one either
+    // A side operator (ParsedOp::side) runs at its join, not at its own index: no group of consecutive operators may hold one either
     bool splits(size_t first, size_t last) const { return group_splits(pm, first, last); }
     size_t skip_reshapes(size_t j) const {
         while (j < n && kind(j) == MF_OP_RESHAPE) ++j;
@@ -119,14 +107,13 @@ static OpSpec op_spec(const ParsedModel &pm, const ParsedOp &po, float cur_scale
     s.c3 = po.c3;
     if (po.kind == MF_OP_AVERAGE_POOL_2D || po.kind == MF_OP_MAX_POOL_2D) s.pool_c0 = po.c0[0], s.pool_c1 = po.c1[0];
     if (po.kind == MF_OP_ADD) { // (the operands' quantisation is the file's, by input position: izp / in_scale are not used)
-        s.add_elems = po.in_elems, s.add_za = po.a_zp, s.add_zb = po.b_zp;
-        s.add_ca = po.c0[0], s.add_cb = po.c1[0];
+        s.add_elems = po.in_elems;
     }
     if (po.kind == MF_OP_CONCATENATION) {
         s.cat_rows = po.cat_rows, s.cat_ca = po.cat_ca, s.cat_cb = po.cat_cb, s.cat_copy_a = po.cat_copy_a, s.cat_copy_b = po.cat_copy_b;
-        s.add_za = po.a_zp, s.add_zb = po.b_zp, s.add_ca = po.c0[0], s.add_cb = po.c1[0];
         s.act = MF_ACT_NONE;
     }
+    if (po.join()) s.join_za = po.a_zp, s.join_zb = po.b_zp, s.join_ca = po.c0[0], s.join_cb = po.c1[0];
     if (po.kind == MF_OP_PAD)
         for (int k = 0; k < 4; ++k) s.pads[k] = po.pads[k];
     return s;
@@ -153,11 +140,11 @@ static void create_operators(GroupBuilder &b) {
     b.n = ops.size();
     b.g.fused.assign(b.n, nullptr);
     b.g.fused_last.assign(b.n, -1);
-    b.g.shortcut.assign(b.n, nullptr);
+    b.g.side_join.assign(b.n, nullptr);
     while (b.g.first_real < (int)b.n && !ops[(size_t)b.g.first_real]) ++b.g.first_real;
     b.g.last_real = (int)b.n - 1;
     while (b.g.last_real >= 0 && !ops[(size_t)b.g.last_real]) --b.g.last_real;
-    // peephole (0): the boundary quantize of M::predict folds into operator 0 when that is the stem -- unless an ADD reads the
+    // peephole (0): the boundary quantize of M::predict folds into operator 0 when that is the stem -- unless a join reads the
     // quantised model input later: nothing would materialise it (the runtime never copies a skip tensor)
     if (!ops.empty() && ops[0] && !b.pm.input_skip) (void)op_set_input_quant(ops[0], b.pm.in_scale, b.pm.in_zp, b.pm.u8);
 }
@@ -168,7 +155,7 @@ static void create_operators(GroupBuilder &b) {
 // (0p) a PAD directly followed by a VALID Conv2D / DepthwiseConv2D -> one launch of the convolution's kernel with explicit pads.
 // In the same loop as (1)-(3) and in front of them: the group at i owns the convolution at i + 1 (the loop continues behind it), so a
 // depthwise there is never also offered to (1) with the 1x1 behind it -- that pair would be formed over the padded tensor, which this
-// launch never writes.  The PAD's output has one reader (the parser's chain: the convolution) unless an ADD reads it too: splits
+// launch never writes.  The PAD's output has one reader (the parser's chain: the convolution) unless a join reads it too: splits
 static void rule_1_2_3_first_level(GroupBuilder &b) {
     const std::vector<OpImpl *> &ops = b.g.ops;
     std::vector<FusedImpl *> &fused = b.g.fused;
@@ -443,22 +430,16 @@ static void rule_6a_conv_pool(GroupBuilder &b) {
     }
 }
 
-// (6b) a side operator -- one Conv2D on a skip edge -- and the ADD that reads its output -> one shortcut_add_rt launch at the ADD
-// (fused_heads.hip: fused_shortcut_add_create), wherever the two stand in file order.  No other rule matches a side operator
-// (splits), so the pair is free; outside the kernel's class the side operator runs its own launch at the ADD, then the ADD
-static void rule_6b_shortcut_add(GroupBuilder &b) {
+// (6b) a side operator -- one Conv2D on a skip edge -- and the join that reads its output -> one launch at the join: shortcut_add_rt
+// with an ADD (fused_heads.hip: fused_shortcut_add_create), side_concat_rt with a CONCATENATION (fused_side_concat_create: a fire
+// module's 1x1 expand and its join), wherever the two stand in file order.  No other rule matches a side operator (splits), so the pair
+// is free; outside the kernel's class the side operator runs its own launch at the join, then the join
+static void rule_6b_side_join(GroupBuilder &b) {
     for (size_t i = 0; i < b.n; ++i) {
-        const int s = shortcut_candidate(b.pm, i); // (what the file says; the builder asks the prepared operators again)
-        if (s >= 0) b.g.shortcut[i] = fused_shortcut_add_create(b.g.ops[(size_t)s], b.g.ops[i], b.po(i).run_input == 1); // (run_input 1: input a is the side operator's)
-    }
-}
-
-// (6c) the same for a CONCATENATION join: a side operator and the CONCATENATION that reads its output -> one side_concat_rt launch at
-// the join (fused_heads.hip: fused_side_concat_create) -- a fire module's 1x1 expand and its join
-static void rule_6c_side_concat(GroupBuilder &b) {
-    for (size_t i = 0; i < b.n; ++i) {
-        const int s = side_concat_candidate(b.pm, i);
-        if (s >= 0) b.g.shortcut[i] = fused_side_concat_create(b.g.ops[(size_t)s], b.g.ops[i], b.po(i).run_input == 1);
+        const int s = side_join_candidate(b.pm, i); // (what the file says; the builder asks the prepared operators again)
+        if (s < 0) continue;
+        const bool conv_first = b.po(i).run_input == 1; // (run_input 1: input a is the side operator's)
+        b.g.side_join[i] = (b.kind(i) == MF_OP_ADD ? fused_shortcut_add_create : fused_side_concat_create)(b.g.ops[(size_t)s], b.g.ops[i], conv_first);
     }
 }
 
@@ -469,7 +450,7 @@ static void rule_7_boundaries(GroupBuilder &b) {
     const ParsedModel &pm = b.pm;
     const ModelGroups &g = b.g;
     const size_t first_real = (size_t)g.first_real;
-    const bool entry = !pm.input_skip; // (an ADD that reads the quantised model input needs it in memory: no f32 entry)
+    const bool entry = !pm.input_skip; // (a join that reads the quantised model input needs it in memory: no f32 entry)
     if (entry && first_real < b.n && g.fused[first_real]) (void)fused_set_input_quant(g.fused[first_real], pm.in_scale, pm.in_zp, pm.u8);
     if (entry && first_real > 0 && first_real < b.n) (void)op_set_input_quant(g.ops[first_real], pm.in_scale, pm.in_zp, pm.u8);
     if (g.last_real >= 0) (void)op_set_output_dequant(g.ops[(size_t)g.last_real], pm.out_scale, pm.out_zp, pm.u8);
@@ -496,8 +477,7 @@ ModelGroups build_groups(const ParsedModel &pm, int device, bool autotune) {
     //   - (5) before (5a): speech.tflite's own geometry keeps (5); (5a), (5b) before (6): a FullyConnected run behind a one-channel
     //     convolution or a global pool is offered there first, (6) takes what they left
     //   - (6a) behind every rule above: a global pool stays with the tail and pool_fc_chain groups, a pair's Conv2D with its pair
-    //   - (6b) anywhere behind the operators: it looks at side operators and their ADDs, which no other rule touches
-    //   - (6c) likewise: side operators and their CONCATENATIONs
+    //   - (6b) anywhere behind the operators: it looks at side operators and their joins, which no other rule touches
     //   - (7) last: it tells every launch that exists by then, at either end of the model, the boundary's quantisation
     create_operators(b);
     rule_1_2_3_first_level(b);
@@ -511,8 +491,7 @@ ModelGroups build_groups(const ParsedModel &pm, int device, bool autotune) {
     rule_5b_pool_fc(b);
     rule_6_fc_chains(b);
     rule_6a_conv_pool(b);
-    rule_6b_shortcut_add(b);
-    rule_6c_side_concat(b);
+    rule_6b_side_join(b);
     rule_7_boundaries(b);
     return std::move(b.g);
 }

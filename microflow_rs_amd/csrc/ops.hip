@@ -782,9 +782,9 @@ void create_add(OpImpl &op, const OpSpec &s, int lo, int hi) {
     op.in_elems = op.in2_elems = op.out_elems = s.add_elems;
     k::AddArgs &a = op.add;
     const int off = s.u8 ? 0 : 128;
-    a.ca = s.add_ca, a.cb = s.add_cb, a.ka = (float)(off + s.add_za), a.kb = (float)(off + s.add_zb);
+    a.ca = s.join_ca, a.cb = s.join_cb, a.ka = (float)(off + s.join_za), a.kb = (float)(off + s.join_zb);
     a.zo_f = (float)s.ozp, a.lo_f = (float)lo, a.hi_f = (float)hi; // (act_bounds: [lo, hi] lies inside T's range)
-    op.add_fma = h_add_fma_form(a.ca, a.cb, off + s.add_za, off + s.add_zb, s.ozp, lo, hi, &a.k1);
+    op.add_fma = h_add_fma_form(a.ca, a.cb, off + s.join_za, off + s.join_zb, s.ozp, lo, hi, &a.k1);
     a.xin4 = 0x80808080u, a.xout4 = s.u8 ? 0x80808080u : 0u;
     op.add_ext = a;
     if (s.u8) op.add_ext.xin4 = op.add_ext.xout4 = 0u; // real u8 bytes
@@ -804,7 +804,7 @@ void create_concat(OpImpl &op, const OpSpec &s) {
     op.out_elems = op.in_elems + op.in2_elems;
     k::ConcatArgs &a = op.cat;
     const int off = s.u8 ? 0 : 128;
-    a.ca = s.add_ca, a.cb = s.add_cb, a.ka = (float)(off + s.add_za), a.kb = (float)(off + s.add_zb);
+    a.ca = s.join_ca, a.cb = s.join_cb, a.ka = (float)(off + s.join_za), a.kb = (float)(off + s.join_zb);
     a.zo_f = (float)s.ozp, a.lo_f = s.u8 ? 0.0f : -128.0f, a.hi_f = s.u8 ? 255.0f : 127.0f;
     a.xin4 = 0x80808080u, a.xout4 = s.u8 ? 0x80808080u : 0u;
     a.Ca = s.cat_ca, a.Cb = s.cat_cb, a.copy_a = s.cat_copy_a, a.copy_b = s.cat_copy_b;

@@ -235,26 +235,26 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
     // same shape, from the graph input through every operator to the graph output.
     int32_t prev_index = g_in.get<int32_t>(0);
     std::vector<int> prev_shape(pm.in_shape, pm.in_shape + pm.in_rank);
-    // ... with skip edges (ADD, below): the output tensor index of every operator so far, and the last ADD -- the point up to which
-    // an earlier skip tensor was alive
+    // ... with skip edges (the joins, below): the output tensor index of every operator so far, and the last join -- the point up to
+    // which an earlier skip tensor was alive
     std::vector<int32_t> out_index;
-    int last_add = -1;
-    // ... and with a side operator (one Conv2D on a skip edge, below): the one whose ADD has not come yet, or -1
+    int last_join = -1;
+    // ... and with a side operator (one Conv2D on a skip edge, below): the one whose join has not come yet, or -1
     int pending_side = -1;
     // who reads tensor t behind operator `from`: joins -- ADDs and CONCATENATIONs -- (any input) and other operators (input 0)
-    auto readers_behind = [&](int32_t t, uint32_t from, int &adds, int &others) {
-        adds = others = 0;
+    auto readers_behind = [&](int32_t t, uint32_t from, int &joins, int &others) {
+        joins = others = 0;
         for (uint32_t k = from + 1; k < operators.size(); ++k) {
             const Table o = operators.table(k);
             const uint32_t c = o.scalar<uint32_t>(0, 0);
             const Vec in_k = vec(o, 1);
             if (c >= opcodes.size() || !in_k.size()) continue; // (refused when the walk reaches it)
             const int code_k = opcodes.table(c).scalar<int8_t>(0, 0);
-            if (code_k == MF_OP_ADD) adds += in_k.get<int32_t>(0) == t || (in_k.size() > 1 && in_k.get<int32_t>(1) == t);
+            if (code_k == MF_OP_ADD) joins += in_k.get<int32_t>(0) == t || (in_k.size() > 1 && in_k.get<int32_t>(1) == t);
             else if (code_k == MF_OP_CONCATENATION) {
                 bool reads = false;
                 for (uint32_t j = 0; j < in_k.size(); ++j) reads = reads || in_k.get<int32_t>(j) == t;
-                adds += reads;
+                joins += reads;
             } else others += in_k.get<int32_t>(0) == t;
         }
     };
@@ -267,6 +267,58 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
         if (a.size() == 1) a.insert(a.begin(), 1);
         if (b.size() == 1) b.insert(b.begin(), 1);
         return a == b;
+    };
+
+    // What the two joins share.  A join reads the running value (in either position) and ONE other tensor, matched by tensor index: an
+    // earlier tensor of the chain or the pending side operator's output; at most one such tensor is alive at a time.  In order: the
+    // operands (two, none constant, of the model's element type with per-tensor quantisation; `fused_act`: the kind takes no fused
+    // activation and the file names one), which input is the running one, the skip source and the three liveness refusals; then the
+    // kind's `own` checks and fields (it gets the second tensor; po.run_input, skip_src and the a_* / b_* fields are set by then, the
+    // shapes not yet); then the shapes and what has to stay in memory up to here.  Every refusal carries the kind's prefix (`refuse`)
+    auto parse_join = [&](ParsedOp &po, uint32_t oi, const Vec &ins, const TensorInfo &in, const TensorInfo &out, int32_t running_index, const char *name,
+                          const auto &refuse, const char *arity, bool fused_act, const auto &own) {
+        if (ins.size() < 2) refuse(arity);
+        const int32_t ia = ins.get<int32_t>(0), ib = ins.get<int32_t>(1);
+        const TensorInfo tb = read_tensor(tensors, buffers, ib);
+        if (in.data_len || tb.data_len) refuse("a constant operand");
+        if (ins.size() != 2) refuse(arity);
+        for (const TensorInfo *t : {&in, &tb, &out}) {
+            if ((t->type != TT_INT8 && t->type != TT_UINT8) || (t->type == TT_UINT8) != pm.u8) refuse("mixed element types");
+            need_quant(*t, name);
+            if (t->scale.size() != 1 || t->zp.size() != 1) refuse("per-channel quantisation on an operand");
+            if (!(t->scale[0] > 0.0f) || !std::isfinite(t->scale[0]))
+                fail(MF_ERR_INVALID_MODEL, std::string("invalid model: ") + name + " scales must be finite and positive");
+        }
+        if (fused_act) refuse("a fused activation");
+        if (ia == ib) refuse("both inputs are the same tensor");
+        if (ia != running_index && ib != running_index) refuse("neither input is the running value");
+        po.run_input = ia == running_index ? 0 : 1;
+        const int32_t is = po.run_input == 0 ? ib : ia;
+        int src = -2;
+        if (is == g_in.get<int32_t>(0)) src = -1;
+        for (size_t j = 0; j < out_index.size(); ++j)
+            if (out_index[j] == is) src = (int)j;
+        if (src == -2) refuse("the other input is no earlier tensor of the chain");
+        for (const ParsedOp &e : pm.ops)
+            if (e.join() && e.skip_src == src) refuse("a fork tensor is used twice");
+        // (a side operator's output: T and S count as one skip, alive from T's producer -- checked at the side operator -- to here)
+        const bool via_side = src >= 0 && pm.ops[(size_t)src].side();
+        if (pending_side >= 0 && src != pending_side) refuse("a side operator while another skip is alive");
+        if (!via_side && src < last_join) refuse("two skip tensors alive at once (overlapping or nested skips)");
+        po.skip_src = src;
+        po.a_scale = in.scale[0], po.b_scale = tb.scale[0];
+        po.a_zp = zp_of(in.zp[0], pm.u8), po.b_zp = zp_of(tb.zp[0], pm.u8);
+        own(tb);
+        set_shapes(po, po.run_input == 0 ? in : tb, out, pm.u8); // (in_scale / in_zp / in_elems: the running operand's)
+        // what has to stay in memory up to here: the skip tensor itself or, through a side operator, its input T (Reshapes are
+        // aliases: the operator that launches the tensor, or the model input); the side operator's output lives in a fork buffer too
+        const int real = pm.launcher(via_side ? pm.ops[(size_t)src].side_src : src);
+        const size_t kept = via_side ? pm.ops[(size_t)src].in_elems : po.skip_elems();
+        if (real < 0) pm.input_skip = true;
+        else if (kept > pm.max_fork_elems) pm.max_fork_elems = kept;
+        if (via_side && po.skip_elems() > pm.max_fork_elems) pm.max_fork_elems = po.skip_elems();
+        pending_side = -1;
+        last_join = (int)oi;
     };
 
     for (uint32_t oi = 0; oi < operators.size(); ++oi) { // lib.rs:130-151
@@ -287,30 +339,30 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
         if (code != MF_OP_ADD && code != MF_OP_CONCATENATION) { // (a join checks its own inputs)
             // A side operator: ONE Conv2D on a skip edge.  Its input 0 is a tensor T of the chain, by index -- the model input or an
             // earlier operator's output -- that the main chain also continues from: either T is not the running value any more (the
-            // side operator stands between the main operators or in front of its ADD), or it still is and a later operator reads
-            // it as well (the side operator stands directly behind the fork).  Its output is read by exactly one later ADD and by
+            // side operator stands between the main operators or in front of its join), or it still is and a later operator reads
+            // it as well (the side operator stands directly behind the fork).  Its output is read by exactly one later join and by
             // nothing else.  It does not become the running value: the chain bookkeeping passes over it
             const int32_t in0 = ins.get<int32_t>(0);
             if (pending_side >= 0 && in0 == out_index[(size_t)pending_side]) refuse_side(oi, "two or more operators on the skip edge");
             int t = in0 == g_in.get<int32_t>(0) ? -1 : -2;
             for (size_t j = 0; j < out_index.size(); ++j)
                 if (out_index[j] == in0 && !pm.ops[j].side()) t = (int)j;
-            int adds = 0, others = 0;
+            int joins = 0, others = 0;
             bool side = false;
             if (t != -2 && in0 != prev_index) side = true;
             else if (t != -2) { // (of two operators that read the running value, the one no further operator reads is off the chain)
-                readers_behind(in0, oi, adds, others);
+                readers_behind(in0, oi, joins, others);
                 const bool read_again = others > 0;
-                readers_behind(outs.get<int32_t>(0), oi, adds, others);
+                readers_behind(outs.get<int32_t>(0), oi, joins, others);
                 side = read_again && others == 0;
             }
             if (side) {
                 if (code != MF_OP_CONV_2D) refuse_side(oi, "a side operator that is not a Conv2D");
-                readers_behind(outs.get<int32_t>(0), oi, adds, others);
-                if (!adds && others == 1) refuse_side(oi, "two or more operators on the skip edge");
-                if (!adds && !others) refuse_side(oi, "its output is never read");
-                if (adds != 1 || others) refuse_side(oi, "its output is read by something other than one ADD");
-                if (pending_side >= 0 || t < last_add) refuse_side(oi, "a side operator while another skip is alive");
+                readers_behind(outs.get<int32_t>(0), oi, joins, others);
+                if (!joins && others == 1) refuse_side(oi, "two or more operators on the skip edge");
+                if (!joins && !others) refuse_side(oi, "its output is never read");
+                if (joins != 1 || others) refuse_side(oi, "its output is read by something other than one ADD");
+                if (pending_side >= 0 || t < last_join) refuse_side(oi, "a side operator while another skip is alive");
                 for (const TensorInfo *ti : {&in, &out})
                     if ((ti->type == TT_INT8 || ti->type == TT_UINT8) && (ti->type == TT_UINT8) != pm.u8) refuse_side(oi, "mixed element types");
                 po.side_src = t;
@@ -455,120 +507,48 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             // tensor of the chain, matched by tensor index; at most one such tensor is alive at a time.  Everything else keeps the
             // reference's answer, with the reason behind it
             auto refuse = [](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: 0 (ADD: " + why + ")"); };
-            if (ins.size() < 2) refuse("it needs two inputs");
-            const int32_t ia = ins.get<int32_t>(0), ib = ins.get<int32_t>(1);
-            TensorInfo tb = read_tensor(tensors, buffers, ib);
-            if (in.data_len || tb.data_len) refuse("a constant operand");
-            if (ins.size() != 2) refuse("it needs two inputs");
-            for (const TensorInfo *t : {&in, &tb, &out}) {
-                if ((t->type != TT_INT8 && t->type != TT_UINT8) || (t->type == TT_UINT8) != pm.u8) refuse("mixed element types");
-                need_quant(*t, "ADD");
-                if (t->scale.size() != 1 || t->zp.size() != 1) refuse("per-channel quantisation on an operand");
-                if (!(t->scale[0] > 0.0f) || !std::isfinite(t->scale[0]))
-                    fail(MF_ERR_INVALID_MODEL, "invalid model: ADD scales must be finite and positive");
-            }
-            if (ia == ib) refuse("both inputs are the same tensor");
-            if (ia != running_index && ib != running_index) refuse("neither input is the running value");
-            po.run_input = ia == running_index ? 0 : 1;
-            const int32_t is = po.run_input == 0 ? ib : ia;
-            int src = -2;
-            if (is == g_in.get<int32_t>(0)) src = -1;
-            for (size_t j = 0; j < out_index.size(); ++j)
-                if (out_index[j] == is) src = (int)j;
-            if (src == -2) refuse("the other input is no earlier tensor of the chain");
-            for (const ParsedOp &e : pm.ops)
-                if (e.join() && e.skip_src == src) refuse("a fork tensor is used twice");
-            // (a side operator's output: T and S count as one skip, alive from T's producer -- checked at the side operator -- to here)
-            const bool via_side = src >= 0 && pm.ops[(size_t)src].side();
-            if (pending_side >= 0 && src != pending_side) refuse("a side operator while another skip is alive");
-            if (!via_side && src < last_add) refuse("two skip tensors alive at once (overlapping or nested skips)");
-            if (in.shape != tb.shape || in.shape != out.shape) refuse("differing shapes (no broadcasting)");
-            if (in.shape.size() != 2 && in.shape.size() != 4) refuse("tensor rank must be 2 or 4");
-            if (in.shape.size() == 4 && in.shape[0] != 1) refuse("tensor batch must be 1");
-            set_shapes(po, po.run_input == 0 ? in : tb, out, pm.u8); // (in_scale / in_zp: the running operand's)
-            po.skip_src = src;
-            po.act = check_act(opt.scalar<int8_t>(0, 0)); // AddOptions { act:0 pot_scale_int16:1 (ignored) }
-            po.a_scale = in.scale[0], po.b_scale = tb.scale[0];
-            po.a_zp = zp_of(in.zp[0], pm.u8), po.b_zp = zp_of(tb.zp[0], pm.u8);
-            po.c0.resize(1), po.c1.resize(1);
-            h_preprocess_add(po.a_scale, po.b_scale, out.scale[0], po.c0.data(), po.c1.data());
-            // what has to stay in memory up to here: the skip tensor itself or, through a side operator, its input T (Reshapes are
-            // aliases: the operator that launches the tensor, or the model input); the side operator's output lives in a fork buffer too
-            const int real = pm.launcher(via_side ? pm.ops[(size_t)src].side_src : src);
-            const size_t kept = via_side ? pm.ops[(size_t)src].in_elems : po.in_elems;
-            if (real < 0) pm.input_skip = true;
-            else if (kept > pm.max_fork_elems) pm.max_fork_elems = kept;
-            if (via_side && po.in_elems > pm.max_fork_elems) pm.max_fork_elems = po.in_elems;
-            pending_side = -1;
-            last_add = (int)oi;
+            parse_join(po, oi, ins, in, out, running_index, "ADD", refuse, "it needs two inputs", false, [&](const TensorInfo &tb) {
+                if (in.shape != tb.shape || in.shape != out.shape) refuse("differing shapes (no broadcasting)");
+                if (in.shape.size() != 2 && in.shape.size() != 4) refuse("tensor rank must be 2 or 4");
+                if (in.shape.size() == 4 && in.shape[0] != 1) refuse("tensor batch must be 1");
+                po.act = check_act(opt.scalar<int8_t>(0, 0)); // AddOptions { act:0 pot_scale_int16:1 (ignored) }
+                po.c0.resize(1), po.c1.resize(1);
+                h_preprocess_add(po.a_scale, po.b_scale, out.scale[0], po.c0.data(), po.c1.data());
+            });
             break;
         }
         case MF_OP_CONCATENATION: { // not in the reference (lib.rs:148 answers "unsupported operator: 2"): the contract is include/microflow_amd.h's
             // A second kind of join beside ADD, in the same graph form: it reads the running value (in either position) and ONE other
             // tensor -- an earlier tensor of the chain or the side operator's output -- along the last axis
             auto refuse = [](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: 2 (CONCATENATION: " + why + ")"); };
-            if (ins.size() != 2) refuse("it needs exactly two inputs");
-            const int32_t ia = ins.get<int32_t>(0), ib = ins.get<int32_t>(1);
-            TensorInfo tb = read_tensor(tensors, buffers, ib);
-            if (in.data_len || tb.data_len) refuse("a constant operand");
-            for (const TensorInfo *t : {&in, &tb, &out}) {
-                if ((t->type != TT_INT8 && t->type != TT_UINT8) || (t->type == TT_UINT8) != pm.u8) refuse("mixed element types");
-                need_quant(*t, "CONCATENATION");
-                if (t->scale.size() != 1 || t->zp.size() != 1) refuse("per-channel quantisation on an operand");
-                if (!(t->scale[0] > 0.0f) || !std::isfinite(t->scale[0]))
-                    fail(MF_ERR_INVALID_MODEL, "invalid model: CONCATENATION scales must be finite and positive");
-            }
+            if (ins.size() != 2) refuse("it needs exactly two inputs"); // (ahead of every other refusal, unlike ADD's)
             // ConcatenationOptions { axis:0 fused_activation_function:1 }
-            if (opt.scalar<int8_t>(1, 0) != MF_ACT_NONE) refuse("a fused activation");
-            if (ia == ib) refuse("both inputs are the same tensor");
-            if (ia != running_index && ib != running_index) refuse("neither input is the running value");
-            po.run_input = ia == running_index ? 0 : 1;
-            const int32_t is = po.run_input == 0 ? ib : ia;
-            int src = -2;
-            if (is == g_in.get<int32_t>(0)) src = -1;
-            for (size_t j = 0; j < out_index.size(); ++j)
-                if (out_index[j] == is) src = (int)j;
-            if (src == -2) refuse("the other input is no earlier tensor of the chain");
-            for (const ParsedOp &e : pm.ops)
-                if (e.join() && e.skip_src == src) refuse("a fork tensor is used twice");
-            const bool via_side = src >= 0 && pm.ops[(size_t)src].side();
-            if (pending_side >= 0 && src != pending_side) refuse("a side operator while another skip is alive");
-            if (!via_side && src < last_add) refuse("two skip tensors alive at once (overlapping or nested skips)");
-            const size_t rank = in.shape.size();
-            if (rank < 2 || rank > 4 || tb.shape.size() != rank || out.shape.size() != rank) refuse("tensor rank must be 2 to 4, the same for all");
-            int axis = opt.scalar<int32_t>(0, 0);
-            if (axis < 0) axis += (int)rank;
-            if (axis != (int)rank - 1) refuse("an axis other than the last");
-            size_t rows = 1;
-            for (size_t d = 0; d + 1 < rank; ++d) {
-                if (in.shape[d] != tb.shape[d]) refuse("the inputs differ in another dimension than the axis");
-                rows *= (size_t)in.shape[d];
-            }
-            if (rank > 2 && in.shape[0] != 1) refuse("tensor batch must be 1");
-            const int Ca = in.shape[rank - 1], Cb = tb.shape[rank - 1];
-            if (Ca <= 0 || Cb <= 0 || !rows) fail(MF_ERR_INVALID_MODEL, "invalid model: bad tensor dimension");
-            for (size_t d = 0; d < rank; ++d)
-                if ((int64_t)out.shape[d] != (d + 1 < rank ? (int64_t)in.shape[d] : (int64_t)Ca + Cb))
-                    fail(MF_ERR_INVALID_MODEL, "invalid model: CONCATENATION output shape is not the two inputs joined");
-            set_shapes(po, po.run_input == 0 ? in : tb, out, pm.u8); // (in_scale / in_zp / in_elems: the running operand's)
-            po.skip_src = src;
-            po.act = MF_ACT_NONE;
-            po.a_scale = in.scale[0], po.b_scale = tb.scale[0];
-            po.a_zp = zp_of(in.zp[0], pm.u8), po.b_zp = zp_of(tb.zp[0], pm.u8);
-            po.cat_rows = rows, po.cat_ca = Ca, po.cat_cb = Cb, po.N = Ca + Cb;
-            po.c0.resize(1), po.c1.resize(1);
-            h_preprocess_concatenation(po.a_scale, po.b_scale, out.scale[0], po.c0.data(), po.c1.data());
-            po.cat_copy_a = h_concat_identity(po.a_scale, po.a_zp, out.scale[0], po.out_zp, po.c0[0]);
-            po.cat_copy_b = h_concat_identity(po.b_scale, po.b_zp, out.scale[0], po.out_zp, po.c1[0]);
-            // what has to stay in memory up to here, as for an ADD: the skip tensor itself or, through a side operator, its input T;
-            // the side operator's output lives in a fork buffer too
-            const int real = pm.launcher(via_side ? pm.ops[(size_t)src].side_src : src);
-            const size_t kept = via_side ? pm.ops[(size_t)src].in_elems : po.skip_elems();
-            if (real < 0) pm.input_skip = true;
-            else if (kept > pm.max_fork_elems) pm.max_fork_elems = kept;
-            if (via_side && po.skip_elems() > pm.max_fork_elems) pm.max_fork_elems = po.skip_elems();
-            pending_side = -1;
-            last_add = (int)oi;
+            const bool fused_act = opt.scalar<int8_t>(1, 0) != MF_ACT_NONE;
+            parse_join(po, oi, ins, in, out, running_index, "CONCATENATION", refuse, "it needs exactly two inputs", fused_act, [&](const TensorInfo &tb) {
+                const size_t rank = in.shape.size();
+                if (rank < 2 || rank > 4 || tb.shape.size() != rank || out.shape.size() != rank) refuse("tensor rank must be 2 to 4, the same for all");
+                int axis = opt.scalar<int32_t>(0, 0);
+                if (axis < 0) axis += (int)rank;
+                if (axis != (int)rank - 1) refuse("an axis other than the last");
+                size_t rows = 1;
+                for (size_t d = 0; d + 1 < rank; ++d) {
+                    if (in.shape[d] != tb.shape[d]) refuse("the inputs differ in another dimension than the axis");
+                    rows *= (size_t)in.shape[d];
+                }
+                if (rank > 2 && in.shape[0] != 1) refuse("tensor batch must be 1");
+                const int Ca = in.shape[rank - 1], Cb = tb.shape[rank - 1];
+                if (Ca <= 0 || Cb <= 0 || !rows) fail(MF_ERR_INVALID_MODEL, "invalid model: bad tensor dimension");
+                for (size_t d = 0; d < rank; ++d)
+                    if ((int64_t)out.shape[d] != (d + 1 < rank ? (int64_t)in.shape[d] : (int64_t)Ca + Cb))
+                        fail(MF_ERR_INVALID_MODEL, "invalid model: CONCATENATION output shape is not the two inputs joined");
+                po.act = MF_ACT_NONE;
+                po.cat_rows = rows, po.cat_ca = Ca, po.cat_cb = Cb, po.N = Ca + Cb;
+                po.c0.resize(1), po.c1.resize(1);
+                h_preprocess_concatenation(po.a_scale, po.b_scale, out.scale[0], po.c0.data(), po.c1.data());
+                const int out_zp = zp_of(out.zp[0], pm.u8);
+                po.cat_copy_a = h_concat_identity(po.a_scale, po.a_zp, out.scale[0], out_zp, po.c0[0]);
+                po.cat_copy_b = h_concat_identity(po.b_scale, po.b_zp, out.scale[0], out_zp, po.c1[0]);
+            });
             break;
         }
         case MF_OP_PAD: { // not in the reference (lib.rs:148 answers "unsupported operator: 34"): the contract is include/microflow_amd.h's

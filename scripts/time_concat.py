@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU box: CONCATENATION alone, and a fire module's 1x1 expand + its CONCATENATION as ONE launch (k_side_concat.hip: side_concat_rt)
+"""GPU box: CONCATENATION alone, and a fire module's 1x1 expand + its CONCATENATION as ONE launch (k_side_join.hip: side_concat_rt)
 against what it replaces, at the fire modules of SqueezeNet 1.1 with the stages at the resolutions a 224 x 224 input gives them.
 
     python scripts/time_concat.py --mode op                      # concat_c4 at the four fire outputs against torch.cat(dim=-1) on int8

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU box: a ResNet projection shortcut -- the 1x1 Conv2D on the skip edge and the ADD that reads it -- as ONE launch
-(k_shortcut_add.hip: shortcut_add_rt) against the two launches it replaces, at the shapes of ResNet-8's stacks, a stride-1 widening and ResNet-18's 128 -> 256, batch 65 536.
+(k_side_join.hip: shortcut_add_rt) against the two launches it replaces, at the shapes of ResNet-8's stacks, a stride-1 widening and ResNet-18's 128 -> 256, batch 65 536.
 
     python scripts/time_shortcut.py --mode ops   [--root DIR]   # the two operators through the operator API: mf_conv_2d_create +
                                                                  # mf_add_create, mf_op_run / mf_op_run2.  Runs on any commit that has

@@ -3,7 +3,7 @@
 //   side <i> <source> ...            every side operator and the operator it reads (-1: the model input)
 //   join <i> <kind> <skip_src> <skip_real> <candidate> <out_elems>
 //                                    every ADD / CONCATENATION: the tensor it reads, the operator whose tensor stays in memory for it,
-//                                    the side operator rule (6b) / (6c) would group with it (-1: none), its output's elements
+//                                    the side operator rule (6b) would group with it (-1: none), its output's elements
 //   span <first> <last> <0|1>        for every pair first <= last: would one launch over first .. last be refused (group_splits)?
 //   forks <max_fork_elems> <input_skip> <max_elems>
 #include <cstdio>
@@ -24,7 +24,7 @@ int main(int argc, char **argv) {
                 if (pm.ops[i].side()) std::printf("side %zu %d\n", i, pm.ops[i].side_src);
                 if (pm.ops[i].join())
                     std::printf("join %zu %d %d %d %d %zu\n", i, pm.ops[i].kind, pm.ops[i].skip_src, pm.skip_real(i),
-                                pm.ops[i].kind == MF_OP_ADD ? mf::shortcut_candidate(pm, i) : mf::side_concat_candidate(pm, i), pm.ops[i].out_elems);
+                                mf::side_join_candidate(pm, i), pm.ops[i].out_elems);
             }
             for (size_t i = 0; i < pm.ops.size(); ++i)
                 for (size_t j = i; j < pm.ops.size(); ++j) std::printf("span %zu %zu %d\n", i, j, mf::group_splits(pm, i, j) ? 1 : 0);

@@ -20,7 +20,7 @@ int main(int argc, char **argv) {
             std::printf("file %s %zu\n", argv[a], pm.ops.size());
             for (size_t i = 0; i < pm.ops.size(); ++i) {
                 if (pm.ops[i].side()) std::printf("side %zu %d\n", i, pm.ops[i].side_src);
-                if (pm.ops[i].kind == MF_OP_ADD) std::printf("add %zu %d %d %d\n", i, pm.ops[i].skip_src, pm.skip_real(i), mf::shortcut_candidate(pm, i));
+                if (pm.ops[i].kind == MF_OP_ADD) std::printf("add %zu %d %d %d\n", i, pm.ops[i].skip_src, pm.skip_real(i), mf::side_join_candidate(pm, i));
             }
             for (size_t i = 0; i < pm.ops.size(); ++i)
                 for (size_t j = i; j < pm.ops.size(); ++j) std::printf("span %zu %zu %d\n", i, j, mf::group_splits(pm, i, j) ? 1 : 0);

@@ -2,7 +2,7 @@
 types and both file orders of the expands, and report the join's skip and the side operator's source; an identity-skip
 concat(x, conv(x)) loads; every refused form gives its status and reason, and the forms refused before keep their messages;
 mf_preprocess_concatenation is the two f32 divisions; the writer's earlier blobs are byte for byte what they were; the host-side
-routing facts (tests/cpp/concat_route.cpp against the built library: the parser, group_splits, side_concat_candidate) say where the
+routing facts (tests/cpp/concat_route.cpp against the built library: the parser, group_splits, side_join_candidate) say where the
 side convolution and its join form one launch; and the numpy restatement of the contract (tests/concat_ref.py) agrees with a scalar
 restatement on all 256 bytes."""
 import os

@@ -1,4 +1,4 @@
-"""shortcut_add_rt (k_shortcut_add.hip) on the device: one projection block per case -- a 1x1 Conv2D on the skip edge, two 3x3 main
+"""shortcut_add_rt (k_side_join.hip) on the device: one projection block per case -- a 1x1 Conv2D on the skip edge, two 3x3 main
 convolutions, the ADD -- written without a head, so the launch's bytes are the model's output.  Expected tensors: tests/shortcut_ref.py
 (the oracle for the convolutions, tests/add_ref.add for the ADD), computed once per case at the largest batch and left unchanged.  Every
 case names the kernel that ran: the fused launch where the class is taken, the two launches where it is not -- a silent fallback cannot

@@ -1,4 +1,4 @@
-"""side_concat_rt (k_side_concat.hip) on the device: one fire module per case -- a squeeze 1x1, the 1x1 expand on the skip edge, the
+"""side_concat_rt (k_side_join.hip) on the device: one fire module per case -- a squeeze 1x1, the 1x1 expand on the skip edge, the
 3x3 expand on the main chain, their CONCATENATION -- written without a head, so the launch's bytes are the model's output.  Expected
 tensors: tests/concat_ref.py (the oracle for the convolutions, concat_ref.concat for the join), computed once per case on UNIQUE rows
 that the larger batches repeat, and left unchanged.  Every case names the kernel that ran: the fused launch where the class is taken,

@@ -2,7 +2,7 @@
 small blocks, both element types, the side convolution first and last in file order -- and report the side operator's source and the
 ADD's skip; every form beside them is refused with the reference-style message and the reason; the writer's earlier blobs are byte for
 byte what they were; and the host-side routing facts (tests/cpp/shortcut_route.cpp against the built library: the parser, group_splits,
-shortcut_candidate) say where the side convolution and its ADD form one launch and that no other group spans a side operator."""
+side_join_candidate) say where the side convolution and its ADD form one launch and that no other group spans a side operator."""
 import hashlib
 import json
 import os
