@@ -7,7 +7,7 @@
 //
 //   microflow::Tensor2D / Tensor4D                      src/tensor.rs:27-47
 //   microflow::FusedActivation, TensorViewPadding       src/activation.rs:6-13, src/tensor.rs:9-15
-//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / average_pool_2d / max_pool_2d (ours) / add (ours) / concatenation (ours) / pad (ours) /
+//   microflow::ops::fully_connected / conv_2d / depthwise_conv_2d / transpose_conv (ours) / average_pool_2d / max_pool_2d (ours) / add (ours) / concatenation (ours) / pad (ours) /
 //                   softmax / reshape                    src/ops/*.rs
 //   microflow::Model  (what #[model("x.tflite")] generates: predict, predict_quantized)
 //                                                        microflow-macros/src/lib.rs:185-203
@@ -115,6 +115,7 @@ struct Conv2DOptions { // src/ops/conv_2d.rs:11-15
     std::array<int, 2> strides{1, 1};
 };
 using DepthwiseConv2DOptions = Conv2DOptions; // src/ops/depthwise_conv_2d.rs:11-15
+using TransposeConvOptions = Conv2DOptions;   // (ours) tflite.fbs TransposeConvOptions: the same three fields
 using AveragePool2DOptions = Conv2DOptions;   // src/ops/average_pool_2d.rs:12-16
 
 struct FullyConnectedConstants { // (Buffer2D<f32,N,1>, f32, Buffer2D<i32,1,N>, i32)
@@ -157,6 +158,24 @@ inline Tensor4D conv_2d(const Tensor4D &input, const Tensor4D &filters, std::arr
                             input.zero_point[0], output_scale[0], output_zero_point[0], (int)options.fused_activation,
                             (int)options.view_padding, options.strides[0], options.strides[1], output_shape[0],
                             output_shape[1], constants.c0.data(), constants.c1.data(), (int)constants.c1.size(), &op));
+    Tensor4D out;
+    out.buffer = detail::run(op, input.buffer, (size_t)input.batches);
+    out.batches = input.batches, out.rows = output_shape[0], out.cols = output_shape[1], out.chans = filters.batches;
+    out.scale = {output_scale[0]}, out.zero_point = {output_zero_point[0]};
+    return out;
+}
+
+// TRANSPOSE_CONV (TFLite builtin 67; the reference has none: microflow_amd.h states the contract).  filters as conv_2d's (OHWI);
+// output_shape = (OH, OW), which SAME or VALID must allow.
+inline Tensor4D transpose_conv(const Tensor4D &input, const Tensor4D &filters, std::array<float, 1> output_scale,
+                               std::array<int8_t, 1> output_zero_point, TransposeConvOptions options, const ConvConstants &constants,
+                               std::array<int, 2> output_shape, int device = 0) {
+    mf_op *op = nullptr;
+    check(mf_transpose_conv_create(device, input.rows, input.cols, input.chans, filters.batches, filters.rows, filters.cols,
+                                   filters.buffer.data(), filters.zero_point.data(), (int)filters.zero_point.size(),
+                                   input.zero_point[0], output_scale[0], output_zero_point[0], (int)options.fused_activation,
+                                   (int)options.view_padding, options.strides[0], options.strides[1], output_shape[0],
+                                   output_shape[1], constants.c0.data(), constants.c1.data(), (int)constants.c1.size(), &op));
     Tensor4D out;
     out.buffer = detail::run(op, input.buffer, (size_t)input.batches);
     out.batches = input.batches, out.rows = output_shape[0], out.cols = output_shape[1], out.chans = filters.batches;

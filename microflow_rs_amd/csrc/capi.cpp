@@ -191,13 +191,13 @@ static std::vector<int> widen(const T *zp, int nq) {
     return std::vector<int>(zp, zp + nq);
 }
 }
-static void create_conv(int device, bool u8, bool dw, int H, int W, int Cin, int N, int KH, int KW,
+static void create_conv(int device, bool u8, int kind, int H, int W, int Cin, int N, int KH, int KW,
                         const void *weights, const std::vector<int> &wzp, int izp, float output_scale,
                         int ozp, int act, int pad, int sh, int sw, int OH, int OW, const float *c0,
                         const float *c1, int nc1, mf_op **op) {
     MF_NEED(op && weights && c0 && c1);
     mf::OpSpec s;
-    s.kind = dw ? MF_OP_DEPTHWISE_CONV_2D : MF_OP_CONV_2D, s.u8 = u8;
+    s.kind = kind, s.u8 = u8;
     s.H = H, s.W = W, s.C = Cin, s.N = N, s.KH = KH, s.KW = KW;
     s.weights = (const int8_t *)weights, s.wzp = wzp.data(), s.nq = (int)wzp.size(), s.izp = izp;
     s.oscale = output_scale, s.ozp = ozp, s.act = check_act_arg(act);
@@ -256,7 +256,7 @@ int mf_conv_2d_create(int device, int H, int W, int C, int N, int KH, int KW, co
                       int view_padding, int stride_h, int stride_w, int OH, int OW,
                       const float *c0, const float *c1, int nc1, mf_op **op) {
     MF_TRY({
-        create_conv(device, false, false, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+        create_conv(device, false, MF_OP_CONV_2D, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
                     input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
                     stride_h, stride_w, OH, OW, c0, c1, nc1, op);
     })
@@ -267,7 +267,30 @@ int mf_conv_2d_create_u8(int device, int H, int W, int C, int N, int KH, int KW,
                          int view_padding, int stride_h, int stride_w, int OH, int OW,
                          const float *c0, const float *c1, int nc1, mf_op **op) {
     MF_TRY({
-        create_conv(device, true, false, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+        create_conv(device, true, MF_OP_CONV_2D, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op);
+    })
+}
+
+int mf_transpose_conv_create(int device, int H, int W, int C, int N, int KH, int KW, const int8_t *filters,
+                             const int8_t *filters_zero_point, int nq, int8_t input_zero_point,
+                             float output_scale, int8_t output_zero_point, int fused_activation,
+                             int view_padding, int stride_h, int stride_w, int OH, int OW,
+                             const float *c0, const float *c1, int nc1, mf_op **op) {
+    MF_TRY({
+        create_conv(device, false, MF_OP_TRANSPOSE_CONV, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op);
+    })
+}
+int mf_transpose_conv_create_u8(int device, int H, int W, int C, int N, int KH, int KW, const uint8_t *filters,
+                                const uint8_t *filters_zero_point, int nq, uint8_t input_zero_point,
+                                float output_scale, uint8_t output_zero_point, int fused_activation,
+                                int view_padding, int stride_h, int stride_w, int OH, int OW,
+                                const float *c0, const float *c1, int nc1, mf_op **op) {
+    MF_TRY({
+        create_conv(device, true, MF_OP_TRANSPOSE_CONV, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
                     input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
                     stride_h, stride_w, OH, OW, c0, c1, nc1, op);
     })
@@ -280,7 +303,7 @@ int mf_depthwise_conv_2d_create(int device, int H, int W, int Cin, int KH, int K
                                 int stride_h, int stride_w, int OH, int OW, const float *c0,
                                 const float *c1, int nc1, mf_op **op) {
     MF_TRY({
-        create_conv(device, false, true, H, W, Cin, C, KH, KW, weights, widen(weights_zero_point, nq),
+        create_conv(device, false, MF_OP_DEPTHWISE_CONV_2D, H, W, Cin, C, KH, KW, weights, widen(weights_zero_point, nq),
                     input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
                     stride_h, stride_w, OH, OW, c0, c1, nc1, op);
     })
@@ -292,7 +315,7 @@ int mf_depthwise_conv_2d_create_u8(int device, int H, int W, int Cin, int KH, in
                                    int stride_h, int stride_w, int OH, int OW, const float *c0,
                                    const float *c1, int nc1, mf_op **op) {
     MF_TRY({
-        create_conv(device, true, true, H, W, Cin, C, KH, KW, weights, widen(weights_zero_point, nq),
+        create_conv(device, true, MF_OP_DEPTHWISE_CONV_2D, H, W, Cin, C, KH, KW, weights, widen(weights_zero_point, nq),
                     input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
                     stride_h, stride_w, OH, OW, c0, c1, nc1, op);
     })

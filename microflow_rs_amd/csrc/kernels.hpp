@@ -834,6 +834,32 @@ bool conv_gemm_plan_pads(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uin
                          int sh, int sw, int OH, int OW, int padt, int padl, bool wz); // explicit top / left pads (PAD + convolution)
 std::vector<int8_t> conv_gemm_weight_image(const int8_t *w /*[N][KH][KW][C]*/, const ConvGemmArgs &a);
 void launch_conv_gemm(const int8_t *in, int8_t *out, const ConvGemmArgs &a, bool wz, int batch, hipStream_t s);
+// TRANSPOSE_CONV split by output phase (k_tconv.hip: tconv_phase_rt): the sh sw phases of a base pixel (q, qx) are stride-1 products
+// over K' = Ty x (Tx C rounded up to 16) each, conv_gemm_rt's K layout on a staged NHWC tile; the operands are wimage.cpp's
+// (build_tconv_image / _kc / _table).  C % 4 == 0, (W C) % 4 == 0, strides <= 4, filter sides <= 8, filter zero points 0.
+struct TconvArgs {
+    int H, W, C, N, KH, KW, sh, sw, OH, OW;
+    int padt, padl;      // TFLite's: max(0, (H - 1) sh + KH - OH) / 2, the same in W
+    int NBY, NBX;        // base rows and pixels per image: ceil((OH + padt) / sh), ceil((OW + padl) / sw)
+    int TYM, TXM;        // most taps of a phase per column / row: ceil(KH / sh), ceil(KW / sw)
+    int NPH, KSUM;       // phases (sh sw), k steps of all phases together
+    int NT, NTS, NSL, TB; // 16-column tiles over N, tiles per resident slice, slices, tiles per block (<= 4)
+    int LP, ROW, RB, TILE, G, BH, NBANDS; // image tile: RB = BH + TYM - 1 rows of ROW bytes, the image LP bytes into a row; G images or bands of BH base rows
+    int xoff, toff, lds; // LDS plan: image tiles, int table, total
+    uint32_t izp4;
+    float lo_f, hi_f;
+    const void *wimg;    // build_tconv_image
+    const int *tab;      // build_tconv_table
+    const float *A;      // [NT * 16], zero beyond N
+    const float *S;      // [NT * 16]
+    const int *Kc;       // [NPH][NT * 16]: build_tconv_kc
+    int magic, xr;
+};
+bool tconv_plan(TconvArgs &a, int H, int W, int C, int N, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl); // false: outside the class
+void launch_tconv_phase(const int8_t *in, int8_t *out, const TconvArgs &a, int batch, hipStream_t s);
+// ... and the operator as include/microflow_amd.h states it, one thread per output byte, filter zero points included (ConvArgs
+// as conv2d_generic's; Kc unused)
+void launch_tconv_generic(const int8_t *in, int8_t *out, const ConvArgs &a, int padt, int padl, size_t batch, hipStream_t s);
 // A Conv2D + the AveragePool2D (more than one output pixel) on exactly its output in one launch (k_conv_pool.hip: conv_pool_rt).  The
 // convolution is conv_gemm_rt's product with the WHOLE weight image resident; its requantised bytes go to an LDS image
 // Y[g][conv row][ox][NP] and the pool (avgpool_generic's arithmetic) reads them there.  A step is G whole images, or one band of PB

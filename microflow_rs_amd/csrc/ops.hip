@@ -646,6 +646,46 @@ void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
                 (long long)c.acc_bound, op.fast == OpImpl::NONE || !c.magic ? "" : c.magic == 2 ? " (bit-pattern int->f32, saturating pack)" : " (bit-pattern int->f32)");
 }
 
+// TRANSPOSE_CONV (include/microflow_amd.h: mf_transpose_conv_create).  conv_2d's constants and epilogue mode (the whole-filter
+// accumulator bound covers every phase's); the placement is TFLite's.  tconv_phase_rt for finite constants, zero filter zero points
+// and a shape its plan takes (k_tconv.hip); tconv_generic for everything else.
+void create_tconv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
+    if (s.H <= 0 || s.W <= 0 || s.C <= 0 || s.N <= 0 || s.KH <= 0 || s.KW <= 0 || s.OH <= 0 || s.OW <= 0 || s.sh <= 0 || s.sw <= 0 || s.nq <= 0 ||
+        s.nc1 <= 0 || !s.weights || !s.wzp || !s.c0 || !s.c1)
+        fail(MF_ERR_INVALID_ARG, "transpose_conv: bad arguments");
+    const long long full_h = ((long long)s.H - 1) * s.sh + s.KH, full_w = ((long long)s.W - 1) * s.sw + s.KW;
+    const bool fits = s.pad == MF_PAD_SAME ? ((long long)s.OH + s.sh - 1) / s.sh == s.H && ((long long)s.OW + s.sw - 1) / s.sw == s.W
+                                           : s.OH == full_h && s.OW == full_w;
+    if (!fits) fail(MF_ERR_INVALID_ARG, std::string("transpose_conv: the output size is not what ") + (s.pad == MF_PAD_SAME ? "SAME" : "VALID") + " gives");
+    if ((long long)s.N * s.KH * s.KW * s.C > 0x7fffffffll || (long long)s.OH * s.OW > 0x7fffffffll / s.N) fail(MF_ERR_INVALID_ARG, "transpose_conv: bad arguments");
+    const int padt = (int)(std::max(0LL, full_h - s.OH) / 2), padl = (int)(std::max(0LL, full_w - s.OW) / 2);
+    op.tc_padt = padt, op.tc_padl = padl;
+    op.in_elems = (size_t)s.H * s.W * s.C;
+    op.out_elems = (size_t)s.OH * s.OW * s.N;
+    dom.apply(s, (size_t)s.N * s.KH * s.KW * s.C);
+    const ConvCtx c = prepare_conv(op, s, false, lo, hi, xr);
+    op.generic_name = "tconv_generic";
+    k::TconvArgs &f = op.tcv;
+    if (switches().no_tconv || switches().no_rt || !c.finite || c.wz ||
+        !k::tconv_plan(f, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, padt, padl))
+        return;
+    const std::vector<int8_t> img = wimage::build_tconv_image(s.weights, s.N, s.KH, s.KW, s.C, s.sh, s.sw, f.NTS);
+    const std::vector<int> tab = wimage::build_tconv_table(s.KH, s.KW, s.C, s.sh, s.sw, f.ROW);
+    const std::vector<int32_t> kc = wimage::build_tconv_kc(s.weights, s.N, s.KH, s.KW, s.C, s.sh, s.sw, s.izp, f.NT * 16);
+    op.d_fcw.upload(img.data(), img.size());
+    op.d_tap.upload(tab.data(), tab.size() * sizeof(int));
+    op.d_fcKc.upload(kc.data(), kc.size() * 4);
+    const ConstPtrs p = row_consts(op, c, (size_t)f.NT * 16, s.N, [](int n) { return n; }); // padded to 16-column tiles
+    f.wimg = op.d_fcw.p, f.tab = op.d_tap.as<int>(), f.Kc = op.d_fcKc.as<int>(), f.A = p.A, f.S = p.S;
+    epi_fields_izp(f, op, c);
+    op.fast = OpImpl::TCONV_PHASE;
+    op.fast_name = "tconv_phase_rt<" + std::to_string(s.sh) + "x" + std::to_string(s.sw) + ">";
+    if (switches().verbose)
+        fprintf(stderr, "[microflow_amd] tconv_phase_rt %dx%dx%d -> %dx%dx%d %dx%d s%dx%d: %d phases, %d k steps, %d tiles in %d slice(s) of %d, %s %d x %d rows, %d B LDS\n",
+                s.H, s.W, s.C, s.OH, s.OW, s.N, s.KH, s.KW, s.sh, s.sw, f.NPH, f.KSUM, f.NT, f.NSL, f.NTS, f.NBANDS > 1 ? "bands of" : "images per step:",
+                f.NBANDS > 1 ? f.BH : f.G, f.RB, f.lds);
+}
+
 void create_pool(OpImpl &op, const OpSpec &s, int lo, int hi, int xr) {
     const bool mx = s.kind == MF_OP_MAX_POOL_2D;
     const std::string nm = mx ? "max_pool_2d" : "average_pool_2d";
@@ -885,6 +925,7 @@ OpImpl *op_create(int device, const OpSpec &spec) {
     switch (s.kind) {
     case MF_OP_CONV_2D:
     case MF_OP_DEPTHWISE_CONV_2D: create_conv(*op, s, dom, lo, hi, xr); break;
+    case MF_OP_TRANSPOSE_CONV: create_tconv(*op, s, dom, lo, hi, xr); break;
     case MF_OP_AVERAGE_POOL_2D:
     case MF_OP_MAX_POOL_2D: create_pool(*op, s, lo, hi, xr); break;
     case MF_OP_FULLY_CONNECTED: create_fc(*op, s, dom, lo, hi, xr); break;
@@ -929,7 +970,7 @@ static bool op_runs_fma(const OpImpl *op) {
            op->fast == OpImpl::PW_MFMA || (op->fast == OpImpl::DW_STEM && !stem_valu);
 }
 int op_epilogue_mode(const OpImpl *op) { // of the operator's own (layer-wise) launch; -1: not a convolution-like operator
-    if (op->s.kind != MF_OP_CONV_2D && op->s.kind != MF_OP_DEPTHWISE_CONV_2D) return -1;
+    if (op->s.kind != MF_OP_CONV_2D && op->s.kind != MF_OP_DEPTHWISE_CONV_2D && op->s.kind != MF_OP_TRANSPOSE_CONV) return -1;
     return op_runs_fma(op) ? 3 : op->magic_mode;
 }
 bool op_has_fma_epilogue(const OpImpl *op) { return op->fma_ok; }
@@ -1004,6 +1045,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             break;
         case OpImpl::CONV_GEMM:
             k::launch_conv_gemm(d_in, d_out, op->cgm, op->rt_wz, (int)batch, s);
+            done = true;
+            break;
+        case OpImpl::TCONV_PHASE:
+            k::launch_tconv_phase(d_in, d_out, op->tcv, (int)batch, s);
             done = true;
             break;
         case OpImpl::DW_GEMM:
@@ -1084,6 +1129,7 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
         switch (sp.kind) {
         case MF_OP_CONV_2D: k::launch_conv2d_generic(d_in, d_out, op->conv, batch, s); break;
         case MF_OP_DEPTHWISE_CONV_2D: k::launch_dwconv_generic(d_in, d_out, op->conv, batch, s); break;
+        case MF_OP_TRANSPOSE_CONV: k::launch_tconv_generic(d_in, d_out, op->conv, op->tc_padt, op->tc_padl, batch, s); break;
         case MF_OP_AVERAGE_POOL_2D: k::launch_avgpool_generic(d_in, d_out, op->pool, batch, s); break;
         case MF_OP_MAX_POOL_2D: k::launch_maxpool_generic(d_in, d_out, op->pool, batch, s); break;
         case MF_OP_FULLY_CONNECTED: k::launch_fc_generic(d_in, d_out, op->fc, batch * sp.M, s); break;

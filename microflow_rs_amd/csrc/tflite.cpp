@@ -255,7 +255,7 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
                 bool reads = false;
                 for (uint32_t j = 0; j < in_k.size(); ++j) reads = reads || in_k.get<int32_t>(j) == t;
                 joins += reads;
-            } else others += in_k.get<int32_t>(0) == t;
+            } else others += in_k.get<int32_t>(code_k == MF_OP_TRANSPOSE_CONV && in_k.size() > 2 ? 2 : 0) == t; // (TRANSPOSE_CONV: operand 2 is the image)
         }
     };
     // the non-linear graphs that stay refused keep the chain check's answer, with the reason behind it
@@ -331,7 +331,10 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
         const Vec ins = vec(op, 1), outs = vec(op, 2);
         const Table opt = op.table(4);
         if (!ins.size() || !outs.size()) fail(MF_ERR_INVALID_MODEL, "invalid model: operator without tensors");
-        TensorInfo in = read_tensor(tensors, buffers, ins.get<int32_t>(0));
+        // the operand that continues the chain: input 0, but TRANSPOSE_CONV's inputs are [output_shape, weights, input, (bias)]
+        const uint32_t run_slot = code == MF_OP_TRANSPOSE_CONV ? 2 : 0;
+        if (ins.size() <= run_slot) fail(MF_ERR_INVALID_MODEL, "invalid model: TRANSPOSE_CONV needs 3 inputs");
+        TensorInfo in = read_tensor(tensors, buffers, ins.get<int32_t>(run_slot));
         TensorInfo out = read_tensor(tensors, buffers, outs.get<int32_t>(0));
         const int32_t running_index = prev_index;
         ParsedOp po;
@@ -342,7 +345,7 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             // side operator stands between the main operators or in front of its join), or it still is and a later operator reads
             // it as well (the side operator stands directly behind the fork).  Its output is read by exactly one later join and by
             // nothing else.  It does not become the running value: the chain bookkeeping passes over it
-            const int32_t in0 = ins.get<int32_t>(0);
+            const int32_t in0 = ins.get<int32_t>(run_slot);
             if (pending_side >= 0 && in0 == out_index[(size_t)pending_side]) refuse_side(oi, "two or more operators on the skip edge");
             int t = in0 == g_in.get<int32_t>(0) ? -1 : -2;
             for (size_t j = 0; j < out_index.size(); ++j)
@@ -626,6 +629,68 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             po.c0.resize(1), po.c1.resize(1);
             h_preprocess_pool(in.scale[0], zp_of(in.zp[0], pm.u8), out.scale[0], zp_of(out.zp[0], pm.u8), po.c0.data(),
                               po.c1.data());
+            break;
+        }
+        case MF_OP_TRANSPOSE_CONV: { // not in the reference (lib.rs:148 answers "unsupported operator: 67"): the contract is include/microflow_amd.h's
+            auto refuse = [](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: 67 (TRANSPOSE_CONV: " + why + ")"); };
+            const TensorInfo os = read_tensor(tensors, buffers, ins.get<int32_t>(0));
+            TensorInfo w = read_tensor(tensors, buffers, ins.get<int32_t>(1));
+            const bool has_bias = ins.size() > 3 && ins.get<int32_t>(3) >= 0; // (optional: index -1, or only three inputs)
+            if (!os.data_len) refuse("a non-constant output_shape");
+            if (!w.data_len) refuse("non-constant weights");
+            for (const TensorInfo *t : {&in, &out, &w})
+                if ((t->type != TT_INT8 && t->type != TT_UINT8) || (t->type == TT_UINT8) != pm.u8) refuse("mixed element types");
+            need_quant(in, "TRANSPOSE_CONV"), need_quant(out, "TRANSPOSE_CONV"), need_quant(w, "TRANSPOSE_CONV");
+            if (in.shape.size() != 4 || out.shape.size() != 4 || w.shape.size() != 4) refuse("tensor rank must be 4");
+            if (in.shape[0] != 1 || out.shape[0] != 1) refuse("tensor batch must be 1");
+            if (os.type != TT_INT32 || os.elems() != 4 || os.data_len < 16)
+                fail(MF_ERR_INVALID_MODEL, "invalid model: TRANSPOSE_CONV output_shape must be a constant INT32 [4]");
+            for (int k = 0; k < 4; ++k) {
+                int32_t d;
+                std::memcpy(&d, os.data + 4 * k, 4);
+                if (d != out.shape[(size_t)k]) fail(MF_ERR_INVALID_MODEL, "invalid model: TRANSPOSE_CONV output_shape disagrees with the output tensor's shape");
+            }
+            set_shapes(po, in, out, pm.u8);
+            po.H = in.shape[1], po.W = in.shape[2], po.C = in.shape[3];
+            po.N = w.shape[0], po.KH = w.shape[1], po.KW = w.shape[2]; // OHWI
+            po.OH = out.shape[1], po.OW = out.shape[2];
+            // TransposeConvOptions { padding:0 stride_w:1 stride_h:2 fused_activation_function:3 } (field 3 absent in older files: NONE)
+            po.pad = check_pad(opt.scalar<int8_t>(0, 0));
+            po.sw = opt.scalar<int32_t>(1, 0);
+            po.sh = opt.scalar<int32_t>(2, 0);
+            po.act = check_act(opt.scalar<int8_t>(3, 0));
+            if (po.sh <= 0 || po.sw <= 0) fail(MF_ERR_INVALID_MODEL, "invalid model: bad strides");
+            if (w.shape[3] != po.C) fail(MF_ERR_INVALID_MODEL, "invalid model: TRANSPOSE_CONV channel mismatch");
+            if (out.shape[3] != po.N) fail(MF_ERR_INVALID_MODEL, "invalid model: TRANSPOSE_CONV output channels");
+            if (po.H <= 0 || po.W <= 0 || po.KH <= 0 || po.KW <= 0 || po.OH <= 0 || po.OW <= 0) fail(MF_ERR_INVALID_MODEL, "invalid model: bad tensor dimension");
+            {
+                const long long fh = ((long long)po.H - 1) * po.sh + po.KH, fw = ((long long)po.W - 1) * po.sw + po.KW;
+                const bool fits = po.pad == MF_PAD_SAME ? ((long long)po.OH + po.sh - 1) / po.sh == po.H && ((long long)po.OW + po.sw - 1) / po.sw == po.W
+                                                        : po.OH == fh && po.OW == fw;
+                if (!fits) fail(MF_ERR_INVALID_MODEL, std::string("invalid model: TRANSPOSE_CONV output size is not what ") + (po.pad == MF_PAD_SAME ? "SAME" : "VALID") + " gives");
+            }
+            if (w.data_len < w.elems()) fail(MF_ERR_INVALID_MODEL, "invalid model: short weight buffer");
+            po.weights.assign((const int8_t *)w.data, (const int8_t *)w.data + w.elems());
+            for (int64_t z : w.zp) po.wzp.push_back(zp_of(z, pm.u8));
+            // no bias operand: a bias of N zeros, scale = the output's (ratio 1), zero point 0 -- c0 must come out +0.0f exactly
+            std::vector<int32_t> bias((size_t)po.N, 0), bzp(1, 0);
+            std::vector<float> bscale(1, out.scale[0]);
+            if (has_bias) {
+                TensorInfo b = read_tensor(tensors, buffers, ins.get<int32_t>(3));
+                fix_rank1(b);
+                need_quant(b, "TRANSPOSE_CONV");
+                if (b.type != TT_INT32) refuse("a bias that is not INT32");
+                if (b.data_len < (size_t)po.N * 4) fail(MF_ERR_INVALID_MODEL, "invalid model: short weight buffer");
+                std::memcpy(bias.data(), b.data, (size_t)po.N * 4);
+                bscale = b.scale, bzp.clear();
+                for (int64_t z : b.zp) bzp.push_back((int32_t)z);
+            }
+            po.c0.resize(po.N), po.c1.resize(w.scale.size());
+            h_preprocess_conv(in.scale[0], po.N, bias.data(), bscale.data(), (int)bscale.size(), bzp.data(), (int)bzp.size(), w.scale.data(),
+                              (int)w.scale.size(), out.scale[0], po.c0.data(), po.c1.data());
+            if (!has_bias)
+                for (float c : po.c0)
+                    if (c != 0.0f || std::signbit(c)) fail(MF_ERR_INVALID_MODEL, "invalid model: TRANSPOSE_CONV without a bias needs a finite positive output scale");
             break;
         }
         case BUILTIN_PADV2:

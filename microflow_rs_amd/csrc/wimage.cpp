@@ -345,5 +345,102 @@ std::vector<uint32_t> build_conv_rows_mask(int RWB, int KG) {
     return mk;
 }
 
+// ---- TRANSPOSE_CONV split by output phase (k_tconv.hip: tconv_phase_rt) ----
+// Output row oy has phase py = (oy + padt) % sh and base q = (oy + padt) / sh; its taps are ky = py + sh t, t < Ty = ceil((KH - py) / sh),
+// and tap t reads input row q - t.  The same in x: the Tx taps of a filter row read the input pixels qx - Tx + 1 .. qx, ONE run of
+// Tx C bytes of the NHWC row.  So phase (py, px) is a stride-1 product over k' = t KWCP + j with KWCP = Tx C rounded up to 16 and
+// j = (Tx - 1 - u) C + c for the tap kx = px + sw u: the sub-filter x-reversed inside a row, rows in the order t (input rows downwards
+// from q).  A phase with py >= KH or px >= KW has no tap: K' = 0.
+std::vector<TconvPhase> tconv_phases(int KH, int KW, int C, int sh, int sw) {
+    std::vector<TconvPhase> ph;
+    for (int py = 0; py < sh; ++py)
+        for (int px = 0; px < sw; ++px) {
+            TconvPhase p{};
+            p.py = py, p.px = px;
+            p.Ty = py < KH ? (KH - py + sh - 1) / sh : 0, p.Tx = px < KW ? (KW - px + sw - 1) / sw : 0;
+            if (!p.Ty || !p.Tx) p.Ty = p.Tx = 0;
+            p.KWCP = (p.Tx * C + 15) & ~15, p.KS = (p.Ty * p.KWCP + 63) / 64;
+            ph.push_back(p);
+        }
+    return ph;
+}
+// A tile row holds LP bytes of left halo (TXM - 1 pixels, rounded up to 16), the base pixels up to max(NBX, W) - 1 and, behind the last
+// one's run, the up to 15 bytes a padded filter row reads (+ 16: the rows' bank offset, as conv_gemm_plan's)
+TconvTile tconv_tile(int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl) {
+    TconvTile t{};
+    t.TYM = (KH + sh - 1) / sh, t.TXM = (KW + sw - 1) / sw;
+    t.NBY = (OH + padt + sh - 1) / sh, t.NBX = (OW + padl + sw - 1) / sw;
+    t.LP = ((t.TXM - 1) * C + 15) & ~15;
+    t.ROW = ((t.LP + (long long)(t.NBX > W ? t.NBX : W) * C + 16 + 15) & ~15LL) + 16;
+    return t;
+}
+// the padded [N][Ty KWCP] matrix of one phase
+std::vector<int8_t> build_tconv_phase_matrix(const int8_t *w /*[N][KH][KW][C]*/, int N, int KH, int KW, int C, int sh, int sw, const TconvPhase &p) {
+    const int K = p.Ty * p.KWCP;
+    std::vector<int8_t> m((size_t)N * K, 0);
+    for (int n = 0; n < N; ++n)
+        for (int t = 0; t < p.Ty; ++t)
+            for (int u = 0; u < p.Tx; ++u)
+                std::memcpy(&m[(size_t)n * K + (size_t)t * p.KWCP + (size_t)(p.Tx - 1 - u) * C],
+                            w + (((size_t)n * KH + p.py + sh * t) * KW + p.px + sw * u) * C, (size_t)C);
+    return m;
+}
+// The launch's weight image: per N slice of NTS 16-column tiles, per phase, the slice's tiles of the fc_rt image of that phase's
+// matrix ([tile][k step][64 lanes][16 bytes]: lane l holds column 16 tile + (l & 15), bytes k' = 64 ks + 16 (l >> 4) ..): a slice is one
+// contiguous run, a phase inside a slice of nts tiles starts nts (k steps of the phases before it) KiB into it
+std::vector<int8_t> build_tconv_image(const int8_t *w, int N, int KH, int KW, int C, int sh, int sw, int NTS) {
+    const std::vector<TconvPhase> ph = tconv_phases(KH, KW, C, sh, sw);
+    const int NT = (N + 15) / 16;
+    int KSUM = 0;
+    for (const TconvPhase &p : ph) KSUM += p.KS;
+    std::vector<int8_t> img((size_t)NT * KSUM * 1024, 0);
+    std::vector<std::vector<int8_t>> mats;
+    for (const TconvPhase &p : ph) mats.push_back(build_tconv_phase_matrix(w, N, KH, KW, C, sh, sw, p));
+    size_t o = 0;
+    for (int nt0 = 0; nt0 < NT; nt0 += NTS)
+        for (size_t pi = 0; pi < ph.size(); ++pi) {
+            const int K = ph[pi].Ty * ph[pi].KWCP;
+            for (int nt = nt0; nt < NT && nt < nt0 + NTS; ++nt)
+                for (int ks = 0; ks < ph[pi].KS; ++ks)
+                    for (int lane = 0; lane < 64; ++lane, o += 16) {
+                        const int n = nt * 16 + (lane & 15), k0 = ks * 64 + (lane >> 4) * 16;
+                        for (int i = 0; i < 16 && n < N && k0 + i < K; ++i) img[o + (size_t)i] = mats[pi][(size_t)n * K + k0 + i];
+                    }
+        }
+    return img;
+}
+// Kc[phase][n] = -izp (sum of the phase's taps of filter n), in wrapping i32; rows of NT16 ints, zero beyond N
+std::vector<int32_t> build_tconv_kc(const int8_t *w, int N, int KH, int KW, int C, int sh, int sw, int izp, int NT16) {
+    const std::vector<TconvPhase> ph = tconv_phases(KH, KW, C, sh, sw);
+    std::vector<int32_t> kc(ph.size() * (size_t)NT16, 0);
+    for (size_t pi = 0; pi < ph.size(); ++pi)
+        for (int n = 0; n < N; ++n) {
+            uint32_t sum = 0;
+            for (int t = 0; t < ph[pi].Ty; ++t)
+                for (int u = 0; u < ph[pi].Tx; ++u)
+                    for (int c = 0; c < C; ++c) sum += (uint32_t)(int32_t)w[(((size_t)n * KH + ph[pi].py + sh * t) * KW + ph[pi].px + sw * u) * C + c];
+            kc[pi * (size_t)NT16 + (size_t)n] = (int32_t)(0u - (uint32_t)izp * sum);
+        }
+    return kc;
+}
+// The launch's int table: 32 ints of phase records (k steps, k steps of the phases before) for up to 16 phases, then per phase
+// [KS][4] byte offsets, from the base pixel (row q, pixel qx) of a staged tile with ROW bytes per row, of the 16 bytes lane group g
+// supplies in k step ks; 0 beyond K' (zero weights)
+std::vector<int> build_tconv_table(int KH, int KW, int C, int sh, int sw, int ROW) {
+    const std::vector<TconvPhase> ph = tconv_phases(KH, KW, C, sh, sw);
+    std::vector<int> tab(32, 0);
+    int pre = 0;
+    for (size_t pi = 0; pi < ph.size(); ++pi) {
+        tab[2 * pi] = ph[pi].KS, tab[2 * pi + 1] = pre;
+        pre += ph[pi].KS;
+        for (int ks = 0; ks < ph[pi].KS; ++ks)
+            for (int g = 0; g < 4; ++g) {
+                const int k0 = ks * 64 + g * 16, t = k0 / ph[pi].KWCP, j = k0 % ph[pi].KWCP;
+                tab.push_back(t < ph[pi].Ty ? -t * ROW + j - (ph[pi].Tx - 1) * C : 0);
+            }
+    }
+    return tab;
+}
+
 } // namespace wimage
 } // namespace mf

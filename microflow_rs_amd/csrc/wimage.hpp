@@ -34,5 +34,24 @@ std::vector<uint32_t> build_conv_rows_pack(const int8_t *w, bool depthwise, int 
 inline std::vector<uint32_t> build_dw_c1_pack(const int8_t *w /*[KH][KW][N], N <= 8*/, int KH, int KW, int N, int KG) { return build_conv_rows_pack(w, true, KH, KW, 1, N, KG, 8); }
 std::vector<uint32_t> build_conv_rows_mask(int RWB /* KW C */, int KG);
 
+// TRANSPOSE_CONV split by output phase (k_tconv.hip): the phases of a filter at strides (sh, sw) in the order py sw + px, and the
+// host-built operands of tconv_phase_rt (wimage.cpp)
+struct TconvPhase {
+    int py, px, Ty, Tx; // taps ky = py + sh t (t < Ty), kx = px + sw u (u < Tx); Ty = Tx = 0: the phase has no tap
+    int KWCP, KS;       // Tx C rounded up to 16; 64-deep k steps over K' = Ty KWCP
+};
+std::vector<TconvPhase> tconv_phases(int KH, int KW, int C, int sh, int sw);
+// the staged tile's geometry, one definition for tconv_plan (k_tconv.hip) and the host checks: base rows / pixels per image, most taps
+// of a phase per column / row, the image's byte offset in a tile row, bytes per tile row; rows of a tile of bh base rows = bh + TYM - 1
+struct TconvTile {
+    int NBY, NBX, TYM, TXM, LP;
+    long long ROW;
+};
+TconvTile tconv_tile(int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl);
+std::vector<int8_t> build_tconv_phase_matrix(const int8_t *w /*[N][KH][KW][C]*/, int N, int KH, int KW, int C, int sh, int sw, const TconvPhase &p);
+std::vector<int8_t> build_tconv_image(const int8_t *w /*[N][KH][KW][C]*/, int N, int KH, int KW, int C, int sh, int sw, int NTS);
+std::vector<int32_t> build_tconv_kc(const int8_t *w /*[N][KH][KW][C]*/, int N, int KH, int KW, int C, int sh, int sw, int izp, int NT16);
+std::vector<int> build_tconv_table(int KH, int KW, int C, int sh, int sw, int ROW);
+
 } // namespace wimage
 } // namespace mf

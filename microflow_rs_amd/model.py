@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 
-OP_NAMES = {0: "add", 1: "average_pool_2d", 2: "concatenation", 3: "conv_2d", 4: "depthwise_conv_2d", 9: "fully_connected", 17: "max_pool_2d",
+OP_NAMES = {0: "add", 1: "average_pool_2d", 2: "concatenation", 3: "conv_2d", 4: "depthwise_conv_2d", 67: "transpose_conv", 9: "fully_connected", 17: "max_pool_2d",
             22: "reshape", 25: "softmax", 34: "pad", 40: "mean"}
 
 

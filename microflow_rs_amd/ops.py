@@ -4,6 +4,7 @@ names, argument order and meaning, executed by the HIP kernels behind the C ABI.
     fully_connected(input, weights, output_scale, output_zero_point, options, constants)
     conv_2d(input, filters, output_scale, output_zero_point, options, constants, output_shape)
     depthwise_conv_2d(input, weights, output_scale, output_zero_point, options, constants, output_shape)
+    transpose_conv(input, filters, output_scale, output_zero_point, options, constants, output_shape)     (not in the reference)
     average_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)
     max_pool_2d(input, filter_shape, output_scale, output_zero_point, options, constants, output_shape)   (not in the reference)
     add(a, b, output_scale, output_zero_point, options, constants)                                        (not in the reference)
@@ -216,6 +217,43 @@ def conv_2d(input: Tensor4D, filters: Tensor4D, output_scale, output_zero_point,
     shp = tuple(input.buffer.shape)
     op = prepare_conv_2d(shp[-3:], filters.buffer, filters.zero_point, input.zero_point[0],
                          output_scale[0], output_zero_point[0], options, constants, output_shape)
+    return Tensor4D(op(input.buffer), list(output_scale), list(output_zero_point))
+
+
+@dataclass
+class TransposeConvOptions:               # (not in the reference) tflite.fbs TransposeConvOptions
+    fused_activation: FusedActivation = FusedActivation.NONE
+    view_padding: TensorViewPadding = TensorViewPadding.SAME
+    strides: Tuple[int, int] = (1, 1)
+
+
+def prepare_transpose_conv(in_hwc, filters, filters_zero_point, input_zero_point, output_scale,
+                           output_zero_point, options, constants, out_hw):
+    """filters: [N][KH][KW][C] (TFLite's OHWI); out_hw: the output's (OH, OW), which the caller gives."""
+    dt = _elem(filters)
+    f = _host(filters, dt)
+    N, KH, KW, Cc = f.shape
+    H, W, C_in = in_hwc
+    if C_in != Cc:
+        raise ValueError("filter channels != input channels")
+    fzp = _host(np.reshape(filters_zero_point, -1), dt)
+    c0, c1 = (_host(np.reshape(c, -1), np.float32) for c in constants)
+    h = C.c_void_p()
+    _lib.check(_fn("mf_transpose_conv_create", dt)(
+        _device(), H, W, Cc, N, KH, KW, _ptr(f), _ptr(fzp), fzp.size, int(input_zero_point),
+        float(output_scale), int(output_zero_point), int(options.fused_activation),
+        int(options.view_padding), options.strides[0], options.strides[1], out_hw[0], out_hw[1],
+        _ptr(c0), _ptr(c1), c1.size, C.byref(h)))
+    return PreparedOp(h, (H, W, Cc), (out_hw[0], out_hw[1], N), dt)
+
+
+def transpose_conv(input: Tensor4D, filters: Tensor4D, output_scale, output_zero_point,
+                   options: TransposeConvOptions, constants, output_shape) -> Tensor4D:
+    """TRANSPOSE_CONV (TFLite builtin 67; the reference has none): every input pixel (iy, ix) adds its product with tap (ky, kx) to
+    output (iy sh + ky - padt, ix sw + kx - padl), TFLite's placement; conv_2d's constants and epilogue (include/microflow_amd.h)."""
+    shp = tuple(input.buffer.shape)
+    op = prepare_transpose_conv(shp[-3:], filters.buffer, filters.zero_point, input.zero_point[0],
+                                output_scale[0], output_zero_point[0], options, constants, output_shape)
     return Tensor4D(op(input.buffer), list(output_scale), list(output_zero_point))
 
 

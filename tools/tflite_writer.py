@@ -29,6 +29,8 @@ Each layer dict (all quantization parameters are given, nothing is derived):
                       paddings (the whole [4, 2] operand, any shape), pad_type (INT32 | INT64), pad_const=False (the operand has no
                       buffer), code ("padv2" | "mirror_pad": the same operator under another builtin code)
     mean              keep_dims (out_shape (1,1,1,C) or (1,C)), out_shape, out_q; axes (default (1, 2)), axes_const=False, axes_type
+    transpose_conv    filters [N,KH,KW,C], fscale, fzp, bias int32 [N] or None (no bias operand), bscale, bzp, padding, strides (h, w),
+                      act, out_shape, out_q.  Negative tests: shape_const=False (output_shape has no buffer), shape (its values)
 """
 import struct
 
@@ -38,10 +40,10 @@ from make_fc_model import FB, Table, TableVec, Vec, emit, prune_2_4
 
 INT32, UINT8, INT64, INT8 = 2, 3, 4, 9
 OPCODES = {"add": 0, "average_pool_2d": 1, "concatenation": 2, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "max_pool_2d": 17, "reshape": 22,
-           "softmax": 25, "pad": 34, "mean": 40, "padv2": 60, "mirror_pad": 100}
+           "softmax": 25, "pad": 34, "mean": 40, "padv2": 60, "transpose_conv": 67, "mirror_pad": 100}
 # BuiltinOptions union type ids (tflite.fbs)
 OPT_TYPE = {"add": 11, "concatenation": 10, "conv_2d": 1, "depthwise_conv_2d": 2, "average_pool_2d": 5, "max_pool_2d": 5, "fully_connected": 8, "softmax": 9,
-            "reshape": 17, "pad": 22, "mean": 27, "padv2": 43, "mirror_pad": 77}
+            "reshape": 17, "pad": 22, "mean": 27, "padv2": 43, "transpose_conv": 49, "mirror_pad": 77}
 ACT = {None: 0, "none": 0, "relu": 1, "relu6": 3, 0: 0, 1: 1, 3: 3}
 PAD = {"same": 0, "valid": 1, 0: 0, 1: 1}
 
@@ -98,6 +100,17 @@ def build_model(input_shape, input_q, layers, elem=INT8):
             ins = [cur, tw, tb]
             if "side_of" in L:
                 ins[0] = first if L["side_of"] < 0 else outs[L["side_of"]]
+        elif op == "transpose_conv":  # inputs [output_shape, weights, input, (bias)]
+            w = np.asarray(L["filters"], wdt)
+            shp = np.asarray(L.get("shape", L["out_shape"]), np.int32)
+            ts = add_tensor(shp.shape, INT32, add_buffer(shp) if L.get("shape_const", True) else 0, 1.0, 0)
+            tw = add_tensor(w.shape, elem, add_buffer(w), L["fscale"], L["fzp"])
+            out = add_tensor(L["out_shape"], elem, 0, *L["out_q"])
+            # TransposeConvOptions { padding:0 stride_w:1 stride_h:2 fused_activation_function:3 }
+            opts = Table({0: ("i8", PAD[L["padding"]]), 1: ("i32", L["strides"][1]), 2: ("i32", L["strides"][0]), 3: ("i8", ACT[L.get("act")])})
+            ins = [ts, tw, cur]
+            if L.get("bias") is not None:
+                ins.append(add_tensor((w.shape[0],), INT32, add_buffer(np.asarray(L["bias"], np.int32)), L["bscale"], L["bzp"]))
         elif op in ("average_pool_2d", "max_pool_2d"):
             out = add_tensor(L["out_shape"], elem, 0, *L["out_q"])
             # Pool2DOptions { padding:0 stride_w:1 stride_h:2 filter_width:3 filter_height:4 act:5 }
@@ -438,6 +451,44 @@ def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", el
     wshape = (1, k, k, n) if dw else (n, k, k, C)
     d["weights" if dw else "filters"] = rng.integers(lo, hi, wshape) if wmax is None else rng.integers(mid - wmax, mid + wmax + 1, wshape)
     return d
+
+
+def _tconv_layer(rng, shape, q, n, k, stride, padding="same", act="relu", elem=INT8, bias=True):
+    """one TRANSPOSE_CONV layer dict: a k x k filter to n channels at `stride` on a tensor shape = (H, W, C) of quantisation q; filter
+    zero points at the type's middle, per-channel scales, the output scale sized for the stride^2 phases' share of the taps"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    H, W, C = (int(v) for v in shape)
+    oh, ow = (H * stride, W * stride) if padding == "same" else ((H - 1) * stride + k, (W - 1) * stride + k)
+    sc = rng.uniform(0.002, 0.01, n).astype(np.float32)
+    osc = float(np.float32(q[0] * float(sc.mean()) * 60.0 * np.sqrt(k * k * C / float(stride * stride))))
+    ozp = lo if act in ("relu", "relu6") else int(rng.integers(lo + 20, hi - 20))
+    return dict(op="transpose_conv", filters=rng.integers(lo, hi, (n, k, k, C)), fscale=sc, fzp=np.full(n, (lo + hi) // 2),
+                bias=rng.integers(-500, 500, n) if bias else None, bscale=(sc * np.float32(q[0])).astype(np.float32), bzp=np.zeros(n, np.int64),
+                padding=padding, strides=(stride, stride), act=act, out_shape=(1, oh, ow, n), out_q=(osc, ozp))
+
+
+def conv_autoencoder_layers(rng, input_shape, widths, k=3, elem=INT8, bias=True):
+    """-> (in_q, layers) of conv_autoencoder"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    H, W, C = input_shape
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers = in_q, []
+    for n in widths:
+        layers.append(_conv_layer(rng, (H, W, C), q, False, n, k, 2, act="relu", elem=elem))
+        q, (_, H, W, C) = layers[-1]["out_q"], layers[-1]["out_shape"]
+    for n in list(widths[-2::-1]) + [widths[0]]:
+        layers.append(_tconv_layer(rng, (H, W, C), q, n, k, 2, elem=elem, bias=bias))
+        q, (_, H, W, C) = layers[-1]["out_q"], layers[-1]["out_shape"]
+    layers.append(_conv_layer(rng, (H, W, C), q, False, input_shape[2], 3, 1, act="none", elem=elem))
+    return in_q, layers
+
+
+def conv_autoencoder(rng, input_shape, widths, k=3, elem=INT8, bias=True):
+    """A convolutional autoencoder: input_shape = (H, W, C); a stride-2 k x k Conv2D (relu) per entry of `widths` down, as many stride-2
+    k x k TRANSPOSE_CONVs (relu; without a bias operand when bias=False) back up to the input's size, and a final 3x3 Conv2D to the
+    input's channels.  H and W must be multiples of 2^len(widths)."""
+    in_q, layers = conv_autoencoder_layers(rng, input_shape, widths, k, elem, bias)
+    return build_model((1,) + tuple(input_shape), in_q, layers, elem)
 
 
 def _fc_layer(rng, K, N, q, act="none", elem=INT8, wzp_off=0):
