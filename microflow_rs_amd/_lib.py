@@ -86,6 +86,11 @@ SIGNATURES = {
                                                               C.c_int8, C.c_int, C.c_int, C.c_int,
                                                               C.c_int, C.c_int, C.c_int, _vp, _vp,
                                                               C.c_int, C.POINTER(_vp)]),
+    # (the same argument lists + dilation_h, dilation_w in front of the handle)
+    "mf_conv_2d_dilated_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
+                                  [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "mf_depthwise_conv_2d_dilated_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
+                                            [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "mf_average_pool_2d_create": (C.c_int, [C.c_int] * 6 + [C.c_float, C.c_int8, C.c_int, C.c_int,
                                                             C.c_int, C.c_int, C.c_int, C.c_int,
                                                             C.c_float, C.c_float, C.POINTER(_vp)]),
@@ -110,6 +115,7 @@ SIGNATURES = {
     "mf_op_output_elems": (C.c_size_t, [_vp]),
     "mf_op_kernel_name": (C.c_char_p, [_vp]),
     "mf_op_set_generic": (C.c_int, [_vp, C.c_int]),
+    "mf_op_get_tile_plan": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "mf_op_destroy": (None, [_vp]),
     "mf_quantize": (C.c_int, [C.c_int, _vp, C.c_size_t, C.c_float, C.c_int8, _vp, _vp]),
     "mf_dequantize": (C.c_int, [C.c_int, _vp, C.c_size_t, C.c_float, C.c_int8, _vp, _vp]),
@@ -122,6 +128,7 @@ SIGNATURES = {
     "mf_model_get_op_skip": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mf_model_get_op_source": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     "mf_model_get_op_pads": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
+    "mf_model_get_op_dilation": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mf_model_prepare": (C.c_int, [_vp, C.c_int, C.c_size_t]),
     "mf_model_set_stream": (C.c_int, [_vp, _vp]),
     "mf_model_sync": (C.c_int, [_vp]),
@@ -167,6 +174,7 @@ SIGNATURES = {
 # T = u8 instantiations: the i8 signature with every int8_t value parameter as uint8_t
 for _n in ("mf_preprocess_fully_connected", "mf_preprocess_average_pool_2d",
            "mf_fully_connected_create", "mf_conv_2d_create", "mf_transpose_conv_create", "mf_depthwise_conv_2d_create",
+           "mf_conv_2d_dilated_create", "mf_depthwise_conv_2d_dilated_create",
            "mf_average_pool_2d_create", "mf_max_pool_2d_create", "mf_add_create", "mf_concatenation_create", "mf_pad_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
            "mf_window_gather_quantize"):
     _r, _a = SIGNATURES[_n]

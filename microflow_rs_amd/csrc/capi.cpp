@@ -194,10 +194,10 @@ static std::vector<int> widen(const T *zp, int nq) {
 static void create_conv(int device, bool u8, int kind, int H, int W, int Cin, int N, int KH, int KW,
                         const void *weights, const std::vector<int> &wzp, int izp, float output_scale,
                         int ozp, int act, int pad, int sh, int sw, int OH, int OW, const float *c0,
-                        const float *c1, int nc1, mf_op **op) {
+                        const float *c1, int nc1, mf_op **op, int dh = 1, int dw = 1) {
     MF_NEED(op && weights && c0 && c1);
     mf::OpSpec s;
-    s.kind = kind, s.u8 = u8;
+    s.kind = kind, s.u8 = u8, s.dh = dh, s.dw = dw;
     s.H = H, s.W = W, s.C = Cin, s.N = N, s.KH = KH, s.KW = KW;
     s.weights = (const int8_t *)weights, s.wzp = wzp.data(), s.nq = (int)wzp.size(), s.izp = izp;
     s.oscale = output_scale, s.ozp = ozp, s.act = check_act_arg(act);
@@ -318,6 +318,54 @@ int mf_depthwise_conv_2d_create_u8(int device, int H, int W, int Cin, int KH, in
         create_conv(device, true, MF_OP_DEPTHWISE_CONV_2D, H, W, Cin, C, KH, KW, weights, widen(weights_zero_point, nq),
                     input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
                     stride_h, stride_w, OH, OW, c0, c1, nc1, op);
+    })
+}
+
+// conv_2d / depthwise_conv_2d with dilation factors (include/microflow_amd.h); the entry points above are these at (1, 1)
+int mf_conv_2d_dilated_create(int device, int H, int W, int C, int N, int KH, int KW, const int8_t *filters,
+                              const int8_t *filters_zero_point, int nq, int8_t input_zero_point,
+                              float output_scale, int8_t output_zero_point, int fused_activation,
+                              int view_padding, int stride_h, int stride_w, int OH, int OW,
+                              const float *c0, const float *c1, int nc1, int dilation_h, int dilation_w, mf_op **op) {
+    MF_TRY({
+        create_conv(device, false, MF_OP_CONV_2D, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op, dilation_h, dilation_w);
+    })
+}
+int mf_conv_2d_dilated_create_u8(int device, int H, int W, int C, int N, int KH, int KW, const uint8_t *filters,
+                                 const uint8_t *filters_zero_point, int nq, uint8_t input_zero_point,
+                                 float output_scale, uint8_t output_zero_point, int fused_activation,
+                                 int view_padding, int stride_h, int stride_w, int OH, int OW,
+                                 const float *c0, const float *c1, int nc1, int dilation_h, int dilation_w, mf_op **op) {
+    MF_TRY({
+        create_conv(device, true, MF_OP_CONV_2D, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op, dilation_h, dilation_w);
+    })
+}
+int mf_depthwise_conv_2d_dilated_create(int device, int H, int W, int Cin, int KH, int KW, int C,
+                                        const int8_t *weights, const int8_t *weights_zero_point, int nq,
+                                        int8_t input_zero_point, float output_scale,
+                                        int8_t output_zero_point, int fused_activation, int view_padding,
+                                        int stride_h, int stride_w, int OH, int OW, const float *c0,
+                                        const float *c1, int nc1, int dilation_h, int dilation_w, mf_op **op) {
+    MF_TRY({
+        create_conv(device, false, MF_OP_DEPTHWISE_CONV_2D, H, W, Cin, C, KH, KW, weights, widen(weights_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op, dilation_h, dilation_w);
+    })
+}
+int mf_depthwise_conv_2d_dilated_create_u8(int device, int H, int W, int Cin, int KH, int KW, int C,
+                                           const uint8_t *weights, const uint8_t *weights_zero_point, int nq,
+                                           uint8_t input_zero_point, float output_scale,
+                                           uint8_t output_zero_point, int fused_activation, int view_padding,
+                                           int stride_h, int stride_w, int OH, int OW, const float *c0,
+                                           const float *c1, int nc1, int dilation_h, int dilation_w, mf_op **op) {
+    MF_TRY({
+        create_conv(device, true, MF_OP_DEPTHWISE_CONV_2D, H, W, Cin, C, KH, KW, weights, widen(weights_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op, dilation_h, dilation_w);
     })
 }
 
@@ -457,6 +505,12 @@ size_t mf_op_input_elems(const mf_op *op) { return op && op->impl ? mf::op_in_el
 size_t mf_op_input2_elems(const mf_op *op) { return op && op->impl ? mf::op_in2_elems(op->impl) : 0; }
 size_t mf_op_output_elems(const mf_op *op) { return op && op->impl ? mf::op_out_elems(op->impl) : 0; }
 const char *mf_op_kernel_name(const mf_op *op) { return op && op->impl ? mf::op_kernel_name(op->impl) : ""; }
+int mf_op_get_tile_plan(const mf_op *op, int *plan) {
+    MF_TRY({
+        MF_NEED(op && op->impl && plan);
+        MF_NEED(mf::op_tile_plan(op->impl, plan));
+    })
+}
 int mf_op_set_generic(mf_op *op, int generic) {
     MF_TRY({
         MF_NEED(op && op->impl);
@@ -551,6 +605,17 @@ int mf_model_get_op(const mf_model *model, int index, mf_op_desc *d) {
         d->in_zero_point = o.in_zp, d->out_zero_point = o.out_zp;
         d->out_elems = o.out_elems;
         d->kernel = mf::model_op_kernel(model->impl, index);
+    })
+}
+
+int mf_model_get_op_dilation(const mf_model *model, int index, int *dilation_h, int *dilation_w) {
+    MF_TRY({
+        MF_NEED(model && model->impl && dilation_h && dilation_w);
+        const mf::ParsedModel &pm = mf::model_parsed(model->impl);
+        MF_NEED(index >= 0 && index < (int)pm.ops.size());
+        const mf::ParsedOp &o = pm.ops[(size_t)index];
+        MF_NEED(o.kind == MF_OP_CONV_2D || o.kind == MF_OP_DEPTHWISE_CONV_2D);
+        *dilation_h = o.dh, *dilation_w = o.dw;
     })
 }
 

@@ -120,6 +120,7 @@ static bool conv1_fc_args(OpImpl *cv, OpImpl *fc, OpImpl *sm, k::Conv1FcArgs &a)
     if (switches().no_conv1_fc || !cv || !fc || cv->force_generic || fc->force_generic) return false;
     const OpSpec &d = cv->s, &q = fc->s;
     if ((d.kind != MF_OP_DEPTHWISE_CONV_2D && d.kind != MF_OP_CONV_2D) || d.C != 1 || q.kind != MF_OP_FULLY_CONNECTED) return false;
+    if (d.dilated()) return false; // (a dilated convolution runs layer-wise)
     if (q.M != 1 || q.u8 != d.u8 || fc->device != cv->device || cv->h_w.empty() || fc->h_w.empty()) return false;
     const k::FcArgs &g = fc->fc;
     if ((int)fc->h_A.size() != g.N || (int)fc->h_Kc.size() != g.N || !std::isfinite(g.S) ||
@@ -195,6 +196,7 @@ FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool) {
     const bool mx = q.kind == MF_OP_MAX_POOL_2D;
     if (d.kind != MF_OP_CONV_2D || (q.kind != MF_OP_AVERAGE_POOL_2D && !mx) || conv->device != pool->device || d.u8 != q.u8) return nullptr;
     if (q.H != d.OH || q.W != d.OW || q.C != d.N) return nullptr; // on exactly the convolution's output
+    if (d.dilated()) return nullptr;                               // (a dilated convolution runs layer-wise)
     if (!conv->finite_consts || !std::isfinite(q.pool_c0) || !std::isfinite(q.pool_c1)) return nullptr;
     if (conv->h_w.size() != (size_t)d.N * d.KH * d.KW * d.C || conv->h_A.size() != (size_t)d.N || conv->h_S.size() != (size_t)d.N ||
         conv->h_Kc.size() != (size_t)d.N || conv->h_wzp.size() != (size_t)d.N)

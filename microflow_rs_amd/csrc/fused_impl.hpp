@@ -161,6 +161,7 @@ inline PairMatch match_dw3x3_pw1x1(const OpImpl *dw, const OpImpl *pw) {
     if (d.kind != MF_OP_DEPTHWISE_CONV_2D || q.kind != MF_OP_CONV_2D) return no;
     if (d.u8 != q.u8) return no;
     if (d.KH != 3 || d.KW != 3 || d.pad != MF_PAD_SAME || d.C != d.N) return no;
+    if (d.dilated()) return no; // (a dilated depthwise runs layer-wise; a 1x1 has no factor left: ops.hip create_conv)
     // (pair + tail demands sh == sw == 1; front pair + tail sh == sw and pair_front_supported's stride, 2)
     if (d.sh != d.sw || (d.sh != 1 && d.sh != 2)) return no;
     // (pair + tail and front pair + tail test KH, KW only: the 1x1 kinds they demand, PW_MFMA / PW_RT, are given at stride 1 alone)

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void dw_gemm_rt(const int8_t *__restrict__ in,
 #pragma unroll
     for (int ks = 0; ks < KSMAX; ++ks) {
         const int t = 4 * ks + g;
-        toff[ks] = t < T ? (t / p.KW) * ROW + (t % p.KW) * C : 0;
+        toff[ks] = t < T ? (t / p.KW) * p.dh * ROW + (t % p.KW) * p.dw * C : 0; // (dilation is geometry here: every tap has its own offset)
     }
     // the ones tile: row r of every real tap has its 1 in byte r (the tap's channel r)
     const int one1 = 1 << (8 * (col & 3));
@@ -172,18 +172,25 @@ bool dw_gemm_plan(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, in
     return dw_gemm_plan_pads(a, H, W, C, KH, KW, sh, sw, OH, OW, pad_same ? (KH - 1) / 2 : 0, pad_same ? (KW - 1) / 2 : 0);
 }
 // ... with the window placement given (k_rt.hip conv_rows_plan_pads): the tile is sized from padt, padl, OH and OW
-bool dw_gemm_plan_pads(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl) {
-    if (padt < 0 || padl < 0) return false;
+// ... and the dilation factors: the taps of a window span the effective extent (K - 1) d + 1 rows / pixels, which is what the bytes
+// right of the image row, the rows of a tile and the rows between bands are sized from ((1, 1): the filter's own sides, as before)
+bool dw_gemm_plan_pads(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl, int dh, int dw) {
+    if (padt < 0 || padl < 0 || dh < 1 || dw < 1) return false;
     if (H < 1 || W < 1 || C < 2 || KH < 1 || KW < 1 || sh < 1 || sw < 1 || OH < 1 || OW < 1) return false;
     if (KH > 7 || KW > 7 || (W * C) % 4 != 0) return false;
+    const long long KEH = (long long)(KH - 1) * dh + 1, KEW = (long long)(KW - 1) * dw + 1;
+    if (KEH > 4096 || KEW > 4096) return false;
     const int LP = (padl * C + 15) & ~15;
     // bytes read right of the image row: the last window's last tap, the last group's 16 bytes from its start (<= C - 1 past the
     // tap's first channel) and the 4 bytes of the aligned reads
-    const int reach = ((OW - 1) * sw - padl + KW) * C + 16 + 4;
-    const int ROW = (LP + std::max(W * C, reach) + 15) & ~15;
-    auto rows_for = [&](int bh) { return (bh - 1) * sh + KH; };
+    const long long reach = ((long long)(OW - 1) * sw - padl + KEW) * C + 16 + 4;
+    const long long ROWL = (LP + std::max((long long)W * C, reach) + 15) & ~15LL;
+    if (ROWL > DW_GEMM_LDS_MAX) return false;
+    const int ROW = (int)ROWL;
+    auto rows_for = [&](int bh) { return (bh - 1) * sh + (int)KEH; };
+    if ((long long)rows_for(1) * ROW > DW_GEMM_LDS_MAX) return false;
     a.H = H, a.W = W, a.C = C, a.KH = KH, a.KW = KW, a.sh = sh, a.sw = sw, a.OH = OH, a.OW = OW;
-    a.padl = padl, a.padt = padt, a.LP = LP, a.ROW = ROW;
+    a.padl = padl, a.padt = padt, a.LP = LP, a.ROW = ROW, a.dh = dh, a.dw = dw;
     a.KS = (KH * KW + 3) / 4, a.NBLK = (C + 15) / 16;
     // C <= 8 at stride 1 along the row: P = 16 / C horizontally adjacent output pixels share one 16-row group -- the 16 bytes at
     // the first one's tap are the tap's bytes of all P (the rows past P C meet zero weights)

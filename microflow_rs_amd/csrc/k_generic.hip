@@ -32,12 +32,12 @@ __global__ __launch_bounds__(256) void conv2d_generic(const int8_t *__restrict__
         const size_t img = t / p.OH;
         const int8_t *ip = in + img * (size_t)p.H * p.W * p.C;
         const int8_t *wp = p.w + (size_t)n * p.KH * p.KW * p.C;
-        const int shy = p.pad_same ? (p.KH - 1) / 2 : 0, shx = p.pad_same ? (p.KW - 1) / 2 : 0;
+        const int shy = p.pad_same ? ((p.KH - 1) * p.dh) / 2 : 0, shx = p.pad_same ? ((p.KW - 1) * p.dw) / 2 : 0; // (the effective extent's)
         int dot = 0, vs = 0;
         for (int ky = 0; ky < p.KH; ++ky) {
-            const int iy = oy * p.sh + ky - shy;
+            const int iy = oy * p.sh + ky * p.dh - shy;
             for (int kx = 0; kx < p.KW; ++kx) {
-                const int ix = ox * p.sw + kx - shx;
+                const int ix = ox * p.sw + kx * p.dw - shx;
                 const bool ok = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
                 const int8_t *vp = ip + ((size_t)iy * p.W + ix) * p.C;
                 const int8_t *fp = wp + ((size_t)ky * p.KW + kx) * p.C;
@@ -103,12 +103,12 @@ __global__ __launch_bounds__(256) void dwconv_generic(const int8_t *__restrict__
         const size_t img = t / p.OH;
         const int ci = c < p.C ? c : 0; // v.get(c).copied().unwrap_or(v[0])  (depthwise_conv_2d.rs:67)
         const int8_t *ip = in + img * (size_t)p.H * p.W * p.C;
-        const int shy = p.pad_same ? (p.KH - 1) / 2 : 0, shx = p.pad_same ? (p.KW - 1) / 2 : 0;
+        const int shy = p.pad_same ? ((p.KH - 1) * p.dh) / 2 : 0, shx = p.pad_same ? ((p.KW - 1) * p.dw) / 2 : 0; // (the effective extent's)
         int dot = 0, vs = 0;
         for (int ky = 0; ky < p.KH; ++ky) {
-            const int iy = oy * p.sh + ky - shy;
+            const int iy = oy * p.sh + ky * p.dh - shy;
             for (int kx = 0; kx < p.KW; ++kx) {
-                const int ix = ox * p.sw + kx - shx;
+                const int ix = ox * p.sw + kx * p.dw - shx;
                 const bool ok = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
                 const int v = ok ? (int)ip[((size_t)iy * p.W + ix) * p.C + ci] : p.izp;
                 dot += v * (int)p.w[((size_t)ky * p.KW + kx) * p.N + c];

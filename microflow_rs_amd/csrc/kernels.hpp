@@ -54,6 +54,8 @@ struct ConvArgs {
     const float *S;     // [N]
     const int *Kc;      // [N]
     int xr;             // 0 (i8) or 0x80 (u8)
+    int dh = 1, dw = 1; // dilation factors: tap (ky, kx) reads input (oy sh - padt + ky dh, ox sw - padl + kx dw); SAME pads by the
+                        // effective extent, ((KH - 1) dh) / 2 (conv2d_generic, dwconv_generic; the other ConvArgs kernels run at 1 x 1 only)
 };
 struct PoolArgs {
     int H, W, C, KH, KW, sh, sw, OH, OW, pad_same;
@@ -834,6 +836,19 @@ bool conv_gemm_plan_pads(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uin
                          int sh, int sw, int OH, int OW, int padt, int padl, bool wz); // explicit top / left pads (PAD + convolution)
 std::vector<int8_t> conv_gemm_weight_image(const int8_t *w /*[N][KH][KW][C]*/, const ConvGemmArgs &a);
 void launch_conv_gemm(const int8_t *in, int8_t *out, const ConvGemmArgs &a, bool wz, int batch, hipStream_t s);
+// Conv2D with dilation factors (dh, dw) != (1, 1), C % 4 == 0 (k_conv_dil.hip: conv_dil_rt): conv_gemm_rt's product -- `g` is its
+// argument block, with the same meaning field for field, and the weight image is conv_gemm_weight_image(w, g) -- on a tile whose rows
+// are staged in dw column-phase planes: plane f holds the halo-extended columns xe = x + padl with xe % dw == f, in order, C bytes each,
+// so that the KW taps of a window (xe = ox sw + kx dw) are KW consecutive positions of ONE plane and a filter row is again one
+// contiguous run of KW C bytes.  A tile row is g.LP bytes, then dw planes of PP bytes; tap table entries are ky dh ROW + j.
+struct ConvDilArgs {
+    ConvGemmArgs g;
+    int dh, dw;
+    int PP;              // plane pitch in bytes: ceil(extended width / dw) positions of C bytes, rounded up to 16
+};
+bool conv_dil_plan(ConvDilArgs &a, std::vector<int> &tap, std::vector<uint32_t> &mask, int H, int W, int C, int N, int KH, int KW, int sh,
+                   int sw, int dh, int dw, int OH, int OW, int padt, int padl, bool wz); // false: outside the class, or beyond the LDS budget
+void launch_conv_dil(const int8_t *in, int8_t *out, const ConvDilArgs &a, bool wz, int batch, hipStream_t s);
 // TRANSPOSE_CONV split by output phase (k_tconv.hip: tconv_phase_rt): the sh sw phases of a base pixel (q, qx) are stride-1 products
 // over K' = Ty x (Tx C rounded up to 16) each, conv_gemm_rt's K layout on a staged NHWC tile; the operands are wimage.cpp's
 // (build_tconv_image / _kc / _table).  C % 4 == 0, (W C) % 4 == 0, strides <= 4, filter sides <= 8, filter zero points 0.
@@ -919,10 +934,13 @@ struct DwGemmArgs {
     const int *Kc;       // [NBLK * 16]
     const int *wzp;      // [NBLK * 16]
     int magic, xr;
+    int dh, dw;          // dilation factors (1, 1 unless the plan was given others): tap (ky, kx) lies ky dh rows and kx dw pixels from the window start
 };
 constexpr int DW_GEMM_LDS_MAX = 160 * 1024 - 1024;
 bool dw_gemm_plan(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, bool pad_same); // false: beyond the limits
-bool dw_gemm_plan_pads(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl); // explicit top / left pads (PAD + convolution)
+// explicit top / left pads (PAD + convolution; a dilated SAME layer's ((K - 1) d) / 2); the halo, the tile rows and the bands are sized
+// from the effective extent (K - 1) d + 1
+bool dw_gemm_plan_pads(DwGemmArgs &a, int H, int W, int C, int KH, int KW, int sh, int sw, int OH, int OW, int padt, int padl, int dh = 1, int dw = 1);
 void launch_dw_gemm(const int8_t *in, int8_t *out, const DwGemmArgs &a, bool wz, int batch, hipStream_t s);
 // Consecutive FullyConnected layers (+ a Softmax over one row) in one launch (k_fc_rt.hip: fc_chain).  Every layer's weight image
 // (its fc_rt image, all tiles) stays resident in LDS; the int8 tensors between the layers never leave LDS.

@@ -93,6 +93,7 @@ struct ParsedOp {
     int in_rank = 0, in_shape[4] = {0, 0, 0, 0};
     int out_rank = 0, out_shape[4] = {0, 0, 0, 0};
     int KH = 0, KW = 0, sh = 0, sw = 0, pad = 0, act = 0;
+    int dh = 1, dw = 1; // Conv2D / DepthwiseConv2D: dilation_h_factor, dilation_w_factor
     float in_scale = 0, out_scale = 0;
     int in_zp = 0, out_zp = 0;
     size_t in_elems = 0, out_elems = 0;
@@ -174,6 +175,8 @@ struct OpSpec {
     bool u8 = false;
     int M = 0, K = 0, N = 0;
     int H = 0, W = 0, C = 0, KH = 0, KW = 0, sh = 1, sw = 1, pad = 0, OH = 0, OW = 0;
+    int dh = 1, dw = 1;      // conv_2d / depthwise_conv_2d: dilation factors (an axis with one tap is kept at 1: op_create)
+    bool dilated() const { return dh != 1 || dw != 1; } // (the fused groups pass such an operator by: it runs layer-wise)
     int act = 0;
     int izp = 0;             // zero point of the running input tensor
     float in_scale = 0;      // softmax only
@@ -218,6 +221,8 @@ int op_epilogue_mode(const OpImpl *op); // k_common.hpp epilogue mode (0 .. 3) o
 bool op_has_fma_epilogue(const OpImpl *op);
 int op_fma_patches(const OpImpl *op); // patched accumulators of the operator's single-fma form (0 for most); -1: no such form // the single-fma form (mode 3) was found for every channel and confirmed on the device
 void op_set_generic(OpImpl *op, bool generic);
+// the staged-tile plan of conv_dil_rt / conv_gemm_rt / dw_gemm_rt (include/microflow_amd.h: mf_op_get_tile_plan); false: another kernel
+bool op_tile_plan(const OpImpl *op, int plan[8]);
 // fuse the model-boundary quantize (f32 -> T) into this operator if it has an f32-input kernel
 bool op_set_input_quant(OpImpl *op, float scale, int zp, bool u8);
 bool op_accepts_f32(const OpImpl *op);

@@ -209,7 +209,8 @@ ConvCtx prepare_conv(OpImpl &op, const OpSpec &s, bool dw, int lo, int hi, int x
     c.zero_wzp = !c.wz && c.finite;
     c.same3x3 = s.KH == 3 && s.KW == 3 && s.pad == MF_PAD_SAME && s.sh == s.sw &&
                 s.OH == (s.H + s.sh - 1) / s.sh && s.OW == (s.W + s.sw - 1) / s.sw;
-    c.padt = s.pad == MF_PAD_SAME ? (s.KH - 1) / 2 : 0, c.padl = s.pad == MF_PAD_SAME ? (s.KW - 1) / 2 : 0;
+    // (with dilation factors: of the effective extent (K - 1) d + 1, include/microflow_amd.h)
+    c.padt = s.pad == MF_PAD_SAME ? ((s.KH - 1) * s.dh) / 2 : 0, c.padl = s.pad == MF_PAD_SAME ? ((s.KW - 1) * s.dw) / 2 : 0;
     c.magic = !no_magic && c.acc_bound < (1 << 22) ? 1 : 0;
     // mode 2 (k_common.hpp): the clamp is the element type's whole range (so a saturating pack can do it) and
     // |x| = |A + S * acc| stays below 2^15 for every input (so x + 128 fits the i16 the pack saturates from)
@@ -242,7 +243,7 @@ ConvCtx prepare_conv(OpImpl &op, const OpSpec &s, bool dw, int lo, int hi, int x
     a.lo_f = (float)lo, a.hi_f = (float)hi;
     a.w = op.d_w.as<int8_t>(), a.wzp = op.d_wzp.as<int>(), a.A = op.d_A.as<float>();
     a.S = op.d_S.as<float>(), a.Kc = op.d_Kc.as<int>();
-    a.xr = xr;
+    a.xr = xr, a.dh = s.dh, a.dw = s.dw;
     op.generic_name = dw ? "dwconv_generic" : "conv2d_generic";
     return c;
 }
@@ -517,14 +518,15 @@ bool route_dw_mm(OpImpl &op, const ConvCtx &c) {
 
 // 10. every other DepthwiseConv2D with one output per channel and whole-dword image rows -- C % 16 != 0, filter zero points, 3x3
 // SAME shapes dw3x3_rt rejects -- : the same block-diagonal product, operand B read at its natural alignment (k_dw_gemm.hip)
+std::string dil_tag(const OpSpec &s) { return s.dilated() ? ",d" + std::to_string(s.dh) + "x" + std::to_string(s.dw) : ""; } // in a kernel name
 bool dw_gemm_candidate(const OpImpl &op, const ConvCtx &c) { // (also of route 13's one-channel case)
     return op.fast == OpImpl::NONE && c.dw && !switches().no_rt && !switches().no_dw_gemm && c.finite;
 }
 bool route_dw_gemm(OpImpl &op, const ConvCtx &c) {
     const OpSpec &s = c.s;
     k::DwGemmArgs &f = op.dwg;
-    if (!(dw_gemm_candidate(op, c) && s.C == s.N && s.C >= 2)) return false;
-    if (!k::dw_gemm_plan_pads(f, s.H, s.W, s.C, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, c.padt, c.padl)) return false;
+    if (!(dw_gemm_candidate(op, c) && s.C == s.N && s.C >= 2 && !(s.dilated() && switches().no_conv_dil))) return false;
+    if (!k::dw_gemm_plan_pads(f, s.H, s.W, s.C, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, c.padt, c.padl, s.dh, s.dw)) return false;
     const bool wz = c.wz;
     const std::vector<int8_t> prep = wimage::build_dw_mm_rt_weights(s.weights, s.KH, s.KW, s.C, f.KS, f.P);
     op.d_wprep.upload(prep.data(), prep.size());
@@ -535,7 +537,7 @@ bool route_dw_gemm(OpImpl &op, const ConvCtx &c) {
     epi_fields_izp(f, op, c);
     op.fast = OpImpl::DW_GEMM;
     op.rt_wz = wz;
-    op.fast_name = "dw_gemm_rt<" + std::to_string(s.KH) + "x" + std::to_string(s.KW) + (wz ? ",wzp>" : ">");
+    op.fast_name = "dw_gemm_rt<" + std::to_string(s.KH) + "x" + std::to_string(s.KW) + dil_tag(s) + (wz ? ",wzp>" : ">");
     if (switches().verbose)
         fprintf(stderr, "[microflow_amd] dw_gemm_rt %dx%dx%d %dx%d: %d k steps, %d channel groups of %d pixels, %s %d x %d rows, %d B LDS\n", s.H,
                 s.W, s.C, s.KH, s.KW, f.KS, f.NBLK, f.P, f.NBANDS > 1 ? "bands of" : "images per step:", f.NBANDS > 1 ? f.BH : f.G, f.RB, f.lds);
@@ -608,11 +610,59 @@ bool route_conv_gemm(OpImpl &op, const ConvCtx &c) {
     return true;
 }
 
+// 14. a Conv2D with a dilation factor and C % 4 == 0: conv_gemm_rt's product on a tile staged in column-phase planes (k_conv_dil.hip).
+// The only Conv2D route that takes a dilated operator (route_allowed); other channel counts, and a shape whose plan does not fit in
+// LDS, stay on conv2d_generic.
+bool route_conv_dil(OpImpl &op, const ConvCtx &c) {
+    const OpSpec &s = c.s;
+    if (!(rt_candidate(op, c) && !c.dw && s.dilated() && !switches().no_conv_dil)) return false;
+    const bool wz = c.wz;
+    std::vector<int> tap;
+    std::vector<uint32_t> mask;
+    k::ConvDilArgs &f = op.cdl;
+    if (!k::conv_dil_plan(f, tap, mask, s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.dh, s.dw, s.OH, s.OW, c.padt, c.padl, wz)) return false;
+    const std::vector<int8_t> img = k::conv_gemm_weight_image(s.weights, f.g);
+    op.d_fcw.upload(img.data(), img.size());
+    op.d_tap.upload(tap.data(), tap.size() * sizeof(int));
+    op.d_cgm_mask.upload(mask.data(), mask.size() * 4);
+    f.g.wimg = op.d_fcw.p, f.g.tap = op.d_tap.as<int>(), f.g.kmask = op.d_cgm_mask.as<uint32_t>();
+    const ConstPtrs p = row_consts(op, c, (size_t)f.g.NT * 16, s.N, [](int n) { return n; }); // padded to 16-column tiles
+    f.g.A = p.A, f.g.S = p.S, f.g.Kc = p.Kc, f.g.wzp = p.wzp;
+    epi_fields_izp(f.g, op, c);
+    op.fast = OpImpl::CONV_DIL;
+    op.rt_wz = wz;
+    op.fast_name = "conv_dil_rt<d" + std::to_string(s.dh) + "x" + std::to_string(s.dw) + (wz ? ",wzp>" : ">");
+    if (switches().verbose)
+        fprintf(stderr, "[microflow_amd] conv_dil_rt %dx%dx%d -> %d %dx%d d%dx%d: %d plane(s) of %d B, K' %d (%d k steps), %d tiles in %d slice(s) of %d, %s %d x %d rows of %d B, %d B LDS\n",
+                s.H, s.W, s.C, s.N, s.KH, s.KW, s.dh, s.dw, f.dw, f.PP, s.KH * f.g.KWCP, f.g.KS, f.g.NT, f.g.NSL, f.g.NTS,
+                f.g.NBANDS > 1 ? "bands of" : "images per step:", f.g.NBANDS > 1 ? f.g.BH : f.g.G, f.g.RB, f.g.ROW, f.g.lds);
+    return true;
+}
+
+// the KeH x KeW filter of a dilated operator in the i8 domain: tap (ky, kx) at (ky dh, kx dw), every other tap the channel's filter zero point
+std::vector<int8_t> stuff_filter(const OpSpec &s, bool dw, int KEH, int KEW) {
+    const int CI = dw ? 1 : s.C; // conv [N][KH][KW][C]; depthwise [KH][KW][N]
+    std::vector<int8_t> f((size_t)s.N * KEH * KEW * CI);
+    for (int n = 0; n < s.N; ++n)
+        for (int y = 0; y < KEH; ++y)
+            for (int x = 0; x < KEW; ++x)
+                for (int ci = 0; ci < CI; ++ci) {
+                    const bool tap = y % s.dh == 0 && x % s.dw == 0;
+                    const size_t o = dw ? ((size_t)y * KEW + x) * s.N + n : (((size_t)n * KEH + y) * KEW + x) * CI + ci;
+                    const size_t i = dw ? ((size_t)(y / s.dh) * s.KW + x / s.dw) * s.N + n : (((size_t)n * s.KH + y / s.dh) * s.KW + x / s.dw) * CI + ci;
+                    f[o] = tap ? s.weights[i] : (int8_t)s.wzp[n < s.nq ? n : 0];
+                }
+    return f;
+}
+
 using Route = bool (*)(OpImpl &, const ConvCtx &);
+// An operator with a dilation factor is refused HERE by every route but the two that place their taps by it: the tables, dw3x3_rt,
+// pw_rt, conv_rows, conv_mm_rt, conv1x1, dw_mm_rt and conv_gemm_rt all rest on adjacent taps.
+bool route_allowed(Route r, const ConvCtx &c) { return !c.s.dilated() || r == route_dw_gemm || r == route_conv_dil; }
 // The order is the contract: every shape keeps the kernel it had.
 const Route TABLE_ROUTES[] = {route_dw_table, route_dw_stem, route_dw_stem_rt, route_dw_c1, route_pw_mfma}; // the first whose condition holds
 const Route RT_ROUTES[] = {route_dw_rt, route_pw_rt, route_conv_rows, route_dw_mm, route_dw_gemm, route_conv_mm, route_conv1x1_row,
-                           route_conv_gemm}; // each one, in turn
+                           route_conv_gemm, route_conv_dil}; // each one, in turn
 
 void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
     const bool dw = s.kind == MF_OP_DEPTHWISE_CONV_2D;
@@ -620,16 +670,55 @@ void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
         s.OW <= 0 || s.sh <= 0 || s.sw <= 0 || s.nq <= 0 || s.nc1 <= 0 || !s.weights || !s.wzp ||
         !s.c0 || !s.c1)
         fail(MF_ERR_INVALID_ARG, "conv: bad arguments");
+    if (s.dh <= 0 || s.dw <= 0) fail(MF_ERR_INVALID_ARG, "conv: a dilation factor is not positive");
+    if (s.KH == 1) s.dh = 1; // one tap along an axis: its factor moves nothing, the operator is the undilated one
+    if (s.KW == 1) s.dw = 1;
+    const long long KEH = ((long long)s.KH - 1) * s.dh + 1, KEW = ((long long)s.KW - 1) * s.dw + 1; // the effective extent
     if (s.pad == MF_PAD_VALID &&
-        ((s.OH - 1) * s.sh + s.KH > s.H || (s.OW - 1) * s.sw + s.KW > s.W))
+        ((s.OH - 1) * (long long)s.sh + KEH > s.H || (s.OW - 1) * (long long)s.sw + KEW > s.W))
         fail(MF_ERR_INVALID_ARG, "conv: VALID view leaves the input (the reference would panic, src/tensor.rs:223)");
+    if (s.dilated()) { // the library's own contract: the one output size the placement gives (a wrong one would walk outside the halo)
+        const bool same = s.pad == MF_PAD_SAME;
+        const long long oh = same ? ((long long)s.H + s.sh - 1) / s.sh : (s.H - KEH + 1 + s.sh - 1) / s.sh;
+        const long long ow = same ? ((long long)s.W + s.sw - 1) / s.sw : (s.W - KEW + 1 + s.sw - 1) / s.sw;
+        if (s.OH != oh || s.OW != ow)
+            fail(MF_ERR_INVALID_ARG, std::string(dw ? "depthwise_conv_2d" : "conv_2d") + " with dilation " + std::to_string(s.dh) + "x" + std::to_string(s.dw) +
+                                         ": the output size is not what " + (same ? "SAME" : "VALID") + " gives");
+    }
     op.in_elems = (size_t)s.H * s.W * s.C;
     op.out_elems = (size_t)s.OH * s.OW * s.N;
     dom.apply(s, dw ? (size_t)s.KH * s.KW * s.N : (size_t)s.N * s.KH * s.KW * s.C);
-    const ConvCtx c = prepare_conv(op, s, dw, lo, hi, xr);
-    for (Route r : TABLE_ROUTES)
-        if (r(op, c)) break;
-    for (Route r : RT_ROUTES) r(op, c);
+    auto route = [&](const ConvCtx &c) {
+        for (Route r : TABLE_ROUTES)
+            if (route_allowed(r, c) && r(op, c)) break;
+        for (Route r : RT_ROUTES)
+            if (route_allowed(r, c)) r(op, c);
+    };
+    // A small effective extent: the operator IS the undilated one with the KeH x KeW filter whose added taps hold the filter zero point
+    // ((w - wzp) = 0 there: the same accumulator, the same Kc, the same bound), and below 3x the taps the undilated kernels run that
+    // filter faster than the plane staging or the dilated tap geometry (x0.95 - x1.02 at 1.7x and 2.8x, x1.06 at 3x).  Taken
+    // where a fast undilated route takes the stuffed operator; else, and from 3x on, the dilated routes.
+    std::vector<int8_t> stuffed;
+    OpSpec t = s;
+    int64_t acc_bound = 0;
+    int magic = 0;
+    bool routed = false;
+    if (s.dilated() && !switches().no_conv_dil && KEH * KEW < 3LL * s.KH * s.KW) {
+        stuffed = stuff_filter(s, dw, (int)KEH, (int)KEW);
+        t.KH = (int)KEH, t.KW = (int)KEW, t.dh = t.dw = 1, t.weights = stuffed.data();
+        const ConvCtx c = prepare_conv(op, t, dw, lo, hi, xr);
+        route(c);
+        acc_bound = c.acc_bound, magic = c.magic;
+        if (op.fast != OpImpl::NONE) op.dil_note = "[" + dil_tag(s).substr(1) + "]", op.fast_name += op.dil_note, s = t, routed = true; // (the operator keeps the stuffed spec)
+    }
+    // (After a stuffed attempt no fast route took, this prepares a second time: constants, weights and the single-fma search again.  What
+    // the first pass left in `op` -- fma_ok, the single-fma constants -- stays valid, because the stuffed and the dilated operator have the
+    // same A, S, Kc and accumulator ranges: the added taps contribute (w - wzp) = 0.)
+    if (!routed) { // not stuffed (every undilated operator: the one preparation it always had), or no fast route took the stuffed one
+        const ConvCtx c = prepare_conv(op, s, dw, lo, hi, xr);
+        route(c);
+        acc_bound = c.acc_bound, magic = c.magic;
+    }
     if (op.fma_ok) { // the single-fma constants beside the two-rounding ones, in the blocks of the kernels that have the form
         op.dwf.A3 = op.pw.A3 = op.d_A3.as<float>(), op.dwf.S3 = op.pw.S3 = op.d_S3.as<float>();
         op.dwf.Kc3 = op.pw.Kc3 = op.d_Kc3.as<int>();
@@ -643,7 +732,7 @@ void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
         fprintf(stderr, "[microflow_amd] %s %dx%dx%d -> %d: kernel %s, worst-case |acc| %lld%s\n",
                 dw ? "depthwise_conv_2d" : "conv_2d", s.H, s.W, s.C, s.N,
                 op.fast != OpImpl::NONE ? op.fast_name.c_str() : op.generic_name.c_str(),
-                (long long)c.acc_bound, op.fast == OpImpl::NONE || !c.magic ? "" : c.magic == 2 ? " (bit-pattern int->f32, saturating pack)" : " (bit-pattern int->f32)");
+                (long long)acc_bound, op.fast == OpImpl::NONE || !magic ? "" : magic == 2 ? " (bit-pattern int->f32, saturating pack)" : " (bit-pattern int->f32)");
 }
 
 // TRANSPOSE_CONV (include/microflow_amd.h: mf_transpose_conv_create).  conv_2d's constants and epilogue mode (the whole-filter
@@ -906,9 +995,11 @@ OpImpl *op_create_padded_conv(const OpImpl *conv, int Hin, int Win, int padt, in
     c.wz = !all_zero(c.wzp), c.zero_wzp = !c.wz && c.finite;
     c.padt = padt, c.padl = padl, c.rows_bytes_any_c = true;
     // the run-time-geometry routes that take a window placement, in create_conv's order; the two-rounding epilogue (no single-fma form)
-    for (Route r : {route_conv_rows, route_dw_mm, route_dw_gemm, route_conv_mm, route_conv_gemm}) r(*op, c);
+    for (Route r : {route_conv_rows, route_dw_mm, route_dw_gemm, route_conv_mm, route_conv_gemm, route_conv_dil})
+        if (route_allowed(r, c)) r(*op, c);
     op->s.weights = nullptr, op->s.wzp = nullptr, op->s.c0 = op->s.c1 = nullptr, op->s.c2 = nullptr;
     if (op->fast == OpImpl::NONE) return nullptr;
+    op->fast_name += conv->dil_note;
     return op.release();
 }
 
@@ -961,6 +1052,18 @@ const char *op_kernel_name(const OpImpl *op) {
                                                              : op->generic_name.c_str();
 }
 void op_set_generic(OpImpl *op, bool g) { op->force_generic = g; }
+bool op_tile_plan(const OpImpl *op, int plan[8]) {
+    auto put = [&](int planes, int pitch, int row, int rb, int nbands, int bh, int g, int nsl) {
+        const int v[8] = {planes, pitch, row, rb, nbands, bh, g, nsl};
+        std::copy(v, v + 8, plan);
+        return true;
+    };
+    const k::ConvGemmArgs &c = op->fast == OpImpl::CONV_DIL ? op->cdl.g : op->cgm;
+    if (op->fast == OpImpl::CONV_DIL) return put(op->cdl.dw, op->cdl.PP, c.ROW, c.RB, c.NBANDS, c.BH, c.G, c.NSL);
+    if (op->fast == OpImpl::CONV_GEMM) return put(1, 0, c.ROW, c.RB, c.NBANDS, c.BH, c.G, c.NSL);
+    if (op->fast == OpImpl::DW_GEMM) return put(1, 0, op->dwg.ROW, op->dwg.RB, op->dwg.NBANDS, op->dwg.BH, op->dwg.G, 1);
+    return false;
+}
 // the layer-wise kernels that have the single-fma epilogue (k_common.hpp mode 3): the matrix-pipe depthwise, the MFMA pointwise, the stem
 static bool op_runs_fma(const OpImpl *op) {
     if (!op->fma_strict()) return false; // (the layer-wise kernels have no patch support)
@@ -1045,6 +1148,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             break;
         case OpImpl::CONV_GEMM:
             k::launch_conv_gemm(d_in, d_out, op->cgm, op->rt_wz, (int)batch, s);
+            done = true;
+            break;
+        case OpImpl::CONV_DIL:
+            k::launch_conv_dil(d_in, d_out, op->cdl, op->rt_wz, (int)batch, s);
             done = true;
             break;
         case OpImpl::TCONV_PHASE:

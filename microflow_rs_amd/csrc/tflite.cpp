@@ -435,6 +435,21 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             po.sh = opt.scalar<int32_t>(2, 0);
             po.act = check_act(opt.scalar<int8_t>(dw ? 4 : 3, 0));
             if (po.sh <= 0 || po.sw <= 0) fail(MF_ERR_INVALID_MODEL, "invalid model: bad strides");
+            // ... dilation_w_factor:4 dilation_h_factor:5 (Conv2DOptions), 5 and 6 (DepthwiseConv2DOptions), default 1: the library's own
+            // contract (include/microflow_amd.h: mf_conv_2d_dilated_create), which fixes the output size
+            po.dw = opt.scalar<int32_t>(dw ? 5 : 4, 1);
+            po.dh = opt.scalar<int32_t>(dw ? 6 : 5, 1);
+            if (po.dh <= 0 || po.dw <= 0)
+                fail(MF_ERR_INVALID_MODEL, std::string("invalid model: ") + nm + " dilation factors " + std::to_string(po.dh) + "x" + std::to_string(po.dw) + " are not positive");
+            if ((po.dh != 1 && po.KH != 1) || (po.dw != 1 && po.KW != 1)) {
+                const long long keh = ((long long)po.KH - 1) * po.dh + 1, kew = ((long long)po.KW - 1) * po.dw + 1;
+                const bool same = po.pad == MF_PAD_SAME;
+                const long long oh = same ? ((long long)po.H + po.sh - 1) / po.sh : (po.H - keh + po.sh) / po.sh;
+                const long long ow = same ? ((long long)po.W + po.sw - 1) / po.sw : (po.W - kew + po.sw) / po.sw;
+                if (po.H < (same ? 1 : keh) || po.W < (same ? 1 : kew) || po.OH != oh || po.OW != ow)
+                    fail(MF_ERR_INVALID_MODEL, std::string("invalid model: ") + nm + " with dilation " + std::to_string(po.dh) + "x" + std::to_string(po.dw) + ": the output shape is not what " +
+                                                   (same ? "SAME" : "VALID") + " gives (" + std::to_string(oh) + " x " + std::to_string(ow) + ")");
+            }
             if (dw) {
                 if (w.shape[0] != 1) fail(MF_ERR_INVALID_MODEL, "invalid model: depthwise weights batch != 1");
                 po.N = w.shape[3];

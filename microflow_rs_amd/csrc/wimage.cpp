@@ -442,5 +442,40 @@ std::vector<int> build_tconv_table(int KH, int KW, int C, int sh, int sw, int RO
     return tab;
 }
 
+// ---- conv_dil_rt (k_conv_dil.hip): a Conv2D with dilation factors on a tile staged in column-phase planes ----
+// The halo-extended columns of a row are xe = x + padl, 0 <= xe < WE, where WE covers the image (padl + W) and the last window's last
+// tap ((OW - 1) sw + (KW - 1) dw).  Plane f holds the columns xe % dw == f at position xe / dw: PL = ceil(WE / dw) positions of C
+// bytes, PP = PL C rounded up to 16 bytes.  A row is LP bytes, the dw planes, and 16 bytes behind the last plane for the up to 15 bytes
+// a padded filter row reads past its KW C real ones (+ 16: the rows' bank offset, as conv_gemm_plan's).  LP: with one plane the image's
+// first byte, LP + padl C, is brought to a 16-byte boundary for the LDS-DMA row copy; with more planes rows are de-interleaved by
+// register copies and LP is 0.  C % 4 == 0 keeps every plane, position and LP on a dword (C % 16 == 0: on 16 bytes).
+ConvDilTile conv_dil_tile(int W, int C, int KW, int sw, int dw, int OW, int padl) {
+    ConvDilTile t{};
+    t.KWCP = (KW * C + 15) & ~15;
+    const long long WE = std::max((long long)padl + W, (long long)(OW - 1) * sw + (long long)(KW - 1) * dw + 1);
+    t.PL = (int)((WE + dw - 1) / dw);
+    t.PP = ((long long)t.PL * C + 15) & ~15LL;
+    t.LP = dw == 1 ? (int)((16 - ((long long)padl * C) % 16) % 16) : 0;
+    t.ROW = ((t.LP + (long long)dw * t.PP + 16 + 15) & ~15LL) + 16;
+    return t;
+}
+// byte offset of halo-extended column xe inside a tile row
+long long conv_dil_column(const ConvDilTile &t, int C, int dw, int xe) { return t.LP + (long long)(xe % dw) * t.PP + (long long)(xe / dw) * C; }
+// conv_gemm_rt's [KS][4] tap table and [KS][4][4] real-byte masks over K' = KH KWCP, the filter rows dh tile rows apart: lane group g
+// of k step ks supplies the 16 bytes at (window start) + ky dh ROW + j; beyond K' offset 0 against zero weights
+void conv_dil_tables(int KH, int KW, int C, int dh, int ROW, std::vector<int> &tap, std::vector<uint32_t> &mask) {
+    const int KWC = KW * C, KWCP = (KWC + 15) & ~15, KS = (KH * KWCP + 63) / 64;
+    tap.assign((size_t)KS * 4, 0);
+    mask.assign((size_t)KS * 16, 0);
+    for (int ks = 0; ks < KS; ++ks)
+        for (int g = 0; g < 4; ++g) {
+            const int k0 = ks * 64 + g * 16, ky = k0 / KWCP, j = k0 % KWCP;
+            if (ky >= KH) continue;
+            tap[(size_t)ks * 4 + g] = ky * dh * ROW + j;
+            for (int i = 0; i < 16; ++i)
+                if (j + i < KWC) mask[(size_t)(ks * 4 + g) * 4 + i / 4] |= 0xffu << (8 * (i & 3));
+        }
+}
+
 } // namespace wimage
 } // namespace mf

@@ -53,5 +53,16 @@ std::vector<int8_t> build_tconv_image(const int8_t *w /*[N][KH][KW][C]*/, int N,
 std::vector<int32_t> build_tconv_kc(const int8_t *w /*[N][KH][KW][C]*/, int N, int KH, int KW, int C, int sh, int sw, int izp, int NT16);
 std::vector<int> build_tconv_table(int KH, int KW, int C, int sh, int sw, int ROW);
 
+// A Conv2D with dilation factors (k_conv_dil.hip): the geometry of a tile row staged in dw column-phase planes, one definition for
+// conv_dil_plan and the host checks; and the tap / mask tables of conv_gemm_rt's K layout with the filter rows dh tile rows apart
+struct ConvDilTile {
+    int KWCP;          // KW C rounded up to 16
+    int PL, LP;        // positions per plane; bytes in front of plane 0
+    long long PP, ROW; // plane pitch, bytes per tile row
+};
+ConvDilTile conv_dil_tile(int W, int C, int KW, int sw, int dw, int OW, int padl);
+long long conv_dil_column(const ConvDilTile &t, int C, int dw, int xe /* x + padl */);
+void conv_dil_tables(int KH, int KW, int C, int dh, int ROW, std::vector<int> &tap, std::vector<uint32_t> &mask);
+
 } // namespace wimage
 } // namespace mf

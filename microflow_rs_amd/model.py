@@ -76,6 +76,13 @@ class Model:
         _lib.check(_lib.lib().mf_model_get_op_pads(self._h, int(i), p))
         return (p[0], p[1]), (p[2], p[3])
 
+    def op_dilation(self, i):
+        """(dilation_h, dilation_w) of Conv2D / DepthwiseConv2D i as the file states them; (1, 1) where it states none.
+        MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
+        dh, dw = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().mf_model_get_op_dilation(self._h, int(i), C.byref(dh), C.byref(dw)))
+        return dh.value, dw.value
+
     def op_source(self, i):
         """the operator whose output side operator i (the Conv2D on a skip edge) reads instead of the running value; -1: the model
         input.  The ADD or CONCATENATION behind it names i as its skip (op_skip).  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""

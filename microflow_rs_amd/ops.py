@@ -38,6 +38,7 @@ class Conv2DOptions:                      # src/ops/conv_2d.rs:11-15
     fused_activation: FusedActivation = FusedActivation.NONE
     view_padding: TensorViewPadding = TensorViewPadding.SAME
     strides: Tuple[int, int] = (1, 1)
+    dilation: Tuple[int, int] = (1, 1)    # (not in the reference) (dilation_h, dilation_w): include/microflow_amd.h mf_conv_2d_dilated_create
 
 
 @dataclass
@@ -45,6 +46,7 @@ class DepthwiseConv2DOptions:             # src/ops/depthwise_conv_2d.rs:11-15
     fused_activation: FusedActivation = FusedActivation.NONE
     view_padding: TensorViewPadding = TensorViewPadding.SAME
     strides: Tuple[int, int] = (1, 1)
+    dilation: Tuple[int, int] = (1, 1)    # (not in the reference) as Conv2DOptions'
 
 
 @dataclass
@@ -101,6 +103,13 @@ class PreparedOp:
     @property
     def kernel(self):
         return _lib.lib().mf_op_kernel_name(self._h).decode()
+
+    def tile_plan(self):
+        """dict(planes, pitch, row, rows, bands, band_rows, images, slices) of a conv_dil_rt / conv_gemm_rt / dw_gemm_rt operator
+        (mf_op_get_tile_plan); MicroflowError for an operator on another kernel"""
+        p = (C.c_int * 8)()
+        _lib.check(_lib.lib().mf_op_get_tile_plan(self._h, p))
+        return dict(zip(("planes", "pitch", "row", "rows", "bands", "band_rows", "images", "slices"), p))
 
     def set_generic(self, generic=True):
         _lib.check(_lib.lib().mf_op_set_generic(self._h, int(generic)))
@@ -203,11 +212,12 @@ def prepare_conv_2d(in_hwc, filters, filters_zero_point, input_zero_point, outpu
     fzp = _host(np.reshape(filters_zero_point, -1), dt)
     c0, c1 = (_host(np.reshape(c, -1), np.float32) for c in constants)
     h = C.c_void_p()
-    _lib.check(_fn("mf_conv_2d_create", dt)(
+    dil = tuple(int(d) for d in getattr(options, "dilation", (1, 1)))
+    _lib.check(_fn("mf_conv_2d_dilated_create", dt)(
         _device(), H, W, Cc, N, KH, KW, _ptr(f), _ptr(fzp), fzp.size, int(input_zero_point),
         float(output_scale), int(output_zero_point), int(options.fused_activation),
         int(options.view_padding), options.strides[0], options.strides[1], out_hw[0], out_hw[1],
-        _ptr(c0), _ptr(c1), c1.size, C.byref(h)))
+        _ptr(c0), _ptr(c1), c1.size, dil[0], dil[1], C.byref(h)))
     return PreparedOp(h, (H, W, Cc), (out_hw[0], out_hw[1], N), dt)
 
 
@@ -268,11 +278,12 @@ def prepare_depthwise_conv_2d(in_hwc, weights, weights_zero_point, input_zero_po
     wzp = _host(np.reshape(weights_zero_point, -1), dt)
     c0, c1 = (_host(np.reshape(c, -1), np.float32) for c in constants)
     h = C.c_void_p()
-    _lib.check(_fn("mf_depthwise_conv_2d_create", dt)(
+    dil = tuple(int(d) for d in getattr(options, "dilation", (1, 1)))
+    _lib.check(_fn("mf_depthwise_conv_2d_dilated_create", dt)(
         _device(), H, W, Cin, KH, KW, WC, _ptr(w), _ptr(wzp), wzp.size, int(input_zero_point),
         float(output_scale), int(output_zero_point), int(options.fused_activation),
         int(options.view_padding), options.strides[0], options.strides[1], out_hw[0], out_hw[1],
-        _ptr(c0), _ptr(c1), c1.size, C.byref(h)))
+        _ptr(c0), _ptr(c1), c1.size, dil[0], dil[1], C.byref(h)))
     return PreparedOp(h, (H, W, Cin), (out_hw[0], out_hw[1], WC), dt)
 
 

@@ -97,6 +97,9 @@ def build_model(input_shape, input_q, layers, elem=INT8):
             else:                # DepthwiseConv2DOptions { padding:0 stride_w:1 stride_h:2 depth_multiplier:3 act:4 }
                 opts = Table({0: ("i8", PAD[L["padding"]]), 1: ("i32", L["strides"][1]), 2: ("i32", L["strides"][0]),
                               3: ("i32", L.get("depth_multiplier", 1)), 4: ("i8", ACT[L.get("act")])})
+            if tuple(L.get("dilation", (1, 1))) != (1, 1):  # dilation_w_factor, dilation_h_factor: fields 4, 5 (Conv2D) / 5, 6 (depthwise)
+                f0 = 4 if op == "conv_2d" else 5
+                opts = Table({**opts.fields, f0: ("i32", L["dilation"][1]), f0 + 1: ("i32", L["dilation"][0])})
             ins = [cur, tw, tb]
             if "side_of" in L:
                 ins[0] = first if L["side_of"] < 0 else outs[L["side_of"]]
@@ -422,16 +425,18 @@ def _same_or_valid(size, k, s, padding):
     return -(-size // s) if padding == "same" else (size - k) // s + 1
 
 
-def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", elem=INT8, wzp="none", wmax=None, act_scale=None):
+def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", elem=INT8, wzp="none", wmax=None, act_scale=None, dilation=(1, 1)):
     """conv_net's per-layer form, one layer dict: a k x k Conv2D to n channels, or (dw) a k x k depthwise, on a tensor shape = (H, W, C)
     of quantisation q; per-channel filter quantisation; the output scale keeps the outputs spread, or is act_scale with
     person_detect_like's filter scales; the output zero point is the type's minimum behind relu / relu6 and a random one without an
     activation.  wzp: filter zero points off the middle -- "conv": Conv2D only, conv_net's draw; "all": the depthwise ones too, both
-    with inverted_residual_net's draw, which never lands on the middle."""
+    with inverted_residual_net's draw, which never lands on the middle.  k: the filter side, or (KH, KW); dilation: (dh, dw), written into
+    the options where it is not (1, 1), the output sized from the effective extent (k - 1) d + 1."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     H, W, C = (int(v) for v in shape)
-    oh, ow = _same_or_valid(H, k, stride, padding), _same_or_valid(W, k, stride, padding)
+    kh, kw = (k, k) if np.isscalar(k) else k
+    oh, ow = _same_or_valid(H, (kh - 1) * dilation[0] + 1, stride, padding), _same_or_valid(W, (kw - 1) * dilation[1] + 1, stride, padding)
     n = C if dw else int(n)
     sc = rng.uniform(0.002, 0.01, n).astype(np.float32)
     if wzp == "all":
@@ -439,7 +444,7 @@ def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", el
         zp[zp == mid] = mid + 5
     else:
         zp = rng.integers(mid - 10, mid + 11, n) if wzp == "conv" and not dw else np.full(n, mid)
-    taps = k * k * (1 if dw else C)
+    taps = kh * kw * (1 if dw else C)
     osc = float(np.float32(q[0] * float(sc.mean()) * 60.0 * np.sqrt(taps)))
     if act_scale is not None:
         sc = (rng.uniform(0.6, 1.4, n) * 2.2 / (74.0 * np.sqrt(taps)) * (128.0 / (wmax or 128))).astype(np.float32)
@@ -448,7 +453,9 @@ def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", el
     d = dict(op="depthwise_conv_2d" if dw else "conv_2d", fscale=sc, fzp=zp, bias=rng.integers(-500, 500, n),
              bscale=(sc * np.float32(q[0])).astype(np.float32), bzp=np.zeros(n, np.int64), padding=padding, strides=(stride, stride),
              act=act, out_shape=(1, oh, ow, n), out_q=(osc, ozp))
-    wshape = (1, k, k, n) if dw else (n, k, k, C)
+    if tuple(dilation) != (1, 1):
+        d["dilation"] = (int(dilation[0]), int(dilation[1]))
+    wshape = (1, kh, kw, n) if dw else (n, kh, kw, C)
     d["weights" if dw else "filters"] = rng.integers(lo, hi, wshape) if wmax is None else rng.integers(mid - wmax, mid + wmax + 1, wshape)
     return d
 
@@ -1184,4 +1191,29 @@ def keras_resnet_stem_layers(rng, side=32, elem=INT8, filters=64):
 def keras_resnet_stem(rng, side=32, elem=INT8, **kw):
     """keras_resnet_stem_layers' model as a flatbuffer"""
     in_shape, in_q, layers = keras_resnet_stem_layers(rng, side, elem, **kw)
+    return build_model(in_shape, in_q, layers, elem)
+
+
+def tcn_layers(rng, T=32, C=8, filters=16, k=3, dilations=(1, 2, 4, 8), classes=6, elem=INT8):
+    """A temporal convolutional network as the converter writes a Keras Conv1D stack: the signal [1, 1, T, C]; a 1x1 Conv2D to
+    `filters` channels; one residual block per dilation d -- the causal left pad of (k - 1) d columns (PAD), a 1 x k VALID Conv2D with
+    dilation_w = d (relu), and an ADD with the block's input --; MEAN over {1, 2}; FullyConnected.  -> build_model's arguments"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    layers = [_conv_layer(rng, (1, T, C), in_q, False, filters, 1, 1, "same", "relu", elem)]
+    q, F = layers[0]["out_q"], int(filters)
+    for d in dilations:
+        skip, q_skip = len(layers) - 1, q
+        layers.append(_pad_layer((1, T, F), q, ((0, 0), ((k - 1) * d, 0))))
+        layers.append(_conv_layer(rng, (1, T + (k - 1) * d, F), q, False, F, (1, k), 1, "valid", "relu", elem, dilation=(1, d)))
+        layers.append(_add_layer(rng, skip, (1, 1, T, F), layers[-1]["out_q"], q_skip, "none", elem))
+        q = layers[-1]["out_q"]
+    layers.append(dict(op="mean", keep_dims=False, out_shape=(1, F), out_q=q))
+    layers.append(_fc_layer(rng, F, int(classes), q, "none", elem))
+    return (1, 1, int(T), int(C)), in_q, layers
+
+
+def tcn(rng, T=32, C=8, filters=16, k=3, dilations=(1, 2, 4, 8), classes=6, elem=INT8):
+    """tcn_layers' model as a flatbuffer"""
+    in_shape, in_q, layers = tcn_layers(rng, T, C, filters, k, dilations, classes, elem)
     return build_model(in_shape, in_q, layers, elem)
