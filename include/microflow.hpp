@@ -114,6 +114,7 @@ struct Conv2DOptions { // src/ops/conv_2d.rs:11-15
     TensorViewPadding view_padding = TensorViewPadding::Same;
     std::array<int, 2> strides{1, 1};
     std::array<int, 2> dilation{1, 1}; // (ours) (dilation_h, dilation_w) of conv_2d / depthwise_conv_2d: microflow_amd.h mf_conv_2d_dilated_create; the other operators ignore it
+    int groups = 1;                    // (ours) conv_2d: filters [N][KH][KW][C / groups] (microflow_amd.h mf_conv_2d_grouped_create); the other operators ignore it
 };
 using DepthwiseConv2DOptions = Conv2DOptions; // src/ops/depthwise_conv_2d.rs:11-15
 using TransposeConvOptions = Conv2DOptions;   // (ours) tflite.fbs TransposeConvOptions: the same three fields
@@ -154,12 +155,12 @@ inline Tensor4D conv_2d(const Tensor4D &input, const Tensor4D &filters, std::arr
                         std::array<int8_t, 1> output_zero_point, Conv2DOptions options, const ConvConstants &constants,
                         std::array<int, 2> output_shape, int device = 0) {
     mf_op *op = nullptr;
-    check(mf_conv_2d_dilated_create(device, input.rows, input.cols, input.chans, filters.batches, filters.rows, filters.cols,
+    check(mf_conv_2d_grouped_create(device, input.rows, input.cols, input.chans, filters.batches, filters.rows, filters.cols,
                                     filters.buffer.data(), filters.zero_point.data(), (int)filters.zero_point.size(),
                                     input.zero_point[0], output_scale[0], output_zero_point[0], (int)options.fused_activation,
                                     (int)options.view_padding, options.strides[0], options.strides[1], output_shape[0],
                                     output_shape[1], constants.c0.data(), constants.c1.data(), (int)constants.c1.size(),
-                                    options.dilation[0], options.dilation[1], &op));
+                                    options.dilation[0], options.dilation[1], options.groups, &op));
     Tensor4D out;
     out.buffer = detail::run(op, input.buffer, (size_t)input.batches);
     out.batches = input.batches, out.rows = output_shape[0], out.cols = output_shape[1], out.chans = filters.batches;

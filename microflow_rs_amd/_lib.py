@@ -89,6 +89,8 @@ SIGNATURES = {
     # (the same argument lists + dilation_h, dilation_w in front of the handle)
     "mf_conv_2d_dilated_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
                                   [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "mf_conv_2d_grouped_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
+                                  [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),  # (+ groups)
     "mf_depthwise_conv_2d_dilated_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
                                             [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "mf_average_pool_2d_create": (C.c_int, [C.c_int] * 6 + [C.c_float, C.c_int8, C.c_int, C.c_int,
@@ -129,6 +131,7 @@ SIGNATURES = {
     "mf_model_get_op_source": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     "mf_model_get_op_pads": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     "mf_model_get_op_dilation": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mf_model_get_op_groups": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     "mf_model_prepare": (C.c_int, [_vp, C.c_int, C.c_size_t]),
     "mf_model_set_stream": (C.c_int, [_vp, _vp]),
     "mf_model_sync": (C.c_int, [_vp]),
@@ -174,7 +177,7 @@ SIGNATURES = {
 # T = u8 instantiations: the i8 signature with every int8_t value parameter as uint8_t
 for _n in ("mf_preprocess_fully_connected", "mf_preprocess_average_pool_2d",
            "mf_fully_connected_create", "mf_conv_2d_create", "mf_transpose_conv_create", "mf_depthwise_conv_2d_create",
-           "mf_conv_2d_dilated_create", "mf_depthwise_conv_2d_dilated_create",
+           "mf_conv_2d_dilated_create", "mf_depthwise_conv_2d_dilated_create", "mf_conv_2d_grouped_create",
            "mf_average_pool_2d_create", "mf_max_pool_2d_create", "mf_add_create", "mf_concatenation_create", "mf_pad_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
            "mf_window_gather_quantize"):
     _r, _a = SIGNATURES[_n]

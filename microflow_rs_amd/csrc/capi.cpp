@@ -194,10 +194,10 @@ static std::vector<int> widen(const T *zp, int nq) {
 static void create_conv(int device, bool u8, int kind, int H, int W, int Cin, int N, int KH, int KW,
                         const void *weights, const std::vector<int> &wzp, int izp, float output_scale,
                         int ozp, int act, int pad, int sh, int sw, int OH, int OW, const float *c0,
-                        const float *c1, int nc1, mf_op **op, int dh = 1, int dw = 1) {
+                        const float *c1, int nc1, mf_op **op, int dh = 1, int dw = 1, int groups = 1) {
     MF_NEED(op && weights && c0 && c1);
     mf::OpSpec s;
-    s.kind = kind, s.u8 = u8, s.dh = dh, s.dw = dw;
+    s.kind = kind, s.u8 = u8, s.dh = dh, s.dw = dw, s.groups = groups;
     s.H = H, s.W = W, s.C = Cin, s.N = N, s.KH = KH, s.KW = KW;
     s.weights = (const int8_t *)weights, s.wzp = wzp.data(), s.nq = (int)wzp.size(), s.izp = izp;
     s.oscale = output_scale, s.ozp = ozp, s.act = check_act_arg(act);
@@ -366,6 +366,30 @@ int mf_depthwise_conv_2d_dilated_create_u8(int device, int H, int W, int Cin, in
         create_conv(device, true, MF_OP_DEPTHWISE_CONV_2D, H, W, Cin, C, KH, KW, weights, widen(weights_zero_point, nq),
                     input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
                     stride_h, stride_w, OH, OW, c0, c1, nc1, op, dilation_h, dilation_w);
+    })
+}
+
+// conv_2d with dilation factors and groups (include/microflow_amd.h); mf_conv_2d_dilated_create is this at groups = 1
+int mf_conv_2d_grouped_create(int device, int H, int W, int C, int N, int KH, int KW, const int8_t *filters,
+                              const int8_t *filters_zero_point, int nq, int8_t input_zero_point,
+                              float output_scale, int8_t output_zero_point, int fused_activation,
+                              int view_padding, int stride_h, int stride_w, int OH, int OW,
+                              const float *c0, const float *c1, int nc1, int dilation_h, int dilation_w, int groups, mf_op **op) {
+    MF_TRY({
+        create_conv(device, false, MF_OP_CONV_2D, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op, dilation_h, dilation_w, groups);
+    })
+}
+int mf_conv_2d_grouped_create_u8(int device, int H, int W, int C, int N, int KH, int KW, const uint8_t *filters,
+                                 const uint8_t *filters_zero_point, int nq, uint8_t input_zero_point,
+                                 float output_scale, uint8_t output_zero_point, int fused_activation,
+                                 int view_padding, int stride_h, int stride_w, int OH, int OW,
+                                 const float *c0, const float *c1, int nc1, int dilation_h, int dilation_w, int groups, mf_op **op) {
+    MF_TRY({
+        create_conv(device, true, MF_OP_CONV_2D, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op, dilation_h, dilation_w, groups);
     })
 }
 
@@ -616,6 +640,16 @@ int mf_model_get_op_dilation(const mf_model *model, int index, int *dilation_h, 
         const mf::ParsedOp &o = pm.ops[(size_t)index];
         MF_NEED(o.kind == MF_OP_CONV_2D || o.kind == MF_OP_DEPTHWISE_CONV_2D);
         *dilation_h = o.dh, *dilation_w = o.dw;
+    })
+}
+
+int mf_model_get_op_groups(const mf_model *model, int index, int *groups) {
+    MF_TRY({
+        MF_NEED(model && model->impl && groups);
+        const mf::ParsedModel &pm = mf::model_parsed(model->impl);
+        MF_NEED(index >= 0 && index < (int)pm.ops.size());
+        MF_NEED(pm.ops[(size_t)index].kind == MF_OP_CONV_2D);
+        *groups = pm.ops[(size_t)index].groups;
     })
 }
 

@@ -9,7 +9,7 @@ FusedImpl *fused_tail_create(OpImpl *pool, OpImpl *conv, OpImpl *sm) {
     const OpSpec &p = pool->s, &c = conv->s, &m = sm->s;
     if (p.u8 != c.u8 || c.u8 != m.u8) return nullptr;
     if (!conv->finite_consts || !std::isfinite(p.pool_c0) || !std::isfinite(p.pool_c1)) return nullptr;
-    if (p.kind != MF_OP_AVERAGE_POOL_2D || c.kind != MF_OP_CONV_2D || m.kind != MF_OP_SOFTMAX) return nullptr;
+    if (p.kind != MF_OP_AVERAGE_POOL_2D || c.kind != MF_OP_CONV_2D || c.grouped() || m.kind != MF_OP_SOFTMAX) return nullptr; // (a grouped Conv2D launches alone)
     if (p.OH != 1 || p.OW != 1) return nullptr;                       // one pooling window
     if (c.KH != 1 || c.KW != 1 || c.H != 1 || c.W != 1 || c.OH != 1 || c.OW != 1 || c.C != p.C) return nullptr;
     if (m.M != 1 || m.N != c.N) return nullptr;                       // softmax over the head's N values
@@ -120,7 +120,7 @@ static bool conv1_fc_args(OpImpl *cv, OpImpl *fc, OpImpl *sm, k::Conv1FcArgs &a)
     if (switches().no_conv1_fc || !cv || !fc || cv->force_generic || fc->force_generic) return false;
     const OpSpec &d = cv->s, &q = fc->s;
     if ((d.kind != MF_OP_DEPTHWISE_CONV_2D && d.kind != MF_OP_CONV_2D) || d.C != 1 || q.kind != MF_OP_FULLY_CONNECTED) return false;
-    if (d.dilated()) return false; // (a dilated convolution runs layer-wise)
+    if (d.dilated() || d.grouped()) return false; // (a dilated or grouped convolution runs layer-wise)
     if (q.M != 1 || q.u8 != d.u8 || fc->device != cv->device || cv->h_w.empty() || fc->h_w.empty()) return false;
     const k::FcArgs &g = fc->fc;
     if ((int)fc->h_A.size() != g.N || (int)fc->h_Kc.size() != g.N || !std::isfinite(g.S) ||
@@ -196,7 +196,7 @@ FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool) {
     const bool mx = q.kind == MF_OP_MAX_POOL_2D;
     if (d.kind != MF_OP_CONV_2D || (q.kind != MF_OP_AVERAGE_POOL_2D && !mx) || conv->device != pool->device || d.u8 != q.u8) return nullptr;
     if (q.H != d.OH || q.W != d.OW || q.C != d.N) return nullptr; // on exactly the convolution's output
-    if (d.dilated()) return nullptr;                               // (a dilated convolution runs layer-wise)
+    if (d.dilated() || d.grouped()) return nullptr;                // (a dilated or grouped convolution runs layer-wise)
     if (!conv->finite_consts || !std::isfinite(q.pool_c0) || !std::isfinite(q.pool_c1)) return nullptr;
     if (conv->h_w.size() != (size_t)d.N * d.KH * d.KW * d.C || conv->h_A.size() != (size_t)d.N || conv->h_S.size() != (size_t)d.N ||
         conv->h_Kc.size() != (size_t)d.N || conv->h_wzp.size() != (size_t)d.N)
@@ -269,6 +269,7 @@ FusedImpl *fused_pad_conv_create(OpImpl *pad, OpImpl *conv) {
     if (p.kind != MF_OP_PAD || (d.kind != MF_OP_CONV_2D && !dw) || d.pad != MF_PAD_VALID || pad->device != conv->device || p.u8 != d.u8) return nullptr;
     if (d.H != p.OH || d.W != p.OW || d.C != p.C) return nullptr; // on exactly the PAD's output
     if (d.KH == 1 && d.KW == 1) return nullptr;
+    if (d.grouped()) return nullptr; // (a grouped Conv2D launches alone; the PAD keeps its own launch)
     if (!conv->finite_consts) return nullptr;
     // the PAD's fill is the byte the kernels put outside the image: the convolution's input zero point (it is, where the model's
     // quantisation is consistent; where not, the two launches compute what the file says)
@@ -360,6 +361,7 @@ static std::unique_ptr<FusedImpl> side_join_group(FusedImpl::Kind kind, OpImpl *
     if ((add ? switches().no_shortcut_add : switches().no_side_concat) || !conv || !join || conv->force_generic || join->force_generic) return nullptr;
     const OpSpec &d = conv->s, &q = join->s;
     if (q.kind != (add ? MF_OP_ADD : MF_OP_CONCATENATION) || conv->device != join->device || d.u8 != q.u8) return nullptr;
+    if (d.grouped()) return nullptr; // (a grouped Conv2D launches alone, then the join)
     const bool zero_wzp = std::all_of(conv->h_wzp.begin(), conv->h_wzp.end(), [](int32_t z) { return z == 0; });
     if (!(add ? shortcut_add_class(d, zero_wzp, conv->finite_consts) : side_concat_class(d, CR, zero_wzp, conv->finite_consts))) return nullptr;
     if (conv->h_w.size() != (size_t)d.N * d.C || !std::isfinite(q.join_ca) || !std::isfinite(q.join_cb)) return nullptr;

@@ -161,6 +161,7 @@ inline PairMatch match_dw3x3_pw1x1(const OpImpl *dw, const OpImpl *pw) {
     if (d.kind != MF_OP_DEPTHWISE_CONV_2D || q.kind != MF_OP_CONV_2D) return no;
     if (d.u8 != q.u8) return no;
     if (d.KH != 3 || d.KW != 3 || d.pad != MF_PAD_SAME || d.C != d.N) return no;
+    if (q.grouped()) return no; // (a grouped Conv2D launches alone)
     if (d.dilated()) return no; // (a dilated depthwise runs layer-wise; a 1x1 has no factor left: ops.hip create_conv)
     // (pair + tail demands sh == sw == 1; front pair + tail sh == sw and pair_front_supported's stride, 2)
     if (d.sh != d.sw || (d.sh != 1 && d.sh != 2)) return no;
@@ -190,7 +191,7 @@ inline BlockMatch match_expand_block(const OpImpl *ex, const OpImpl *dw, const O
     m.pair = match_dw3x3_pw1x1(dw, pw);
     if (!ex || !m.pair) return no;
     const OpSpec &e = ex->s, &d = *m.pair.d, &q = *m.pair.q;
-    if (e.kind != MF_OP_CONV_2D || ex->device != dw->device || e.u8 != d.u8 || !ex->finite_consts) return no;
+    if (e.kind != MF_OP_CONV_2D || e.grouped() || ex->device != dw->device || e.u8 != d.u8 || !ex->finite_consts) return no; // (a grouped Conv2D launches alone)
     if (e.KH != 1 || e.KW != 1 || e.sh != 1 || e.sw != 1 || e.OH != e.H || e.OW != e.W) return no;
     if (e.H != d.H || e.W != d.W || e.N != d.C) return no; // on exactly the depthwise's input
     if (ex->force_generic || dw->force_generic || pw->force_generic) return no; // (generic operators stay launches of their own)

@@ -10,6 +10,7 @@ namespace mf {
 static std::unique_ptr<FusedImpl> table_pair_create(OpImpl *dw, OpImpl *pw) {
     if (!dw || !pw || dw->fast != OpImpl::DW_NHWC || pw->fast != OpImpl::PW_MFMA) return nullptr;
     const OpSpec &d = dw->s, &q = pw->s;
+    if (q.grouped()) return nullptr; // (a grouped Conv2D, or its twin, launches alone)
     // the pointwise conv must consume exactly the depthwise output tensor
     if (q.H != d.OH || q.W != d.OW || q.C != d.N || dw->device != pw->device) return nullptr;
     const char *nm = k::dwpw_name(d.H, d.W, d.C, d.sh, q.N);

@@ -31,7 +31,9 @@ __global__ __launch_bounds__(256) void conv2d_generic(const int8_t *__restrict__
         const int oy = (int)(t % p.OH);
         const size_t img = t / p.OH;
         const int8_t *ip = in + img * (size_t)p.H * p.W * p.C;
-        const int8_t *wp = p.w + (size_t)n * p.KH * p.KW * p.C;
+        // (grouped: output n of group n / (N / groups) reads that group's C / groups input channels; filters [N][KH][KW][C / groups])
+        const int Cg = p.C / p.groups, c0 = (n / (p.N / p.groups)) * Cg;
+        const int8_t *wp = p.w + (size_t)n * p.KH * p.KW * Cg;
         const int shy = p.pad_same ? ((p.KH - 1) * p.dh) / 2 : 0, shx = p.pad_same ? ((p.KW - 1) * p.dw) / 2 : 0; // (the effective extent's)
         int dot = 0, vs = 0;
         for (int ky = 0; ky < p.KH; ++ky) {
@@ -39,9 +41,9 @@ __global__ __launch_bounds__(256) void conv2d_generic(const int8_t *__restrict__
             for (int kx = 0; kx < p.KW; ++kx) {
                 const int ix = ox * p.sw + kx * p.dw - shx;
                 const bool ok = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-                const int8_t *vp = ip + ((size_t)iy * p.W + ix) * p.C;
-                const int8_t *fp = wp + ((size_t)ky * p.KW + kx) * p.C;
-                for (int c = 0; c < p.C; ++c) {
+                const int8_t *vp = ip + ((size_t)iy * p.W + ix) * p.C + c0;
+                const int8_t *fp = wp + ((size_t)ky * p.KW + kx) * Cg;
+                for (int c = 0; c < Cg; ++c) {
                     const int v = ok ? (int)vp[c] : p.izp;
                     dot += v * (int)fp[c];
                     vs += v;

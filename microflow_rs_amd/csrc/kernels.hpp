@@ -56,6 +56,7 @@ struct ConvArgs {
     int xr;             // 0 (i8) or 0x80 (u8)
     int dh = 1, dw = 1; // dilation factors: tap (ky, kx) reads input (oy sh - padt + ky dh, ox sw - padl + kx dw); SAME pads by the
                         // effective extent, ((KH - 1) dh) / 2 (conv2d_generic, dwconv_generic; the other ConvArgs kernels run at 1 x 1 only)
+    int groups = 1;     // conv2d_generic: filters [N][KH][KW][C / groups], output n reads the input channels of group n / (N / groups); the other kernels run at 1 only
 };
 struct PoolArgs {
     int H, W, C, KH, KW, sh, sw, OH, OW, pad_same;
@@ -849,6 +850,28 @@ struct ConvDilArgs {
 bool conv_dil_plan(ConvDilArgs &a, std::vector<int> &tap, std::vector<uint32_t> &mask, int H, int W, int C, int N, int KH, int KW, int sh,
                    int sw, int dh, int dw, int OH, int OW, int padt, int padl, bool wz); // false: outside the class, or beyond the LDS budget
 void launch_conv_dil(const int8_t *in, int8_t *out, const ConvDilArgs &a, bool wz, int batch, hipStream_t s);
+// Grouped Conv2D (k_conv_grp.hip: conv_grp_rt): filters [N][KH][KW][Cg], Cg = C / groups, Ng = N / groups; output n of group n / Ng reads
+// input channels [g Cg, (g + 1) Cg).  `g` is conv_gemm_rt's argument block with the same meaning field for field where the kernel reads
+// it (the staged tile, the bands, the N slices, the constants -- here per TILE COLUMN, not per channel); what differs is the product:
+//   tiles : a 16-column tile never mixes operands.  Ng >= 16: TPG = ceil(Ng / 16) tiles per group, the columns past Ng dead.  Ng < 16: a
+//           tile packs GPT = min(groups, 16 / Ng) whole groups, its weights block-diagonal over the tile's SPAN = GPT Cg channels.
+//           colch[tile 16 + j] is column j's output channel, -1 for a dead one.
+//   K     : k = (ky KW + kx) SPAN + c over the tile's channel span, KS = ceil(KH KW SPAN / 64); the [KS][4][4] table holds the byte offset
+//           of every k dword from (window start + the tile's channel base); dwords past K read offset 0 against zero weights.
+//   WZ    : the image holds, behind a tile's KS weight pieces, KS pieces of ones over the real k bytes of each column's own group, so
+//           the window sum of a column's group is one more MFMA per k step and chunk (PW = 2 KS pieces per tile, else KS).
+struct ConvGrpArgs {
+    ConvGemmArgs g;
+    int groups, Cg, Ng;
+    int SPAN, GPT, TPG;  // channels a tile reads; groups per tile (Ng < 16, else 0); tiles per group (Ng >= 16, else 0)
+    int PW;              // 1 KiB pieces per tile in the image
+    const int *colch;    // [NT * 16]
+};
+// false: outside the class (Cg % 4, C % 4, (W C) % 4 != 0), KS > CONV_GEMM_KS_MAX, or beyond the LDS budget.  colch: NT * 16 entries
+bool conv_grp_plan(ConvGrpArgs &a, std::vector<int> &tap, std::vector<int> &colch, int H, int W, int C, int N, int groups, int KH, int KW, int sh,
+                   int sw, int OH, int OW, int padt, int padl, bool wz);
+std::vector<int8_t> conv_grp_weight_image(const int8_t *w /*[N][KH][KW][Cg]*/, const ConvGrpArgs &a, const std::vector<int> &colch, bool wz);
+void launch_conv_grp(const int8_t *in, int8_t *out, const ConvGrpArgs &a, bool wz, int batch, hipStream_t s);
 // TRANSPOSE_CONV split by output phase (k_tconv.hip: tconv_phase_rt): the sh sw phases of a base pixel (q, qx) are stride-1 products
 // over K' = Ty x (Tx C rounded up to 16) each, conv_gemm_rt's K layout on a staged NHWC tile; the operands are wimage.cpp's
 // (build_tconv_image / _kc / _table).  C % 4 == 0, (W C) % 4 == 0, strides <= 4, filter sides <= 8, filter zero points 0.

@@ -94,6 +94,7 @@ struct ParsedOp {
     int out_rank = 0, out_shape[4] = {0, 0, 0, 0};
     int KH = 0, KW = 0, sh = 0, sw = 0, pad = 0, act = 0;
     int dh = 1, dw = 1; // Conv2D / DepthwiseConv2D: dilation_h_factor, dilation_w_factor
+    int groups = 1;     // Conv2D: the input's C over the filter's C (filters [N][KH][KW][C / groups])
     float in_scale = 0, out_scale = 0;
     int in_zp = 0, out_zp = 0;
     size_t in_elems = 0, out_elems = 0;
@@ -177,6 +178,9 @@ struct OpSpec {
     int H = 0, W = 0, C = 0, KH = 0, KW = 0, sh = 1, sw = 1, pad = 0, OH = 0, OW = 0;
     int dh = 1, dw = 1;      // conv_2d / depthwise_conv_2d: dilation factors (an axis with one tap is kept at 1: op_create)
     bool dilated() const { return dh != 1 || dw != 1; } // (the fused groups pass such an operator by: it runs layer-wise)
+    int groups = 1;          // conv_2d: filters [N][KH][KW][C / groups] (include/microflow_amd.h: mf_conv_2d_grouped_create)
+    int twin_of = 0;         // ... or the group count of the grouped operator this dense one is the block-diagonal twin of (ops.hip create_conv)
+    bool grouped() const { return groups != 1 || twin_of != 0; } // (the fused groups pass such an operator by: it launches alone)
     int act = 0;
     int izp = 0;             // zero point of the running input tensor
     float in_scale = 0;      // softmax only

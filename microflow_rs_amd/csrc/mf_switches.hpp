@@ -48,6 +48,7 @@ struct Switches {
     bool no_pair_wz = false;       // MF_NO_PAIR_WZ       pairs with filter zero points one launch per operator (dw3x3_rt<S,wzp>, pw_rt<K,N,wzp>), not one pair_wz_rt launch (k_pair_wz.hip)
     bool no_conv_gemm = false;     // MF_NO_CONV_GEMM     Conv2D shapes outside the other Conv2D kernels take conv2d_generic, not conv_gemm_rt (k_conv_gemm.hip)
     bool no_conv_dil = false;      // MF_NO_CONV_DIL      every Conv2D / DepthwiseConv2D with a dilation factor takes conv2d_generic / dwconv_generic, not conv_dil_rt (k_conv_dil.hip) / dw_gemm_rt
+    bool no_conv_grp = false;      // MF_NO_CONV_GRP      every grouped Conv2D runs as its block-diagonal dense twin on the dense routes (kernel name + "[g<G>]"), not on conv_grp_rt (k_conv_grp.hip)
     bool no_tconv = false;         // MF_NO_TCONV         every TRANSPOSE_CONV takes tconv_generic, not tconv_phase_rt (k_tconv.hip)
     bool no_dw_gemm = false;       // MF_NO_DW_GEMM       DepthwiseConv2D shapes outside the other depthwise kernels take dwconv_generic, not dw_gemm_rt / conv_gemm_rt<dw> (k_dw_gemm.hip)
     bool no_dwfc = false;          // MF_NO_DWFC          no depthwise + FC + softmax kernel (k_dwfc.hip, speech)

@@ -94,7 +94,7 @@ static OpSpec op_spec(const ParsedModel &pm, const ParsedOp &po, float cur_scale
     s.H = po.H, s.W = po.W, s.C = po.C, s.KH = po.KH, s.KW = po.KW;
     s.sh = po.sh ? po.sh : 1, s.sw = po.sw ? po.sw : 1, s.pad = po.pad;
     s.OH = po.OH, s.OW = po.OW, s.act = po.act;
-    s.dh = po.dh, s.dw = po.dw;
+    s.dh = po.dh, s.dw = po.dw, s.groups = po.groups;
     s.izp = cur_zp;          // input.zero_point[0] of the running tensor (conv_2d.rs:56)
     s.in_scale = cur_scale;  // input.scale[0] of the running tensor (softmax.rs:20)
     s.oscale = po.out_scale, s.ozp = po.out_zp;

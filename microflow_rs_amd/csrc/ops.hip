@@ -114,9 +114,10 @@ int64_t fold_conv_constants(const OpSpec &s, bool depthwise, std::vector<float> 
             for (int t = 0; t < taps; ++t) tap(s.weights[(size_t)t * N + c]);
             T = taps;
         } else { // filters [N][KH][KW][C]
-            const int8_t *f = s.weights + (size_t)c * taps * s.C;
-            for (int t = 0; t < taps * s.C; ++t) tap(f[t]);
-            T = taps * s.C;
+            const int cg = s.C / s.groups; // (a grouped filter: the fan-in of a group)
+            const int8_t *f = s.weights + (size_t)c * taps * cg;
+            for (int t = 0; t < taps * cg; ++t) tap(f[t]);
+            T = taps * cg;
         }
         acc_range_per_channel.push_back({amin, amax});
         max_wabs = std::max(max_wabs, wabs);
@@ -225,7 +226,7 @@ ConvCtx prepare_conv(OpImpl &op, const OpSpec &s, bool dw, int lo, int hi, int x
         fprintf(stderr, "[epi] %s %dx%dx%d -> %d: |acc| < %lld, clamp [%d, %d] -> mode %d\n", dw ? "depthwise" : "conv", s.H, s.W, s.C, s.N,
                 (long long)c.acc_bound, lo, hi, c.magic);
     op.magic_mode = c.magic;
-    const size_t wbytes = dw ? (size_t)s.KH * s.KW * s.N : (size_t)s.N * s.KH * s.KW * s.C;
+    const size_t wbytes = dw ? (size_t)s.KH * s.KW * s.N : (size_t)s.N * s.KH * s.KW * (s.C / s.groups);
     op.h_w.assign(s.weights, s.weights + wbytes);
     op.d_w.upload(s.weights, wbytes);
     op.d_wzp.upload(c.wzp.data(), c.wzp.size() * 4);
@@ -243,7 +244,7 @@ ConvCtx prepare_conv(OpImpl &op, const OpSpec &s, bool dw, int lo, int hi, int x
     a.lo_f = (float)lo, a.hi_f = (float)hi;
     a.w = op.d_w.as<int8_t>(), a.wzp = op.d_wzp.as<int>(), a.A = op.d_A.as<float>();
     a.S = op.d_S.as<float>(), a.Kc = op.d_Kc.as<int>();
-    a.xr = xr, a.dh = s.dh, a.dw = s.dw;
+    a.xr = xr, a.dh = s.dh, a.dw = s.dw, a.groups = s.groups;
     op.generic_name = dw ? "dwconv_generic" : "conv2d_generic";
     return c;
 }
@@ -639,6 +640,51 @@ bool route_conv_dil(OpImpl &op, const ConvCtx &c) {
     return true;
 }
 
+// 15. a grouped Conv2D with Cg % 4 == 0, C % 4 == 0 and whole-dword image rows, no dilation: tiles that never mix groups, K over each
+// tile's own channel span (k_conv_grp.hip).  The only route that takes a grouped operator (route_allowed); every other grouped shape runs
+// as its dense twin (create_conv).
+bool route_conv_grp(OpImpl &op, const ConvCtx &c) {
+    const OpSpec &s = c.s;
+    if (!(rt_candidate(op, c) && !c.dw && s.groups != 1 && !s.dilated() && !switches().no_conv_grp)) return false;
+    const bool wz = c.wz;
+    std::vector<int> tap, colch;
+    k::ConvGrpArgs &f = op.cgp;
+    if (!k::conv_grp_plan(f, tap, colch, s.H, s.W, s.C, s.N, s.groups, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, c.padt, c.padl, wz)) return false;
+    const std::vector<int8_t> img = k::conv_grp_weight_image(s.weights, f, colch, wz);
+    op.d_fcw.upload(img.data(), img.size());
+    op.d_tap.upload(tap.data(), tap.size() * sizeof(int));
+    op.d_colch.upload(colch.data(), colch.size() * sizeof(int));
+    f.g.wimg = op.d_fcw.p, f.g.tap = op.d_tap.as<int>(), f.g.kmask = nullptr, f.colch = op.d_colch.as<int>();
+    int rows = 0; // the constants per tile column: the real columns of the tiles are a prefix-free map, so give every column its channel's
+    for (size_t r = 0; r < colch.size(); ++r)
+        if (colch[r] >= 0) rows = (int)r + 1;
+    const ConstPtrs p = row_consts(op, c, colch.size(), rows, [&](int r) { return std::max(colch[(size_t)r], 0); });
+    f.g.A = p.A, f.g.S = p.S, f.g.Kc = p.Kc, f.g.wzp = p.wzp;
+    epi_fields_izp(f.g, op, c);
+    op.fast = OpImpl::CONV_GRP;
+    op.rt_wz = wz;
+    op.fast_name = "conv_grp_rt<g" + std::to_string(s.groups) + (wz ? ",wzp>" : ">");
+    if (switches().verbose)
+        fprintf(stderr, "[microflow_amd] conv_grp_rt %dx%dx%d -> %d %dx%d g%d: %s %d, span %d, %d k steps, %d tiles in %d slice(s) of %d, %s %d x %d rows of %d B, %d B LDS\n",
+                s.H, s.W, s.C, s.N, s.KH, s.KW, s.groups, f.GPT ? "groups per tile" : "tiles per group", f.GPT ? f.GPT : f.TPG, f.SPAN, f.g.KS, f.g.NT,
+                f.g.NSL, f.g.NTS, f.g.NBANDS > 1 ? "bands of" : "images per step:", f.g.NBANDS > 1 ? f.g.BH : f.g.G, f.g.RB, f.g.ROW, f.g.lds);
+    return true;
+}
+
+// the dense [N][KH][KW][C] twin of a grouped filter [N][KH][KW][C / groups] in the i8 domain: block-diagonal, every element outside a
+// channel's own group that channel's filter zero point ((w - wzp) = 0 there: the same accumulator, the same Kc, the same bound)
+std::vector<int8_t> twin_filter(const OpSpec &s) {
+    const int T = s.KH * s.KW, Cg = s.C / s.groups, Ng = s.N / s.groups;
+    std::vector<int8_t> f((size_t)s.N * T * s.C);
+    for (int n = 0; n < s.N; ++n)
+        for (int t = 0; t < T; ++t)
+            for (int c = 0; c < s.C; ++c) {
+                const int ci = c - (n / Ng) * Cg;
+                f[((size_t)n * T + t) * s.C + c] = ci >= 0 && ci < Cg ? s.weights[((size_t)n * T + t) * Cg + ci] : (int8_t)s.wzp[n < s.nq ? n : 0];
+            }
+    return f;
+}
+
 // the KeH x KeW filter of a dilated operator in the i8 domain: tap (ky, kx) at (ky dh, kx dw), every other tap the channel's filter zero point
 std::vector<int8_t> stuff_filter(const OpSpec &s, bool dw, int KEH, int KEW) {
     const int CI = dw ? 1 : s.C; // conv [N][KH][KW][C]; depthwise [KH][KW][N]
@@ -658,11 +704,15 @@ std::vector<int8_t> stuff_filter(const OpSpec &s, bool dw, int KEH, int KEW) {
 using Route = bool (*)(OpImpl &, const ConvCtx &);
 // An operator with a dilation factor is refused HERE by every route but the two that place their taps by it: the tables, dw3x3_rt,
 // pw_rt, conv_rows, conv_mm_rt, conv1x1, dw_mm_rt and conv_gemm_rt all rest on adjacent taps.
-bool route_allowed(Route r, const ConvCtx &c) { return !c.s.dilated() || r == route_dw_gemm || r == route_conv_dil; }
+// A grouped operator (filters [N][KH][KW][C / groups]) is refused by every route but conv_grp_rt's: all others read C-channel filters.
+bool route_allowed(Route r, const ConvCtx &c) {
+    if (c.s.groups != 1) return r == route_conv_grp;
+    return !c.s.dilated() || r == route_dw_gemm || r == route_conv_dil;
+}
 // The order is the contract: every shape keeps the kernel it had.
 const Route TABLE_ROUTES[] = {route_dw_table, route_dw_stem, route_dw_stem_rt, route_dw_c1, route_pw_mfma}; // the first whose condition holds
 const Route RT_ROUTES[] = {route_dw_rt, route_pw_rt, route_conv_rows, route_dw_mm, route_dw_gemm, route_conv_mm, route_conv1x1_row,
-                           route_conv_gemm, route_conv_dil}; // each one, in turn
+                           route_conv_gemm, route_conv_dil, route_conv_grp}; // each one, in turn
 
 void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
     const bool dw = s.kind == MF_OP_DEPTHWISE_CONV_2D;
@@ -685,9 +735,11 @@ void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
             fail(MF_ERR_INVALID_ARG, std::string(dw ? "depthwise_conv_2d" : "conv_2d") + " with dilation " + std::to_string(s.dh) + "x" + std::to_string(s.dw) +
                                          ": the output size is not what " + (same ? "SAME" : "VALID") + " gives");
     }
+    if (s.groups < 1 || (s.groups != 1 && (dw || s.C % s.groups != 0 || s.N % s.groups != 0)))
+        fail(MF_ERR_INVALID_ARG, "conv_2d: " + std::to_string(s.groups) + " groups do not divide " + std::to_string(s.C) + " input and " + std::to_string(s.N) + " output channels");
     op.in_elems = (size_t)s.H * s.W * s.C;
     op.out_elems = (size_t)s.OH * s.OW * s.N;
-    dom.apply(s, dw ? (size_t)s.KH * s.KW * s.N : (size_t)s.N * s.KH * s.KW * s.C);
+    dom.apply(s, dw ? (size_t)s.KH * s.KW * s.N : (size_t)s.N * s.KH * s.KW * (s.C / s.groups));
     auto route = [&](const ConvCtx &c) {
         for (Route r : TABLE_ROUTES)
             if (route_allowed(r, c) && r(op, c)) break;
@@ -698,12 +750,30 @@ void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
     // ((w - wzp) = 0 there: the same accumulator, the same Kc, the same bound), and below 3x the taps the undilated kernels run that
     // filter faster than the plane staging or the dilated tap geometry (x0.95 - x1.02 at 1.7x and 2.8x, x1.06 at 3x).  Taken
     // where a fast undilated route takes the stuffed operator; else, and from 3x on, the dilated routes.
-    std::vector<int8_t> stuffed;
-    OpSpec t = s;
+    std::vector<int8_t> stuffed, twin;
     int64_t acc_bound = 0;
     int magic = 0;
     bool routed = false;
-    if (s.dilated() && !switches().no_conv_dil && KEH * KEW < 3LL * s.KH * s.KW) {
+    // A grouped operator: conv_grp_rt where it takes the shape.  Every other one -- Cg % 4 or C % 4 != 0, image rows that are not whole
+    // dwords, a dilation factor, MF_NO_CONV_GRP -- IS the dense Conv2D with the block-diagonal twin filter, and runs as that operator on
+    // the dense routes below (conv2d_generic where none takes it), "[g<G>]" behind its kernel name.  (As with a stuffed filter, what a first
+    // preparation left in `op` stays valid for the twin: the same A, S, Kc and accumulator ranges.)
+    // Measured (profiles/r25/time_grouped.txt): conv_grp_rt beats the twin at every timed 3x3 (G = 2 .. 32, x1.4 - x10.4) and at
+    // the 1x1 with G = 8 (x1.68), and loses at the 1x1 with G = 3, whose twin pw_rt takes (x0.43).  So a 1x1 with G <= 3 (G = 2: the twin
+    // wastes less still) tries the twin first and comes back to conv_grp_rt only where no fast dense route takes it.
+    const bool twin_first = s.groups != 1 && s.KH == 1 && s.KW == 1 && s.groups <= 3;
+    const OpSpec sg = s;
+    if (s.groups != 1) {
+        if (!s.dilated() && !switches().no_conv_grp && !twin_first) {
+            const ConvCtx c = prepare_conv(op, s, dw, lo, hi, xr);
+            route(c);
+            acc_bound = c.acc_bound, magic = c.magic;
+        }
+        if (op.fast != OpImpl::NONE) routed = true;
+        else twin = twin_filter(s), s.weights = twin.data(), s.twin_of = s.groups, s.groups = 1, op.grp_note = "[g" + std::to_string(s.twin_of) + "]";
+    }
+    OpSpec t = s;
+    if (!routed && s.dilated() && !switches().no_conv_dil && KEH * KEW < 3LL * s.KH * s.KW) {
         stuffed = stuff_filter(s, dw, (int)KEH, (int)KEW);
         t.KH = (int)KEH, t.KW = (int)KEW, t.dh = t.dw = 1, t.weights = stuffed.data();
         const ConvCtx c = prepare_conv(op, t, dw, lo, hi, xr);
@@ -719,6 +789,19 @@ void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
         route(c);
         acc_bound = c.acc_bound, magic = c.magic;
     }
+    // (a twin-first 1x1 that no fast dense route took: the grouped operator after all, but only where conv_grp_rt is sure to take it --
+    // its plan, asked here on a scratch block, and rt_candidate's conditions -- so that every other one stays the twin on conv2d_generic)
+    if (twin_first && op.fast == OpImpl::NONE && !sg.dilated() && !switches().no_conv_grp && !switches().no_rt && op.finite_consts) {
+        k::ConvGrpArgs scratch{};
+        std::vector<int> tap, colch;
+        if (k::conv_grp_plan(scratch, tap, colch, sg.H, sg.W, sg.C, sg.N, sg.groups, 1, 1, sg.sh, sg.sw, sg.OH, sg.OW, 0, 0, !all_zero(op.h_wzp))) {
+            s = sg, op.grp_note.clear();
+            const ConvCtx c = prepare_conv(op, s, dw, lo, hi, xr);
+            route(c);
+            acc_bound = c.acc_bound, magic = c.magic;
+        }
+    }
+    op.fast_name += op.grp_note, op.generic_name += op.grp_note;
     if (op.fma_ok) { // the single-fma constants beside the two-rounding ones, in the blocks of the kernels that have the form
         op.dwf.A3 = op.pw.A3 = op.d_A3.as<float>(), op.dwf.S3 = op.pw.S3 = op.d_S3.as<float>();
         op.dwf.Kc3 = op.pw.Kc3 = op.d_Kc3.as<int>();
@@ -1060,6 +1143,7 @@ bool op_tile_plan(const OpImpl *op, int plan[8]) {
     };
     const k::ConvGemmArgs &c = op->fast == OpImpl::CONV_DIL ? op->cdl.g : op->cgm;
     if (op->fast == OpImpl::CONV_DIL) return put(op->cdl.dw, op->cdl.PP, c.ROW, c.RB, c.NBANDS, c.BH, c.G, c.NSL);
+    if (op->fast == OpImpl::CONV_GRP) return put(1, 0, op->cgp.g.ROW, op->cgp.g.RB, op->cgp.g.NBANDS, op->cgp.g.BH, op->cgp.g.G, op->cgp.g.NSL);
     if (op->fast == OpImpl::CONV_GEMM) return put(1, 0, c.ROW, c.RB, c.NBANDS, c.BH, c.G, c.NSL);
     if (op->fast == OpImpl::DW_GEMM) return put(1, 0, op->dwg.ROW, op->dwg.RB, op->dwg.NBANDS, op->dwg.BH, op->dwg.G, 1);
     return false;
@@ -1152,6 +1236,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             break;
         case OpImpl::CONV_DIL:
             k::launch_conv_dil(d_in, d_out, op->cdl, op->rt_wz, (int)batch, s);
+            done = true;
+            break;
+        case OpImpl::CONV_GRP:
+            k::launch_conv_grp(d_in, d_out, op->cgp, op->rt_wz, (int)batch, s);
             done = true;
             break;
         case OpImpl::TCONV_PHASE:

@@ -66,8 +66,9 @@ struct OpImpl {
     bool finite_consts = true; // A / S all finite (the shape-specialised and fused epilogues assume it)
     std::string generic_name, fast_name;
     std::string dil_note;      // "[d{dh}x{dw}]" behind the kernel name of a dilated operator that runs as the undilated one with the stuffed filter (ops.hip create_conv)
+    std::string grp_note;      // "[g{G}]" behind the kernel name of a grouped operator that runs as its block-diagonal dense twin (ops.hip create_conv)
     enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM, FC_RT,
-                CONV_GEMM, DW_GEMM, FC_SPARSE24, MAXPOOL_C4, ADD_C16, PAD_C4, CONCAT_C4, TCONV_PHASE, CONV_DIL } fast = NONE;
+                CONV_GEMM, DW_GEMM, FC_SPARSE24, MAXPOOL_C4, ADD_C16, PAD_C4, CONCAT_C4, TCONV_PHASE, CONV_DIL, CONV_GRP } fast = NONE;
     int *d_rowsum = nullptr; // FC_MFMA / FC_SPARSE24 with wzp != 0: per-row input sums
     size_t rowsum_cap = 0, rowsum_rows = 0; // (ints allocated; the row count the counter pairs currently sit behind)
     int8_t *d_ext = nullptr; // op_run_external on a u8 operator: input moved to the i8 domain
@@ -144,6 +145,8 @@ struct OpImpl {
     DevBuf d_cgm_mask;     // ... constants padded to 16-column tiles in d_rtA, d_rtS, d_rtKc, d_rtwzp; window-sum byte masks
     k::DwGemmArgs dwg{};   // DepthwiseConv2D of any C on the matrix pipe (k_dw_gemm.hip); operand A in d_wprep, constants as cgm's
     k::ConvDilArgs cdl{};  // Conv2D with dilation factors in column-phase planes (k_conv_dil.hip); image, tables, masks and constants as cgm's
+    k::ConvGrpArgs cgp{};  // grouped Conv2D (k_conv_grp.hip); image in d_fcw, k dword table in d_tap, per-tile-column constants as cgm's, the column map in d_colch
+    DevBuf d_colch;
     k::TconvArgs tcv{};    // TRANSPOSE_CONV by output phase (k_tconv.hip); image in d_fcw, table in d_tap, per-phase Kc in d_fcKc, A / S as cgm's
     int tc_padt = 0, tc_padl = 0; // ... the operator's placement (TFLite's), for either of its kernels
     DevBuf d_crw, d_crm;   // conv_rows_lds: packed weights, tap masks

@@ -81,6 +81,7 @@ Switches switches_parse() {
     s.pair_wz_gmul = (int)env_ll("MF_PAIR_WZ_GMUL", 2);
     s.no_conv_gemm = env_set("MF_NO_CONV_GEMM");
     s.no_conv_dil = env_set("MF_NO_CONV_DIL");
+    s.no_conv_grp = env_set("MF_NO_CONV_GRP");
     s.no_tconv = env_set("MF_NO_TCONV");
     s.no_dw_gemm = env_set("MF_NO_DW_GEMM");
     s.no_fc_sparse = env_set("MF_NO_FC_SPARSE");

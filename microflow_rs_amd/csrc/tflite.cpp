@@ -455,7 +455,13 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
                 po.N = w.shape[3];
             } else {
                 po.N = w.shape[0];
-                if (w.shape[3] != po.C) fail(MF_ERR_INVALID_MODEL, "invalid model: Conv2D channel mismatch");
+                // a filter with fewer input channels than the input: a grouped Conv2D (Keras' Conv2D(groups=G)), the group count implicit
+                // in the shapes (include/microflow_amd.h: mf_conv_2d_grouped_create)
+                if (w.shape[3] <= 0 || po.C % w.shape[3] != 0) fail(MF_ERR_INVALID_MODEL, "invalid model: Conv2D channel mismatch");
+                po.groups = po.C / w.shape[3];
+                if (po.N % po.groups != 0)
+                    fail(MF_ERR_INVALID_MODEL, "invalid model: Conv2D with " + std::to_string(po.groups) + " groups (filter C " + std::to_string(w.shape[3]) + " of " + std::to_string(po.C) +
+                                                   "): they do not divide its " + std::to_string(po.N) + " output channels");
             }
             if (out.shape[3] != po.N) fail(MF_ERR_INVALID_MODEL, std::string("invalid model: ") + nm + " output channels");
             if (w.data_len < w.elems() || b.data_len < (size_t)po.N * 4)

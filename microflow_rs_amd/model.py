@@ -50,7 +50,8 @@ class Model:
     def op(self, i):
         d = _lib.OpDesc()
         _lib.check(_lib.lib().mf_model_get_op(self._h, i, C.byref(d)))
-        return dict(kind=d.kind, name=OP_NAMES.get(d.kind, "?"),
+        return dict(groups=self.op_groups(i) if OP_NAMES.get(d.kind) == "conv_2d" else 1,
+                    kind=d.kind, name=OP_NAMES.get(d.kind, "?"),
                     in_shape=tuple(d.in_shape[: d.in_rank]), out_shape=tuple(d.out_shape[: d.out_rank]),
                     KH=d.KH, KW=d.KW, sh=d.stride_h, sw=d.stride_w, pad=d.padding, act=d.activation,
                     n_c0=d.n_c0, n_c1=d.n_c1, in_scale=np.float32(d.in_scale),
@@ -82,6 +83,13 @@ class Model:
         dh, dw = C.c_int(0), C.c_int(0)
         _lib.check(_lib.lib().mf_model_get_op_dilation(self._h, int(i), C.byref(dh), C.byref(dw)))
         return dh.value, dw.value
+
+    def op_groups(self, i):
+        """group count of Conv2D i: the input's C over the filter's C (1: an ordinary Conv2D).  MicroflowError (MF_ERR_INVALID_ARG)
+        for any other operator."""
+        g = C.c_int(0)
+        _lib.check(_lib.lib().mf_model_get_op_groups(self._h, int(i), C.byref(g)))
+        return g.value
 
     def op_source(self, i):
         """the operator whose output side operator i (the Conv2D on a skip edge) reads instead of the running value; -1: the model

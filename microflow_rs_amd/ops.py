@@ -39,6 +39,7 @@ class Conv2DOptions:                      # src/ops/conv_2d.rs:11-15
     view_padding: TensorViewPadding = TensorViewPadding.SAME
     strides: Tuple[int, int] = (1, 1)
     dilation: Tuple[int, int] = (1, 1)    # (not in the reference) (dilation_h, dilation_w): include/microflow_amd.h mf_conv_2d_dilated_create
+    groups: int = 1                       # (not in the reference) filters [N][KH][KW][C / groups]: include/microflow_amd.h mf_conv_2d_grouped_create
 
 
 @dataclass
@@ -105,7 +106,7 @@ class PreparedOp:
         return _lib.lib().mf_op_kernel_name(self._h).decode()
 
     def tile_plan(self):
-        """dict(planes, pitch, row, rows, bands, band_rows, images, slices) of a conv_dil_rt / conv_gemm_rt / dw_gemm_rt operator
+        """dict(planes, pitch, row, rows, bands, band_rows, images, slices) of a conv_dil_rt / conv_grp_rt / conv_gemm_rt / dw_gemm_rt operator
         (mf_op_get_tile_plan); MicroflowError for an operator on another kernel"""
         p = (C.c_int * 8)()
         _lib.check(_lib.lib().mf_op_get_tile_plan(self._h, p))
@@ -207,18 +208,20 @@ def prepare_conv_2d(in_hwc, filters, filters_zero_point, input_zero_point, outpu
     f = _host(filters, dt)
     N, KH, KW, Cc = f.shape
     H, W, C_in = in_hwc
-    if C_in != Cc:
-        raise ValueError("filter channels != input channels")
+    groups = int(getattr(options, "groups", 1))
+    # (filters [N][KH][KW][C / groups]; a group count that divides nothing is the library's to refuse)
+    if groups >= 1 and C_in % groups == 0 and C_in != Cc * groups:
+        raise ValueError("filter channels != input channels / groups")
     fzp = _host(np.reshape(filters_zero_point, -1), dt)
     c0, c1 = (_host(np.reshape(c, -1), np.float32) for c in constants)
     h = C.c_void_p()
     dil = tuple(int(d) for d in getattr(options, "dilation", (1, 1)))
-    _lib.check(_fn("mf_conv_2d_dilated_create", dt)(
-        _device(), H, W, Cc, N, KH, KW, _ptr(f), _ptr(fzp), fzp.size, int(input_zero_point),
+    _lib.check(_fn("mf_conv_2d_grouped_create", dt)(
+        _device(), H, W, C_in, N, KH, KW, _ptr(f), _ptr(fzp), fzp.size, int(input_zero_point),
         float(output_scale), int(output_zero_point), int(options.fused_activation),
         int(options.view_padding), options.strides[0], options.strides[1], out_hw[0], out_hw[1],
-        _ptr(c0), _ptr(c1), c1.size, dil[0], dil[1], C.byref(h)))
-    return PreparedOp(h, (H, W, Cc), (out_hw[0], out_hw[1], N), dt)
+        _ptr(c0), _ptr(c1), c1.size, dil[0], dil[1], groups, C.byref(h)))
+    return PreparedOp(h, (H, W, C_in), (out_hw[0], out_hw[1], N), dt)
 
 
 def conv_2d(input: Tensor4D, filters: Tensor4D, output_scale, output_zero_point,

@@ -425,13 +425,14 @@ def _same_or_valid(size, k, s, padding):
     return -(-size // s) if padding == "same" else (size - k) // s + 1
 
 
-def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", elem=INT8, wzp="none", wmax=None, act_scale=None, dilation=(1, 1)):
+def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", elem=INT8, wzp="none", wmax=None, act_scale=None, dilation=(1, 1), groups=1):
     """conv_net's per-layer form, one layer dict: a k x k Conv2D to n channels, or (dw) a k x k depthwise, on a tensor shape = (H, W, C)
     of quantisation q; per-channel filter quantisation; the output scale keeps the outputs spread, or is act_scale with
     person_detect_like's filter scales; the output zero point is the type's minimum behind relu / relu6 and a random one without an
     activation.  wzp: filter zero points off the middle -- "conv": Conv2D only, conv_net's draw; "all": the depthwise ones too, both
     with inverted_residual_net's draw, which never lands on the middle.  k: the filter side, or (KH, KW); dilation: (dh, dw), written into
-    the options where it is not (1, 1), the output sized from the effective extent (k - 1) d + 1."""
+    the options where it is not (1, 1), the output sized from the effective extent (k - 1) d + 1.  groups: a grouped Conv2D as the converter writes
+    Keras' Conv2D(groups=G): filters [n][k][k][C / groups], the group count implicit in the shapes."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     H, W, C = (int(v) for v in shape)
@@ -444,7 +445,7 @@ def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", el
         zp[zp == mid] = mid + 5
     else:
         zp = rng.integers(mid - 10, mid + 11, n) if wzp == "conv" and not dw else np.full(n, mid)
-    taps = kh * kw * (1 if dw else C)
+    taps = kh * kw * (1 if dw else C // groups)
     osc = float(np.float32(q[0] * float(sc.mean()) * 60.0 * np.sqrt(taps)))
     if act_scale is not None:
         sc = (rng.uniform(0.6, 1.4, n) * 2.2 / (74.0 * np.sqrt(taps)) * (128.0 / (wmax or 128))).astype(np.float32)
@@ -455,7 +456,7 @@ def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", el
              act=act, out_shape=(1, oh, ow, n), out_q=(osc, ozp))
     if tuple(dilation) != (1, 1):
         d["dilation"] = (int(dilation[0]), int(dilation[1]))
-    wshape = (1, kh, kw, n) if dw else (n, kh, kw, C)
+    wshape = (1, kh, kw, n) if dw else (n, kh, kw, C // groups)
     d["weights" if dw else "filters"] = rng.integers(lo, hi, wshape) if wmax is None else rng.integers(mid - wmax, mid + wmax + 1, wshape)
     return d
 
@@ -1216,4 +1217,35 @@ def tcn_layers(rng, T=32, C=8, filters=16, k=3, dilations=(1, 2, 4, 8), classes=
 def tcn(rng, T=32, C=8, filters=16, k=3, dilations=(1, 2, 4, 8), classes=6, elem=INT8):
     """tcn_layers' model as a flatbuffer"""
     in_shape, in_q, layers = tcn_layers(rng, T, C, filters, k, dilations, classes, elem)
+    return build_model(in_shape, in_q, layers, elem)
+
+
+def resnext_layers(rng, side=16, C=8, stem=16, blocks=((1, 16, 16), (2, 32, 32)), groups=4, classes=6, elem=INT8, wzp="none"):
+    """A ResNeXt-style network: a 3x3 stem Conv2D to `stem` channels (relu); one bottleneck block per (stride, width, out) -- a 1x1
+    Conv2D to `width` (relu), a GROUPED 3x3 Conv2D of `groups` groups at `stride` (relu), a 1x1 Conv2D to `out` (no activation) and an
+    ADD (relu) with the block's input, or, where the stride is not 1 or `out` differs from the input's channels, with a 1x1 projection
+    Conv2D of the block's input at that stride --; MEAN over {1, 2}; FullyConnected.  -> build_model's arguments"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    layers = [_conv_layer(rng, (side, side, C), in_q, False, stem, 3, 1, "same", "relu", elem, wzp=wzp)]
+    q, H, W, Cc = layers[0]["out_q"], side, side, int(stem)
+    for s, width, out in blocks:
+        skip, q_skip = len(layers) - 1, q
+        if s != 1 or out != Cc:
+            layers.append(dict(_conv_layer(rng, (H, W, Cc), q, False, out, 1, s, "same", "none", elem, wzp=wzp), side_of=skip))
+            skip, q_skip = len(layers) - 1, layers[-1]["out_q"]
+        layers.append(_conv_layer(rng, (H, W, Cc), q, False, width, 1, 1, "same", "relu", elem, wzp=wzp))
+        layers.append(_conv_layer(rng, (H, W, width), layers[-1]["out_q"], False, width, 3, s, "same", "relu", elem, wzp=wzp, groups=groups))
+        H, W = layers[-1]["out_shape"][1:3]
+        layers.append(_conv_layer(rng, (H, W, width), layers[-1]["out_q"], False, out, 1, 1, "same", "none", elem, wzp=wzp))
+        layers.append(_add_layer(rng, skip, (1, H, W, out), layers[-1]["out_q"], q_skip, "relu", elem))
+        q, Cc = layers[-1]["out_q"], int(out)
+    layers.append(dict(op="mean", keep_dims=False, out_shape=(1, Cc), out_q=q))
+    layers.append(_fc_layer(rng, Cc, int(classes), q, "none", elem))
+    return (1, int(side), int(side), int(C)), in_q, layers
+
+
+def resnext(rng, side=16, C=8, stem=16, blocks=((1, 16, 16), (2, 32, 32)), groups=4, classes=6, elem=INT8, wzp="none"):
+    """resnext_layers' model as a flatbuffer"""
+    in_shape, in_q, layers = resnext_layers(rng, side, C, stem, blocks, groups, classes, elem, wzp)
     return build_model(in_shape, in_q, layers, elem)
