@@ -18,6 +18,7 @@ MF_OP_ADD = 0
 MF_OP_CONCATENATION = 2
 MF_OP_PAD, MF_OP_MEAN = 34, 40   # (not in the reference: include/microflow_amd.h mf_pad_create)
 MF_OP_TRANSPOSE_CONV = 67   # (not in the reference: include/microflow_amd.h mf_transpose_conv_create)
+MF_OP_RESIZE_NEAREST_NEIGHBOR = 97   # (not in the reference: include/microflow_amd.h mf_resize_nearest_create)
 STATUS_NAMES = {0: "MF_OK", 1: "MF_ERR_INVALID_MODEL", 2: "MF_ERR_UNSUPPORTED",
                 3: "MF_ERR_INVALID_ARG", 4: "MF_ERR_NO_DEVICE", 5: "MF_ERR_HIP", 6: "MF_ERR_OOM"}
 
@@ -91,6 +92,9 @@ SIGNATURES = {
                                   [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "mf_conv_2d_grouped_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
                                   [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),  # (+ groups)
+    "mf_conv_2d_upsampled_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
+                                    [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),  # (+ up_h, up_w)
+    "mf_resize_nearest_create": (C.c_int, [C.c_int] * 6 + [C.POINTER(_vp)]),
     "mf_depthwise_conv_2d_dilated_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
                                             [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "mf_average_pool_2d_create": (C.c_int, [C.c_int] * 6 + [C.c_float, C.c_int8, C.c_int, C.c_int,
@@ -132,6 +136,7 @@ SIGNATURES = {
     "mf_model_get_op_pads": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     "mf_model_get_op_dilation": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mf_model_get_op_groups": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
+    "mf_model_get_op_upsample": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mf_model_prepare": (C.c_int, [_vp, C.c_int, C.c_size_t]),
     "mf_model_set_stream": (C.c_int, [_vp, _vp]),
     "mf_model_sync": (C.c_int, [_vp]),
@@ -177,7 +182,7 @@ SIGNATURES = {
 # T = u8 instantiations: the i8 signature with every int8_t value parameter as uint8_t
 for _n in ("mf_preprocess_fully_connected", "mf_preprocess_average_pool_2d",
            "mf_fully_connected_create", "mf_conv_2d_create", "mf_transpose_conv_create", "mf_depthwise_conv_2d_create",
-           "mf_conv_2d_dilated_create", "mf_depthwise_conv_2d_dilated_create", "mf_conv_2d_grouped_create",
+           "mf_conv_2d_dilated_create", "mf_depthwise_conv_2d_dilated_create", "mf_conv_2d_grouped_create", "mf_conv_2d_upsampled_create",
            "mf_average_pool_2d_create", "mf_max_pool_2d_create", "mf_add_create", "mf_concatenation_create", "mf_pad_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
            "mf_window_gather_quantize"):
     _r, _a = SIGNATURES[_n]

@@ -194,10 +194,10 @@ static std::vector<int> widen(const T *zp, int nq) {
 static void create_conv(int device, bool u8, int kind, int H, int W, int Cin, int N, int KH, int KW,
                         const void *weights, const std::vector<int> &wzp, int izp, float output_scale,
                         int ozp, int act, int pad, int sh, int sw, int OH, int OW, const float *c0,
-                        const float *c1, int nc1, mf_op **op, int dh = 1, int dw = 1, int groups = 1) {
+                        const float *c1, int nc1, mf_op **op, int dh = 1, int dw = 1, int groups = 1, int up_h = 1, int up_w = 1) {
     MF_NEED(op && weights && c0 && c1);
     mf::OpSpec s;
-    s.kind = kind, s.u8 = u8, s.dh = dh, s.dw = dw, s.groups = groups;
+    s.kind = kind, s.u8 = u8, s.dh = dh, s.dw = dw, s.groups = groups, s.up_h = up_h, s.up_w = up_w;
     s.H = H, s.W = W, s.C = Cin, s.N = N, s.KH = KH, s.KW = KW;
     s.weights = (const int8_t *)weights, s.wzp = wzp.data(), s.nq = (int)wzp.size(), s.izp = izp;
     s.oscale = output_scale, s.ozp = ozp, s.act = check_act_arg(act);
@@ -393,6 +393,30 @@ int mf_conv_2d_grouped_create_u8(int device, int H, int W, int C, int N, int KH,
     })
 }
 
+// conv_2d on the input resized (nearest neighbour) by (up_h, up_w) (include/microflow_amd.h); mf_conv_2d_create is this at (1, 1)
+int mf_conv_2d_upsampled_create(int device, int H, int W, int C, int N, int KH, int KW, const int8_t *filters,
+                                const int8_t *filters_zero_point, int nq, int8_t input_zero_point,
+                                float output_scale, int8_t output_zero_point, int fused_activation,
+                                int view_padding, int stride_h, int stride_w, int OH, int OW,
+                                const float *c0, const float *c1, int nc1, int up_h, int up_w, mf_op **op) {
+    MF_TRY({
+        create_conv(device, false, MF_OP_CONV_2D, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op, 1, 1, 1, up_h, up_w);
+    })
+}
+int mf_conv_2d_upsampled_create_u8(int device, int H, int W, int C, int N, int KH, int KW, const uint8_t *filters,
+                                   const uint8_t *filters_zero_point, int nq, uint8_t input_zero_point,
+                                   float output_scale, uint8_t output_zero_point, int fused_activation,
+                                   int view_padding, int stride_h, int stride_w, int OH, int OW,
+                                   const float *c0, const float *c1, int nc1, int up_h, int up_w, mf_op **op) {
+    MF_TRY({
+        create_conv(device, true, MF_OP_CONV_2D, H, W, C, N, KH, KW, filters, widen(filters_zero_point, nq),
+                    input_zero_point, output_scale, output_zero_point, fused_activation, view_padding,
+                    stride_h, stride_w, OH, OW, c0, c1, nc1, op, 1, 1, 1, up_h, up_w);
+    })
+}
+
 int mf_average_pool_2d_create(int device, int H, int W, int C, int FH, int FW, float output_scale,
                               int8_t output_zero_point, int fused_activation, int view_padding,
                               int stride_h, int stride_w, int OH, int OW, float c0, float c1,
@@ -482,6 +506,19 @@ int mf_pad_create(int device, int H, int W, int C, int top, int bottom, int left
 }
 int mf_pad_create_u8(int device, int H, int W, int C, int top, int bottom, int left, int right, uint8_t zero_point, mf_op **op) {
     MF_TRY({ create_pad(device, true, H, W, C, top, bottom, left, right, zero_point, op); })
+}
+
+// RESIZE_NEAREST_NEIGHBOR by integer factors (include/microflow_amd.h: the library's own contract); one entry for both element types
+int mf_resize_nearest_create(int device, int H, int W, int C, int sy, int sx, mf_op **op) {
+    MF_TRY({
+        MF_NEED(op);
+        if (H <= 0 || W <= 0 || C <= 0 || sy < 1 || sx < 1 || (long long)H * sy > (1 << 24) || (long long)W * sx > (1 << 24))
+            mf::fail(MF_ERR_INVALID_ARG, "resize_nearest: bad arguments");
+        mf::OpSpec s;
+        s.kind = MF_OP_RESIZE_NEAREST_NEIGHBOR;
+        s.H = H, s.W = W, s.C = C, s.N = C, s.up_h = sy, s.up_w = sx, s.OH = H * sy, s.OW = W * sx;
+        wrap_op(mf::op_create(device, s), op);
+    })
 }
 
 // CONCATENATION (include/microflow_amd.h: the library's own contract).  Bad scales are a bad argument whether or not there is a device
@@ -640,6 +677,16 @@ int mf_model_get_op_dilation(const mf_model *model, int index, int *dilation_h, 
         const mf::ParsedOp &o = pm.ops[(size_t)index];
         MF_NEED(o.kind == MF_OP_CONV_2D || o.kind == MF_OP_DEPTHWISE_CONV_2D);
         *dilation_h = o.dh, *dilation_w = o.dw;
+    })
+}
+
+int mf_model_get_op_upsample(const mf_model *model, int index, int *sy, int *sx) {
+    MF_TRY({
+        MF_NEED(model && model->impl && sy && sx);
+        const mf::ParsedModel &pm = mf::model_parsed(model->impl);
+        MF_NEED(index >= 0 && index < (int)pm.ops.size());
+        MF_NEED(pm.ops[(size_t)index].kind == MF_OP_RESIZE_NEAREST_NEIGHBOR);
+        *sy = pm.ops[(size_t)index].up_h, *sx = pm.ops[(size_t)index].up_w;
     })
 }
 

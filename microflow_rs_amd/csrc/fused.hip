@@ -102,6 +102,10 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
         if ((uintptr_t)d_out & 15) fail(MF_ERR_INVALID_ARG, "pad+conv: the output pointer is not 16-byte aligned");
         op_run(f->padconv.get(), d_in, batch, d_out, st);
         break;
+    case FusedImpl::RESIZECONV: // (as PADCONV: the inner operator has no generic kernel)
+        if ((uintptr_t)d_out & 15) fail(MF_ERR_INVALID_ARG, "resize+conv: the output pointer is not 16-byte aligned");
+        op_run(f->padconv.get(), d_in, batch, d_out, st);
+        break;
     case FusedImpl::SHORTCUT: fail(MF_ERR_INVALID_ARG, "shortcut_add_rt takes two inputs: fused_run2"); break;
     case FusedImpl::SIDECONCAT: fail(MF_ERR_INVALID_ARG, "side_concat_rt takes two inputs: fused_run2"); break;
     case FusedImpl::DWPW: {

@@ -282,6 +282,30 @@ FusedImpl *fused_pad_conv_create(OpImpl *pad, OpImpl *conv) {
     return f.release();
 }
 
+// A RESIZE_NEAREST_NEIGHBOR directly followed by a Conv2D on exactly its output, as ONE upconv_rt launch (k_upconv.hip): the
+// convolution taken as an operator on the source image that resizes while it stages (ops.hip op_create_upsampled_conv).  The resize
+// moves bytes and the convolution reads them with its own input zero point: the same bytes as the two launches.  Same device and element
+// type, neither forced generic, upconv_rt's class (route_upconv).  nullptr: the two launches stay
+FusedImpl *fused_resize_conv_create(OpImpl *resize, OpImpl *conv) {
+    if (switches().no_upconv || !resize || !conv || resize->force_generic || conv->force_generic) return nullptr;
+    const OpSpec &r = resize->s, &d = conv->s;
+    if (r.kind != MF_OP_RESIZE_NEAREST_NEIGHBOR || d.kind != MF_OP_CONV_2D || resize->device != conv->device || r.u8 != d.u8) return nullptr;
+    if (d.H != r.OH || d.W != r.OW || d.C != r.C) return nullptr; // on exactly the resize's output
+    if (!r.upsampled() || !conv->finite_consts) return nullptr;
+    // Excluded by measurement: the group is formed only where upconv_rt beat the convolution's own launch on the resized
+    // tensor by more than the spread -- a convolution whose own kernel is conv_gemm_rt (x1.03 at 8x8x128 -> 128), and factors of 4 in both
+    // axes (x1.02 at 8x8x64 -> 64).  At smaller factors a convolution on conv_mm_rt (or any other kernel) did not clear (x0.94 - x1.01):
+    // those run resize_nn_c4 + their own kernel.  MF_UPCONV_ALL (tests, measurements): the whole class of upconv_rt
+    const bool clears = conv->fast == OpImpl::CONV_GEMM || (r.up_h >= 4 && r.up_w >= 4);
+    if (!clears && !switches().upconv_all) return nullptr;
+    std::shared_ptr<OpImpl> inner(op_create_upsampled_conv(conv, r.H, r.W, r.up_h, r.up_w), op_destroy);
+    if (!inner) return nullptr;
+    std::unique_ptr<FusedImpl> f = make_group(FusedImpl::RESIZECONV, resize, conv, nullptr, "resize+" + inner->fast_name);
+    f->padconv = inner;
+    f->epi_mode = conv->magic_mode;
+    return f.release();
+}
+
 // DepthwiseConv2D with one input channel (the dw_c1_lds operator) -> [Reshape] -> FullyConnected + Softmax group, as
 // one kernel (k_dwfc.hip; speech.tflite ops 1..3).  Second level like the stage: the operator and the group inside
 // stay available for mf_model_run_until.  nullptr when the shapes are not the compiled instance.

@@ -17,7 +17,7 @@ namespace mf {
 // One argument block (or a named sub-struct: block + what the launch path needs beside it) per kind; a group uses its own kind's.
 // Plain members, no variant: the chain planner swaps whole groups (std::swap(*groups[i], *trial)).
 struct FusedImpl {
-    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK, CONVPOOL, SHORTCUT, PADCONV, SIDECONCAT } kind = DWPW;
+    enum Kind { DWPW, TAIL, FCSM, STAGE, DWFC, PAIRTAIL, QUAD, CHAIN, FCCHAIN, POOLFC, PAIRBAND, PAIRWZ, CONV1FC, BLOCK, CONVPOOL, SHORTCUT, PADCONV, SIDECONCAT, RESIZECONV } kind = DWPW;
     OpImpl *a = nullptr, *b = nullptr, *c = nullptr;
     std::string name;
     std::vector<std::unique_ptr<DevBuf>> owned; // the group's own operand arrays and tables (keep)
@@ -85,6 +85,9 @@ struct FusedImpl {
     // a = the PAD, b = the convolution.  padconv = that convolution taken as an operator on the UNPADDED image with the PAD's top / left
     // rows and columns as its window placement (ops.hip op_create_padded_conv): it borrows b's weights and constants, owns the images
     // and tables of its plan, and has no generic kernel -- the group runs it on 16-byte aligned pointers only
+    // RESIZECONV: a RESIZE_NEAREST_NEIGHBOR + the Conv2D on its output as one upconv_rt launch (k_upconv.hip); a = the resize, b = the
+    // convolution.  padconv = that convolution taken as an operator on the SOURCE image that resizes while it stages (ops.hip
+    // op_create_upsampled_conv), under the same terms
     std::shared_ptr<OpImpl> padconv;
     // the model's f32 boundary inside this group's launch (fused_set_input_quant / fused_set_output_dequant; KindFacts f32_in / f32_out)
     k::F32Edge edge{};
@@ -117,6 +120,7 @@ inline KindFacts kind_facts(FusedImpl::Kind kind) {
     case FusedImpl::BLOCK: return {"block_band_rt", true, false, false};
     case FusedImpl::CONVPOOL: return {"conv_pool_rt", true, false, false};
     case FusedImpl::PADCONV: return {"pad+conv", true, false, false};
+    case FusedImpl::RESIZECONV: return {"resize+conv", true, false, false};
     case FusedImpl::SIDECONCAT: return {nullptr, false, false, false}; // (as SHORTCUT)
     case FusedImpl::SHORTCUT: return {nullptr, false, false, false}; // (16-byte words at all three pointers, the caller's output buffer among them: fused_run2 checks the alignment itself)
     }

@@ -872,6 +872,32 @@ bool conv_grp_plan(ConvGrpArgs &a, std::vector<int> &tap, std::vector<int> &colc
                    int sw, int OH, int OW, int padt, int padl, bool wz);
 std::vector<int8_t> conv_grp_weight_image(const int8_t *w /*[N][KH][KW][Cg]*/, const ConvGrpArgs &a, const std::vector<int> &colch, bool wz);
 void launch_conv_grp(const int8_t *in, int8_t *out, const ConvGrpArgs &a, bool wz, int batch, hipStream_t s);
+// RESIZE_NEAREST_NEIGHBOR by integer factors (k_resize.hip): out[oy][ox][c] = in[oy / sy][ox / sx][c], bytes moved as they are.
+struct ResizeArgs {
+    int H, W, C, sy, sx;
+};
+// resize_nn_generic: any shape and pointers, one output byte per thread.  resize_nn_c4 (unit = 4: C % 4 == 0, pointers 4-byte aligned;
+// unit = 16: C % 16 == 0, pointers 16-byte aligned): every source word loaded once, stored sy sx times from registers, no LDS
+void launch_resize_generic(const int8_t *in, int8_t *out, const ResizeArgs &a, size_t batch, hipStream_t s);
+void launch_resize_c4(const int8_t *in, int8_t *out, const ResizeArgs &a, size_t batch, int unit, hipStream_t s);
+// RESIZE_NEAREST_NEIGHBOR by (sy, sx) + stride-1 Conv2D on its result as one product on the matrix pipe (k_upconv.hip: upconv_rt).  `g` is
+// conv_gemm_rt's argument block with the same meaning field for field -- H, W are the SOURCE image's, OH, OW, padt, padl the convolution's
+// on the sy H x sx W upsampled image; the weight image is conv_gemm_weight_image(w, g), the constants conv_gemm_rt's -- but the staged tile
+// holds SOURCE rows, each written with every pixel repeated sx times (so a tile row looks like a row of the upsampled image, halo
+// included), and nothing is repeated in y: output row oy = sy q + py reads, for filter row ky, tile row (q - q0) + d(py, ky) - dmin with
+// d = floor((py + ky - padt) / sy), from one of sy tap tables [py][KS][4] whose entries are (d - dmin) ROW + j.  A band starts on a
+// multiple of sy output rows (BH % sy == 0 where NBANDS > 1).  C % 4 == 0, 1 <= sy, sx <= 4, filter sides <= 7, filter zero points 0.
+struct UpconvArgs {
+    ConvGemmArgs g;
+    int sy, sx;
+    int dmin;            // floor(-padt / sy): the source row, relative to q, that tile row 0 holds for the band's first output row
+};
+bool upconv_plan(UpconvArgs &a, std::vector<int> &tap, int H, int W, int C, int N, int KH, int KW, int sy, int sx, int OH, int OW, int padt,
+                 int padl); // false: outside the class, or a band of sy output rows does not fit beside one resident tile
+void launch_upconv(const int8_t *in, int8_t *out, const UpconvArgs &a, int batch, hipStream_t s);
+// the same contract in plain C++, one thread per output byte, filter zero points included: `a` is the convolution's block with H, W the
+// SOURCE image's and OH, OW the output's (strides as given)
+void launch_upconv_generic(const int8_t *in, int8_t *out, const ConvArgs &a, int sy, int sx, size_t batch, hipStream_t s);
 // TRANSPOSE_CONV split by output phase (k_tconv.hip: tconv_phase_rt): the sh sw phases of a base pixel (q, qx) are stride-1 products
 // over K' = Ty x (Tx C rounded up to 16) each, conv_gemm_rt's K layout on a staged NHWC tile; the operands are wimage.cpp's
 // (build_tconv_image / _kc / _table).  C % 4 == 0, (W C) % 4 == 0, strides <= 4, filter sides <= 8, filter zero points 0.

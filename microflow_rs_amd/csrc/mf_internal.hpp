@@ -129,6 +129,8 @@ struct ParsedOp {
     bool side() const { return side_src != -2; }
     // PAD only: new rows / columns (top, bottom, left, right); H, W, C the input, OH, OW the output
     int pads[4] = {0, 0, 0, 0};
+    // RESIZE_NEAREST_NEIGHBOR only: the integer factors (OH = up_h H, OW = up_w W)
+    int up_h = 1, up_w = 1;
     // what mf_model_get_op reports as the kind: the file's.  A MEAN over {1, 2} is parsed into a global AveragePool2D (kind), so that
     // every rule that matches one sees it, and reports MF_OP_MEAN; -1: kind
     int file_kind = -1;
@@ -181,6 +183,9 @@ struct OpSpec {
     int groups = 1;          // conv_2d: filters [N][KH][KW][C / groups] (include/microflow_amd.h: mf_conv_2d_grouped_create)
     int twin_of = 0;         // ... or the group count of the grouped operator this dense one is the block-diagonal twin of (ops.hip create_conv)
     bool grouped() const { return groups != 1 || twin_of != 0; } // (the fused groups pass such an operator by: it launches alone)
+    int up_h = 1, up_w = 1;  // conv_2d: the H x W x C input is resized (nearest neighbour) by these integer factors first, OH and OW refer to the
+                             // resized image (include/microflow_amd.h: mf_conv_2d_upsampled_create); RESIZE_NEAREST_NEIGHBOR: the operator's factors
+    bool upsampled() const { return up_h != 1 || up_w != 1; }
     int act = 0;
     int izp = 0;             // zero point of the running input tensor
     float in_scale = 0;      // softmax only
@@ -261,6 +266,13 @@ FusedImpl *fused_pad_conv_create(OpImpl *pad, OpImpl *conv);
 // and padl columns left of it, everything outside the image reading the input zero point; OH, OW stay.  It borrows conv's weights and
 // constants (destroy it first), has a matrix-pipe / row kernel or does not exist (nullptr), and must only be run on 16-byte aligned pointers
 OpImpl *op_create_padded_conv(const OpImpl *conv, int Hin, int Win, int padt, int padl);
+// a RESIZE_NEAREST_NEIGHBOR + the Conv2D on exactly its output as ONE upconv_rt launch (k_upconv.hip), or nullptr: outside the kernel's
+// class (or a class the route excludes by measurement), forced generic, MF_NO_UPCONV -- the two launches stay
+FusedImpl *fused_resize_conv_create(OpImpl *resize, OpImpl *conv);
+// the convolution `conv` (on the up_h Hin x up_w Win resized image) as an operator on the Hin x Win source image that resizes while it
+// stages; it borrows conv's weights and constants (destroy it first), runs upconv_rt or does not exist (nullptr), and must only be run
+// on 16-byte aligned pointers
+OpImpl *op_create_upsampled_conv(const OpImpl *conv, int Hin, int Win, int up_h, int up_w);
 FusedImpl *fused_conv_pool_create(OpImpl *conv, OpImpl *pool); // a Conv2D + the AveragePool2D (k_conv_pool.hip) or MaxPool2D (k_conv_maxpool.hip) with more than one output pixel on its output in one launch, or nullptr
 // fused tail: AveragePool2D (1x1 output) -> Conv2D 1x1 (N <= 8) -> Softmax (one row of N)
 FusedImpl *fused_tail_create(OpImpl *pool, OpImpl *conv, OpImpl *softmax);

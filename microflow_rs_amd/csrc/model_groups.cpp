@@ -67,7 +67,7 @@ struct GroupBuilder {
     }
     // a first-level pair group: operators i and i + 1
     // (a depthwise + 1x1 pair of rule (1): the PAD + convolution group has two operators too and is none)
-    bool is_pair_group(size_t i) const { return g.fused[i] && g.fused_last[i] == (int)i + 1 && kind(i) != MF_OP_PAD; }
+    bool is_pair_group(size_t i) const { return g.fused[i] && g.fused_last[i] == (int)i + 1 && kind(i) != MF_OP_PAD && kind(i) != MF_OP_RESIZE_NEAREST_NEIGHBOR; }
     // an operator with a launch of its own that no group starts at, covers or owns
     bool free_op(size_t i) const { return g.ops[i] && !g.fused[i] && !covered(i) && !owned(i); }
     bool free_fc(size_t i) const { return i < n && kind(i) == MF_OP_FULLY_CONNECTED && free_op(i); }
@@ -117,6 +117,7 @@ static OpSpec op_spec(const ParsedModel &pm, const ParsedOp &po, float cur_scale
     if (po.join()) s.join_za = po.a_zp, s.join_zb = po.b_zp, s.join_ca = po.c0[0], s.join_cb = po.c1[0];
     if (po.kind == MF_OP_PAD)
         for (int k = 0; k < 4; ++k) s.pads[k] = po.pads[k];
+    if (po.kind == MF_OP_RESIZE_NEAREST_NEIGHBOR) s.up_h = po.up_h, s.up_w = po.up_w;
     return s;
 }
 
@@ -154,6 +155,8 @@ static void create_operators(GroupBuilder &b) {
 // (2) AveragePool2D (1x1 output) -> Conv2D 1x1 -> [Reshape] -> Softmax -> one tail kernel.
 // (3) FullyConnected (few outputs, one row) -> [Reshape] -> Softmax -> one kernel.
 // (0p) a PAD directly followed by a VALID Conv2D / DepthwiseConv2D -> one launch of the convolution's kernel with explicit pads.
+// (0r) a RESIZE_NEAREST_NEIGHBOR directly followed by a Conv2D in upconv_rt's class -> one upconv_rt launch; the resized tensor is never
+// written, so a resize whose output a join reads too (splits) keeps its launch.
 // In the same loop as (1)-(3) and in front of them: the group at i owns the convolution at i + 1 (the loop continues behind it), so a
 // depthwise there is never also offered to (1) with the 1x1 behind it -- that pair would be formed over the padded tensor, which this
 // launch never writes.  The PAD's output has one reader (the parser's chain: the convolution) unless a join reads it too: splits
@@ -164,6 +167,8 @@ static void rule_1_2_3_first_level(GroupBuilder &b) {
     for (size_t i = 0; i + 1 < b.n; ++i) {
         if (b.kind(i) == MF_OP_PAD && (b.kind(i + 1) == MF_OP_CONV_2D || b.kind(i + 1) == MF_OP_DEPTHWISE_CONV_2D)) {
             if (!b.splits(i, i + 1) && (fused[i] = fused_pad_conv_create(ops[i], ops[i + 1]))) fused_last[i] = (int)i + 1;
+        } else if (b.kind(i) == MF_OP_RESIZE_NEAREST_NEIGHBOR && b.kind(i + 1) == MF_OP_CONV_2D) { // (0r), beside (0p) and under its terms
+            if (!b.splits(i, i + 1) && (fused[i] = fused_resize_conv_create(ops[i], ops[i + 1]))) fused_last[i] = (int)i + 1;
         } else if (b.kind(i) == MF_OP_DEPTHWISE_CONV_2D && b.kind(i + 1) == MF_OP_CONV_2D) {
             if (!b.splits(i, i + 1) && (fused[i] = fused_create(ops[i], ops[i + 1]))) fused_last[i] = (int)i + 1;
         } else if (b.kind(i) == MF_OP_AVERAGE_POOL_2D && b.kind(i + 1) == MF_OP_CONV_2D) {

@@ -198,7 +198,7 @@ void find_fma_form(OpImpl &op, const ConvCtx &c) {
 
 // Everything a convolution-like operator decides before it picks a kernel: the folded constants (uploaded, and kept on the host
 // in the operator), the epilogue mode, the single-fma form, the generic kernel's argument block.
-ConvCtx prepare_conv(OpImpl &op, const OpSpec &s, bool dw, int lo, int hi, int xr) {
+ConvCtx prepare_conv(OpImpl &op, const OpSpec &s, bool dw, int lo, int hi, int xr, bool fma_form = true) {
     ConvCtx c{s, dw, op.h_A, op.h_S, op.h_Kc, op.h_wzp};
     c.lo = lo, c.hi = hi, c.xr = xr;
     // the fast kernels may convert the accumulator to f32 by bit pattern when it provably
@@ -237,7 +237,7 @@ ConvCtx prepare_conv(OpImpl &op, const OpSpec &s, bool dw, int lo, int hi, int x
         const std::vector<int> zeros((size_t)k::DYNQ_INTS * k::DYNQ_RING, 0);
         op.d_queue.upload(zeros.data(), zeros.size() * sizeof(int));
     }
-    find_fma_form(op, c);
+    if (fma_form) find_fma_form(op, c); // (not for an operator none of whose kernels has the form: create_upconv)
     k::ConvArgs &a = op.conv;
     a.H = s.H, a.W = s.W, a.C = s.C, a.N = s.N, a.KH = s.KH, a.KW = s.KW, a.sh = s.sh, a.sw = s.sw;
     a.OH = s.OH, a.OW = s.OW, a.pad_same = s.pad == MF_PAD_SAME, a.izp = s.izp;
@@ -671,6 +671,57 @@ bool route_conv_grp(OpImpl &op, const ConvCtx &c) {
     return true;
 }
 
+// 16. a Conv2D on a resized input (OpSpec::up_h, up_w; s.H, s.W the SOURCE image's) with C % 4 == 0, strides (1, 1), factors <= 4, filter
+// sides <= 7, zero filter zero points: the resize happens while the tile is staged (k_upconv.hip).  The only route that takes such an
+// operator (create_upconv, op_create_upsampled_conv); every other shape stays on upconv_generic.
+bool route_upconv(OpImpl &op, const ConvCtx &c) {
+    const OpSpec &s = c.s;
+    if (!(rt_candidate(op, c) && !c.dw && s.upsampled() && !c.wz && s.sh == 1 && s.sw == 1 && !s.dilated() && s.groups == 1 && !switches().no_upconv))
+        return false;
+    std::vector<int> tap;
+    k::UpconvArgs &f = op.upc;
+    if (!k::upconv_plan(f, tap, s.H, s.W, s.C, s.N, s.KH, s.KW, s.up_h, s.up_w, s.OH, s.OW, c.padt, c.padl)) return false;
+    const std::vector<int8_t> img = k::conv_gemm_weight_image(s.weights, f.g);
+    op.d_fcw.upload(img.data(), img.size());
+    op.d_tap.upload(tap.data(), tap.size() * sizeof(int));
+    f.g.wimg = op.d_fcw.p, f.g.tap = op.d_tap.as<int>(), f.g.kmask = nullptr;
+    const ConstPtrs p = row_consts(op, c, (size_t)f.g.NT * 16, s.N, [](int n) { return n; }); // padded to 16-column tiles
+    f.g.A = p.A, f.g.S = p.S, f.g.Kc = p.Kc, f.g.wzp = p.wzp;
+    epi_fields_izp(f.g, op, c);
+    op.fast = OpImpl::UPCONV;
+    op.rt_wz = false;
+    op.fast_name = "upconv_rt<" + std::to_string(s.up_h) + "x" + std::to_string(s.up_w) + ">";
+    if (switches().verbose)
+        fprintf(stderr, "[microflow_amd] upconv_rt %dx%dx%d x%dx%d -> %d %dx%d: K' %d (%d k steps), %d tiles in %d slice(s) of %d, %s %d x %d source rows of %d B, %d B LDS\n",
+                s.H, s.W, s.C, s.up_h, s.up_w, s.N, s.KH, s.KW, s.KH * f.g.KWCP, f.g.KS, f.g.NT, f.g.NSL, f.g.NTS,
+                f.g.NBANDS > 1 ? "bands of" : "images per step:", f.g.NBANDS > 1 ? f.g.BH : f.g.G, f.g.RB, f.g.ROW, f.g.lds);
+    return true;
+}
+
+// the output size conv_2d's placement gives on the up_h H x up_w W resized image; false: none, or not the one stated
+static bool upsampled_geometry_ok(const OpSpec &s) {
+    const long long UH = (long long)s.H * s.up_h, UW = (long long)s.W * s.up_w, same = s.pad == MF_PAD_SAME;
+    const long long oh = same ? (UH + s.sh - 1) / s.sh : (UH - s.KH + 1 + s.sh - 1) / s.sh, ow = same ? (UW + s.sw - 1) / s.sw : (UW - s.KW + 1 + s.sw - 1) / s.sw;
+    return UH <= (1 << 24) && UW <= (1 << 24) && oh >= 1 && ow >= 1 && (same || (UH >= s.KH && UW >= s.KW)) && s.OH == oh && s.OW == ow;
+}
+
+// conv_2d on a resized input (include/microflow_amd.h: mf_conv_2d_upsampled_create).  conv_2d's constants and epilogue mode; upconv_rt
+// for the class of route_upconv, upconv_generic for everything else
+void create_upconv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
+    if (s.up_h < 1 || s.up_w < 1) fail(MF_ERR_INVALID_ARG, "conv_2d on a resized input: a factor is not positive");
+    if (s.kind != MF_OP_CONV_2D || s.dh != 1 || s.dw != 1 || s.groups != 1) fail(MF_ERR_INVALID_ARG, "conv_2d on a resized input: dilation 1 and one group only");
+    if (!upsampled_geometry_ok(s))
+        fail(MF_ERR_INVALID_ARG, "conv_2d on an input resized by " + std::to_string(s.up_h) + "x" + std::to_string(s.up_w) + ": the output size is not what " +
+                                     (s.pad == MF_PAD_SAME ? "SAME" : "VALID") + " gives on the resized image");
+    if ((long long)s.N * s.KH * s.KW * s.C > 0x7fffffffll) fail(MF_ERR_INVALID_ARG, "conv: bad arguments");
+    op.in_elems = (size_t)s.H * s.W * s.C;
+    op.out_elems = (size_t)s.OH * s.OW * s.N;
+    dom.apply(s, (size_t)s.N * s.KH * s.KW * s.C);
+    const ConvCtx c = prepare_conv(op, s, false, lo, hi, xr, false);
+    op.generic_name = "upconv_generic";
+    route_upconv(op, c);
+}
+
 // the dense [N][KH][KW][C] twin of a grouped filter [N][KH][KW][C / groups] in the i8 domain: block-diagonal, every element outside a
 // channel's own group that channel's filter zero point ((w - wzp) = 0 there: the same accumulator, the same Kc, the same bound)
 std::vector<int8_t> twin_filter(const OpSpec &s) {
@@ -721,6 +772,7 @@ void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
         !s.c0 || !s.c1)
         fail(MF_ERR_INVALID_ARG, "conv: bad arguments");
     if (s.dh <= 0 || s.dw <= 0) fail(MF_ERR_INVALID_ARG, "conv: a dilation factor is not positive");
+    if (s.upsampled()) return create_upconv(op, s, dom, lo, hi, xr); // (factors (1, 1): the operator it always was, below)
     if (s.KH == 1) s.dh = 1; // one tap along an axis: its factor moves nothing, the operator is the undilated one
     if (s.KW == 1) s.dw = 1;
     const long long KEH = ((long long)s.KH - 1) * s.dh + 1, KEW = ((long long)s.KW - 1) * s.dw + 1; // the effective extent
@@ -1052,7 +1104,51 @@ void create_pad(OpImpl &op, const OpSpec &s) {
     }
 }
 
+// RESIZE_NEAREST_NEIGHBOR: no weights, no constants, no zero point (bytes are copied; the u8 internal domain flips both sides alike)
+void create_resize(OpImpl &op, const OpSpec &s) {
+    if (s.H <= 0 || s.W <= 0 || s.C <= 0 || s.up_h < 1 || s.up_w < 1) fail(MF_ERR_INVALID_ARG, "resize_nearest: bad arguments");
+    const long long OH = (long long)s.H * s.up_h, OW = (long long)s.W * s.up_w;
+    if (OH != s.OH || OW != s.OW || OH > (1 << 24) || OW > (1 << 24) || OW * s.C > 0x7fffffffll) fail(MF_ERR_INVALID_ARG, "resize_nearest: the output shape is not input x factors");
+    op.in_elems = (size_t)s.H * s.W * s.C;
+    op.out_elems = (size_t)OH * (size_t)OW * s.C;
+    op.rsz = k::ResizeArgs{s.H, s.W, s.C, s.up_h, s.up_w};
+    op.generic_name = "resize_nn_generic";
+    if (s.C % 4 == 0) { // whole words per pixel
+        op.rsz_unit = s.C % 16 == 0 ? 16 : 4;
+        op.fast = OpImpl::RESIZE_C4, op.fast_name = op.rsz_unit == 16 ? "resize_nn_c4<v16>" : "resize_nn_c4";
+    }
+}
+
 } // namespace
+
+OpImpl *op_create_upsampled_conv(const OpImpl *conv, int Hin, int Win, int up_h, int up_w) {
+    const OpSpec &q = conv->s;
+    if (q.kind != MF_OP_CONV_2D || q.upsampled() || q.grouped() || q.dilated() || Hin <= 0 || Win <= 0 || up_h < 1 || up_w < 1 ||
+        (long long)Hin * up_h != q.H || (long long)Win * up_w != q.W || conv->h_w.empty())
+        return nullptr;
+    MF_HIP(hipSetDevice(conv->device));
+    std::unique_ptr<OpImpl> op(new OpImpl);
+    op->device = conv->device;
+    op->s = q;
+    op->s.H = Hin, op->s.W = Win, op->s.up_h = up_h, op->s.up_w = up_w;
+    if (!upsampled_geometry_ok(op->s)) return nullptr;
+    op->s.weights = conv->h_w.data(); // (i8 domain, as uploaded: what the image builder reads; cleared again below)
+    op->in_elems = (size_t)Hin * Win * q.C, op->out_elems = conv->out_elems;
+    op->h_A = conv->h_A, op->h_S = conv->h_S, op->h_Kc = conv->h_Kc, op->h_wzp = conv->h_wzp;
+    op->finite_consts = conv->finite_consts, op->magic_mode = conv->magic_mode;
+    op->conv = conv->conv; // the borrowed device arrays (w, wzp, A, S, Kc), the clamp, the input zero point
+    op->conv.H = Hin, op->conv.W = Win;
+    op->generic_name = "(none)";
+    ConvCtx c{op->s, false, op->h_A, op->h_S, op->h_Kc, op->h_wzp};
+    c.lo = (int)conv->conv.lo_f, c.hi = (int)conv->conv.hi_f, c.xr = conv->conv.xr;
+    c.magic = conv->magic_mode, c.finite = conv->finite_consts;
+    c.wz = !all_zero(c.wzp), c.zero_wzp = !c.wz && c.finite;
+    c.padt = q.pad == MF_PAD_SAME ? (q.KH - 1) / 2 : 0, c.padl = q.pad == MF_PAD_SAME ? (q.KW - 1) / 2 : 0;
+    route_upconv(*op, c); // the two-rounding epilogue (no single-fma form)
+    op->s.weights = nullptr, op->s.wzp = nullptr, op->s.c0 = op->s.c1 = nullptr, op->s.c2 = nullptr;
+    if (op->fast == OpImpl::NONE) return nullptr;
+    return op.release();
+}
 
 OpImpl *op_create_padded_conv(const OpImpl *conv, int Hin, int Win, int padt, int padl) {
     const OpSpec &q = conv->s;
@@ -1107,6 +1203,7 @@ OpImpl *op_create(int device, const OpSpec &spec) {
     case MF_OP_ADD: create_add(*op, s, lo, hi); break;
     case MF_OP_CONCATENATION: create_concat(*op, s); break;
     case MF_OP_PAD: create_pad(*op, s); break;
+    case MF_OP_RESIZE_NEAREST_NEIGHBOR: create_resize(*op, s); break;
     default: fail(MF_ERR_UNSUPPORTED, "unsupported operator kind " + std::to_string(s.kind));
     }
     op->s = s;
@@ -1145,6 +1242,7 @@ bool op_tile_plan(const OpImpl *op, int plan[8]) {
     if (op->fast == OpImpl::CONV_DIL) return put(op->cdl.dw, op->cdl.PP, c.ROW, c.RB, c.NBANDS, c.BH, c.G, c.NSL);
     if (op->fast == OpImpl::CONV_GRP) return put(1, 0, op->cgp.g.ROW, op->cgp.g.RB, op->cgp.g.NBANDS, op->cgp.g.BH, op->cgp.g.G, op->cgp.g.NSL);
     if (op->fast == OpImpl::CONV_GEMM) return put(1, 0, c.ROW, c.RB, c.NBANDS, c.BH, c.G, c.NSL);
+    if (op->fast == OpImpl::UPCONV) return put(1, 0, op->upc.g.ROW, op->upc.g.RB, op->upc.g.NBANDS, op->upc.g.BH, op->upc.g.G, op->upc.g.NSL); // (rows: SOURCE rows)
     if (op->fast == OpImpl::DW_GEMM) return put(1, 0, op->dwg.ROW, op->dwg.RB, op->dwg.NBANDS, op->dwg.BH, op->dwg.G, 1);
     return false;
 }
@@ -1242,6 +1340,14 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             k::launch_conv_grp(d_in, d_out, op->cgp, op->rt_wz, (int)batch, s);
             done = true;
             break;
+        case OpImpl::UPCONV:
+            k::launch_upconv(d_in, d_out, op->upc, (int)batch, s);
+            done = true;
+            break;
+        case OpImpl::RESIZE_C4:
+            k::launch_resize_c4(d_in, d_out, op->rsz, batch, op->rsz_unit, s);
+            done = true;
+            break;
         case OpImpl::TCONV_PHASE:
             k::launch_tconv_phase(d_in, d_out, op->tcv, (int)batch, s);
             done = true;
@@ -1322,7 +1428,11 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
     }
     if (!done) {
         switch (sp.kind) {
-        case MF_OP_CONV_2D: k::launch_conv2d_generic(d_in, d_out, op->conv, batch, s); break;
+        case MF_OP_CONV_2D:
+            if (sp.upsampled()) k::launch_upconv_generic(d_in, d_out, op->conv, sp.up_h, sp.up_w, batch, s);
+            else k::launch_conv2d_generic(d_in, d_out, op->conv, batch, s);
+            break;
+        case MF_OP_RESIZE_NEAREST_NEIGHBOR: k::launch_resize_generic(d_in, d_out, op->rsz, batch, s); break;
         case MF_OP_DEPTHWISE_CONV_2D: k::launch_dwconv_generic(d_in, d_out, op->conv, batch, s); break;
         case MF_OP_TRANSPOSE_CONV: k::launch_tconv_generic(d_in, d_out, op->conv, op->tc_padt, op->tc_padl, batch, s); break;
         case MF_OP_AVERAGE_POOL_2D: k::launch_avgpool_generic(d_in, d_out, op->pool, batch, s); break;

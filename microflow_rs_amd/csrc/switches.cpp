@@ -74,6 +74,8 @@ Switches switches_parse() {
     s.no_expand_block = env_set("MF_NO_EXPAND_BLOCK");
     s.no_conv_pool = env_set("MF_NO_CONV_POOL");
     s.no_pad_conv = env_set("MF_NO_PAD_CONV");
+    s.no_upconv = env_set("MF_NO_UPCONV");
+    s.upconv_all = env_set("MF_UPCONV_ALL");
     s.conv_pool_all = env_set("MF_CONV_POOL_ALL");
     s.no_pair_wz = env_set("MF_NO_PAIR_WZ");
     s.no_shortcut_add = env_set("MF_NO_SHORTCUT_ADD");

@@ -78,6 +78,7 @@ Vec vec(const Table &t, int id) {
 
 enum { TT_INT32 = 2, TT_UINT8 = 3, TT_INT64 = 4, TT_INT8 = 9 };
 enum { BUILTIN_PADV2 = 60, BUILTIN_MIRROR_PAD = 100 }; // the neighbours of PAD, refused by name
+enum { BUILTIN_RESIZE_BILINEAR = 23 };                 // the neighbour of RESIZE_NEAREST_NEIGHBOR, refused by name
 
 struct TensorInfo {
     std::vector<int> shape;
@@ -714,6 +715,39 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
                     if (c != 0.0f || std::signbit(c)) fail(MF_ERR_INVALID_MODEL, "invalid model: TRANSPOSE_CONV without a bias needs a finite positive output scale");
             break;
         }
+        case MF_OP_RESIZE_NEAREST_NEIGHBOR: { // not in the reference (lib.rs:148 answers "unsupported operator: 97"): the contract is include/microflow_amd.h's
+            auto refuse = [](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: 97 (RESIZE_NEAREST_NEIGHBOR: " + why + ")"); };
+            if (ins.size() != 2) refuse("it needs an input and a size operand");
+            for (const TensorInfo *t : {&in, &out}) {
+                if ((t->type != TT_INT8 && t->type != TT_UINT8) || (t->type == TT_UINT8) != pm.u8) refuse("mixed element types");
+                need_quant(*t, "RESIZE_NEAREST_NEIGHBOR");
+                if (t->scale.size() != 1 || t->zp.size() != 1) refuse("per-channel quantisation on an operand");
+            }
+            if (in.data_len) refuse("a constant operand");
+            if (in.shape.size() != 4 || out.shape.size() != 4) refuse("tensor rank must be 4");
+            if (in.shape[0] != 1 || out.shape[0] != 1) refuse("tensor batch must be 1");
+            // ResizeNearestNeighborOptions { align_corners:0 half_pixel_centers:1 }: with align_corners = false both settings of
+            // half_pixel_centers give floor(o / s) for an integer factor s (floor((o + 1/2) / s) = floor(o / s))
+            if (opt.scalar<uint8_t>(0, 0) != 0) refuse("align_corners = true");
+            const TensorInfo sz = read_tensor(tensors, buffers, ins.get<int32_t>(1));
+            if (!sz.data_len) refuse("a non-constant size");
+            if (sz.type != TT_INT32 || sz.shape != std::vector<int>{2} || sz.data_len < 8)
+                fail(MF_ERR_INVALID_MODEL, "invalid model: RESIZE_NEAREST_NEIGHBOR size must be a constant INT32 [2]");
+            int32_t hw[2];
+            std::memcpy(hw, sz.data, 8);
+            if (hw[0] != out.shape[1] || hw[1] != out.shape[2] || out.shape[3] != in.shape[3])
+                fail(MF_ERR_INVALID_MODEL, "invalid model: RESIZE_NEAREST_NEIGHBOR size disagrees with the output tensor's shape");
+            if (out.shape[1] % in.shape[1] != 0 || out.shape[2] % in.shape[2] != 0) refuse("a non-integer ratio");
+            if (std::memcmp(&in.scale[0], &out.scale[0], sizeof(float)) != 0 || zp_of(in.zp[0], pm.u8) != zp_of(out.zp[0], pm.u8))
+                refuse("input and output quantisation differ");
+            set_shapes(po, in, out, pm.u8);
+            po.H = in.shape[1], po.W = in.shape[2], po.C = in.shape[3], po.N = po.C;
+            po.OH = out.shape[1], po.OW = out.shape[2];
+            po.up_h = po.OH / po.H, po.up_w = po.OW / po.W;
+            break;
+        }
+        case BUILTIN_RESIZE_BILINEAR:
+            fail(MF_ERR_UNSUPPORTED, "unsupported operator: 23 (RESIZE_BILINEAR: only RESIZE_NEAREST_NEIGHBOR by integer factors is supported)");
         case BUILTIN_PADV2:
             fail(MF_ERR_UNSUPPORTED, "unsupported operator: 60 (PADV2: only PAD, whose fill is the tensor's zero point, is supported)");
         case BUILTIN_MIRROR_PAD:

@@ -477,5 +477,24 @@ void conv_dil_tables(int KH, int KW, int C, int dh, int ROW, std::vector<int> &t
         }
 }
 
+// ---- upconv_rt (k_upconv.hip): RESIZE_NEAREST_NEIGHBOR by (sy, .) + Conv2D on a tile that holds SOURCE rows ----
+// Output row oy = sy q + py reads, for filter row ky, source row q + d with d = floor((py + ky - padt) / sy); tile row 0 of a band
+// holds source row q0 + dmin, dmin = floor(-padt / sy) (the smallest d there is: py = ky = 0).  sy tables [py][KS][4] of
+// (d - dmin) ROW + j, in conv_gemm_rt's sense of j; beyond K' offset 0 against zero weights
+int upconv_dmin(int padt, int sy) { return -((padt + sy - 1) / sy); }
+std::vector<int> upconv_tables(int KH, int KW, int C, int sy, int padt, int ROW) {
+    const int KWCP = (KW * C + 15) & ~15, KS = (KH * KWCP + 63) / 64, dmin = upconv_dmin(padt, sy);
+    std::vector<int> tap((size_t)sy * KS * 4, 0);
+    for (int py = 0; py < sy; ++py)
+        for (int ks = 0; ks < KS; ++ks)
+            for (int g = 0; g < 4; ++g) {
+                const int k0 = ks * 64 + g * 16, ky = k0 / KWCP, j = k0 % KWCP;
+                if (ky >= KH) continue;
+                const int a = py + ky - padt, d = a >= 0 ? a / sy : -((-a + sy - 1) / sy);
+                tap[((size_t)py * KS + ks) * 4 + g] = (d - dmin) * ROW + j;
+            }
+    return tap;
+}
+
 } // namespace wimage
 } // namespace mf

@@ -64,5 +64,10 @@ ConvDilTile conv_dil_tile(int W, int C, int KW, int sw, int dw, int OW, int padl
 long long conv_dil_column(const ConvDilTile &t, int C, int dw, int xe /* x + padl */);
 void conv_dil_tables(int KH, int KW, int C, int dh, int ROW, std::vector<int> &tap, std::vector<uint32_t> &mask);
 
+// A resize by (sy, .) + Conv2D on a tile of source rows (k_upconv.hip): the source row, relative to an output row's own, that tile row 0
+// stands for, and the sy y-phase tap tables [py][KS][4]
+int upconv_dmin(int padt, int sy);
+std::vector<int> upconv_tables(int KH, int KW, int C, int sy, int padt, int ROW);
+
 } // namespace wimage
 } // namespace mf

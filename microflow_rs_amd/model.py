@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 
 OP_NAMES = {0: "add", 1: "average_pool_2d", 2: "concatenation", 3: "conv_2d", 4: "depthwise_conv_2d", 67: "transpose_conv", 9: "fully_connected", 17: "max_pool_2d",
-            22: "reshape", 25: "softmax", 34: "pad", 40: "mean"}
+            22: "reshape", 25: "softmax", 34: "pad", 40: "mean", 97: "resize_nearest_neighbor"}
 
 
 class Model:
@@ -83,6 +83,12 @@ class Model:
         dh, dw = C.c_int(0), C.c_int(0)
         _lib.check(_lib.lib().mf_model_get_op_dilation(self._h, int(i), C.byref(dh), C.byref(dw)))
         return dh.value, dw.value
+
+    def op_upsample(self, i):
+        """(sy, sx) of RESIZE_NEAREST_NEIGHBOR i: the integer factors.  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
+        sy, sx = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().mf_model_get_op_upsample(self._h, int(i), C.byref(sy), C.byref(sx)))
+        return sy.value, sx.value
 
     def op_groups(self, i):
         """group count of Conv2D i: the input's C over the filter's C (1: an ordinary Conv2D).  MicroflowError (MF_ERR_INVALID_ARG)

@@ -10,6 +10,7 @@ names, argument order and meaning, executed by the HIP kernels behind the C ABI.
     add(a, b, output_scale, output_zero_point, options, constants)                                        (not in the reference)
     concatenation(a, b, output_scale, output_zero_point, options, constants)                              (not in the reference)
     pad(input, pads)                                                                                      (not in the reference)
+    resize_nearest(input, factors)                                                                        (not in the reference)
     softmax(input, output_scale, output_zero_point)
     reshape(input, output_shape)
 
@@ -40,6 +41,7 @@ class Conv2DOptions:                      # src/ops/conv_2d.rs:11-15
     strides: Tuple[int, int] = (1, 1)
     dilation: Tuple[int, int] = (1, 1)    # (not in the reference) (dilation_h, dilation_w): include/microflow_amd.h mf_conv_2d_dilated_create
     groups: int = 1                       # (not in the reference) filters [N][KH][KW][C / groups]: include/microflow_amd.h mf_conv_2d_grouped_create
+    upsample: Tuple[int, int] = (1, 1)    # (not in the reference) the input is resized (nearest neighbour) by (up_h, up_w) first; output_shape refers to the resized image: include/microflow_amd.h mf_conv_2d_upsampled_create
 
 
 @dataclass
@@ -216,6 +218,16 @@ def prepare_conv_2d(in_hwc, filters, filters_zero_point, input_zero_point, outpu
     c0, c1 = (_host(np.reshape(c, -1), np.float32) for c in constants)
     h = C.c_void_p()
     dil = tuple(int(d) for d in getattr(options, "dilation", (1, 1)))
+    up = tuple(int(u) for u in getattr(options, "upsample", (1, 1)))
+    if up != (1, 1):
+        if dil != (1, 1) or groups != 1:
+            raise ValueError("an upsampled conv_2d takes dilation (1, 1) and one group")
+        _lib.check(_fn("mf_conv_2d_upsampled_create", dt)(
+            _device(), H, W, C_in, N, KH, KW, _ptr(f), _ptr(fzp), fzp.size, int(input_zero_point),
+            float(output_scale), int(output_zero_point), int(options.fused_activation),
+            int(options.view_padding), options.strides[0], options.strides[1], out_hw[0], out_hw[1],
+            _ptr(c0), _ptr(c1), c1.size, up[0], up[1], C.byref(h)))
+        return PreparedOp(h, (H, W, C_in), (out_hw[0], out_hw[1], N), dt)
     _lib.check(_fn("mf_conv_2d_grouped_create", dt)(
         _device(), H, W, C_in, N, KH, KW, _ptr(f), _ptr(fzp), fzp.size, int(input_zero_point),
         float(output_scale), int(output_zero_point), int(options.fused_activation),
@@ -437,6 +449,23 @@ def pad(input: Tensor4D, pads) -> Tensor4D:
     average_pool_2d with the whole image as filter."""
     shp = tuple(input.buffer.shape)
     op = prepare_pad(shp[-3:], pads, input.zero_point[0], dtype=_elem(input.buffer))
+    return Tensor4D(op(input.buffer), list(input.scale), list(input.zero_point))
+
+
+def prepare_resize_nearest(in_hwc, factors, dtype=np.int8):
+    """factors: (sy, sx), integers >= 1; the output is (sy H, sx W, C)."""
+    H, W, Cc = (int(d) for d in in_hwc)
+    sy, sx = (int(v) for v in factors)
+    h = C.c_void_p()
+    _lib.check(_lib.lib().mf_resize_nearest_create(_device(), H, W, Cc, sy, sx, C.byref(h)))
+    return PreparedOp(h, (H, W, Cc), (H * sy, W * sx, Cc), dtype)
+
+
+def resize_nearest(input: Tensor4D, factors) -> Tensor4D:
+    """RESIZE_NEAREST_NEIGHBOR (TFLite builtin 97, Keras' UpSampling2D; the reference has none) by integer factors (sy, sx):
+    out[oy][ox][c] = in[oy // sy][ox // sx][c]; scale and zero point stay (include/microflow_amd.h)."""
+    shp = tuple(input.buffer.shape)
+    op = prepare_resize_nearest(shp[-3:], factors, dtype=_elem(input.buffer))
     return Tensor4D(op(input.buffer), list(input.scale), list(input.zero_point))
 
 

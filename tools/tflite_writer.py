@@ -31,6 +31,8 @@ Each layer dict (all quantization parameters are given, nothing is derived):
     mean              keep_dims (out_shape (1,1,1,C) or (1,C)), out_shape, out_q; axes (default (1, 2)), axes_const=False, axes_type
     transpose_conv    filters [N,KH,KW,C], fscale, fzp, bias int32 [N] or None (no bias operand), bscale, bzp, padding, strides (h, w),
                       act, out_shape, out_q.  Negative tests: shape_const=False (output_shape has no buffer), shape (its values)
+    resize_nearest_neighbor   out_shape, out_q (the input's, for a model that loads).  Negative tests: size (the operand's values, default
+                      out_shape's H and W), size_const=False, align_corners, half_pixel_centers, code ("resize_bilinear")
 """
 import struct
 
@@ -40,10 +42,10 @@ from make_fc_model import FB, Table, TableVec, Vec, emit, prune_2_4
 
 INT32, UINT8, INT64, INT8 = 2, 3, 4, 9
 OPCODES = {"add": 0, "average_pool_2d": 1, "concatenation": 2, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_connected": 9, "max_pool_2d": 17, "reshape": 22,
-           "softmax": 25, "pad": 34, "mean": 40, "padv2": 60, "transpose_conv": 67, "mirror_pad": 100}
+           "softmax": 25, "pad": 34, "mean": 40, "padv2": 60, "transpose_conv": 67, "mirror_pad": 100, "resize_bilinear": 23, "resize_nearest_neighbor": 97}
 # BuiltinOptions union type ids (tflite.fbs)
 OPT_TYPE = {"add": 11, "concatenation": 10, "conv_2d": 1, "depthwise_conv_2d": 2, "average_pool_2d": 5, "max_pool_2d": 5, "fully_connected": 8, "softmax": 9,
-            "reshape": 17, "pad": 22, "mean": 27, "padv2": 43, "transpose_conv": 49, "mirror_pad": 77}
+            "reshape": 17, "pad": 22, "mean": 27, "padv2": 43, "transpose_conv": 49, "mirror_pad": 77, "resize_bilinear": 15, "resize_nearest_neighbor": 74}
 ACT = {None: 0, "none": 0, "relu": 1, "relu6": 3, 0: 0, 1: 1, 3: 3}
 PAD = {"same": 0, "valid": 1, 0: 0, 1: 1}
 
@@ -160,6 +162,13 @@ def build_model(input_shape, input_q, layers, elem=INT8):
             out = add_tensor(L["out_shape"], L.get("out_type", elem), 0, *L["out_q"])
             opts = Table({})  # PadOptions {}
             ins = [cur, tp]
+        elif op == "resize_nearest_neighbor":
+            sz = np.asarray(L.get("size", L["out_shape"][1:3]), np.int32)
+            tsz = add_tensor(sz.shape, INT32, add_buffer(sz) if L.get("size_const", True) else 0, 1.0, 0)
+            out = add_tensor(L["out_shape"], L.get("out_type", elem), 0, *L["out_q"])
+            # ResizeNearestNeighborOptions { align_corners:0 half_pixel_centers:1 } (ResizeBilinearOptions: fields 2, 3)
+            opts = Table({0: ("u8", int(bool(L.get("align_corners", False)))), 1: ("u8", int(bool(L.get("half_pixel_centers", False))))})
+            ins = [cur, tsz]
         elif op == "mean":
             ax = np.asarray(L.get("axes", (1, 2)), np.int32)
             ta = add_tensor(ax.shape, L.get("axes_type", INT32), add_buffer(ax) if L.get("axes_const", True) else 0, 1.0, 0)
@@ -496,6 +505,63 @@ def conv_autoencoder(rng, input_shape, widths, k=3, elem=INT8, bias=True):
     k x k TRANSPOSE_CONVs (relu; without a bias operand when bias=False) back up to the input's size, and a final 3x3 Conv2D to the
     input's channels.  H and W must be multiples of 2^len(widths)."""
     in_q, layers = conv_autoencoder_layers(rng, input_shape, widths, k, elem, bias)
+    return build_model((1,) + tuple(input_shape), in_q, layers, elem)
+
+
+def _resize_layer(shape, q, factors):
+    """one RESIZE_NEAREST_NEIGHBOR layer dict on a tensor shape = (H, W, C) of quantisation q (which its output keeps); factors (sy, sx)"""
+    H, W, C = (int(v) for v in shape)
+    return dict(op="resize_nearest_neighbor", out_shape=(1, H * int(factors[0]), W * int(factors[1]), C), out_q=q)
+
+
+def upsample_autoencoder_layers(rng, input_shape, widths, k=3, factor=2, elem=INT8):
+    """-> (in_q, layers) of upsample_autoencoder"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    H, W, C = input_shape
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers = in_q, []
+    for n in widths:
+        layers.append(_conv_layer(rng, (H, W, C), q, False, n, k, 2, act="relu", elem=elem))
+        q, (_, H, W, C) = layers[-1]["out_q"], layers[-1]["out_shape"]
+    for n in list(widths[-2::-1]) + [widths[0]]:
+        layers.append(_resize_layer((H, W, C), q, (factor, factor)))
+        layers.append(_conv_layer(rng, layers[-1]["out_shape"][1:], q, False, n, 3, 1, act="relu", elem=elem))
+        q, (_, H, W, C) = layers[-1]["out_q"], layers[-1]["out_shape"]
+    layers.append(_conv_layer(rng, (H, W, C), q, False, input_shape[2], 3, 1, act="none", elem=elem))
+    return in_q, layers
+
+
+def upsample_autoencoder(rng, input_shape, widths, k=3, factor=2, elem=INT8):
+    """conv_autoencoder's encoder (a stride-2 k x k Conv2D, relu, per entry of `widths`) with Keras' UpSampling2D(factor) + 3x3 SAME
+    Conv2D (relu) stages as decoder -- RESIZE_NEAREST_NEIGHBOR + CONV_2D in the file -- and a final 3x3 Conv2D to the input's channels.
+    With factor 2, H and W must be multiples of 2^len(widths) for the output to have the input's size."""
+    in_q, layers = upsample_autoencoder_layers(rng, input_shape, widths, k, factor, elem)
+    return build_model((1,) + tuple(input_shape), in_q, layers, elem)
+
+
+def unet1_layers(rng, input_shape, widths, elem=INT8):
+    """-> (in_q, layers) of unet1"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    H, W, C = input_shape
+    w0, w1 = widths
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    layers = [_conv_layer(rng, (H, W, C), in_q, False, w0, 3, 1, act="relu", elem=elem)]                       # 0: the skip source
+    q0 = layers[0]["out_q"]
+    layers.append(dict(op="max_pool_2d", filter=(2, 2), padding="valid", strides=(2, 2), act="none", out_shape=(1, H // 2, W // 2, w0), out_q=q0))
+    layers.append(_conv_layer(rng, (H // 2, W // 2, w0), q0, False, w1, 3, 1, act="relu", elem=elem))
+    q = layers[-1]["out_q"]
+    layers.append(_resize_layer((H // 2, W // 2, w1), q, (2, 2)))
+    layers.append(_conv_layer(rng, (H, W, w1), q, False, w0, 3, 1, act="relu", elem=elem))
+    q = layers[-1]["out_q"]
+    layers.append(_concat_layer(0, (1, H, W, 2 * w0), q))
+    layers.append(_conv_layer(rng, (H, W, 2 * w0), q, False, C, 3, 1, act="none", elem=elem))
+    return in_q, layers
+
+
+def unet1(rng, input_shape, widths, elem=INT8):
+    """A one-level U-Net: input_shape = (H, W, C), H and W even, widths = (w0, w1).  3x3 Conv2D to w0 (relu) -> [skip] -> MaxPool2D 2x2 ->
+    3x3 Conv2D to w1 (relu) -> RESIZE_NEAREST_NEIGHBOR x2 -> 3x3 Conv2D to w0 (relu) -> CONCATENATION with the skip -> 3x3 Conv2D to C."""
+    in_q, layers = unet1_layers(rng, input_shape, widths, elem)
     return build_model((1,) + tuple(input_shape), in_q, layers, elem)
 
 
