@@ -28,14 +28,15 @@ KIND = {"average_pool_2d": 1, "conv_2d": 3, "depthwise_conv_2d": 4, "fully_conne
 
 
 class Case:
-    def __init__(self, name, shape, segments, elem=I8, wzp="none", act_scale=None, seed=0, expect=(), outcomes=(), never=(), front=None, rows=ROWS):
+    def __init__(self, name, shape, segments, elem=I8, wzp="none", act_scale=None, seed=0, expect=(), outcomes=(), never=(), front=None, rows=ROWS, interpreter=None):
         self.name, self.shape, self.segments, self.elem, self.wzp, self.act_scale = name, tuple(shape), list(segments), elem, wzp, act_scale
         self.seed, self.expect, self.outcomes, self.never, self.front, self.rows = seed, list(expect), list(outcomes), tuple(never), front, rows
+        self.interpreter = interpreter   # (tw, O, in_shape, in_q, layers, elem) -> run: maxpool_ref.segments unless the case names another
         self._model = None
 
     @property
     def contested(self):
-        return not self.expect
+        return bool(self.outcomes)
 
     def model(self):
         """(input shape, input quantisation, layer dicts): build_model's arguments.  front = a flat input shape: a Reshape to the
@@ -71,10 +72,10 @@ class Case:
 
 def expected(case, O, x=None):
     """every operator's tensor [rows, out_elems] for the rows x (the case's own by default): tests/maxpool_ref.segments -- the oracle
-    between max pools, the numpy restatement at them"""
+    between max pools, the numpy restatement at them -- or the case's own interpreter (tests/composed_graph.py: graph_ref.interpret)"""
     import tflite_writer as tw
     in_shape, in_q, layers = case.model()
-    run = R.segments(tw, O, in_shape, in_q, layers, case.elem)
+    run = (case.interpreter or R.segments)(tw, O, in_shape, in_q, layers, case.elem)
     return run(case.inputs() if x is None else x)
 
 

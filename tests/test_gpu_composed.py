@@ -15,6 +15,7 @@ from tests.conftest import ROUTING_SWITCHED
 pytestmark = pytest.mark.gpu
 
 FUSED = C.FUSED
+FUSED_SIDE = {0: "(fused into its ADD)", 2: "(fused into its CONCATENATION)"}   # join kind -> what its side operator reports inside the join's launch
 CASES = C.cases()
 IDS = [c.name for c in CASES]
 BATCHES = (1, 17, 257)
@@ -127,14 +128,19 @@ def check_batches_on_the_device(p):
 
 def check_routing_report(p):
     """the report is consistent with itself: a Reshape reports nothing and every other operator something; the first launching operator
-    is not fused into a previous one; with fusion off nothing is"""
+    is not fused into a previous one; with fusion off nothing is.  A side operator that runs inside its join's launch reports that join's
+    kind (FUSED_SIDE), no other operator does, and the join then names the launch"""
     m = p.m
     kinds = [o["kind"] for o in m.ops]
+    join_of = {m.op_skip(j)[0]: j for j, k in enumerate(kinds) if k in FUSED_SIDE}   # skip source -> its join
 
     def consistent(ns):
         first = True
         for i, (k, nm) in enumerate(zip(kinds, ns)):
             assert (nm == "") == (k == 22), (i, ns)
+            if nm in FUSED_SIDE.values():
+                j = join_of.get(i)
+                assert k == 3 and j is not None and nm == FUSED_SIDE[kinds[j]] and ns[j] not in ("", FUSED) + tuple(FUSED_SIDE.values()), (i, ns)
             if k != 22:
                 assert not (first and nm == FUSED), ns
                 first = False
@@ -146,7 +152,7 @@ def check_routing_report(p):
     finally:
         m.set_fusion(True)
     consistent(off)
-    assert FUSED not in off, off
+    assert FUSED not in off and not set(off) & set(FUSED_SIDE.values()), off
     assert names(m) == on
 
 

@@ -1079,7 +1079,20 @@ def stack_layers(rng, input_shape, segments, elem=INT8, wzp="none", act_scale=No
     tensor at that scale) with act_scale; the output zero point behind relu / relu6 is the type's minimum; a pool keeps its input's
     quantisation.  A Conv2D directly followed by a pool is conv_pool_layers' stage (without act_scale, which that form does not have).
     wzp: "none"; "conv" -- Conv2D filter zero points off the middle; "all" -- depthwise and FullyConnected ones too, as
-    inverted_residual_net(wzp_nonzero=True) and mlp(wzp_nonzero=True) draw them."""
+    inverted_residual_net(wzp_nonzero=True) and mlp(wzp_nonzero=True) draw them.
+
+    Graphs (chains with skip edges, what the library loads): a segment may end in a dict of keyword options, and there are
+        ("conv", ..., dict(dilation=(dh, dw), groups=G)) / ("dw", ..., dict(dilation=(dh, dw)))    K may be (KH, KW)
+        ("tconv", N, K, stride, padding="same", act="relu")     TRANSPOSE_CONV
+        ("resize", sy, sx)                                      RESIZE_NEAREST_NEIGHBOR
+        ("pad", ((top, bottom), (left, right)))                 PAD
+        ("mean",)                                               MEAN over H and W without keep_dims: the tensor is [1, C] behind it
+        ("mark", name)                                          names the running tensor as a skip source; "input" names the model input
+        ("add", name, act="none", dict(swap=False))             ADD of the running tensor and the marked one ([marked, running] with swap)
+        ("concat", name, dict(swap=False))                      CONCATENATION along the channels, with the running tensor's quantisation
+        ("side", name, N, K, stride=1, padding="same", act="none", dict(dilation=, groups=))
+                                                                one Conv2D on the skip edge from `name`, where the segment stands in the
+                                                                file; the next join of `name` reads its output instead of the marked tensor"""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     if wzp not in ("none", "conv", "all"):
         raise ValueError(wzp)
@@ -1089,6 +1102,21 @@ def stack_layers(rng, input_shape, segments, elem=INT8, wzp="none", act_scale=No
         in_q = (float(np.float32(act_scale)), in_q[1])
     q, layers, flat = in_q, [], None       # flat: the row length once the tensor is [1, K]
     segs = [tuple(s) for s in segments]
+    opts = [s[-1] if s and isinstance(s[-1], dict) else {} for s in segs]
+    segs = [s[:-1] if s and isinstance(s[-1], dict) else s for s in segs]
+    marks = {"input": (-1, (1, H, W, C), in_q)}   # name -> (layer whose output it is, its shape, its quantisation)
+    sides = {}                                    # name -> (the side operator's layer, its output shape, its quantisation)
+
+    def operand(name):
+        """the second operand of a join of `name`, and the side operator's entry used up"""
+        skip, shape, q_skip = sides.pop(name, None) or marks[name]
+        cur = (1, H, W, C) if flat is None else (1, flat)
+        if tuple(shape[:-1]) != cur[:-1]:
+            raise ValueError("segment %d joins %s with %s" % (i, cur, tuple(shape)))
+        return skip, tuple(shape), q_skip, cur
+
+    def side_k(k):
+        return tuple(int(v) for v in k) if isinstance(k, tuple) else int(k)
 
     def pool_args(seg):
         kind, window, stride = seg[:3]
@@ -1107,7 +1135,7 @@ def stack_layers(rng, input_shape, segments, elem=INT8, wzp="none", act_scale=No
             image()
             n, k, stride = seg[1:4]
             padding, act = (seg[4] if len(seg) > 4 else "same"), (seg[5] if len(seg) > 5 else "relu6")
-            if nxt and nxt[0] in ("avgpool", "maxpool") and act_scale is None:
+            if nxt and nxt[0] in ("avgpool", "maxpool") and act_scale is None and not opts[i]:
                 window, pstride, ppad = pool_args(nxt)
                 stage, (H, W, C), q = conv_pool_layers(rng, (H, W, C), q, int(n), int(k), stride=int(stride), padding=padding, act=act, pool=window,
                                                        pool_stride=pstride, pool_padding=ppad, elem=elem, wzp_nonzero=wzp != "none",
@@ -1115,16 +1143,60 @@ def stack_layers(rng, input_shape, segments, elem=INT8, wzp="none", act_scale=No
                 layers += stage
                 i += 2
                 continue
-            d = _conv_layer(rng, (H, W, C), q, False, n, int(k), int(stride), padding, act, elem, wzp, act_scale=act_scale)
+            d = _conv_layer(rng, (H, W, C), q, False, n, side_k(k), int(stride), padding, act, elem, wzp, act_scale=act_scale, **opts[i])
             layers.append(d)
             q, (_, H, W, C) = d["out_q"], d["out_shape"]
         elif kind == "dw":
             image()
             k, stride = seg[1:3]
-            d = _conv_layer(rng, (H, W, C), q, True, C, int(k), int(stride), "same", seg[3] if len(seg) > 3 else "relu6", elem,
-                            wzp if wzp == "all" else "none", act_scale=act_scale)
+            d = _conv_layer(rng, (H, W, C), q, True, C, side_k(k), int(stride), "same", seg[3] if len(seg) > 3 else "relu6", elem,
+                            wzp if wzp == "all" else "none", act_scale=act_scale, **opts[i])
             layers.append(d)
             q, (_, H, W, C) = d["out_q"], d["out_shape"]
+        elif kind == "tconv":
+            image()
+            n, k, stride = (int(v) for v in seg[1:4])
+            d = _tconv_layer(rng, (H, W, C), q, n, k, stride, seg[4] if len(seg) > 4 else "same", seg[5] if len(seg) > 5 else "relu", elem)
+            layers.append(d)
+            q, (_, H, W, C) = d["out_q"], d["out_shape"]
+        elif kind == "resize":
+            image()
+            layers.append(_resize_layer((H, W, C), q, seg[1:3]))
+            _, H, W, C = layers[-1]["out_shape"]
+        elif kind == "pad":
+            image()
+            layers.append(_pad_layer((H, W, C), q, seg[1]))
+            _, H, W, C = layers[-1]["out_shape"]
+        elif kind == "mean":
+            image()
+            layers.append(dict(op="mean", keep_dims=False, out_shape=(1, C), out_q=q))
+            H, W, flat = 1, 1, C
+        elif kind == "mark":
+            if any("side_of" in L for L in layers[-1:]):
+                raise ValueError("a mark behind a side segment")
+            marks[seg[1]] = (len(layers) - 1, (1, H, W, C) if flat is None else (1, flat), q)
+        elif kind == "side":
+            src, shape, q_src = marks[seg[1]]
+            if len(shape) != 4:
+                raise ValueError("a side segment on a flat tensor")
+            n, k = seg[2:4]
+            stride, padding, act = (seg[4] if len(seg) > 4 else 1), (seg[5] if len(seg) > 5 else "same"), (seg[6] if len(seg) > 6 else "none")
+            d = dict(_conv_layer(rng, shape[1:], q_src, False, n, side_k(k), int(stride), padding, act, elem, wzp, act_scale=act_scale, **opts[i]), side_of=src)
+            layers.append(d)
+            sides[seg[1]] = (len(layers) - 1, d["out_shape"], d["out_q"])
+        elif kind == "add":
+            skip, shape, q_skip, cur = operand(seg[1])
+            if shape != cur:
+                raise ValueError("segment %d adds %s to %s" % (i, shape, cur))
+            layers.append(_add_layer(rng, skip, cur, q, q_skip, seg[2] if len(seg) > 2 else "none", elem, swap=opts[i].get("swap", False)))
+            q = layers[-1]["out_q"]
+        elif kind == "concat":
+            skip, shape, q_skip, cur = operand(seg[1])
+            layers.append(_concat_layer(skip, cur[:-1] + (cur[-1] + shape[-1],), q, swap=opts[i].get("swap", False)))
+            if flat is None:
+                C += shape[-1]
+            else:
+                flat += shape[-1]
         elif kind in ("avgpool", "maxpool"):
             image()
             window, stride, padding = pool_args(seg)
