@@ -120,6 +120,7 @@ SIGNATURES = {
     "mf_op_input_elems": (C.c_size_t, [_vp]),
     "mf_op_output_elems": (C.c_size_t, [_vp]),
     "mf_op_kernel_name": (C.c_char_p, [_vp]),
+    "mf_op_kernel_name_at": (C.c_int, [_vp, C.c_size_t, C.c_char_p, C.c_size_t]),
     "mf_op_set_generic": (C.c_int, [_vp, C.c_int]),
     "mf_op_get_tile_plan": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "mf_op_destroy": (None, [_vp]),

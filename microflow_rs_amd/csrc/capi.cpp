@@ -566,6 +566,14 @@ size_t mf_op_input_elems(const mf_op *op) { return op && op->impl ? mf::op_in_el
 size_t mf_op_input2_elems(const mf_op *op) { return op && op->impl ? mf::op_in2_elems(op->impl) : 0; }
 size_t mf_op_output_elems(const mf_op *op) { return op && op->impl ? mf::op_out_elems(op->impl) : 0; }
 const char *mf_op_kernel_name(const mf_op *op) { return op && op->impl ? mf::op_kernel_name(op->impl) : ""; }
+int mf_op_kernel_name_at(const mf_op *op, size_t batch, char *buf, size_t len) {
+    MF_TRY({
+        MF_NEED(op && op->impl && buf && len > 0);
+        const std::string name = mf::op_kernel_name_at(op->impl, batch);
+        MF_NEED(name.size() < len);
+        memcpy(buf, name.c_str(), name.size() + 1);
+    })
+}
 int mf_op_get_tile_plan(const mf_op *op, int *plan) {
     MF_TRY({
         MF_NEED(op && op->impl && plan);

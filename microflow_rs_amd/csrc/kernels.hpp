@@ -837,6 +837,37 @@ bool conv_gemm_plan_pads(ConvGemmArgs &a, std::vector<int> &tap, std::vector<uin
                          int sh, int sw, int OH, int OW, int padt, int padl, bool wz); // explicit top / left pads (PAD + convolution)
 std::vector<int8_t> conv_gemm_weight_image(const int8_t *w /*[N][KH][KW][C]*/, const ConvGemmArgs &a);
 void launch_conv_gemm(const int8_t *in, int8_t *out, const ConvGemmArgs &a, bool wz, int batch, hipStream_t s);
+// Deep Conv2D (C % 128 == 0, N % 128 == 0, zero filter zero points) as a weight-streaming implicit GEMM over the output pixels of the
+// whole batch (k_conv_stream.hip: conv_stream_rt): W is the filter as stored, the rows of A are gathered by the staging DMAs, taps
+// outside the image read a line of the input zero point.  Selected per launch, from min_rows rows on (ops.hip conv_stream_selected).
+struct ConvStreamArgs {
+    int H, W, C, N, KH, KW, sh, sw, OH, OW;
+    int padt, padl;
+    int K;               // KH KW C
+    int M;               // batch OH OW: set per launch
+    int min_rows;        // the launch-time threshold of the operator's class
+    const int8_t *w;     // [N][KH][KW][C], the operator's filter as uploaded
+    const int8_t *zline; // 128 bytes of the input zero point
+    const float *A;      // [N]
+    const float *S;      // [N]
+    const int *Kc;       // [N]
+    float lo_f, hi_f;
+    int magic, xr;
+};
+struct ConvStreamSpec { // what conv_stream_plan decides on
+    int H, W, C, N, KH, KW, sh, sw, OH, OW, padt, padl;
+    int dh = 1, dw = 1, groups = 1;
+    bool depthwise = false, wz = false, finite = true;
+};
+// Thresholds by class, measured on row sweeps (profiles/r27/time_conv_stream.txt).  Filters beyond 96 KiB with C > 128: 1x1, and K x K
+// with K' >= 4096, win from the smallest swept counts on (x1.35 at 294 rows, x1.8 at 512); K x K with K' < 4096 (3x3x256: conv_gemm_rt needs few
+// slices) loses up to 1176 rows on 14x14 images and wins x1.6 at 4116.  C = 128 wins from 8192 (N = 256) or 16 384 (N = 128) rows.  Filters of at
+// most 96 KiB, resident whole in pw_rt today (1x1 stride 1), from 32 768 rows; in conv_mm_rt (strided) from 256.
+constexpr int CONV_STREAM_MIN_ROWS = 512, CONV_STREAM_MIN_ROWS_KXK_SHORT = 4096, CONV_STREAM_MIN_ROWS_C128 = 16384, CONV_STREAM_MIN_ROWS_SMALL_S1 = 32768;
+bool conv_stream_plan(ConvStreamArgs &a, const ConvStreamSpec &s); // fills the geometry and min_rows; false: outside the class
+bool conv_stream_rows_ok(const ConvStreamArgs &a, size_t rows);    // a launch of `rows` output pixels runs conv_stream_rt
+int conv_stream_tile(const ConvStreamArgs &a, size_t rows);        // ... on tiles of 256 x 256 (8 waves) or 128 x 128 (4 waves)
+void launch_conv_stream(const int8_t *in, int8_t *out, const ConvStreamArgs &a, hipStream_t s); // a.M set
 // Conv2D with dilation factors (dh, dw) != (1, 1), C % 4 == 0 (k_conv_dil.hip: conv_dil_rt): conv_gemm_rt's product -- `g` is its
 // argument block, with the same meaning field for field, and the weight image is conv_gemm_weight_image(w, g) -- on a tile whose rows
 // are staged in dw column-phase planes: plane f holds the halo-extended columns xe = x + padl with xe % dw == f, in order, C bytes each,

@@ -226,6 +226,9 @@ size_t op_in_elems(const OpImpl *op);
 size_t op_in2_elems(const OpImpl *op); // the second input of an ADD or a CONCATENATION; 0 otherwise
 size_t op_out_elems(const OpImpl *op);
 const char *op_kernel_name(const OpImpl *op);
+// the kernel a run of `batch` inferences launches (16-byte aligned buffers): op_kernel_name but for the operator that chooses per launch --
+// a deep Conv2D runs conv_stream_rt from its class's row count on (ops.hip conv_stream_selected)
+std::string op_kernel_name_at(const OpImpl *op, size_t batch);
 int op_epilogue_mode(const OpImpl *op); // k_common.hpp epilogue mode (0 .. 3) of the operator's own launch; -1: no requantising epilogue of that kind
 bool op_has_fma_epilogue(const OpImpl *op);
 int op_fma_patches(const OpImpl *op); // patched accumulators of the operator's single-fma form (0 for most); -1: no such form // the single-fma form (mode 3) was found for every channel and confirmed on the device

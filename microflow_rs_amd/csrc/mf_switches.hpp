@@ -49,7 +49,9 @@ struct Switches {
     bool no_side_concat = false;   // MF_NO_SIDE_CONCAT   a 1x1 side convolution and its CONCATENATION as two launches (the convolution's own into a fork buffer, then concat_c4), not one side_concat_rt launch (k_side_join.hip)
     bool no_pair_wz = false;       // MF_NO_PAIR_WZ       pairs with filter zero points one launch per operator (dw3x3_rt<S,wzp>, pw_rt<K,N,wzp>), not one pair_wz_rt launch (k_pair_wz.hip)
     bool no_conv_gemm = false;     // MF_NO_CONV_GEMM     Conv2D shapes outside the other Conv2D kernels take conv2d_generic, not conv_gemm_rt (k_conv_gemm.hip)
-    bool no_conv_dil = false;      // MF_NO_CONV_DIL      every Conv2D / DepthwiseConv2D with a dilation factor takes conv2d_generic / dwconv_generic, not conv_dil_rt (k_conv_dil.hip) / dw_gemm_rt
+    bool no_conv_stream = false;   // MF_NO_CONV_STREAM   deep Conv2D launches of many rows run the operator's prepare-time kernel (conv_gemm_rt, conv_mm_rt, pw_rt or conv2d_generic), never conv_stream_rt (k_conv_stream.hip)
+    int conv_stream_min_rows = 0;  // MF_CONV_STREAM_MIN_ROWS  measurements: the row count from which a launch selects conv_stream_rt, for every class (0: the measured thresholds of kernels.hpp)
+    bool no_conv_dil = false;      // MF_NO_CONV_DIL     every Conv2D / DepthwiseConv2D with a dilation factor takes conv2d_generic / dwconv_generic, not conv_dil_rt (k_conv_dil.hip) / dw_gemm_rt
     bool no_conv_grp = false;      // MF_NO_CONV_GRP      every grouped Conv2D runs as its block-diagonal dense twin on the dense routes (kernel name + "[g<G>]"), not on conv_grp_rt (k_conv_grp.hip)
     bool no_tconv = false;         // MF_NO_TCONV         every TRANSPOSE_CONV takes tconv_generic, not tconv_phase_rt (k_tconv.hip)
     bool no_dw_gemm = false;       // MF_NO_DW_GEMM       DepthwiseConv2D shapes outside the other depthwise kernels take dwconv_generic, not dw_gemm_rt / conv_gemm_rt<dw> (k_dw_gemm.hip)

@@ -765,6 +765,29 @@ const Route TABLE_ROUTES[] = {route_dw_table, route_dw_stem, route_dw_stem_rt, r
 const Route RT_ROUTES[] = {route_dw_rt, route_pw_rt, route_conv_rows, route_dw_mm, route_dw_gemm, route_conv_mm, route_conv1x1_row,
                            route_conv_gemm, route_conv_dil, route_conv_grp}; // each one, in turn
 
+// A deep Conv2D whose route ended at conv_gemm_rt, conv_mm_rt or pw_rt (zero filter zero points) or on conv2d_generic additionally gets the arguments of
+// conv_stream_rt (k_conv_stream.hip): the weight-streaming GEMM over the output pixels of the whole batch, which a LAUNCH of at least
+// cst.min_rows rows runs instead (conv_stream_selected below).  The operator's kernel label stays the prepare-time one, as it does
+// for fc_mfma below 64 rows; op_kernel_name_at tells what a given batch launches.  Operands: the filter as uploaded (d_w: OHWI is
+// the GEMM's [N][K']), the operator's own constants (d_A, d_S, d_Kc) and epilogue mode.
+void prepare_conv_stream(OpImpl &op, const OpSpec &s, bool dw) {
+    if (switches().no_conv_stream || switches().no_rt) return;
+    // (the 1x1 filters of the class that fit conv_mm_rt's / pw_rt's 96 KiB of resident weights end on those routes: the same choice)
+    const bool dense_rt = op.fast == OpImpl::CONV_GEMM || (op.fast == OpImpl::CONV_MM && !op.cmm.dwise) || op.fast == OpImpl::PW_RT;
+    if (!(op.fast == OpImpl::NONE || (dense_rt && !op.rt_wz))) return;
+    k::ConvStreamSpec sp{s.H, s.W, s.C, s.N, s.KH, s.KW, s.sh, s.sw, s.OH, s.OW, s.pad == MF_PAD_SAME ? (s.KH - 1) / 2 : 0, s.pad == MF_PAD_SAME ? (s.KW - 1) / 2 : 0};
+    sp.dh = s.dh, sp.dw = s.dw, sp.groups = s.groups, sp.depthwise = dw, sp.wz = !all_zero(op.h_wzp), sp.finite = op.finite_consts;
+    k::ConvStreamArgs &f = op.cst;
+    if (!k::conv_stream_plan(f, sp)) return;
+    const std::vector<int8_t> line(128, (int8_t)s.izp);
+    op.d_zline.upload(line.data(), line.size());
+    f.w = op.conv.w, f.zline = op.d_zline.as<int8_t>(), f.A = op.conv.A, f.S = op.conv.S, f.Kc = op.conv.Kc;
+    f.lo_f = op.conv.lo_f, f.hi_f = op.conv.hi_f, f.magic = op.magic_mode, f.xr = op.conv.xr;
+    op.cst_ok = true;
+    if (switches().verbose)
+        fprintf(stderr, "[microflow_amd] conv_stream_rt %dx%dx%d -> %d %dx%d: K' %d, launches of >= %d rows\n", s.H, s.W, s.C, s.N, s.KH, s.KW, f.K, f.min_rows);
+}
+
 void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
     const bool dw = s.kind == MF_OP_DEPTHWISE_CONV_2D;
     if (s.H <= 0 || s.W <= 0 || s.C <= 0 || s.N <= 0 || s.KH <= 0 || s.KW <= 0 || s.OH <= 0 ||
@@ -854,6 +877,7 @@ void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
         }
     }
     op.fast_name += op.grp_note, op.generic_name += op.grp_note;
+    prepare_conv_stream(op, s, dw);
     if (op.fma_ok) { // the single-fma constants beside the two-rounding ones, in the blocks of the kernels that have the form
         op.dwf.A3 = op.pw.A3 = op.d_A3.as<float>(), op.dwf.S3 = op.pw.S3 = op.d_S3.as<float>();
         op.dwf.Kc3 = op.pw.Kc3 = op.d_Kc3.as<int>();
@@ -1232,6 +1256,15 @@ const char *op_kernel_name(const OpImpl *op) {
                                                              : op->generic_name.c_str();
 }
 void op_set_generic(OpImpl *op, bool g) { op->force_generic = g; }
+// The run-time choices of op_run.  A deep Conv2D (prepare_conv_stream) launched on at least cst.min_rows output pixels runs
+// conv_stream_rt, whatever its prepare-time route was.
+static bool conv_stream_selected(const OpImpl *op, size_t batch) {
+    return op->cst_ok && !op->force_generic && batch <= 0x7fffffffull / 4 && k::conv_stream_rows_ok(op->cst, batch * (size_t)op->s.OH * op->s.OW);
+}
+std::string op_kernel_name_at(const OpImpl *op, size_t batch) {
+    if (conv_stream_selected(op, batch)) return "conv_stream_rt<" + std::to_string(k::conv_stream_tile(op->cst, batch * (size_t)op->s.OH * op->s.OW)) + ">";
+    return op_kernel_name(op);
+}
 bool op_tile_plan(const OpImpl *op, int plan[8]) {
     auto put = [&](int planes, int pitch, int row, int rb, int nbands, int bh, int g, int nsl) {
         const int v[8] = {planes, pitch, row, rb, nbands, bh, g, nsl};
@@ -1261,6 +1294,12 @@ int op_epilogue_mode(const OpImpl *op) { // of the operator's own (layer-wise) l
 bool op_has_fma_epilogue(const OpImpl *op) { return op->fma_ok; }
 int op_fma_patches(const OpImpl *op) { return op->fma_ok ? op->fma_patch.n : -1; }
 
+static void run_conv_stream(const OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, hipStream_t s) {
+    k::ConvStreamArgs a = op->cst;
+    a.M = (int)(batch * (size_t)op->s.OH * op->s.OW); // (conv_stream_rows_ok: at most 2^30)
+    k::launch_conv_stream(d_in, d_out, a, s);
+}
+
 void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream) {
     if (!batch) return;
     if (!d_in || !d_out) fail(MF_ERR_INVALID_ARG, "op_run: null device pointer");
@@ -1275,7 +1314,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
     bool done = false;
     if (fast) {
         if (batch > 0x7fffffffull / 4) fail(MF_ERR_INVALID_ARG, "batch too large for one launch");
-        switch (op->fast) {
+        if (conv_stream_selected(op, batch)) { // (a deep Conv2D on conv_gemm_rt, conv_mm_rt or pw_rt, launched on many rows)
+            run_conv_stream(op, d_in, batch, d_out, s);
+            done = true;
+        } else switch (op->fast) {
         case OpImpl::DW_NHWC: {
             k::DwFastArgs f3 = op->dwf;
             const bool fma = op_runs_fma(op) && f3.use_fma();
@@ -1430,6 +1472,7 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
         switch (sp.kind) {
         case MF_OP_CONV_2D:
             if (sp.upsampled()) k::launch_upconv_generic(d_in, d_out, op->conv, sp.up_h, sp.up_w, batch, s);
+            else if (op->fast == OpImpl::NONE && aligned && conv_stream_selected(op, batch)) run_conv_stream(op, d_in, batch, d_out, s); // (K' beyond conv_gemm_rt's limit)
             else k::launch_conv2d_generic(d_in, d_out, op->conv, batch, s);
             break;
         case MF_OP_RESIZE_NEAREST_NEIGHBOR: k::launch_resize_generic(d_in, d_out, op->rsz, batch, s); break;

@@ -146,6 +146,9 @@ struct OpImpl {
     DevBuf d_tap;          // conv_mm_rt: tap offset table
     k::ConvGemmArgs cgm{}; // Conv2D of any C and N on the matrix pipe (k_conv_gemm.hip); tap table in d_tap, image in d_fcw,
     DevBuf d_cgm_mask;     // ... constants padded to 16-column tiles in d_rtA, d_rtS, d_rtKc, d_rtwzp; window-sum byte masks
+    k::ConvStreamArgs cst{}; // deep Conv2D as a weight-streaming GEMM (k_conv_stream.hip), beside the prepare-time route (conv_gemm_rt, conv_mm_rt, pw_rt or none): the
+    bool cst_ok = false;     // ... kernel of a LAUNCH of at least cst.min_rows rows (ops.hip conv_stream_selected); filter in d_w, constants d_A, d_S, d_Kc
+    DevBuf d_zline;          // ... its 128-byte line of the input zero point
     k::DwGemmArgs dwg{};   // DepthwiseConv2D of any C on the matrix pipe (k_dw_gemm.hip); operand A in d_wprep, constants as cgm's
     k::ConvDilArgs cdl{};  // Conv2D with dilation factors in column-phase planes (k_conv_dil.hip); image, tables, masks and constants as cgm's
     k::ConvGrpArgs cgp{};  // grouped Conv2D (k_conv_grp.hip); image in d_fcw, k dword table in d_tap, per-tile-column constants as cgm's, the column map in d_colch

@@ -82,6 +82,8 @@ Switches switches_parse() {
     s.no_side_concat = env_set("MF_NO_SIDE_CONCAT");
     s.pair_wz_gmul = (int)env_ll("MF_PAIR_WZ_GMUL", 2);
     s.no_conv_gemm = env_set("MF_NO_CONV_GEMM");
+    s.no_conv_stream = env_set("MF_NO_CONV_STREAM");
+    s.conv_stream_min_rows = (int)env_ll("MF_CONV_STREAM_MIN_ROWS", 0);
     s.no_conv_dil = env_set("MF_NO_CONV_DIL");
     s.no_conv_grp = env_set("MF_NO_CONV_GRP");
     s.no_tconv = env_set("MF_NO_TCONV");

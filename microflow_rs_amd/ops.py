@@ -107,6 +107,12 @@ class PreparedOp:
     def kernel(self):
         return _lib.lib().mf_op_kernel_name(self._h).decode()
 
+    def kernel_at(self, batch):
+        """the kernel a run of `batch` inferences launches (mf_op_kernel_name_at): `kernel`, but for the operators that choose per launch"""
+        buf = C.create_string_buffer(128)
+        _lib.check(_lib.lib().mf_op_kernel_name_at(self._h, int(batch), buf, len(buf)))
+        return buf.value.decode()
+
     def tile_plan(self):
         """dict(planes, pitch, row, rows, bands, band_rows, images, slices) of a conv_dil_rt / conv_grp_rt / conv_gemm_rt / dw_gemm_rt operator
         (mf_op_get_tile_plan); MicroflowError for an operator on another kernel"""
