@@ -868,6 +868,16 @@ bool conv_stream_plan(ConvStreamArgs &a, const ConvStreamSpec &s); // fills the 
 bool conv_stream_rows_ok(const ConvStreamArgs &a, size_t rows);    // a launch of `rows` output pixels runs conv_stream_rt
 int conv_stream_tile(const ConvStreamArgs &a, size_t rows);        // ... on tiles of 256 x 256 (8 waves) or 128 x 128 (4 waves)
 void launch_conv_stream(const int8_t *in, int8_t *out, const ConvStreamArgs &a, hipStream_t s); // a.M set
+// The same product with a 2:4-sparse filter (fc_sparse24_eligible on the [N][K'] bytes) on v_smfmac_i32_16x16x128_i8
+// (k_conv_stream_sparse.hip: conv_stream_sp24): ConvStreamArgs::w = fc_sparse24_image of the filter, everything else as above.  A launch
+// that selects conv_stream_rt takes it from the class's row count on; 0: the class stays on conv_stream_rt.  Measured against the parent
+// build on the same pruned filters (profiles/r28/time_conv_sparse.txt): K x K filters win beyond the spread from 256
+// (3x3x128 -> 128), 2048 (3x3x512 -> 512) and 4096 rows (3x3x256 -> 256) on and keep winning -- x1.01 - x1.06 up to 8192 rows, x1.14 -
+// x1.42 from 16 384 --, so the class takes the largest of the three; both swept 1x1 filters win from the smallest swept count (294 rows,
+// x1.02 - x1.04; x1.10 - x1.36 from 4116).  No class is excluded.
+constexpr int CONV_SPARSE_MIN_ROWS_KXK = 4096, CONV_SPARSE_MIN_ROWS_1X1 = 256;
+int conv_stream_sp24_min_rows(const ConvStreamArgs &a); // from how many rows a launch runs conv_stream_sp24 (at least a.min_rows); 0: never
+void launch_conv_stream_sp24(const int8_t *in, int8_t *out, const ConvStreamArgs &a, hipStream_t s); // a.w the image, a.M set
 // Conv2D with dilation factors (dh, dw) != (1, 1), C % 4 == 0 (k_conv_dil.hip: conv_dil_rt): conv_gemm_rt's product -- `g` is its
 // argument block, with the same meaning field for field, and the weight image is conv_gemm_weight_image(w, g) -- on a tile whose rows
 // are staged in dw column-phase planes: plane f holds the halo-extended columns xe = x + padl with xe % dw == f, in order, C bytes each,

@@ -51,6 +51,8 @@ struct Switches {
     bool no_conv_gemm = false;     // MF_NO_CONV_GEMM     Conv2D shapes outside the other Conv2D kernels take conv2d_generic, not conv_gemm_rt (k_conv_gemm.hip)
     bool no_conv_stream = false;   // MF_NO_CONV_STREAM   deep Conv2D launches of many rows run the operator's prepare-time kernel (conv_gemm_rt, conv_mm_rt, pw_rt or conv2d_generic), never conv_stream_rt (k_conv_stream.hip)
     int conv_stream_min_rows = 0;  // MF_CONV_STREAM_MIN_ROWS  measurements: the row count from which a launch selects conv_stream_rt, for every class (0: the measured thresholds of kernels.hpp)
+    bool no_conv_sparse = false;   // MF_NO_CONV_SPARSE   deep Conv2D launches with a 2:4-sparse filter run conv_stream_rt on the dense filter, never conv_stream_sp24 (k_conv_stream_sparse.hip)
+    bool conv_sparse_all = false;  // MF_CONV_SPARSE_ALL  measurements (scripts/time_conv_sparse.py sweeps below the thresholds with it): every 2:4-sparse launch that selects conv_stream_rt runs conv_stream_sp24, whatever the class's own row count; no class is excluded today, so it only moves K x K launches below 4096 rows
     bool no_conv_dil = false;      // MF_NO_CONV_DIL     every Conv2D / DepthwiseConv2D with a dilation factor takes conv2d_generic / dwconv_generic, not conv_dil_rt (k_conv_dil.hip) / dw_gemm_rt
     bool no_conv_grp = false;      // MF_NO_CONV_GRP      every grouped Conv2D runs as its block-diagonal dense twin on the dense routes (kernel name + "[g<G>]"), not on conv_grp_rt (k_conv_grp.hip)
     bool no_tconv = false;         // MF_NO_TCONV         every TRANSPOSE_CONV takes tconv_generic, not tconv_phase_rt (k_tconv.hip)

@@ -786,6 +786,15 @@ void prepare_conv_stream(OpImpl &op, const OpSpec &s, bool dw) {
     op.cst_ok = true;
     if (switches().verbose)
         fprintf(stderr, "[microflow_amd] conv_stream_rt %dx%dx%d -> %d %dx%d: K' %d, launches of >= %d rows\n", s.H, s.W, s.C, s.N, s.KH, s.KW, f.K, f.min_rows);
+    // A 2:4-sparse filter (judged on the stored bytes in the i8 domain, as for FullyConnected) additionally gets its compressed image:
+    // such launches run conv_stream_sp24 (k_conv_stream_sparse.hip) from the class's measured row count on.  The dense filter stays for
+    // the launches below it and for set_generic.
+    if (switches().no_conv_sparse || !k::fc_sparse24_eligible(s.weights, s.N, f.K)) return;
+    op.cst_sp_rows = k::conv_stream_sp24_min_rows(f);
+    if (!op.cst_sp_rows) return;
+    const std::vector<int8_t> img = k::fc_sparse24_image(s.weights, s.N, f.K);
+    op.d_cst_sp24.upload(img.data(), img.size());
+    if (switches().verbose) fprintf(stderr, "[microflow_amd] ... 2:4-sparse filter: conv_stream_sp24 for launches of >= %d rows\n", op.cst_sp_rows);
 }
 
 void create_conv(OpImpl &op, OpSpec &s, I8Domain &dom, int lo, int hi, int xr) {
@@ -1261,7 +1270,12 @@ void op_set_generic(OpImpl *op, bool g) { op->force_generic = g; }
 static bool conv_stream_selected(const OpImpl *op, size_t batch) {
     return op->cst_ok && !op->force_generic && batch <= 0x7fffffffull / 4 && k::conv_stream_rows_ok(op->cst, batch * (size_t)op->s.OH * op->s.OW);
 }
+// ... and conv_stream_sp24 where the filter is 2:4-sparse and the class's measured row count is reached (prepare_conv_stream)
+static bool conv_stream_sparse_selected(const OpImpl *op, size_t batch) {
+    return op->cst_sp_rows > 0 && conv_stream_selected(op, batch) && batch * (size_t)op->s.OH * op->s.OW >= (size_t)op->cst_sp_rows;
+}
 std::string op_kernel_name_at(const OpImpl *op, size_t batch) {
+    if (conv_stream_sparse_selected(op, batch)) return "conv_stream_sp24<" + std::to_string(k::conv_stream_tile(op->cst, batch * (size_t)op->s.OH * op->s.OW)) + ">";
     if (conv_stream_selected(op, batch)) return "conv_stream_rt<" + std::to_string(k::conv_stream_tile(op->cst, batch * (size_t)op->s.OH * op->s.OW)) + ">";
     return op_kernel_name(op);
 }
@@ -1297,7 +1311,10 @@ int op_fma_patches(const OpImpl *op) { return op->fma_ok ? op->fma_patch.n : -1;
 static void run_conv_stream(const OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, hipStream_t s) {
     k::ConvStreamArgs a = op->cst;
     a.M = (int)(batch * (size_t)op->s.OH * op->s.OW); // (conv_stream_rows_ok: at most 2^30)
-    k::launch_conv_stream(d_in, d_out, a, s);
+    if (conv_stream_sparse_selected(op, batch)) {
+        a.w = op->d_cst_sp24.as<int8_t>();
+        k::launch_conv_stream_sp24(d_in, d_out, a, s);
+    } else k::launch_conv_stream(d_in, d_out, a, s);
 }
 
 void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *stream) {

@@ -149,6 +149,8 @@ struct OpImpl {
     k::ConvStreamArgs cst{}; // deep Conv2D as a weight-streaming GEMM (k_conv_stream.hip), beside the prepare-time route (conv_gemm_rt, conv_mm_rt, pw_rt or none): the
     bool cst_ok = false;     // ... kernel of a LAUNCH of at least cst.min_rows rows (ops.hip conv_stream_selected); filter in d_w, constants d_A, d_S, d_Kc
     DevBuf d_zline;          // ... its 128-byte line of the input zero point
+    DevBuf d_cst_sp24;       // ... a 2:4-sparse filter's compressed image (fc_sparse24_image of the [N][K'] bytes), beside the dense filter in d_w
+    int cst_sp_rows = 0;     // ... and the row count from which such a launch runs conv_stream_sp24 instead (k_conv_stream_sparse.hip); 0: never
     k::DwGemmArgs dwg{};   // DepthwiseConv2D of any C on the matrix pipe (k_dw_gemm.hip); operand A in d_wprep, constants as cgm's
     k::ConvDilArgs cdl{};  // Conv2D with dilation factors in column-phase planes (k_conv_dil.hip); image, tables, masks and constants as cgm's
     k::ConvGrpArgs cgp{};  // grouped Conv2D (k_conv_grp.hip); image in d_fcw, k dword table in d_tap, per-tile-column constants as cgm's, the column map in d_colch

@@ -84,6 +84,8 @@ Switches switches_parse() {
     s.no_conv_gemm = env_set("MF_NO_CONV_GEMM");
     s.no_conv_stream = env_set("MF_NO_CONV_STREAM");
     s.conv_stream_min_rows = (int)env_ll("MF_CONV_STREAM_MIN_ROWS", 0);
+    s.no_conv_sparse = env_set("MF_NO_CONV_SPARSE");
+    s.conv_sparse_all = env_set("MF_CONV_SPARSE_ALL");
     s.no_conv_dil = env_set("MF_NO_CONV_DIL");
     s.no_conv_grp = env_set("MF_NO_CONV_GRP");
     s.no_tconv = env_set("MF_NO_TCONV");

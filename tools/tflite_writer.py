@@ -394,7 +394,7 @@ def pool_head(rng, shape, sizes, elem=INT8, wzp_nonzero=False, softmax=False, sa
     return build_model((1, H, W, C), in_q, layers, elem)
 
 
-def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, wmax=None, in_zp=None, act_scale=None):
+def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, wmax=None, in_zp=None, act_scale=None, prune24=()):
     """A convolution stack: input_shape = (H, W, C); convs = [(op, N, K, stride), ...] with op "conv" (KxK Conv2D to N channels)
     or "dw" (KxK depthwise, N ignored), all SAME, relu6; per-channel filter quantization, filter zero points off the middle when
     wzp_nonzero (Conv2D only: the depthwise kernels keep theirs at the middle).  head = classes: AveragePool over the whole
@@ -403,7 +403,8 @@ def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, w
     the epilogue form); `in_zp`: the input's zero point (None: a random one; every later tensor's is the type's minimum);
     `act_scale`: every tensor, the input included, has this scale (6 / 255: relu6 is then the type's whole range, as in
     person_detect.tflite) and the filter scales are person_detect_like's, which keep the activations of a deep stack spread over it --
-    the default's growing output scales leave relu6 a few dozen levels after a few layers."""
+    the default's growing output scales leave relu6 a few dozen levels after a few layers.  `prune24`: indices of Conv2D layers whose
+    filters are pruned to 2:4 sparsity (_conv_layer)."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     H, W, C = input_shape
@@ -413,8 +414,9 @@ def conv_net(rng, input_shape, convs, elem=INT8, wzp_nonzero=False, head=None, w
     if act_scale is not None:
         in_q = (float(np.float32(act_scale)), in_q[1])
     q, layers = in_q, []
-    for op, n, k, s in convs:
-        d = _conv_layer(rng, (H, W, C), q, op == "dw", n, k, s, elem=elem, wzp="conv" if wzp_nonzero else "none", wmax=wmax, act_scale=act_scale)
+    for i, (op, n, k, s) in enumerate(convs):
+        d = _conv_layer(rng, (H, W, C), q, op == "dw", n, k, s, elem=elem, wzp="conv" if wzp_nonzero else "none", wmax=wmax, act_scale=act_scale,
+                        prune24=i in prune24)
         layers.append(d)
         q, (_, H, W, C) = d["out_q"], d["out_shape"]
     if head:
@@ -434,14 +436,16 @@ def _same_or_valid(size, k, s, padding):
     return -(-size // s) if padding == "same" else (size - k) // s + 1
 
 
-def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", elem=INT8, wzp="none", wmax=None, act_scale=None, dilation=(1, 1), groups=1):
+def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", elem=INT8, wzp="none", wmax=None, act_scale=None, dilation=(1, 1), groups=1, prune24=False):
     """conv_net's per-layer form, one layer dict: a k x k Conv2D to n channels, or (dw) a k x k depthwise, on a tensor shape = (H, W, C)
     of quantisation q; per-channel filter quantisation; the output scale keeps the outputs spread, or is act_scale with
     person_detect_like's filter scales; the output zero point is the type's minimum behind relu / relu6 and a random one without an
     activation.  wzp: filter zero points off the middle -- "conv": Conv2D only, conv_net's draw; "all": the depthwise ones too, both
     with inverted_residual_net's draw, which never lands on the middle.  k: the filter side, or (KH, KW); dilation: (dh, dw), written into
     the options where it is not (1, 1), the output sized from the effective extent (k - 1) d + 1.  groups: a grouped Conv2D as the converter writes
-    Keras' Conv2D(groups=G): filters [n][k][k][C / groups], the group count implicit in the shapes."""
+    Keras' Conv2D(groups=G): filters [n][k][k][C / groups], the group count implicit in the shapes.  prune24: a Conv2D's filter pruned to 2:4
+    sparsity along (ky, kx, c) in the int8 domain (make_fc_model.prune_2_4), as a pruning pass followed by quantisation leaves it;
+    C % 4 == 0, filter zero points at the middle."""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     mid = (lo + hi) // 2
     H, W, C = (int(v) for v in shape)
@@ -467,6 +471,9 @@ def _conv_layer(rng, shape, q, dw, n, k, stride, padding="same", act="relu6", el
         d["dilation"] = (int(dilation[0]), int(dilation[1]))
     wshape = (1, kh, kw, n) if dw else (n, kh, kw, C // groups)
     d["weights" if dw else "filters"] = rng.integers(lo, hi, wshape) if wmax is None else rng.integers(mid - wmax, mid + wmax + 1, wshape)
+    if prune24:
+        assert not dw and wzp == "none" and (C // groups) % 4 == 0
+        d["filters"] = prune_2_4((d["filters"] - mid).astype(np.int8)).astype(np.int64) + mid
     return d
 
 
