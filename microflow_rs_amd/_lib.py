@@ -19,6 +19,7 @@ MF_OP_CONCATENATION = 2
 MF_OP_PAD, MF_OP_MEAN = 34, 40   # (not in the reference: include/microflow_amd.h mf_pad_create)
 MF_OP_TRANSPOSE_CONV = 67   # (not in the reference: include/microflow_amd.h mf_transpose_conv_create)
 MF_OP_RESIZE_NEAREST_NEIGHBOR = 97   # (not in the reference: include/microflow_amd.h mf_resize_nearest_create)
+MF_OP_RESIZE_BILINEAR = 23   # (not in the reference: include/microflow_amd.h mf_resize_bilinear_create)
 STATUS_NAMES = {0: "MF_OK", 1: "MF_ERR_INVALID_MODEL", 2: "MF_ERR_UNSUPPORTED",
                 3: "MF_ERR_INVALID_ARG", 4: "MF_ERR_NO_DEVICE", 5: "MF_ERR_HIP", 6: "MF_ERR_OOM"}
 
@@ -95,6 +96,7 @@ SIGNATURES = {
     "mf_conv_2d_upsampled_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
                                     [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),  # (+ up_h, up_w)
     "mf_resize_nearest_create": (C.c_int, [C.c_int] * 6 + [C.POINTER(_vp)]),
+    "mf_resize_bilinear_create": (C.c_int, [C.c_int] * 6 + [C.POINTER(_vp)]),
     "mf_depthwise_conv_2d_dilated_create": (C.c_int, [C.c_int] * 7 + [_vp, _vp, C.c_int, C.c_int8, C.c_float, C.c_int8] + [C.c_int] * 6 +
                                             [_vp, _vp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "mf_average_pool_2d_create": (C.c_int, [C.c_int] * 6 + [C.c_float, C.c_int8, C.c_int, C.c_int,
@@ -184,7 +186,7 @@ SIGNATURES = {
 for _n in ("mf_preprocess_fully_connected", "mf_preprocess_average_pool_2d",
            "mf_fully_connected_create", "mf_conv_2d_create", "mf_transpose_conv_create", "mf_depthwise_conv_2d_create",
            "mf_conv_2d_dilated_create", "mf_depthwise_conv_2d_dilated_create", "mf_conv_2d_grouped_create", "mf_conv_2d_upsampled_create",
-           "mf_average_pool_2d_create", "mf_max_pool_2d_create", "mf_add_create", "mf_concatenation_create", "mf_pad_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
+           "mf_average_pool_2d_create", "mf_max_pool_2d_create", "mf_add_create", "mf_concatenation_create", "mf_pad_create", "mf_resize_bilinear_create", "mf_softmax_create", "mf_quantize", "mf_dequantize",
            "mf_window_gather_quantize"):
     _r, _a = SIGNATURES[_n]
     SIGNATURES[_n + "_u8"] = (_r, [C.c_uint8 if t is C.c_int8 else t for t in _a])

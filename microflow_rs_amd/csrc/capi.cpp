@@ -521,6 +521,24 @@ int mf_resize_nearest_create(int device, int H, int W, int C, int sy, int sx, mf
     })
 }
 
+// RESIZE_BILINEAR by integer factors, half-pixel centres (include/microflow_amd.h: the library's own contract).  The rounding is on the
+// value as T, so the element type gets an entry each
+static void create_resize_bilinear(int device, bool u8, int H, int W, int C, int sy, int sx, mf_op **op) {
+    MF_NEED(op);
+    if (H <= 0 || W <= 0 || C <= 0 || sy < 1 || sx < 1 || (long long)H * sy > (1 << 24) || (long long)W * sx > (1 << 24))
+        mf::fail(MF_ERR_INVALID_ARG, "resize_bilinear: bad arguments");
+    mf::OpSpec s;
+    s.kind = MF_OP_RESIZE_BILINEAR, s.u8 = u8;
+    s.H = H, s.W = W, s.C = C, s.N = C, s.up_h = sy, s.up_w = sx, s.OH = H * sy, s.OW = W * sx;
+    wrap_op(mf::op_create(device, s), op);
+}
+int mf_resize_bilinear_create(int device, int H, int W, int C, int sy, int sx, mf_op **op) {
+    MF_TRY({ create_resize_bilinear(device, false, H, W, C, sy, sx, op); })
+}
+int mf_resize_bilinear_create_u8(int device, int H, int W, int C, int sy, int sx, mf_op **op) {
+    MF_TRY({ create_resize_bilinear(device, true, H, W, C, sy, sx, op); })
+}
+
 // CONCATENATION (include/microflow_amd.h: the library's own contract).  Bad scales are a bad argument whether or not there is a device
 static void create_concatenation(int device, bool u8, size_t rows, int Ca, int Cb, float sa, int za, float sb, int zb, float so, int zo,
                                  float ca, float cb, mf_op **op) {
@@ -693,7 +711,7 @@ int mf_model_get_op_upsample(const mf_model *model, int index, int *sy, int *sx)
         MF_NEED(model && model->impl && sy && sx);
         const mf::ParsedModel &pm = mf::model_parsed(model->impl);
         MF_NEED(index >= 0 && index < (int)pm.ops.size());
-        MF_NEED(pm.ops[(size_t)index].kind == MF_OP_RESIZE_NEAREST_NEIGHBOR);
+        MF_NEED(pm.ops[(size_t)index].kind == MF_OP_RESIZE_NEAREST_NEIGHBOR || pm.ops[(size_t)index].kind == MF_OP_RESIZE_BILINEAR);
         *sy = pm.ops[(size_t)index].up_h, *sx = pm.ops[(size_t)index].up_w;
     })
 }

@@ -921,6 +921,24 @@ struct ResizeArgs {
 // unit = 16: C % 16 == 0, pointers 16-byte aligned): every source word loaded once, stored sy sx times from registers, no LDS
 void launch_resize_generic(const int8_t *in, int8_t *out, const ResizeArgs &a, size_t batch, hipStream_t s);
 void launch_resize_c4(const int8_t *in, int8_t *out, const ResizeArgs &a, size_t batch, int unit, hipStream_t s);
+// RESIZE_BILINEAR by integer factors, half-pixel centres (k_resize_bilinear.hip; the contract: include/microflow_amd.h
+// mf_resize_bilinear_create).  resize_bl_generic: ResizeArgs, any shape, factors and pointers, one output byte per thread.
+// resize_bl_c4: C % 4 == 0, 1 <= sy, sx <= 4 (not both 1), pointers 16-byte aligned; a step is G whole images or one band of BH source
+// rows of one image, staged in LDS with a clamped row above and below and a clamped pixel left and right of every row.
+struct ResizeBlArgs {
+    int H, W, C, sy, sx;
+    int u8;              // round on the unsigned value (half up); 0: on the signed one (half away from zero)
+    int unit;            // bytes per word: 16 (C % 16 == 0) or 4
+    int wpp, wpr;        // words per pixel and per source row
+    int ROWB, ROWP;      // bytes of a source row; pitch of a tile row: (W + 2) C rounded up to 16
+    int RB, TILE;        // tile rows per image (BH + 2) and their bytes
+    int NBANDS, BH, G;   // row bands per image, source rows per band, images per step (G > 1 only with NBANDS == 1)
+    int lds;             // G * TILE
+    uint32_t m_wpr, m_bh, m_wpp; // ceil(2^32 / d): i / d == umulhi(i, m) for i, d < 2^16 (a step has fewer than 2^16 cells)
+};
+bool resize_bl_plan(ResizeBlArgs &a, int H, int W, int C, int sy, int sx, bool u8); // false: outside the class, or three tile rows exceed the LDS budget
+void launch_resize_bl(const int8_t *in, int8_t *out, const ResizeBlArgs &a, size_t batch, hipStream_t s);
+void launch_resize_bl_generic(const int8_t *in, int8_t *out, const ResizeArgs &a, bool u8, size_t batch, hipStream_t s);
 // RESIZE_NEAREST_NEIGHBOR by (sy, sx) + stride-1 Conv2D on its result as one product on the matrix pipe (k_upconv.hip: upconv_rt).  `g` is
 // conv_gemm_rt's argument block with the same meaning field for field -- H, W are the SOURCE image's, OH, OW, padt, padl the convolution's
 // on the sy H x sx W upsampled image; the weight image is conv_gemm_weight_image(w, g), the constants conv_gemm_rt's -- but the staged tile

@@ -129,7 +129,7 @@ struct ParsedOp {
     bool side() const { return side_src != -2; }
     // PAD only: new rows / columns (top, bottom, left, right); H, W, C the input, OH, OW the output
     int pads[4] = {0, 0, 0, 0};
-    // RESIZE_NEAREST_NEIGHBOR only: the integer factors (OH = up_h H, OW = up_w W)
+    // RESIZE_NEAREST_NEIGHBOR and RESIZE_BILINEAR only: the integer factors (OH = up_h H, OW = up_w W)
     int up_h = 1, up_w = 1;
     // what mf_model_get_op reports as the kind: the file's.  A MEAN over {1, 2} is parsed into a global AveragePool2D (kind), so that
     // every rule that matches one sees it, and reports MF_OP_MEAN; -1: kind

@@ -117,7 +117,7 @@ static OpSpec op_spec(const ParsedModel &pm, const ParsedOp &po, float cur_scale
     if (po.join()) s.join_za = po.a_zp, s.join_zb = po.b_zp, s.join_ca = po.c0[0], s.join_cb = po.c1[0];
     if (po.kind == MF_OP_PAD)
         for (int k = 0; k < 4; ++k) s.pads[k] = po.pads[k];
-    if (po.kind == MF_OP_RESIZE_NEAREST_NEIGHBOR) s.up_h = po.up_h, s.up_w = po.up_w;
+    if (po.kind == MF_OP_RESIZE_NEAREST_NEIGHBOR || po.kind == MF_OP_RESIZE_BILINEAR) s.up_h = po.up_h, s.up_w = po.up_w; // (no rule groups a RESIZE_BILINEAR: it runs layer-wise)
     return s;
 }
 

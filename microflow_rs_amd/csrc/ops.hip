@@ -1152,6 +1152,20 @@ void create_resize(OpImpl &op, const OpSpec &s) {
     }
 }
 
+// RESIZE_BILINEAR (include/microflow_amd.h mf_resize_bilinear_create): no weights, no constants; the zero point never enters (the
+// weights sum to the divisor), the element type does: the one rounding is on the value as T
+void create_resize_bilinear(OpImpl &op, const OpSpec &s) {
+    if (s.H <= 0 || s.W <= 0 || s.C <= 0 || s.up_h < 1 || s.up_w < 1) fail(MF_ERR_INVALID_ARG, "resize_bilinear: bad arguments");
+    const long long OH = (long long)s.H * s.up_h, OW = (long long)s.W * s.up_w;
+    if (OH != s.OH || OW != s.OW || OH > (1 << 24) || OW > (1 << 24) || OW * s.C > 0x7fffffffll) fail(MF_ERR_INVALID_ARG, "resize_bilinear: the output shape is not input x factors");
+    op.in_elems = (size_t)s.H * s.W * s.C;
+    op.out_elems = (size_t)OH * (size_t)OW * s.C;
+    op.rsz = k::ResizeArgs{s.H, s.W, s.C, s.up_h, s.up_w};
+    op.generic_name = "resize_bl_generic";
+    if (k::resize_bl_plan(op.rbl, s.H, s.W, s.C, s.up_h, s.up_w, s.u8))
+        op.fast = OpImpl::RESIZE_BL, op.fast_name = op.rbl.unit == 16 ? "resize_bl_c4<v16>" : "resize_bl_c4";
+}
+
 } // namespace
 
 OpImpl *op_create_upsampled_conv(const OpImpl *conv, int Hin, int Win, int up_h, int up_w) {
@@ -1237,6 +1251,7 @@ OpImpl *op_create(int device, const OpSpec &spec) {
     case MF_OP_CONCATENATION: create_concat(*op, s); break;
     case MF_OP_PAD: create_pad(*op, s); break;
     case MF_OP_RESIZE_NEAREST_NEIGHBOR: create_resize(*op, s); break;
+    case MF_OP_RESIZE_BILINEAR: create_resize_bilinear(*op, s); break;
     default: fail(MF_ERR_UNSUPPORTED, "unsupported operator kind " + std::to_string(s.kind));
     }
     op->s = s;
@@ -1291,6 +1306,7 @@ bool op_tile_plan(const OpImpl *op, int plan[8]) {
     if (op->fast == OpImpl::CONV_GEMM) return put(1, 0, c.ROW, c.RB, c.NBANDS, c.BH, c.G, c.NSL);
     if (op->fast == OpImpl::UPCONV) return put(1, 0, op->upc.g.ROW, op->upc.g.RB, op->upc.g.NBANDS, op->upc.g.BH, op->upc.g.G, op->upc.g.NSL); // (rows: SOURCE rows)
     if (op->fast == OpImpl::DW_GEMM) return put(1, 0, op->dwg.ROW, op->dwg.RB, op->dwg.NBANDS, op->dwg.BH, op->dwg.G, 1);
+    if (op->fast == OpImpl::RESIZE_BL) return put(1, 0, op->rbl.ROWP, op->rbl.RB, op->rbl.NBANDS, op->rbl.BH, op->rbl.G, 1); // (rows: SOURCE rows)
     return false;
 }
 // the layer-wise kernels that have the single-fma epilogue (k_common.hpp mode 3): the matrix-pipe depthwise, the MFMA pointwise, the stem
@@ -1407,6 +1423,10 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             k::launch_resize_c4(d_in, d_out, op->rsz, batch, op->rsz_unit, s);
             done = true;
             break;
+        case OpImpl::RESIZE_BL:
+            k::launch_resize_bl(d_in, d_out, op->rbl, batch, s);
+            done = true;
+            break;
         case OpImpl::TCONV_PHASE:
             k::launch_tconv_phase(d_in, d_out, op->tcv, (int)batch, s);
             done = true;
@@ -1493,6 +1513,7 @@ void op_run(OpImpl *op, const int8_t *d_in, size_t batch, int8_t *d_out, void *s
             else k::launch_conv2d_generic(d_in, d_out, op->conv, batch, s);
             break;
         case MF_OP_RESIZE_NEAREST_NEIGHBOR: k::launch_resize_generic(d_in, d_out, op->rsz, batch, s); break;
+        case MF_OP_RESIZE_BILINEAR: k::launch_resize_bl_generic(d_in, d_out, op->rsz, sp.u8, batch, s); break;
         case MF_OP_DEPTHWISE_CONV_2D: k::launch_dwconv_generic(d_in, d_out, op->conv, batch, s); break;
         case MF_OP_TRANSPOSE_CONV: k::launch_tconv_generic(d_in, d_out, op->conv, op->tc_padt, op->tc_padl, batch, s); break;
         case MF_OP_AVERAGE_POOL_2D: k::launch_avgpool_generic(d_in, d_out, op->pool, batch, s); break;

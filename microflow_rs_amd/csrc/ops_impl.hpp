@@ -68,7 +68,7 @@ struct OpImpl {
     std::string dil_note;      // "[d{dh}x{dw}]" behind the kernel name of a dilated operator that runs as the undilated one with the stuffed filter (ops.hip create_conv)
     std::string grp_note;      // "[g{G}]" behind the kernel name of a grouped operator that runs as its block-diagonal dense twin (ops.hip create_conv)
     enum Fast { NONE, DW_NHWC, DW_STEM, DW_STEM_RT, DW_C1, PW_MFMA, FC_ROWWAVE, FC_MFMA, POOL_C4, CONV1X1_ROW, DW_RT, PW_RT, CONV_ROWS, CONV_MM, FC_RT,
-                CONV_GEMM, DW_GEMM, FC_SPARSE24, MAXPOOL_C4, ADD_C16, PAD_C4, CONCAT_C4, TCONV_PHASE, CONV_DIL, CONV_GRP, RESIZE_C4, UPCONV } fast = NONE;
+                CONV_GEMM, DW_GEMM, FC_SPARSE24, MAXPOOL_C4, ADD_C16, PAD_C4, CONCAT_C4, TCONV_PHASE, CONV_DIL, CONV_GRP, RESIZE_C4, UPCONV, RESIZE_BL } fast = NONE;
     int *d_rowsum = nullptr; // FC_MFMA / FC_SPARSE24 with wzp != 0: per-row input sums
     size_t rowsum_cap = 0, rowsum_rows = 0; // (ints allocated; the row count the counter pairs currently sit behind)
     int8_t *d_ext = nullptr; // op_run_external on a u8 operator: input moved to the i8 domain
@@ -127,6 +127,7 @@ struct OpImpl {
     int pad_unit = 0;            // ... bytes per word of pad_c4: 4 or 16 (0: the shape has no word kernel)
     k::ResizeArgs rsz{};         // RESIZE_NEAREST_NEIGHBOR (k_resize.hip)
     int rsz_unit = 0;            // ... bytes per word of resize_nn_c4: 4 or 16 (0: the shape has no word kernel)
+    k::ResizeBlArgs rbl{};       // RESIZE_BILINEAR on resize_bl_c4 (k_resize_bilinear.hip); resize_bl_generic takes rsz
     k::UpconvArgs upc{};         // resize + Conv2D in one product (k_upconv.hip); image in d_fcw, phase tables in d_tap, constants as cgm's
     k::FcArgs fc{};
     k::SoftmaxArgs sm{};

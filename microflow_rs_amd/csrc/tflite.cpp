@@ -78,7 +78,6 @@ Vec vec(const Table &t, int id) {
 
 enum { TT_INT32 = 2, TT_UINT8 = 3, TT_INT64 = 4, TT_INT8 = 9 };
 enum { BUILTIN_PADV2 = 60, BUILTIN_MIRROR_PAD = 100 }; // the neighbours of PAD, refused by name
-enum { BUILTIN_RESIZE_BILINEAR = 23 };                 // the neighbour of RESIZE_NEAREST_NEIGHBOR, refused by name
 
 struct TensorInfo {
     std::vector<int> shape;
@@ -715,12 +714,15 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
                     if (c != 0.0f || std::signbit(c)) fail(MF_ERR_INVALID_MODEL, "invalid model: TRANSPOSE_CONV without a bias needs a finite positive output scale");
             break;
         }
-        case MF_OP_RESIZE_NEAREST_NEIGHBOR: { // not in the reference (lib.rs:148 answers "unsupported operator: 97"): the contract is include/microflow_amd.h's
-            auto refuse = [](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: 97 (RESIZE_NEAREST_NEIGHBOR: " + why + ")"); };
+        case MF_OP_RESIZE_BILINEAR:           // (mf_resize_bilinear_create: the same operands and refusals, half-pixel centres only)
+        case MF_OP_RESIZE_NEAREST_NEIGHBOR: { // not in the reference (lib.rs:148 answers "unsupported operator: 97" / "23"): the contract is include/microflow_amd.h's
+            const bool bilinear = code == MF_OP_RESIZE_BILINEAR;
+            const std::string opname = bilinear ? "RESIZE_BILINEAR" : "RESIZE_NEAREST_NEIGHBOR";
+            auto refuse = [&](const std::string &why) { fail(MF_ERR_UNSUPPORTED, "unsupported operator: " + std::to_string(code) + " (" + opname + ": " + why + ")"); };
             if (ins.size() != 2) refuse("it needs an input and a size operand");
             for (const TensorInfo *t : {&in, &out}) {
                 if ((t->type != TT_INT8 && t->type != TT_UINT8) || (t->type == TT_UINT8) != pm.u8) refuse("mixed element types");
-                need_quant(*t, "RESIZE_NEAREST_NEIGHBOR");
+                need_quant(*t, opname.c_str());
                 if (t->scale.size() != 1 || t->zp.size() != 1) refuse("per-channel quantisation on an operand");
             }
             if (in.data_len) refuse("a constant operand");
@@ -728,15 +730,18 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             if (in.shape[0] != 1 || out.shape[0] != 1) refuse("tensor batch must be 1");
             // ResizeNearestNeighborOptions { align_corners:0 half_pixel_centers:1 }: with align_corners = false both settings of
             // half_pixel_centers give floor(o / s) for an integer factor s (floor((o + 1/2) / s) = floor(o / s))
-            if (opt.scalar<uint8_t>(0, 0) != 0) refuse("align_corners = true");
+            // ResizeBilinearOptions { new_height:0 new_width:1 (both deprecated) align_corners:2 half_pixel_centers:3 }: the legacy sampling
+            // (half_pixel_centers = false: src = o / s, another operator) is refused
+            if (opt.scalar<uint8_t>(bilinear ? 2 : 0, 0) != 0) refuse("align_corners = true");
+            if (bilinear && opt.scalar<uint8_t>(3, 0) == 0) refuse("half_pixel_centers = false");
             const TensorInfo sz = read_tensor(tensors, buffers, ins.get<int32_t>(1));
             if (!sz.data_len) refuse("a non-constant size");
             if (sz.type != TT_INT32 || sz.shape != std::vector<int>{2} || sz.data_len < 8)
-                fail(MF_ERR_INVALID_MODEL, "invalid model: RESIZE_NEAREST_NEIGHBOR size must be a constant INT32 [2]");
+                fail(MF_ERR_INVALID_MODEL, "invalid model: " + opname + " size must be a constant INT32 [2]");
             int32_t hw[2];
             std::memcpy(hw, sz.data, 8);
             if (hw[0] != out.shape[1] || hw[1] != out.shape[2] || out.shape[3] != in.shape[3])
-                fail(MF_ERR_INVALID_MODEL, "invalid model: RESIZE_NEAREST_NEIGHBOR size disagrees with the output tensor's shape");
+                fail(MF_ERR_INVALID_MODEL, "invalid model: " + opname + " size disagrees with the output tensor's shape");
             if (out.shape[1] % in.shape[1] != 0 || out.shape[2] % in.shape[2] != 0) refuse("a non-integer ratio");
             if (std::memcmp(&in.scale[0], &out.scale[0], sizeof(float)) != 0 || zp_of(in.zp[0], pm.u8) != zp_of(out.zp[0], pm.u8))
                 refuse("input and output quantisation differ");
@@ -746,8 +751,6 @@ ParsedModel parse_tflite(const uint8_t *data, size_t len) {
             po.up_h = po.OH / po.H, po.up_w = po.OW / po.W;
             break;
         }
-        case BUILTIN_RESIZE_BILINEAR:
-            fail(MF_ERR_UNSUPPORTED, "unsupported operator: 23 (RESIZE_BILINEAR: only RESIZE_NEAREST_NEIGHBOR by integer factors is supported)");
         case BUILTIN_PADV2:
             fail(MF_ERR_UNSUPPORTED, "unsupported operator: 60 (PADV2: only PAD, whose fill is the tensor's zero point, is supported)");
         case BUILTIN_MIRROR_PAD:

@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 
 OP_NAMES = {0: "add", 1: "average_pool_2d", 2: "concatenation", 3: "conv_2d", 4: "depthwise_conv_2d", 67: "transpose_conv", 9: "fully_connected", 17: "max_pool_2d",
-            22: "reshape", 25: "softmax", 34: "pad", 40: "mean", 97: "resize_nearest_neighbor"}
+            22: "reshape", 23: "resize_bilinear", 25: "softmax", 34: "pad", 40: "mean", 97: "resize_nearest_neighbor"}
 
 
 class Model:
@@ -85,7 +85,7 @@ class Model:
         return dh.value, dw.value
 
     def op_upsample(self, i):
-        """(sy, sx) of RESIZE_NEAREST_NEIGHBOR i: the integer factors.  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
+        """(sy, sx) of RESIZE_NEAREST_NEIGHBOR or RESIZE_BILINEAR i: the integer factors.  MicroflowError (MF_ERR_INVALID_ARG) for any other operator."""
         sy, sx = C.c_int(0), C.c_int(0)
         _lib.check(_lib.lib().mf_model_get_op_upsample(self._h, int(i), C.byref(sy), C.byref(sx)))
         return sy.value, sx.value

@@ -11,6 +11,7 @@ names, argument order and meaning, executed by the HIP kernels behind the C ABI.
     concatenation(a, b, output_scale, output_zero_point, options, constants)                              (not in the reference)
     pad(input, pads)                                                                                      (not in the reference)
     resize_nearest(input, factors)                                                                        (not in the reference)
+    resize_bilinear(input, factors)                                                                       (not in the reference)
     softmax(input, output_scale, output_zero_point)
     reshape(input, output_shape)
 
@@ -472,6 +473,24 @@ def resize_nearest(input: Tensor4D, factors) -> Tensor4D:
     out[oy][ox][c] = in[oy // sy][ox // sx][c]; scale and zero point stay (include/microflow_amd.h)."""
     shp = tuple(input.buffer.shape)
     op = prepare_resize_nearest(shp[-3:], factors, dtype=_elem(input.buffer))
+    return Tensor4D(op(input.buffer), list(input.scale), list(input.zero_point))
+
+
+def prepare_resize_bilinear(in_hwc, factors, dtype=np.int8):
+    """factors: (sy, sx), integers >= 1; the output is (sy H, sx W, C).  The rounding is on the value as `dtype`."""
+    H, W, Cc = (int(d) for d in in_hwc)
+    sy, sx = (int(v) for v in factors)
+    h = C.c_void_p()
+    _lib.check(_fn("mf_resize_bilinear_create", dtype)(_device(), H, W, Cc, sy, sx, C.byref(h)))
+    return PreparedOp(h, (H, W, Cc), (H * sy, W * sx, Cc), dtype)
+
+
+def resize_bilinear(input: Tensor4D, factors) -> Tensor4D:
+    """RESIZE_BILINEAR (TFLite builtin 23, Keras' UpSampling2D(interpolation="bilinear"); the reference has none) by integer factors
+    (sy, sx) with half-pixel centres: the exact integer 2-D sum of the four taps, rounded once, half away from zero; scale and zero
+    point stay (include/microflow_amd.h mf_resize_bilinear_create)."""
+    shp = tuple(input.buffer.shape)
+    op = prepare_resize_bilinear(shp[-3:], factors, dtype=_elem(input.buffer))
     return Tensor4D(op(input.buffer), list(input.scale), list(input.zero_point))
 
 

@@ -33,6 +33,8 @@ Each layer dict (all quantization parameters are given, nothing is derived):
                       act, out_shape, out_q.  Negative tests: shape_const=False (output_shape has no buffer), shape (its values)
     resize_nearest_neighbor   out_shape, out_q (the input's, for a model that loads).  Negative tests: size (the operand's values, default
                       out_shape's H and W), size_const=False, align_corners, half_pixel_centers, code ("resize_bilinear")
+    resize_bilinear   the same fields, written as ResizeBilinearOptions (align_corners, half_pixel_centers in fields 2 and 3);
+                      half_pixel_centers defaults to True, what the TF2 converter writes for Keras' UpSampling2D(interpolation="bilinear")
 """
 import struct
 
@@ -168,6 +170,13 @@ def build_model(input_shape, input_q, layers, elem=INT8):
             out = add_tensor(L["out_shape"], L.get("out_type", elem), 0, *L["out_q"])
             # ResizeNearestNeighborOptions { align_corners:0 half_pixel_centers:1 } (ResizeBilinearOptions: fields 2, 3)
             opts = Table({0: ("u8", int(bool(L.get("align_corners", False)))), 1: ("u8", int(bool(L.get("half_pixel_centers", False))))})
+            ins = [cur, tsz]
+        elif op == "resize_bilinear":
+            sz = np.asarray(L.get("size", L["out_shape"][1:3]), np.int32)
+            tsz = add_tensor(sz.shape, INT32, add_buffer(sz) if L.get("size_const", True) else 0, 1.0, 0)
+            out = add_tensor(L["out_shape"], L.get("out_type", elem), 0, *L["out_q"])
+            # ResizeBilinearOptions { new_height:0 new_width:1 (deprecated, not written) align_corners:2 half_pixel_centers:3 }
+            opts = Table({2: ("u8", int(bool(L.get("align_corners", False)))), 3: ("u8", int(bool(L.get("half_pixel_centers", True))))})
             ins = [cur, tsz]
         elif op == "mean":
             ax = np.asarray(L.get("axes", (1, 2)), np.int32)
@@ -515,13 +524,20 @@ def conv_autoencoder(rng, input_shape, widths, k=3, elem=INT8, bias=True):
     return build_model((1,) + tuple(input_shape), in_q, layers, elem)
 
 
-def _resize_layer(shape, q, factors):
-    """one RESIZE_NEAREST_NEIGHBOR layer dict on a tensor shape = (H, W, C) of quantisation q (which its output keeps); factors (sy, sx)"""
+def _resize_layer(shape, q, factors, bilinear=False):
+    """one RESIZE_NEAREST_NEIGHBOR (bilinear: RESIZE_BILINEAR, half-pixel centres) layer dict on a tensor shape = (H, W, C) of quantisation
+    q (which its output keeps); factors (sy, sx)"""
     H, W, C = (int(v) for v in shape)
-    return dict(op="resize_nearest_neighbor", out_shape=(1, H * int(factors[0]), W * int(factors[1]), C), out_q=q)
+    return dict(op="resize_bilinear" if bilinear else "resize_nearest_neighbor", out_shape=(1, H * int(factors[0]), W * int(factors[1]), C), out_q=q)
 
 
-def upsample_autoencoder_layers(rng, input_shape, widths, k=3, factor=2, elem=INT8):
+def _bilinear(interpolation):
+    if interpolation not in ("nearest", "bilinear"):
+        raise ValueError(interpolation)
+    return interpolation == "bilinear"
+
+
+def upsample_autoencoder_layers(rng, input_shape, widths, k=3, factor=2, elem=INT8, interpolation="nearest"):
     """-> (in_q, layers) of upsample_autoencoder"""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     H, W, C = input_shape
@@ -531,22 +547,22 @@ def upsample_autoencoder_layers(rng, input_shape, widths, k=3, factor=2, elem=IN
         layers.append(_conv_layer(rng, (H, W, C), q, False, n, k, 2, act="relu", elem=elem))
         q, (_, H, W, C) = layers[-1]["out_q"], layers[-1]["out_shape"]
     for n in list(widths[-2::-1]) + [widths[0]]:
-        layers.append(_resize_layer((H, W, C), q, (factor, factor)))
+        layers.append(_resize_layer((H, W, C), q, (factor, factor), _bilinear(interpolation)))
         layers.append(_conv_layer(rng, layers[-1]["out_shape"][1:], q, False, n, 3, 1, act="relu", elem=elem))
         q, (_, H, W, C) = layers[-1]["out_q"], layers[-1]["out_shape"]
     layers.append(_conv_layer(rng, (H, W, C), q, False, input_shape[2], 3, 1, act="none", elem=elem))
     return in_q, layers
 
 
-def upsample_autoencoder(rng, input_shape, widths, k=3, factor=2, elem=INT8):
+def upsample_autoencoder(rng, input_shape, widths, k=3, factor=2, elem=INT8, interpolation="nearest"):
     """conv_autoencoder's encoder (a stride-2 k x k Conv2D, relu, per entry of `widths`) with Keras' UpSampling2D(factor) + 3x3 SAME
-    Conv2D (relu) stages as decoder -- RESIZE_NEAREST_NEIGHBOR + CONV_2D in the file -- and a final 3x3 Conv2D to the input's channels.
-    With factor 2, H and W must be multiples of 2^len(widths) for the output to have the input's size."""
-    in_q, layers = upsample_autoencoder_layers(rng, input_shape, widths, k, factor, elem)
+    Conv2D (relu) stages as decoder -- RESIZE_NEAREST_NEIGHBOR (interpolation="bilinear": RESIZE_BILINEAR) + CONV_2D in the file -- and a
+    final 3x3 Conv2D to the input's channels.  With factor 2, H and W must be multiples of 2^len(widths) for the output to have the input's size."""
+    in_q, layers = upsample_autoencoder_layers(rng, input_shape, widths, k, factor, elem, interpolation)
     return build_model((1,) + tuple(input_shape), in_q, layers, elem)
 
 
-def unet1_layers(rng, input_shape, widths, elem=INT8):
+def unet1_layers(rng, input_shape, widths, elem=INT8, interpolation="nearest"):
     """-> (in_q, layers) of unet1"""
     lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
     H, W, C = input_shape
@@ -557,7 +573,7 @@ def unet1_layers(rng, input_shape, widths, elem=INT8):
     layers.append(dict(op="max_pool_2d", filter=(2, 2), padding="valid", strides=(2, 2), act="none", out_shape=(1, H // 2, W // 2, w0), out_q=q0))
     layers.append(_conv_layer(rng, (H // 2, W // 2, w0), q0, False, w1, 3, 1, act="relu", elem=elem))
     q = layers[-1]["out_q"]
-    layers.append(_resize_layer((H // 2, W // 2, w1), q, (2, 2)))
+    layers.append(_resize_layer((H // 2, W // 2, w1), q, (2, 2), _bilinear(interpolation)))
     layers.append(_conv_layer(rng, (H, W, w1), q, False, w0, 3, 1, act="relu", elem=elem))
     q = layers[-1]["out_q"]
     layers.append(_concat_layer(0, (1, H, W, 2 * w0), q))
@@ -565,10 +581,33 @@ def unet1_layers(rng, input_shape, widths, elem=INT8):
     return in_q, layers
 
 
-def unet1(rng, input_shape, widths, elem=INT8):
+def unet1(rng, input_shape, widths, elem=INT8, interpolation="nearest"):
     """A one-level U-Net: input_shape = (H, W, C), H and W even, widths = (w0, w1).  3x3 Conv2D to w0 (relu) -> [skip] -> MaxPool2D 2x2 ->
-    3x3 Conv2D to w1 (relu) -> RESIZE_NEAREST_NEIGHBOR x2 -> 3x3 Conv2D to w0 (relu) -> CONCATENATION with the skip -> 3x3 Conv2D to C."""
-    in_q, layers = unet1_layers(rng, input_shape, widths, elem)
+    3x3 Conv2D to w1 (relu) -> RESIZE_NEAREST_NEIGHBOR (interpolation="bilinear": RESIZE_BILINEAR) x2 -> 3x3 Conv2D to w0 (relu) ->
+    CONCATENATION with the skip -> 3x3 Conv2D to C."""
+    in_q, layers = unet1_layers(rng, input_shape, widths, elem, interpolation)
+    return build_model((1,) + tuple(input_shape), in_q, layers, elem)
+
+
+def seg_head_layers(rng, input_shape, widths, classes, elem=INT8):
+    """-> (in_q, layers) of seg_head"""
+    lo, hi = (0, 256) if elem == UINT8 else (-128, 128)
+    H, W, C = input_shape
+    in_q = (float(np.float32(rng.uniform(0.02, 0.08))), int(rng.integers(lo + 20, hi - 20)))
+    q, layers = in_q, []
+    for n in widths:
+        layers.append(_conv_layer(rng, (H, W, C), q, False, n, 3, 2, act="relu", elem=elem))
+        q, (_, H, W, C) = layers[-1]["out_q"], layers[-1]["out_shape"]
+    layers.append(_conv_layer(rng, (H, W, C), q, False, classes, 1, 1, act="none", elem=elem))
+    q = layers[-1]["out_q"]
+    layers.append(_resize_layer((H, W, classes), q, (4, 4), bilinear=True))
+    return in_q, layers
+
+
+def seg_head(rng, input_shape, widths, classes, elem=INT8):
+    """A segmentation head: input_shape = (H, W, C), H and W multiples of 4, widths = (w0, w1).  Two stride-2 3x3 Conv2D (relu), a 1x1
+    Conv2D to `classes` logits and, as the model's last operator, RESIZE_BILINEAR x 4 back to the input's size ("logits x 4, bilinear")."""
+    in_q, layers = seg_head_layers(rng, input_shape, widths, classes, elem)
     return build_model((1,) + tuple(input_shape), in_q, layers, elem)
 
 
