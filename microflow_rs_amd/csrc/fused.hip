@@ -45,7 +45,8 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
     int8_t *d_out = (int8_t *)out;
     const size_t limit = batch_limit(*f, edge);
     if (limit && batch > limit) fail(MF_ERR_INVALID_ARG, "batch too large for one launch");
-    if (!fused_input_ok(f, d_in)) fail(MF_ERR_INVALID_ARG, std::string(kind_facts(f->kind).in16) + ": the input pointer is not 16-byte aligned");
+    if (!fused_input_ok(f, d_in))
+        fail(MF_ERR_INVALID_ARG, std::string(f->kind == FusedImpl::BLOCK && f->block_deep ? "block_slice_rt" : kind_facts(f->kind).in16) + ": the input pointer is not 16-byte aligned");
     switch (f->kind) {
     case FusedImpl::STAGE: {
         const OpSpec &d = f->a->s;
@@ -57,7 +58,10 @@ static void launch(FusedImpl *f, const void *in, size_t batch, void *out, int ed
         if (f->pairband.KSC == 8) k::launch_pair_band_deep(d_in, d_out, f->pairband, (int)batch, st);
         else k::launch_pair_band(d_in, d_out, f->pairband, (int)batch, st);
         break;
-    case FusedImpl::BLOCK: k::launch_block_band(d_in, d_out, f->block, (int)batch, st); break;
+    case FusedImpl::BLOCK:
+        if (f->block_deep) k::launch_block_slice(d_in, d_out, f->slice, (int)batch, st);
+        else k::launch_block_band(d_in, d_out, f->block, (int)batch, st);
+        break;
     case FusedImpl::CONVPOOL:
         if (f->convpool.mx) k::launch_conv_maxpool(d_in, d_out, f->convpool.args, f->convpool.wz, (int)batch, st);
         else k::launch_conv_pool(d_in, d_out, f->convpool.args, f->convpool.wz, (int)batch, st);

@@ -67,6 +67,9 @@ struct FusedImpl {
     } conv1fc;
     // BLOCK: a 1x1 expand + depthwise 3x3 + 1x1 project block in row bands (k_block_band.hip); a = the expand, b = the depthwise, c = the project
     k::BlockBandArgs block{};
+    // ... or, with 320 <= E <= 1024, slice by slice (k_block_slice.hip: block_deep, the same kind and members)
+    k::BlockSliceArgs slice{};
+    bool block_deep = false;
     size_t block_max_batch = 0; // 0: any batch; else the largest batch at which the block launch runs (fused_batch_ok): above it the launches it replaces
     // CONVPOOL: a Conv2D + the AveragePool2D (k_conv_pool.hip) or MaxPool2D (mx; k_conv_maxpool.hip) on its output in one launch;
     // a = the convolution, b = the pool
@@ -130,7 +133,7 @@ inline KindFacts kind_facts(FusedImpl::Kind kind) {
 // f32 end (`edge`) is limited whatever the kind: batch x 4 bytes per element stay below 2^31
 inline size_t batch_limit(const FusedImpl &f, int edge) {
     if (!kind_facts(f.kind).batch_limit && !edge) return 0;
-    return 0x7fffffffull / 4 / (f.kind == FusedImpl::PAIRBAND ? (size_t)f.pairband.NB : f.kind == FusedImpl::BLOCK ? (size_t)f.block.b.NB :
+    return 0x7fffffffull / 4 / (f.kind == FusedImpl::PAIRBAND ? (size_t)f.pairband.NB : f.kind == FusedImpl::BLOCK ? (size_t)(f.block_deep ? f.slice.b.NB : f.block.b.NB) :
                                  f.kind == FusedImpl::CONVPOOL ? (size_t)f.convpool.args.NB : 1);
 }
 
@@ -206,6 +209,31 @@ inline BlockMatch match_expand_block(const OpImpl *ex, const OpImpl *dw, const O
     const int C = e.C, E = d.C, N = q.N;
     if (E <= C || E <= N) return no; // the tensor inside is the widest: what makes the launch pay, and what no chain of pairs has
     if (E % 16 != 0 || E < 32 || E > 256 || C % 4 != 0 || C < 4 || C > 128 || N % 4 != 0 || N < 4 || N > 256) return no;
+    m.pair.geom.izp4 = 0x01010101u * (uint32_t)(uint8_t)(int8_t)dw->conv.izp; // (whatever kernel the depthwise runs alone)
+    m.CI = C, m.ok = true;
+    return m;
+}
+// ---- the block block_slice_rt starts from (k_block_slice.hip): match_expand_block's block with 320 <= E <= 1024 ----
+// The same three operators on the same terms -- a Conv2D 1x1 at stride 1 on exactly the input of a pair match_dw3x3_pw1x1 accepts (which
+// bounds no channel count), E > C and E > N, one device, one element type, finite constants, zero filter zero points in the i8 domain on
+// all three, none forced generic, W even at stride 2 -- with the channel ranges of block_slice_plan: E in whole sixty-fours (a slice is
+// one k step), C up to 192 (three k steps of the expand), N up to 320.  States every condition itself: match_expand_block stays as it is.
+inline BlockMatch match_expand_block_deep(const OpImpl *ex, const OpImpl *dw, const OpImpl *pw) {
+    BlockMatch no, m;
+    m.pair = match_dw3x3_pw1x1(dw, pw);
+    if (!ex || !m.pair) return no;
+    const OpSpec &e = ex->s, &d = *m.pair.d, &q = *m.pair.q;
+    if (e.kind != MF_OP_CONV_2D || e.grouped() || ex->device != dw->device || e.u8 != d.u8 || !ex->finite_consts) return no;
+    if (e.KH != 1 || e.KW != 1 || e.sh != 1 || e.sw != 1 || e.OH != e.H || e.OW != e.W) return no;
+    if (e.H != d.H || e.W != d.W || e.N != d.C) return no; // on exactly the depthwise's input
+    if (ex->force_generic || dw->force_generic || pw->force_generic) return no; // (generic operators stay launches of their own)
+    for (const OpImpl *o : {ex, dw, pw})
+        for (int32_t z : o->h_wzp)
+            if (z != 0) return no;
+    if (d.sh == 2 && d.W % 2 != 0) return no; // (the plan's stride-2 column units)
+    const int C = e.C, E = d.C, N = q.N;
+    if (E <= C || E <= N) return no; // the tensor inside is the widest
+    if (E % 64 != 0 || E < 320 || E > 1024 || C % 4 != 0 || C < 4 || C > 192 || N % 4 != 0 || N < 4 || N > 320) return no;
     m.pair.geom.izp4 = 0x01010101u * (uint32_t)(uint8_t)(int8_t)dw->conv.izp; // (whatever kernel the depthwise runs alone)
     m.CI = C, m.ok = true;
     return m;

@@ -281,10 +281,73 @@ static std::unique_ptr<FusedImpl> pair_wz_create(OpImpl *dw, OpImpl *pw) {
 // Every operand image is built here from the members' host copies and every constant array is the member's own (the project's padded
 // to whole 16-channel tiles where N % 16 != 0), so the block does not depend on which kernels the members run alone.
 static constexpr int BLOCK_LIMIT_STEPS = 512;
+// ---- the same block with 320 <= E <= 1024, slice by slice (k_block_slice.hip): where match_expand_block has refused the block on E ----
+// The same kind, members and controls as the block below.  The expand's image is the one block_band_rt takes (a slice's four tiles are
+// consecutive in it); the project's is slice-major: block_slice_rt streams one k step of every output tile per slice.
+static FusedImpl *block_slice_create(OpImpl *ex, OpImpl *dw, OpImpl *pw, bool pair_grouped) {
+    if (switches().no_block_slice) return nullptr;
+    const BlockMatch m = match_expand_block_deep(ex, dw, pw);
+    if (!m) return nullptr;
+    const OpSpec &e = ex->s, &d = *m.pair.d, &q = *m.pair.q;
+    const int CI = m.CI, E = d.C, N = q.N;
+    if (ex->h_w.size() != (size_t)E * CI || dw->h_w.size() != (size_t)9 * E || pw->h_w.size() != (size_t)N * E) return nullptr;
+    if (ex->h_A.size() != (size_t)E || dw->h_A.size() != (size_t)E || pw->h_A.size() != (size_t)N || pw->h_S.size() != (size_t)N || pw->h_Kc.size() != (size_t)N) return nullptr;
+    std::unique_ptr<FusedImpl> c = make_group(FusedImpl::BLOCK, ex, dw, pw, "");
+    c->block_deep = true;
+    k::BlockSliceArgs &bs = c->slice;
+    k::PairBandArgs &a = bs.b;
+    if (!k::block_slice_plan(m.pair.geom, CI, bs)) return nullptr;
+    // Classes measured NOT faster than the launches they replace by more than the larger spread of the repeats (profiles/r30/time_block_slice.txt:
+    // scripts/time_expand_block.py --deep --all, then its sweep over batches 16 .. 1024 of the classes that lose at 4096):
+    //   the depthwise + project pair has a launch of its own (pair_band_deep_rt: two launches are replaced, not three) --
+    //   14x14x96 -> 512 -> 320 ran 1.404 ms against 0.947 (x0.67): keeps its launches;
+    //   one k step of C (C <= 64: both 1x1s alone run the weights-in-registers pw_rt) at stride 1 with the image in one band --
+    //   at 4096 14x14x64 -> 384 -> 64 x1.00, -> 96 x1.07 inside 0.12, 6x6x64 -> 384 x0.78 / x0.81, 6x6x8 -> 320 -> 8 x0.96, 9x7x16 -> 384 -> 24
+    //   x1.09 inside 0.11; below, 14x14x64 loses at 16 and 64 (x0.74 - x0.91) and the small images win inside spreads of 0.25 - 0.44
+    //   except at 256: no one limit holds for the class, it keeps its launches.  (Stride 2 -- 10x10x24 -> 320 s2 -> 32 x1.46 -- and
+    //   bands -- 40x40x16 -> 320 -> 16 x1.25 -- stay.)
+    //   less than one 16-pixel chunk per image (3x3x160 -> 960 -> 160 / 320) -- x0.90 / x0.60 at 4096, x1.23 inside 0.25 / x0.64 at 1024,
+    //   x1.70 - x1.85 at 16, 64 and 256 with spreads up to 0.13: one launch up to 256 images (block_max_batch), its launches above.
+    const bool every = switches().block_slice_all; // (the measurement itself)
+    if (!every && (pair_grouped || (bs.KSI == 1 && d.sh == 1 && a.NB == 1))) return nullptr;
+    if (!every && d.H * d.W < 16) c->block_max_batch = 256;
+    const int magic = std::min(ex->magic_mode, std::min(dw->magic_mode, pw->magic_mode));
+    if (!k::block_slice_instance(bs.UPW, bs.KSI, magic)) return nullptr; // (no compiled instance: the block keeps its launches)
+    const std::vector<int8_t> exw = wimage::build_pw_rt_reg_weights(ex->h_w.data(), CI, E, 1, 1, E / 16); // [E][1][1][CI], i8 domain
+    bs.ex_w = keep(*c, exw.data(), exw.size());
+    bs.exA = ex->conv.A, bs.exS = ex->conv.S, bs.exK = ex->conv.Kc, bs.ex_lo = ex->conv.lo_f, bs.ex_hi = ex->conv.hi_f;
+    const std::vector<int8_t> taps = wimage::build_dw_mm_weights(dw->h_w.data(), E); // [3][3][E], i8 domain
+    a.dw_wmm = keep(*c, taps.data(), taps.size());
+    // the project filter [N][1][1][E]: build_pw_rt_reg_weights lays it out [tile][k step][1 KiB] (rows past N zero); slice-major is [k step][tile]
+    const std::vector<int8_t> prep = wimage::build_pw_rt_reg_weights(pw->h_w.data(), E, N, 1, 1, bs.NT);
+    std::vector<int8_t> major(prep.size());
+    for (int t = 0; t < bs.NT; ++t)
+        for (int sl = 0; sl < bs.NS; ++sl) std::copy_n(prep.begin() + ((size_t)t * bs.NS + sl) * 1024, 1024, major.begin() + ((size_t)sl * bs.NT + t) * 1024);
+    a.pw_w = keep(*c, major.data(), major.size());
+    set_pair_consts(a, dw->conv, pw->conv);
+    if (N % 16 != 0) { // a lane fetches the constants of its four channels whether or not they are below N
+        const size_t np = (size_t)bs.NT * 16;
+        auto padded = [&](const auto &src) {
+            auto h = src;
+            h.resize(np, 0);
+            return keep(*c, h.data(), np * 4);
+        };
+        a.pwA = (const float *)padded(pw->h_A), a.pwS = (const float *)padded(pw->h_S), a.pwK = (const int *)padded(pw->h_Kc);
+    }
+    a.magic = magic, a.xr = d.u8 ? 0x80 : 0;
+    a.queue = (int *)ex->d_queue.p, a.qlaunch = &ex->q_launches;
+    c->epi_mode = magic;
+    c->name = "block_slice_rt<" + std::to_string(e.H) + "x" + std::to_string(e.W) + "x" + std::to_string(CI) + "-" + std::to_string(E) + (d.sh == 2 ? "s2" : "") + "-" + std::to_string(N) +
+              ";RB" + std::to_string(a.RB) + ";NB" + std::to_string(a.NB) + ">";
+    if (switches().chain_verbose)
+        fprintf(stderr, "[microflow_amd] block group %s: %d slices, input band %d B, slice tile %d rows x %d B, slice MID %d B, lds %d B, %d workgroup%s per CU, %d chunks x %d output tiles on %d x %d waves of %d units, k steps of C %d, mode %d\n",
+                c->name.c_str(), bs.NS, bs.in_bytes, a.TR, a.ROW, a.mid_bytes, a.lds_bytes, a.wgs, a.wgs == 1 ? "" : "s", a.NCH, bs.NT, 1 << bs.lgWC, 8 >> bs.lgWC, bs.UPW, bs.KSI, magic);
+    return c.release();
+}
 FusedImpl *fused_block_create(OpImpl *ex, OpImpl *dw, OpImpl *pw, bool pair_grouped) {
     if (switches().no_expand_block) return nullptr;
     const BlockMatch m = match_expand_block(ex, dw, pw);
-    if (!m) return nullptr;
+    if (!m) return block_slice_create(ex, dw, pw, pair_grouped); // (refused on E, or on what the deep route refuses too)
     const OpSpec &e = ex->s, &d = *m.pair.d, &q = *m.pair.q;
     const int CI = m.CI, E = d.C, N = q.N;
     if (ex->h_w.size() != (size_t)E * CI || dw->h_w.size() != (size_t)9 * E || pw->h_w.size() != (size_t)N * E) return nullptr;

@@ -513,6 +513,34 @@ bool block_band_plan(const ChainGeom &g, int CI, BlockBandArgs &a);
 bool block_band_instance(int KSC, int KSI, int magic); // a compiled kernel exists
 void launch_block_band(const int8_t *in, int8_t *out, const BlockBandArgs &a, int batch, hipStream_t s);
 
+// ---- the same block with 320 <= E <= 1024, slice by slice (k_block_slice.hip: block_slice_rt) ----
+// A step is a band as above, but E is walked in slices of 64 channels: per slice the expand writes a 64-channel tile, the depthwise a
+// 64-channel MID, and the project adds MID x the slice's k step of its filter to i32 accumulators that stay in registers until the last
+// slice.  LDS holds one slice whatever E is; the project filter streams.  Wave w owns a PC x PT rectangle of (16-pixel chunk, 16-channel
+// output tile) units for the whole launch; the instance is named by its units per wave, UPW = PC PT.
+constexpr int block_slice_pc(int UPW) { return UPW >= 8 ? 4 : (UPW >= 4 ? 2 : 1); }   // chunks of a wave's rectangle
+constexpr int block_slice_pt(int UPW) { return UPW >= 16 ? 4 : (UPW >= 2 ? 2 : 1); }  // output tiles of a wave's rectangle
+struct BlockSliceArgs {
+    PairBandArgs b;                // ONE SLICE as the depthwise phase takes it: C = 64, NQ = 4, its tile / MID geometry and LDS regions; N as
+                                   // the model states it; dw_wmm and the depthwise constants over all of E; pw_w the slice-major image
+                                   // [slice][tile of N][lane][16 B] (tile rows past N zero); the project's constants padded to whole tiles
+    int E, NS, NT;                 // the tensor inside; its slices, E / 64; 16-channel tiles of N, ceil(N / 16)
+    int CI, KSI;                   // the expand's input channels; 64-deep k steps over them (1 .. 3: the kernel instance's)
+    int UPW, lgWC;                 // units per wave (1, 2, 4, 8, 16: the kernel instance's); 2^lgWC waves along the chunks, 8 >> lgWC along the tiles
+    int in_off, in_bytes;          // LDS region of the staged input band, as BlockBandArgs'
+    uint32_t wmagic;               // ceil(2^32 / W), as BlockBandArgs'
+    const void *ex_w;              // build_pw_rt_reg_weights(CI, E, group 1, TB 1, E / 16): a slice's four tiles are consecutive
+    const float *exA, *exS;
+    const int *exK;
+    float ex_lo, ex_hi;
+};
+// fills the geometry and the LDS plan (everything but the operand pointers, clamps and modes); false: a channel count outside the
+// ranges (E 320 .. 1024 in whole sixty-fours, CI 4 .. 192 and N 4 .. 320 in whole fours), an odd width at stride 2, or no band whose
+// regions fit PAIR_BAND_LDS_MAX and whose units fit eight rectangles of sixteen.  g.C is E.
+bool block_slice_plan(const ChainGeom &g, int CI, BlockSliceArgs &a);
+bool block_slice_instance(int UPW, int KSI, int magic); // a compiled kernel exists
+void launch_block_slice(const int8_t *in, int8_t *out, const BlockSliceArgs &a, int batch, hipStream_t s);
+
 // ---- one pair whose filters carry zero points, whole images in LDS (k_pair_wz.hip: pair_wz_rt) ----
 // chain_rt's single-pair step plus the reference's two zero-point terms: acc -= wzp[c] * (window sum) in the depthwise,
 // acc[n] -= wzp[n] * (the pixel's sum over its C intermediate bytes) in the 1x1.  Geometry and LDS plan are chain_plan's with n = 1.

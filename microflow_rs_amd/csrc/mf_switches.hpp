@@ -40,6 +40,8 @@ struct Switches {
     bool no_pool_fc = false;      // MF_NO_POOL_FC      global AveragePool2D + FullyConnected (+ Softmax) heads one launch per operator, not one pool_fc_chain launch (k_pool_fc.hip)
     bool no_pair_band = false;     // MF_NO_PAIR_BAND     pairs too large for chain_rt one launch per operator, not one pair_band_rt / pair_band_deep_rt launch (k_pair_band.hip, k_pair_band_deep.hip)
     bool no_expand_block = false;  // MF_NO_EXPAND_BLOCK  1x1 expand + depthwise 3x3 + 1x1 project blocks as the launches they had before (the expand's own, then the pair's group or operators), not one block_band_rt launch (k_block_band.hip)
+    bool no_block_slice = false;   // MF_NO_BLOCK_SLICE   such blocks with 320 <= E <= 1024 as the launches they had before, not one block_slice_rt launch (k_block_slice.hip); MF_NO_EXPAND_BLOCK turns this route off too
+    bool block_slice_all = false;  // MF_BLOCK_SLICE_ALL  measurements (scripts/time_expand_block.py --deep --all): also the blocks block_slice_create excludes by measurement run as one block_slice_rt launch -- every block the plan accepts
     bool no_upconv = false;        // MF_NO_UPCONV        a Conv2D on a resized input (mf_conv_2d_upsampled_create) on upconv_generic, not upconv_rt; and a RESIZE_NEAREST_NEIGHBOR + the Conv2D behind it one launch per operator (fused_heads.hip fused_resize_conv_create)
     bool upconv_all = false;       // MF_UPCONV_ALL       measurements and tests: also the resize + Conv2D classes rule (0r) excludes by measurement run as one upconv_rt launch
     bool no_pad_conv = false;      // MF_NO_PAD_CONV      a PAD + the VALID Conv2D / DepthwiseConv2D behind it one launch per operator, not one launch of the convolution's kernel with explicit pads (fused_heads.hip fused_pad_conv_create)

@@ -72,6 +72,8 @@ Switches switches_parse() {
     s.no_conv_rows_bytes = env_set("MF_NO_CONV_ROWS_BYTES");
     s.no_pair_band = env_set("MF_NO_PAIR_BAND");
     s.no_expand_block = env_set("MF_NO_EXPAND_BLOCK");
+    s.no_block_slice = env_set("MF_NO_BLOCK_SLICE");
+    s.block_slice_all = env_set("MF_BLOCK_SLICE_ALL");
     s.no_conv_pool = env_set("MF_NO_CONV_POOL");
     s.no_pad_conv = env_set("MF_NO_PAD_CONV");
     s.no_upconv = env_set("MF_NO_UPCONV");

@@ -3,6 +3,7 @@
 the same model with fusion off (one launch per operator), in the same process, back to back.
 
     python scripts/time_expand_block.py [--reps 20] [--only 3] [--sweep]
+    python scripts/time_expand_block.py --deep [--all] [--shapes 0,1,...] [--root <parent tree>] [--batches 16,64,...]
 
 --sweep times a second set instead: the blocks that did not clear the routing rule at the batches above, each at batches 16 .. 4096 (one
 model, one line per batch).  Below some batch three launches cost more than the work inside them; fused_block_create's batch limits
@@ -10,6 +11,12 @@ model, one line per batch).  Below some batch three launches cost more than the 
 
 Under MF_DEV=1 MF_NO_EXPAND_BLOCK=1 the first column is the routing without the block group (the expand's own launch, then the pair's
 group where it has one): the other half of the routing rule of DESIGN 4.16.
+
+--deep times a third set: the blocks with E > 256 (k_block_slice.hip: block_slice_rt) -- full-width MobileNet-v2's at 224 input and their
+6x6 / 3x3 variants for 96-pixel inputs -- at batch 4096 (or at each of --batches), one child process per (shape, routing): the default
+routing against the same build under MF_DEV=1 MF_NO_BLOCK_SLICE=1 (the routing without the route), and with --root also the tree given
+there (the parent commit, as cross-check).  --all puts the first column under MF_DEV=1 MF_BLOCK_SLICE_ALL=1, so that the classes
+fused_pairs.hip excludes by measurement are timed on block_slice_rt too: that is how profiles/r30/time_block_slice.txt is regenerated.  Three repeats of the median of --reps; the spread is that of all samples.  DESIGN 4.31.
 
 One line per shape: the median of --reps runs of each path, each timed with HIP events after warm-up, the spread of the repeats
 ((max - min) / median of each path), their ratio, and hbm_frac = batch x (H W C + OH OW N) bytes (the least a launch must move) over
@@ -40,6 +47,15 @@ SWEEP_SHAPES = [(6, 6, 8, 32, 1, 8), (9, 7, 16, 64, 1, 24), (13, 11, 12, 48, 1, 
                 (28, 28, 24, 144, 2, 32), (56, 56, 24, 144, 2, 32), (14, 14, 32, 192, 1, 32), (28, 28, 32, 192, 1, 32), (24, 24, 24, 144, 1, 24)]
 SWEEP_BATCHES = (16, 64, 128, 256, 512, 1024, 4096)
 STEP_TIMEOUT = 240  # seconds per shape
+# --deep: (H, W, C, E, stride, N) of full-width MobileNet-v2's blocks with E > 256 at 224 input, then at 96 input
+DEEP_SHAPES = [(14, 14, 64, 384, 1, 64), (14, 14, 64, 384, 1, 96), (14, 14, 96, 576, 1, 96), (14, 14, 96, 576, 2, 160), (7, 7, 160, 960, 1, 160),
+               (7, 7, 160, 960, 1, 320), (6, 6, 64, 384, 1, 64), (6, 6, 64, 384, 1, 96), (6, 6, 96, 576, 1, 96), (6, 6, 96, 576, 2, 160),
+               (3, 3, 160, 960, 1, 160), (3, 3, 160, 960, 1, 320),
+               # narrow ends around a wide inside (tests/test_gpu_block_slice.py's smallest cases): the classes the models above do not hold
+               (6, 6, 8, 320, 1, 8), (9, 7, 16, 384, 1, 24), (10, 10, 24, 320, 2, 32), (40, 40, 16, 320, 1, 16),
+               # the depthwise + project pair has a launch of its own (pair_band_deep_rt): two launches are replaced, not three
+               (14, 14, 96, 512, 1, 320)]
+DEEP_BATCH = 4096
 
 
 def times_ms(fn, reps, warm=3, inner=1):
@@ -127,12 +143,65 @@ def sweep(idx, reps):
             label, batch, "+".join(n.split(";")[0] for n in first if n and not n.startswith("("))[:44], t_first, s_first, t_ops, s_ops, t_ops / t_first, same), flush=True)
 
 
+def deep_child(idx, reps, batch, root):
+    """one (shape, routing): 'DEEP <median of the three repeat medians> <spread of all samples> <kernels>' and the output's checksum"""
+    if root:
+        sys.path[:2] = [root, os.path.join(root, "tools")]
+    import torch
+    import microflow_rs_amd as mf
+    import tflite_writer as tw
+    assert torch.cuda.is_available(), "needs the GPU"
+    H, W, C, E, S, N = DEEP_SHAPES[idx]
+    blob = tw.conv_net(np.random.default_rng(idx), (H, W, C), [("conv", E, 1, 1), ("dw", 0, 3, S), ("conv", N, 1, 1)], act_scale=6.0 / 255.0)
+    m = mf.Model(blob)
+    m.prepare(batch)
+    x = torch.randint(-128, 128, (batch, m.input_elems), dtype=torch.int8, device="cuda", generator=torch.Generator(device="cuda").manual_seed(idx))
+    out = m.run_quantized(x).clone()
+    inner = 10 if batch < 1024 else 1
+    meds, spreads = zip(*(times_ms(lambda: m.run_quantized(x, out=out), reps, inner=inner) for _ in range(3)))
+    names = "+".join(n for n in (m.op(i)["kernel"] for i in range(m.num_ops)) if n and not n.startswith("("))
+    print("DEEP %.5f %.3f %s %d" % (float(np.median(meds)), max(spreads), names, int(out.to(torch.int64).sum().item())), flush=True)
+
+
+def deep(reps, root, batches, every, shapes):
+    for batch in batches:
+        for idx, (H, W, C, E, S, N) in enumerate(DEEP_SHAPES):
+            if shapes and idx not in shapes:
+                continue
+            res = []
+            for env_add, tree in [({"MF_DEV": "1", "MF_BLOCK_SLICE_ALL": "1"} if every else {}, None), ({"MF_DEV": "1", "MF_NO_BLOCK_SLICE": "1"}, None)] + ([({}, root)] if root else []):
+                env = {k: v for k, v in os.environ.items() if not k.startswith("MF_")}
+                env.update(env_add)
+                cmd = [sys.executable, os.path.abspath(__file__), "--deep", "--reps", str(reps), "--only", str(idx), "--batches", str(batch)] + (["--root", tree] if tree else [])
+                try:
+                    r = subprocess.run(cmd, timeout=STEP_TIMEOUT, env=env, capture_output=True, text=True)
+                except subprocess.TimeoutExpired:
+                    sys.exit("shape %d ran into its %d s limit: nothing more is started" % (idx, STEP_TIMEOUT))
+                line = [l for l in r.stdout.splitlines() if l.startswith("DEEP ")]
+                if r.returncode != 0 or not line:
+                    sys.exit("shape %d ended with status %d: nothing more is started\n%s" % (idx, r.returncode, r.stderr[-2000:]))
+                f = line[0].split()
+                res.append((float(f[1]), float(f[2]), f[3], f[4]))
+            (t1, s1, k1, c1), (t0, s0, k0, c0) = res[0], res[1]
+            tail = "  parent tree %8.4f ms (spread %.3f) same=%s" % (res[2][0], res[2][1], res[2][3] == c1) if root else ""
+            print("%3dx%3dx%3d -> %3d%s -> %-3d batch %5d  %-40s %8.4f ms (spread %.3f)  without the route %8.4f ms (spread %.3f; %s)  x%5.2f  same=%s%s" % (
+                H, W, C, E, "s2" if S == 2 else "  ", N, batch, k1, t1, s1, t0, s0, k0, t0 / t1, c0 == c1, tail), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--only", type=int, default=-1, help="run this shape in this process (what the parent starts per shape)")
     ap.add_argument("--sweep", action="store_true", help="the blocks at parity or slower at large batches, at batches 16 .. 4096")
+    ap.add_argument("--deep", action="store_true", help="the blocks with E > 256: the default routing against MF_NO_BLOCK_SLICE")
+    ap.add_argument("--root", default="", help="--deep: a second tree (the parent commit) to time as cross-check")
+    ap.add_argument("--batches", default=str(DEEP_BATCH), help="--deep: comma-separated batch sizes")
+    ap.add_argument("--all", action="store_true", help="--deep: the first column under MF_BLOCK_SLICE_ALL (the excluded classes on block_slice_rt too)")
+    ap.add_argument("--shapes", default="", help="--deep: comma-separated indices into DEEP_SHAPES (default: all)")
     a = ap.parse_args()
+    if a.deep:
+        batches = [int(b) for b in a.batches.split(",")]
+        return deep_child(a.only, a.reps, batches[0], a.root) if a.only >= 0 else deep(a.reps, a.root, batches, a.all, [int(i) for i in a.shapes.split(",") if i])
     if a.only >= 0:
         return sweep(a.only, a.reps) if a.sweep else one(a.only, a.reps)
     for idx in range(len(SWEEP_SHAPES if a.sweep else SHAPES) + 1):
